@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Benchmark of the SimSeg hot path on MI355X (contract in the task statement / SURVEY.md 8d).
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3                      # the headline only: set-up, warm-up, timed steps, one JSON line
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full               # + every secondary leg: other dtypes and forms of the step, the
+                                                                        #   instrumented roofline step, seg / retrieval legs, CPU baselines
+    python bench.py --gpus 1 --steps 10 --warmup 3 --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P bench.py --gpus 8 ...
 
 Workload (BASELINE.json configs[2], weak-scaled): ViT-B/16 + BERT-base contrastive pre-training step on synthetic
@@ -685,11 +688,43 @@ def guarded(name, fn, *a, all_ranks=True, **kw):
     return res if err is None else err
 
 
+DUMP_SAMPLE_PER_TENSOR = 4096
+
+
+def dump_outputs(path, model, last):
+    """--dump-outputs: what the last timed step computed, as <path>/<name>.npy (float64 scalars, float32 samples), so that two builds can be
+    compared output for output on identical inputs.  `last` is what the model handed the step: the loss dict and the two in-batch
+    retrieval accuracies.  The step's other product, the updated parameters and the gradients they were updated with (~1.6 GB in fp32), is
+    a fixed sample: DUMP_SAMPLE_PER_TENSOR positions per parameter tensor (all of a smaller one), drawn from a generator seeded once, over
+    the parameters in model order.  Gradients are as the backward left them (scaled by the loss scale under fp16 AMP); none = zeros."""
+    import numpy as np
+    loss_dict, i2t_acc, t2i_acc = last
+    arrays = {k: v for k, v in loss_dict.items()}
+    arrays.update(i2t_acc=i2t_acc, t2i_acc=t2i_acc)
+    arrays = {k: torch.as_tensor(v).detach().double().cpu().numpy() for k, v in arrays.items()}
+    g = torch.Generator().manual_seed(0)
+    ps, gs = [], []
+    with torch.no_grad():
+        for _, p in model.named_parameters():
+            n = p.numel()
+            idx = (torch.randint(n, (DUMP_SAMPLE_PER_TENSOR,), generator=g) if n > DUMP_SAMPLE_PER_TENSOR else torch.arange(n)).to(p.device)
+            ps.append(p.reshape(-1)[idx].float())
+            gs.append(p.grad.reshape(-1)[idx].float() if p.grad is not None else torch.zeros(idx.numel(), device=p.device))
+    arrays["params_sample"] = torch.cat(ps).cpu().numpy()
+    arrays["grads_sample"] = torch.cat(gs).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs would write {total} bytes"
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    log(f"outputs of the last timed step: {', '.join(sorted(arrays))} -> {path} ({total / 1e6:.1f} MB)")
+
+
 def self_launch(n):
-    """`python bench.py --gpus N` outside a launcher: become `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same
+    """`python bench.py --gpus N` outside a launcher: start `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <same
     arguments>` - one rank per GPU over RCCL, rendezvous on 127.0.0.1 and a free port (the reference: launch.py:33-70 builds
     `torch.distributed.launch --nproc_per_node`, simseg/core/initial.py:54 calls init_process_group from the environment).  The ranks inherit
-    stdout, so rank 0's one JSON line is still the only thing on it; the launcher's exit code is this process's."""
+    stdout, so rank 0's one JSON line is still the only thing on it; the launcher's exit code is this process's.  Does not return."""
     import socket
     try:
         have = torch.cuda.device_count()
@@ -707,7 +742,8 @@ def self_launch(n):
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     log("self-launch: " + " ".join(cmd))
     sys.stdout.flush(); sys.stderr.flush()
-    os.execvpe(cmd[0], cmd, env)
+    import subprocess
+    sys.exit(subprocess.call(cmd, env=env))      # a child process, not an exec: device_count() above may have opened the HIP runtime here
 
 
 def main():
@@ -723,12 +759,18 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-seg", action="store_true", help="skip the zero-shot-seg eval stage measurement")
     ap.add_argument("--retrieval", action="store_true", help="with --no-seg: still run the (quick) retrieval metric legs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary measurement: the step in its other forms and 16-bit type, the instrumented "
+                         "roofline step and kernel rooflines, the seg / retrieval evaluation legs and the CPU baselines (default: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (loss, accuracies, a seeded sample of the updated parameters "
+                         "and their gradients)")
     ap.add_argument("--local_rank", "--local-rank", type=int, default=None,
                     help="set by torch.distributed.launch-style launchers (the reference's launch.py:33-70); torch.distributed.run sets LOCAL_RANK instead")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        self_launch(args.gpus)                             # does not return: this process becomes the launcher of N ranks
+        self_launch(args.gpus)                             # does not return: the N ranks run in a launcher started as a child process
     # stdout carries the ONE JSON line and nothing else: file descriptor 1 is parked and re-pointed at stderr for the whole run, so whatever a
     # library writes to the C-level stdout (RCCL prints a version banner there, flushed at exit - i.e. AFTER the line - when stdout is a
     # pipe) cannot land next to it; rank 0 writes the line to the parked descriptor at the end.
@@ -873,12 +915,14 @@ def main():
         return out
 
     ZERO_COPY = os.environ.get("SIMSEG_BENCH_SYNC_ZERO_COPY", "0") != "0"      # (measured 0.7 ms SLOWER than the bucket copies: profiles/r4_gradsync_events_ab.txt)
+    last = [None]                        # what the model handed the latest step (loss dict, accuracies): --dump-outputs
 
     def step():
         opt.zero_grad(set_to_none=(world == 1 or sync is not None))     # under DDP the grads are views into the all-reduce buckets
         if sync is not None and ZERO_COPY:
             sync.begin()                                                 # the large weight gradients are written straight into the exchange buffer
-        loss_dict, _, _ = net(next_batch())
+        loss_dict, i2t_acc, t2i_acc = net(next_batch())
+        last[0] = (loss_dict, i2t_acc, t2i_acc)
         amp = mode[0] == "fp16"
         (scaler.scale(loss_dict["nce_loss"]) if amp else loss_dict["nce_loss"]).backward()
         if sync is not None:
@@ -897,7 +941,7 @@ def main():
         bdf = f"{pr.pci_domain_id:04x}:{pr.pci_bus_id:02x}:{pr.pci_device_id:02x}.0"
     except Exception:       # noqa: BLE001  (older torch: no PCI fields - rocm-smi then)
         pass
-    clocks = ClockSampler(bdf=bdf) if rank == 0 else None      # clock / power from a side thread: the chip is power-capped under this load
+    clocks = ClockSampler(bdf=bdf) if rank == 0 and args.full else None      # clock / power from a side thread: the chip is power-capped under this load
     for i in range(args.warmup):
         step()
         if i == 0:
@@ -926,6 +970,56 @@ def main():
         amp_info = {"loss_scale": scaler.get_scale(), "optimizer_steps_taken": opt.steps_taken() - taken0, "steps": args.steps,
                     "note": "GradScaler live: scaled backward; overflow check = one read-only kernel, unscale + skip decision inside the AdamW "
                             "kernel on the device (no host read in the step)"}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, model, last[0])       # before any secondary leg steps the model further
+    env_ts = os.environ.get("SIMSEG_AMD_TWO_STREAMS")
+    two_streams = (env_ts != "0") if env_ts is not None else world == 1      # the default of simseg/models/pipelines/clip.py
+    if sync is not None:
+        two_streams = os.environ.get("SIMSEG_AMD_TWO_STREAMS") != "0"
+
+    def headline_config(**extra):
+        return {"workload": f"ViT-B/16 + BERT-base contrastive pretrain step (fwd + global InfoNCE + bwd + AdamW), "
+                            f"{B} pairs/GPU, {args.img}x{args.img} images, {L}-token captions (BASELINE configs[2], weak-scaled)",
+                "image_encoder": args.tag, "text_encoder": "bert-base-uncased", "global_batch": world * B,
+                "pairs_per_gpu": B, "seq_len": L, "img_size": args.img, "parallelism": f"dp{world}",
+                "process_group": pg_info, "batches_rotated": NB, **extra,
+                "caption_lengths": ("host-side token counts travel with the batch (no host read in the step)" if HOST_LENGTHS
+                                    else "derived from the device mask (one host read per step)"),
+                "gradient_sync": ((f"simseg_amd.parallel.GradSync ({dp})" + ((" [forced on one rank: every collective issued on the one-rank " + str(pg_info["backend"]) + " group]" if os.environ.get("SIMSEG_FORCE_COLLECTIVES", "0") == "1"
+                                                                                 else " [forced on one rank: no collective]") if world == 1 else "")) if sync is not None
+                                  else ("none" if world == 1 else "torch DDP")),
+                "gradient_sync_detail": ({"zero_copy_weight_gradients": ZERO_COPY, "gradients_copied_per_step": sync.copied_last,
+                                          "events_per_step": sync.events_last, "buckets": len(sync.buckets)} if sync is not None else None),
+                "optimizer_streams": ("text tower's parameters updated on its own stream (starts when that tower's backward ends)" if OPT_STREAMS else "one launch on the main stream"),
+                "tower_streams": 2 if two_streams else 1,
+                "persistent_gemm_reserved_cus": int(os.environ.get("SIMSEG_GEMM_PP2_RESERVE", "0")),
+                "bert_dropout": 0.1, "optimizer": "AdamW (fused HIP kernel)",
+                "captions": "ragged, lengths U{8..L}" + ("; the padded token rows of the text tower are not computed (same loss and "
+                            "gradients as computing them: SIMSEG_AMD_PACKED_TEXT=0)" if os.environ.get("SIMSEG_AMD_PACKED_TEXT", "1") != "0" else "; padded token rows computed")}
+
+    def headline(**config_extra):
+        return {"metric": "image-text pairs/sec (train) + seg images/sec (eval), ViT-B", "value": round(world * B * args.steps / elapsed, 2), "unit": "pairs/s",
+                "value_is": "training image-text pairs/s over all ranks; the zero-shot-seg eval rate is reported in seg_eval", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": HEAD, "data": "synthetic",
+                "dtype_is": ("fp16 compute with fp32 accumulation and fp32 master weights under a live GradScaler - the reference's own AMP arithmetic "
+                             "(clip_runner.py:226-230, core/hooks/optimizer.py:73-82)" if HEAD == "fp16" else "bf16 compute, fp32 accumulation, fp32 master weights, no loss scaling"),
+                "amp": amp_info, "full": bool(args.full), "config": headline_config(**config_extra)}
+
+    if not args.full:
+        # the headline only: every secondary figure (other forms and types of the step, the instrumented roofline step, the evaluation
+        # legs, the CPU baselines) is behind --full, and its keys are absent from this line
+        if rank == 0:
+            out = headline()
+            out["value_is"] = "training image-text pairs/s over all ranks (the zero-shot-seg eval rate: --full)"
+            out["final_loss"] = round(float(loss.detach()), 4)
+            sys.stdout.flush()
+            os.write(_JSON_FD, (json.dumps(out) + "\n").encode())
+        if dist.is_initialized():
+            if world > 1:
+                dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- the same step with the padded caption tokens computed, as HF's BertModel does (secondary figure, same process) ----------
     dense_text = None
@@ -1037,10 +1131,6 @@ def main():
     # ---- roofline of the dominant kernel: one extra instrumented step, events around every GEMM launch -------------
     # The timed steps run the two towers on two HIP streams (their kernels share the GPU, so a per-kernel duration is not
     # that kernel's own speed); the instrumented step runs them on ONE stream so that each launch is timed alone.
-    env_ts = os.environ.get("SIMSEG_AMD_TWO_STREAMS")
-    two_streams = (env_ts != "0") if env_ts is not None else world == 1      # the default of simseg/models/pipelines/clip.py
-    if sync is not None:
-        two_streams = os.environ.get("SIMSEG_AMD_TWO_STREAMS") != "0"
     os.environ["SIMSEG_AMD_TWO_STREAMS"] = "0"
     ops.PROFILE = []
     prof_lens = batches[step_no[0] % NB]["attention_mask"].sum(1).cpu()      # caption lengths of the instrumented step's batch
@@ -1123,8 +1213,6 @@ def main():
     if rank == 0:
         n_patches = (args.img // 16) ** 2
         fpp = flops_per_pair(n_patches, dim, L)
-        pairs = world * B * args.steps
-        value = pairs / elapsed
         dom = max(agg, key=lambda k: agg[k][2])
         packed = os.environ.get("SIMSEG_AMD_PACKED_TEXT", "1") != "0" and os.environ.get("SIMSEG_AMD_SKIP_PAD_ROWS", "1") != "0"
         t_img = n_patches + 1
@@ -1181,33 +1269,9 @@ def main():
                      "seg_eval_vit_s_512_bf16_windows_per_s": _pick(seg, "vit_s_512_bf16", "windows_per_s"),
                      "seg_slide_512x1024_bf16_images_per_s": _pick(seg, "slide_512x1024", "bf16", "images_per_s"),
                      "seg_slide_512x1024_bf16_crf_images_per_s": _pick(seg, "slide_512x1024", "bf16_crf", "images_per_s")}
-        out = {
-            "metric": "image-text pairs/sec (train) + seg images/sec (eval), ViT-B", "value": round(value, 2), "unit": "pairs/s",
-            "value_is": "training image-text pairs/s over all ranks; the zero-shot-seg eval rate is reported in seg_eval", "n_gpus": world,
-            "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(1e3 * elapsed / args.steps, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": HEAD, "data": "synthetic",
-            "dtype_is": ("fp16 compute with fp32 accumulation and fp32 master weights under a live GradScaler - the reference's own AMP arithmetic "
-                         "(clip_runner.py:226-230, core/hooks/optimizer.py:73-82)" if HEAD == "fp16" else "bf16 compute, fp32 accumulation, fp32 master weights, no loss scaling"),
-            "amp": amp_info,
+        out = headline(secondary_figures=secondary)
+        out.update({
             f"value_{OTHER}": other_leg["pairs_per_s"] if other_leg else None, f"ms_per_step_{OTHER}": other_leg["ms_per_step"] if other_leg else None,
-            "config": {"workload": f"ViT-B/16 + BERT-base contrastive pretrain step (fwd + global InfoNCE + bwd + AdamW), "
-                                   f"{B} pairs/GPU, {args.img}x{args.img} images, {L}-token captions (BASELINE configs[2], weak-scaled)",
-                       "image_encoder": args.tag, "text_encoder": "bert-base-uncased", "global_batch": world * B,
-                       "pairs_per_gpu": B, "seq_len": L, "img_size": args.img, "parallelism": f"dp{world}",
-                       "process_group": pg_info, "batches_rotated": NB, "secondary_figures": secondary,
-                       "caption_lengths": ("host-side token counts travel with the batch (no host read in the step)" if HOST_LENGTHS
-                                           else "derived from the device mask (one host read per step)"),
-                       "gradient_sync": ((f"simseg_amd.parallel.GradSync ({dp})" + ((" [forced on one rank: every collective issued on the one-rank " + str(pg_info["backend"]) + " group]" if os.environ.get("SIMSEG_FORCE_COLLECTIVES", "0") == "1"
-                                                                                        else " [forced on one rank: no collective]") if world == 1 else "")) if sync is not None
-                                         else ("none" if world == 1 else "torch DDP")),
-                       "gradient_sync_detail": ({"zero_copy_weight_gradients": ZERO_COPY, "gradients_copied_per_step": sync.copied_last,
-                                                 "events_per_step": sync.events_last, "buckets": len(sync.buckets)} if sync is not None else None),
-                       "optimizer_streams": ("text tower's parameters updated on its own stream (starts when that tower's backward ends)" if OPT_STREAMS else "one launch on the main stream"),
-                       "tower_streams": 2 if two_streams else 1,
-                       "persistent_gemm_reserved_cus": int(os.environ.get("SIMSEG_GEMM_PP2_RESERVE", "0")),
-                       "bert_dropout": 0.1, "optimizer": "AdamW (fused HIP kernel)",
-                       "captions": "ragged, lengths U{8..L}" + ("; the padded token rows of the text tower are not computed (same loss and "
-                                   "gradients as computing them: SIMSEG_AMD_PACKED_TEXT=0)" if os.environ.get("SIMSEG_AMD_PACKED_TEXT", "1") != "0" else "; padded token rows computed")},
             "roofline": {"bound": "mfma", "kernel": f"{kdesc} <{dom}>",
                          "achieved": round(achieved, 2), "peak": PEAK_BF16 / 1e12, "unit": "TFLOP/s",
                          "frac": round(achieved * 1e12 / PEAK_BF16, 4), "traffic": traffic, "traffic_source": traffic_src,
@@ -1250,7 +1314,7 @@ def main():
             "seg_eval": seg,
             "retrieval_eval": retr,
             "cpu_baseline": cpu,
-        }
+        })
         sys.stdout.flush()
         os.write(_JSON_FD, (json.dumps(out) + "\n").encode())
     if dist.is_initialized():

@@ -2,6 +2,7 @@
 in the build container.  TEST INFRASTRUCTURE -- never imported by the product.
 
     python oracle/make_golden.py            # rewrites every fixture (deterministic seeds)
+    python oracle/make_golden.py --check    # regenerates them elsewhere and compares with tests/golden/ bit for bit
 
 What is pinned here (and what is not) is listed in oracle/simseg_ref.py's header.  The reference's
 Python never travels to the GPU box; only the .npz inputs/outputs written here do.
@@ -260,6 +261,29 @@ def gold_config():
     print("wrote config.json", errs)
 
 
+def gold_tool_imports():
+    """The `simseg.*` names the reference's evaluation tools import (tools/seg_evaluation.py:19-28, tools/retrieval_evaluation.py:13-22),
+    read from their syntax trees: module -> imported names (JSON; `import simseg.x` is recorded as module simseg.x with no names)."""
+    import ast
+    import json
+    out = {}
+    for tool in ("seg_evaluation", "retrieval_evaluation"):
+        tree = ast.parse(open(os.path.join(REF, "tools", tool + ".py")).read())
+        mods = {}
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ImportFrom) and node.level == 0 and (node.module or "").split(".")[0] == "simseg":
+                mods.setdefault(node.module, []).extend(a.name for a in node.names)
+            elif isinstance(node, ast.Import):
+                for a in node.names:
+                    if a.name.split(".")[0] == "simseg":
+                        mods.setdefault(a.name, [])
+        out[f"tools/{tool}.py"] = {m: sorted(set(v)) for m, v in sorted(mods.items())}
+    os.makedirs(GOLD, exist_ok=True)
+    with open(os.path.join(GOLD, "reference_tool_imports.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+    print("wrote reference_tool_imports.json")
+
+
 # ---------------------------------------------------------------------------------------------
 TINY_ARGV = ["transforms.input_size=96", "model.image_encoder.tag=vit_test_patch16",
              "model.image_encoder.embedding_dim=128", "model.image_encoder.pretrained=False",
@@ -415,8 +439,36 @@ def gold_dist(world, group_size=None):
     _save(f"clip_train_ws{world}" + (f"g{group_size}" if group_size and group_size != world else ""), **flat)
 
 
+def check():
+    """Every committed fixture under tests/golden/ is what this recipe writes today, bit for bit (the recipe runs in a child process that
+    writes into a temporary directory)."""
+    import json
+    import subprocess
+    import tempfile
+    gold = os.path.join(REPO, "tests", "golden")
+    with tempfile.TemporaryDirectory() as tmp:
+        env = dict(os.environ, SIMSEG_GOLDEN_OUT=tmp, PYTHONPATH="")
+        r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+        names = sorted(f for f in os.listdir(gold) if f.endswith((".npz", ".json")))
+        assert sorted(os.listdir(tmp)) == names, (sorted(os.listdir(tmp)), names)
+        for f in names:
+            if f.endswith(".json"):
+                assert json.load(open(os.path.join(tmp, f))) == json.load(open(os.path.join(gold, f))), f
+                continue
+            new, old = np.load(os.path.join(tmp, f)), np.load(os.path.join(gold, f))
+            assert set(new.files) == set(old.files), f
+            for k in old.files:
+                assert new[k].dtype == old[k].dtype and new[k].shape == old[k].shape, (f, k)
+                assert np.array_equal(new[k], old[k], equal_nan=True), (f, k)
+    print(f"{len(names)} fixtures reproduced bit for bit")
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["config", "heads", "retrieval", "miou", "interp_pe", "seg_block", "bert", "vit", "clip_glue", "dist1", "dist2", "dist4", "dist4g2"]
+    if sys.argv[1:] == ["--check"]:
+        check()
+        sys.exit(0)
+    which = sys.argv[1:] or ["config", "tool_imports", "heads", "retrieval", "miou", "interp_pe", "seg_block", "bert", "vit", "clip_glue", "dist1", "dist2", "dist4", "dist4g2"]
     torch.set_num_threads(4)
     _import_reference()
     for w in which:

@@ -2,6 +2,7 @@
 reduce-scatter-equivalent backward), group construction and the plain gather helpers.  The loss arithmetic between the
 collectives is the oracle's here (the HIP loss kernel needs a GPU); what is pinned is the exchange step, against the
 gradients the REFERENCE's GatherLayer + NCE produced in a 2-process run (tests/golden/clip_train_ws2.npz)."""
+import copy
 import os
 import socket
 
@@ -66,10 +67,14 @@ def _worker(rank, world, port, q):
     torch.manual_seed(0)
     lin = torch.nn.Sequential(torch.nn.Linear(4, 3), torch.nn.Linear(3, 2))
     lin[1].bias.requires_grad_(False)
-    sync = GradSync(lin.parameters())
     x = torch.full((5, 4), float(rank + 1))
+    # this rank's own gradients from a twin without the exchange: with overlap (the default) a bucket's all-reduce is started by the
+    # hooks inside the backward and runs in place on .grad, so a copy of lin's gradients taken after backward() may already be partly reduced
+    twin = copy.deepcopy(lin)
+    twin(x).square().sum().backward()
+    local = [p.grad.clone() for p in twin.parameters() if p.requires_grad]
+    sync = GradSync(lin.parameters())
     lin(x).square().sum().backward()
-    local = [p.grad.clone() for p in lin.parameters() if p.requires_grad]
     sync()
     res["gsync"] = ([g_.tolist() for g_ in local], [p.grad.tolist() for p in lin.parameters() if p.requires_grad],
                     all(p.grad.data_ptr() == v.data_ptr() for p, v in zip(sync.params, sync.views)))

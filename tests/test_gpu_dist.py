@@ -382,7 +382,7 @@ def test_bench_self_launches_two_ranks_on_rccl():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--pairs-per-gpu", "64",
-                          "--no-seg", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                          "--no-seg", "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])
     pg = line["config"]["process_group"]
@@ -421,7 +421,7 @@ def test_bench_comm_roofline_on_one_rank_rccl_group():
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", SIMSEG_FORCE_COLLECTIVES="1", SIMSEG_BENCH_FORCE_SYNC="1", SIMSEG_BENCH_OTHER_DTYPE_LEG="0",
                SIMSEG_BENCH_GELU16_LEG="0", SIMSEG_AMD_PACKED_TEXT="1")
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "2", "--pairs-per-gpu", "64", "--no-seg",
-                          "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                          "--no-cpu-baseline", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = out.stdout.strip().splitlines()
     assert len(lines) == 1, lines
@@ -442,7 +442,8 @@ def test_bench_two_ranks_gloo_bringup_reports_comm_roofline():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", SIMSEG_DIST_BACKEND="gloo", SIMSEG_BENCH_DEVICE="0", SIMSEG_BENCH_OTHER_DTYPE_LEG="0",
                SIMSEG_BENCH_GELU16_LEG="0")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs-per-gpu", "32", "--no-seg", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--pairs-per-gpu", "32", "--no-seg", "--no-cpu-baseline",
+           "--full"]
     bad = subprocess.run(cmd, env=dict(env, SIMSEG_BENCH_SABOTAGE_PREFLIGHT="1"), capture_output=True, text=True, timeout=300)
     assert bad.returncode != 0
     err = json.loads(bad.stdout.strip().splitlines()[-1])

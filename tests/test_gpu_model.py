@@ -699,3 +699,30 @@ def test_text_tower_update_on_its_own_stream_matches_single_launch(golden, monke
     assert all(np.isfinite(l1)) and max(abs(a - b) for a, b in zip(l0, l1)) < 2e-3 * max(abs(x) for x in l0), (l0, l1)
     worst = max(float((runs[False][1][n] - runs[True][1][n]).abs().max() / (runs[False][1][n].abs().max() + 1e-12)) for n in runs[False][1])
     assert worst < 5e-2, worst
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`python bench.py --gpus 1 --steps K --warmup W` without --full: set-up, warm-up, K timed steps and one JSON line carrying the headline
+    keys only (no secondary leg ran); --dump-outputs DIR writes what the last timed step computed - loss, accuracies, a seeded sample of the
+    updated parameters and their gradients - as float .npy files."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--pairs-per-gpu", "32",
+                          "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    lines = out.stdout.strip().splitlines()
+    assert len(lines) == 1, lines
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False and line["dtype"] == "fp16" and line["unit"] == "pairs/s"
+    assert line["higher_is_better"] is True and line["value"] > 0
+    assert abs(line["value"] - 32 * 3 / (line["ms_per_step"] * 3 / 1e3)) < 1e-2 * line["value"]
+    assert not {"roofline", "step_model", "seg_eval", "retrieval_eval", "cpu_baseline"} & set(line)
+    assert line["amp"]["steps"] == 3
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == {"nce_loss", "i2t_acc", "t2i_acc", "params_sample", "grads_sample"}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in got.values())
+    assert abs(float(got["nce_loss"]) - line["final_loss"]) < 1e-4
+    assert got["params_sample"].shape == got["grads_sample"].shape and 1e5 < got["params_sample"].size < 4e6
+    assert np.abs(got["grads_sample"]).max() > 0

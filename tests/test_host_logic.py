@@ -159,12 +159,13 @@ def test_lr_schedules_match_reference_formulas():
     assert lr_multiplier("cosine_schedule_with_warmup", 1000, num_warmup_steps=0, num_training_steps=1000) == 0.0
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/tools"), reason="reference checkout not present (GPU box)")
 def test_reference_tools_import_against_this_package(monkeypatch):
     """Every `simseg.*` name the reference's unmodified eval tools import resolves to this repo's package
-    (tools/seg_evaluation.py:19-28, tools/retrieval_evaluation.py:13-22).  cv2 / pydensecrf are third-party CPU
-    post-processing libraries absent from the image: stubbed, never called."""
-    import importlib.util
+    (tools/seg_evaluation.py:19-28, tools/retrieval_evaluation.py:13-22; the names are recorded in tests/golden/reference_tool_imports.json
+    by oracle/make_golden.py).  cv2 / pydensecrf, which the tools import beside them, are third-party CPU post-processing libraries absent
+    from the image: stubbed, never called."""
+    import importlib
+    import json
     import sys
     import types
     for name in ("cv2", "pydensecrf", "pydensecrf.densecrf"):
@@ -173,11 +174,16 @@ def test_reference_tools_import_against_this_package(monkeypatch):
     sys.modules["pydensecrf"].densecrf = sys.modules["pydensecrf.densecrf"]
     import simseg
     assert simseg.__file__.startswith(REPO)
-    for tool in ("seg_evaluation", "retrieval_evaluation"):
-        spec = importlib.util.spec_from_file_location(f"_ref_tool_{tool}", f"/root/reference/tools/{tool}.py")
-        mod = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(mod)              # runs the tool's imports and definitions, not its main()
-        assert hasattr(mod, "evaluate_benchmark") and hasattr(mod, "main")
+    with open(os.path.join(REPO, "tests", "golden", "reference_tool_imports.json")) as f:
+        tools = json.load(f)
+    assert set(tools) == {"tools/seg_evaluation.py", "tools/retrieval_evaluation.py"}
+    for tool, mods in tools.items():
+        assert "simseg.models" in mods and "simseg.core" in mods, tool
+        for mod_name, names in mods.items():
+            mod = importlib.import_module(mod_name)
+            assert os.path.abspath(mod.__file__).startswith(REPO), (tool, mod_name, mod.__file__)
+            missing = [n for n in names if not hasattr(mod, n)]
+            assert not missing, (tool, mod_name, missing)
     assert sys.modules["simseg.models"].__file__.startswith(REPO)
 
 
@@ -399,26 +405,29 @@ def test_gradsync_zero_copy_target_is_handed_out_once_and_only_without_a_gradien
 
 
 def test_bench_self_launch_builds_the_torchrun_command(monkeypatch):
-    """`python bench.py --gpus N` outside a launcher re-executes itself as `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
-    --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>` (the reference's launch.py:33-70); round 4's bench.py asserted
-    WORLD_SIZE == --gpus instead, the first thing an 8-GPU `python bench.py --gpus 8` would have hit."""
+    """`python bench.py --gpus N` outside a launcher runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N
+    --master-addr 127.0.0.1 --master-port <free> bench.py <same arguments>` as a child process and exits with its status (the reference's
+    launch.py:33-70); round 4's bench.py asserted WORLD_SIZE == --gpus instead, the first thing an 8-GPU `python bench.py --gpus 8` would
+    have hit."""
     import importlib.util
+    import subprocess
     import sys
     spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(REPO, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
     seen = {}
 
-    def fake_exec(file, argv, env):
-        seen.update(file=file, argv=argv, env=env)
-        raise SystemExit(0)
+    def fake_call(argv, env):
+        seen.update(argv=argv, env=env)
+        return 0
 
-    monkeypatch.setattr(os, "execvpe", fake_exec)
+    monkeypatch.setattr(subprocess, "call", fake_call)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "4", "--steps", "7", "--warmup", "2"])
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     monkeypatch.setenv("SIMSEG_BENCH_DEVICE", "0")           # (no GPU in the build container: skip the visible-device check)
-    with pytest.raises(SystemExit):
+    with pytest.raises(SystemExit) as ended:
         bench.main()
+    assert ended.value.code == 0                              # the launcher's exit status
     a = seen["argv"]
     assert a[:3] == [sys.executable, "-m", "torch.distributed.run"] and "--nnodes=1" in a and "--nproc-per-node=4" in a
     assert a[a.index("--master-addr") + 1] == "127.0.0.1" and int(a[a.index("--master-port") + 1]) > 0

@@ -1,5 +1,5 @@
 # CU partition experiment: weight-gradient GEMMs on a side stream with a capped block count, persistent GEMMs leaving CUs free
-run() { python bench.py --steps 12 --warmup 4 --no-seg --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys;d=json.loads(sys.stdin.read());print('$1',d['ms_per_step'], d['step_model']['final_loss'])"; }
+run() { python bench.py --full --steps 12 --warmup 4 --no-seg --no-cpu-baseline 2>/dev/null | tail -1 | python -c "import json,sys;d=json.loads(sys.stdin.read());print('$1',d['ms_per_step'], d['step_model']['final_loss'])"; }
 export SIMSEG_BENCH_FP16=0
 run base
 SIMSEG_AMD_WGRAD_STREAM=1 run wgstream

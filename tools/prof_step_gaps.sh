@@ -6,7 +6,7 @@ tag=${1:-r4}
 R=$GRAFT_REPO_ROOT
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/prof_g
-SIMSEG_BENCH_FP16=0 timeout 400 rocprofv3 --kernel-trace -d /tmp/prof_g -o g -- python $R/bench.py --steps 6 --warmup 3 --no-seg --no-cpu-baseline > /tmp/prof_g.log 2>/tmp/prof_g.err
+SIMSEG_BENCH_FP16=0 timeout 400 rocprofv3 --kernel-trace -d /tmp/prof_g -o g -- python $R/bench.py --full --steps 6 --warmup 3 --no-seg --no-cpu-baseline > /tmp/prof_g.log 2>/tmp/prof_g.err
 db=$(find /tmp/prof_g -name "*.db" 2>/dev/null | head -1)
 { echo "# rocprofv3 --kernel-trace -- python bench.py --steps 6 --warmup 3 --no-seg --no-cpu-baseline   (default schedule: two tower streams; tools/rocpd_step_gaps.py, gaps >= 20 us listed)";
   echo "# ms_per_step of this traced run: $(python -c "import json,sys; print(json.loads(open('/tmp/prof_g.log').read().strip().splitlines()[-1])['ms_per_step'])" 2>/dev/null)";
