@@ -306,6 +306,23 @@ int simseg_seg_masks_rect(const float* sim, const int* cand_idx, float* prob, vo
  * nh = n + (wy-1)*step, nw = n + (wx-1)*step: per cell the mean over the covering windows, summed in (i, j) order.  step = 0: the plain
  * mean over all windows (with n = 1: image-level class scores from per-window scores). */
 int simseg_stitch_windows(const float* win, float* out, int64_t B, int64_t wy, int64_t wx, int64_t n, int64_t step, int64_t C, void* stream);
+/* Sliding windows over B images of ANY sizes (segpost.slide_windows, DESIGN.md "Sliding windows on any image size").  Tables (device,
+ * built by simseg_amd.ops.slide_plan): img_tab int64 [B, 8] = (src_off, H, W, out_off, wstart, ny, nx, 0) per image - element offset of
+ * its [3, H, W] pixels in `images`, its extent, element offset (a multiple of 16) of its [ncand, H, W] planes in prob / mask, its first
+ * window and its window grid; win_tab int64 [Nw, 3] = (image, y0, x0) per window, an image's windows consecutive and row-major.
+ * extract: out [Nw, 3, win, win] fp32 = the windows of win_tab, zero where a window runs past the image. */
+int simseg_slide_extract(const float* images, const int64_t* img_tab, const int64_t* win_tab, float* out, int64_t Nw, int64_t win, void* stream);
+/* out [B, C] = per image, the fp32 sum of its windows' rows of win_scores [Nw, C] in window order, divided once by their count. */
+int simseg_slide_scores(const float* win_scores, const int64_t* img_tab, float* out, int64_t B, int64_t C, void* stream);
+/* For every visited slot (cand_idx [B, ncand] >= 0) of every image: the pixel-resolution stitch of sim_w [Nw, n*n, C] fp32 (pixel (y, x)
+ * = the mean over its covering windows, summed in window order, of their cell ((y - y0) / 16, (x - x0) / 16)), min-max normalised over the
+ * image -> prob (fp32) and mask (uint8 0 / 255, prob > 0.5) at out_off + k*H*W; minmax [B, ncand, 2] = the stitched map's min and max.
+ * Unvisited slots are not written.  max_h / max_w / max_hw: the largest H, W and H*W over the images; workspace: fp32, of
+ * simseg_slide_stitch_workspace_bytes(B, ncand, max_h, max_w) bytes.  No limit on the number of patches of an image. */
+int64_t simseg_slide_stitch_workspace_bytes(int64_t B, int64_t ncand, int64_t max_h, int64_t max_w);
+int simseg_slide_stitch(const float* sim_w, const int64_t* img_tab, const int64_t* win_tab, const int* cand_idx, float* prob, void* mask,
+                        float* minmax, float* workspace, int64_t B, int64_t ncand, int64_t n, int64_t C, int64_t win, int64_t max_h,
+                        int64_t max_w, int64_t max_hw, void* stream);
 /* cv2.dilate / cv2.erode with a 7x7 ones kernel, ONE iteration (the third positional argument in :156-157 is `dst`, not
  * `iterations`), default border (never wins) on byte images [M,H,W]; erode = 0 dilate, 1 erode.  out must not alias in. */
 int simseg_morph7(const void* in, void* out, int64_t M, int64_t H, int64_t W, int erode, void* stream);

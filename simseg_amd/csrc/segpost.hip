@@ -332,6 +332,224 @@ __global__ __launch_bounds__(256) void seg_predict_kernel(const unsigned char* _
         if (lh[i]) atomicAdd(&hist[i], (unsigned long long)lh[i]);
 }
 
+// ---- sliding windows over images of any size (segpost.slide_windows; DESIGN.md "Sliding windows on any image size") -----------------
+// Tables shared by the three kernels below (built on the host by ops.slide_plan):
+//   img_tab int64 [B, SLIDE_IT]: src_off (element offset of image b in the packed fp32 [3, H, W] images), H, W, out_off (element offset of
+//     image b's [ncand, H, W] planes in the stitched outputs, a multiple of 16), wstart (its first window), ny, nx (its window grid), 0
+//   win_tab int64 [Nw, 3]: image, y0, x0 - an image's windows consecutive, row-major over its grid, y0 / x0 strictly increasing.
+constexpr int SLIDE_IT = 8;
+
+// K21 extract: out [Nw, 3, win, win] fp32 = the window cut from its image, zero where it runs past the bottom / right border.  One float4
+// store per thread and step (win is a multiple of 16: every output row is 64-byte aligned); source rows are unaligned when x0 % 4 != 0,
+// so the load is one float4 only where the four source floats are aligned and inside the row, else four scalar loads.
+__global__ __launch_bounds__(256) void slide_extract_kernel(const float* __restrict__ src, const int64_t* __restrict__ img_tab,
+                                                            const int64_t* __restrict__ win_tab, float* __restrict__ out, long n4, int win) {
+    const int q = win >> 2;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n4; e += (long)gridDim.x * 256) {
+        const int c4 = (int)(e % q);
+        long r = e / q;
+        const int row = (int)(r % win); r /= win;
+        const int ch = (int)(r % 3);
+        const long w = r / 3;
+        const int64_t* wt = win_tab + w * 3;
+        const int64_t* it = img_tab + wt[0] * SLIDE_IT;
+        const long H = it[1], W = it[2];
+        const long y = wt[1] + row, x = wt[2] + 4 * c4;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (y < H) {
+            const long s = it[0] + (ch * H + y) * W + x;
+            if (x + 3 < W && (s & 3) == 0) {
+                v = *reinterpret_cast<const f32x4*>(src + s);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (x + k < W) v[k] = src[s + k];
+            }
+        }
+        *reinterpret_cast<f32x4*>(out + e * 4) = v;
+    }
+}
+
+// K22 scores: out [B, C] = the fp32 sum of the image's window score rows in window order, divided once by the window count (the order
+// of simseg_stitch_windows with n = 1, step = 0).  One thread per (image, class).
+__global__ __launch_bounds__(256) void slide_scores_kernel(const float* __restrict__ sc, const int64_t* __restrict__ img_tab, float* __restrict__ out,
+                                                           int B, int C) {
+    const long e = (long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (long)B * C) return;
+    const int b = (int)(e / C), c = (int)(e % C);
+    const int64_t* it = img_tab + (long)b * SLIDE_IT;
+    const long w0 = it[4], nwin = it[5] * it[6];
+    float acc = 0.f;
+    for (long w = 0; w < nwin; ++w) acc += sc[(w0 + w) * C + c];
+    out[e] = acc / (float)nwin;
+}
+
+// K23 stitch, pass 1: one block per (64 x 64 pixel tile, candidate slot, image); visited slots only.  Each pixel (y, x) sums sim_w[w, cell, c]
+// over the windows w that cover it, in window order, cell = ((y - y0) / 16, (x - x0) / 16), and divides once by their count.  A window's
+// candidate column is n*n floats at a stride of C; the tile needs at most 5 x 5 of its cells, gathered ONCE per block into LDS (chunks of
+// ST_WCH windows, in window order), so every pixel reads at most ceil(win / stride)^2 LDS values.  The stitched value goes to `prob` (pass 3
+// normalises it in place) and the tile's min / max to `partial`.  Thread t owns columns 4 (t % 16) .. +3 of rows t / 16 + 16 r, r < 4.
+constexpr int ST_T = 64, ST_CELLS = ST_T / 16 + 1, ST_WCH = 16;
+__global__ __launch_bounds__(256) void slide_stitch_kernel(const float* __restrict__ sim, const int64_t* __restrict__ img_tab,
+                                                           const int64_t* __restrict__ win_tab, const int* __restrict__ cand_idx, int K, int C,
+                                                           int win, int n, int tiles_max, float* __restrict__ prob, float* __restrict__ partial) {
+    __shared__ float vals[ST_WCH][ST_CELLS][ST_CELLS];
+    __shared__ int meta[ST_WCH][4];                // y0, x0, first cell row, first cell column
+    __shared__ int range[4];                       // window rows i0..i1, columns j0..j1 touching the tile
+    __shared__ float red[2][4];
+    const int t = blockIdx.x, k = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
+    const int idx = cand_idx[b * K + k];
+    if (idx < 0) return;
+    const int64_t* it = img_tab + (long)b * SLIDE_IT;
+    const int H = (int)it[1], W = (int)it[2], ny = (int)it[5], nx = (int)it[6];
+    const long wstart = it[4];
+    const int tw = (W + ST_T - 1) / ST_T, th = (H + ST_T - 1) / ST_T;
+    if (t >= tw * th) return;
+    const int ty0 = (t / tw) * ST_T, tx0 = (t % tw) * ST_T;
+    const int ty1 = min(ty0 + ST_T, H), tx1 = min(tx0 + ST_T, W);
+    if (tid == 0) { range[0] = 0x7fffffff; range[1] = -1; range[2] = 0x7fffffff; range[3] = -1; }
+    __syncthreads();
+    for (int i = tid; i < ny; i += 256) {
+        const int y0 = (int)win_tab[(wstart + (long)i * nx) * 3 + 1];
+        if (y0 < ty1 && y0 + win > ty0) { atomicMin(&range[0], i); atomicMax(&range[1], i); }
+    }
+    for (int j = tid; j < nx; j += 256) {
+        const int x0 = (int)win_tab[(wstart + j) * 3 + 2];
+        if (x0 < tx1 && x0 + win > tx0) { atomicMin(&range[2], j); atomicMax(&range[3], j); }
+    }
+    __syncthreads();
+    const int i0 = range[0], nj = range[3] - range[2] + 1, j0 = range[2];
+    const int nwin = (range[1] - i0 + 1) * nj;
+    const int lx = 4 * (tid & 15), ly = tid >> 4;
+    float acc[4][4];
+    int cnt[4][4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { acc[r][q] = 0.f; cnt[r][q] = 0; }
+    const long nn = (long)n * n;
+    for (int c0 = 0; c0 < nwin; c0 += ST_WCH) {
+        const int m = min(ST_WCH, nwin - c0);
+        if (tid < m) {
+            const int wl = c0 + tid;
+            const long w = wstart + (long)(i0 + wl / nj) * nx + (j0 + wl % nj);
+            const int y0 = (int)win_tab[w * 3 + 1], x0 = (int)win_tab[w * 3 + 2];
+            meta[tid][0] = y0; meta[tid][1] = x0;
+            meta[tid][2] = max(ty0 - y0, 0) >> 4; meta[tid][3] = max(tx0 - x0, 0) >> 4;
+        }
+        __syncthreads();
+        for (int e = tid; e < m * ST_CELLS * ST_CELLS; e += 256) {
+            const int wl = e / (ST_CELLS * ST_CELLS), cy = meta[wl][2] + (e / ST_CELLS) % ST_CELLS, cx = meta[wl][3] + e % ST_CELLS;
+            const long w = wstart + (long)(i0 + (c0 + wl) / nj) * nx + (j0 + (c0 + wl) % nj);
+            vals[wl][(e / ST_CELLS) % ST_CELLS][e % ST_CELLS] = (cy < n && cx < n) ? sim[(w * nn + (long)cy * n + cx) * C + idx] : 0.f;
+        }
+        __syncthreads();
+        for (int wl = 0; wl < m; ++wl) {
+            const int y0 = meta[wl][0], x0 = meta[wl][1], cy0 = meta[wl][2], cx0 = meta[wl][3];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int dy = ty0 + ly + 16 * r - y0;
+                if (dy < 0 || dy >= win) continue;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int dx = tx0 + lx + q - x0;
+                    if (dx < 0 || dx >= win) continue;
+                    acc[r][q] += vals[wl][(dy >> 4) - cy0][(dx >> 4) - cx0];
+                    cnt[r][q] += 1;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    float mn = INFINITY, mx = -INFINITY;
+    float* plane = prob + it[3] + (long)k * H * W;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int y = ty0 + ly + 16 * r, x = tx0 + lx;
+        if (y >= H || x >= W) continue;
+        f32x4 v;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            v[q] = acc[r][q] / (float)cnt[r][q];
+            if (x + q < W) { mn = fminf(mn, v[q]); mx = fmaxf(mx, v[q]); }
+        }
+        float* dst = plane + (long)y * W + x;
+        if (x + 3 < W && ((uintptr_t)dst & 15) == 0) {
+            *reinterpret_cast<f32x4*>(dst) = v;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (x + q < W) dst[q] = v[q];
+        }
+    }
+    mn = wave_min(mn); mx = wave_max(mx);
+    if ((tid & 63) == 0) { red[0][tid >> 6] = mn; red[1][tid >> 6] = mx; }
+    __syncthreads();
+    if (tid == 0) {
+        float* p = partial + (((long)b * K + k) * tiles_max + t) * 2;
+        p[0] = fminf(fminf(red[0][0], red[0][1]), fminf(red[0][2], red[0][3]));
+        p[1] = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+    }
+}
+
+// K23 pass 2: one block per (slot, image): the min / max of the stitched map over the image's H x W pixels from the tiles' partials.
+__global__ __launch_bounds__(256) void slide_minmax_kernel(const int64_t* __restrict__ img_tab, const int* __restrict__ cand_idx, int K, int tiles_max,
+                                                           const float* __restrict__ partial, float* __restrict__ minmax) {
+    __shared__ float red[2][4];
+    const int k = blockIdx.x, b = blockIdx.y, tid = threadIdx.x;
+    if (cand_idx[b * K + k] < 0) return;
+    const int64_t* it = img_tab + (long)b * SLIDE_IT;
+    const int tiles = (int)(((it[1] + ST_T - 1) / ST_T) * ((it[2] + ST_T - 1) / ST_T));
+    const float* p = partial + ((long)b * K + k) * tiles_max * 2;
+    float mn = INFINITY, mx = -INFINITY;
+    for (int i = tid; i < tiles; i += 256) { mn = fminf(mn, p[2 * i]); mx = fmaxf(mx, p[2 * i + 1]); }
+    mn = wave_min(mn); mx = wave_max(mx);
+    if ((tid & 63) == 0) { red[0][tid >> 6] = mn; red[1][tid >> 6] = mx; }
+    __syncthreads();
+    if (tid == 0) {
+        minmax[((long)b * K + k) * 2] = fminf(fminf(red[0][0], red[0][1]), fminf(red[0][2], red[0][3]));
+        minmax[((long)b * K + k) * 2 + 1] = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+    }
+}
+
+// K23 pass 3: prob = (S - min) / (max - min) in place (a constant map gives 0/0 = NaN, never > 0.5, as seg_mask_kernel), mask = prob > 0.5
+// ? 255 : 0.  A thread takes 16 elements at a 16-aligned flat position: four float4 loads / stores and one 16-byte mask store inside the
+// plane (planes start at multiples of 16 elements only per image, so a plane's first and last chunks may be partial: element by element).
+__global__ __launch_bounds__(256) void slide_norm_kernel(const int64_t* __restrict__ img_tab, const int* __restrict__ cand_idx, int K,
+                                                         const float* __restrict__ minmax, float* __restrict__ prob, unsigned char* __restrict__ mask) {
+    const int k = blockIdx.y, b = blockIdx.z;
+    if (cand_idx[b * K + k] < 0) return;
+    const int64_t* it = img_tab + (long)b * SLIDE_IT;
+    const long HW = it[1] * it[2];
+    const long p0 = it[3] + (long)k * HW, p1 = p0 + HW;
+    const float mn = minmax[((long)b * K + k) * 2], range = minmax[((long)b * K + k) * 2 + 1] - mn;
+    for (long a = (p0 & ~15L) + 16 * ((long)blockIdx.x * 256 + threadIdx.x); a < p1; a += 16L * gridDim.x * 256) {
+        if (a >= p0 && a + 16 <= p1) {
+            unsigned int mw[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                f32x4 v = *reinterpret_cast<const f32x4*>(prob + a + 4 * g);
+                unsigned int bits = 0;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    v[q] = (v[q] - mn) / range;
+                    bits |= (v[q] > 0.5f ? 0xffu : 0u) << (8 * q);
+                }
+                *reinterpret_cast<f32x4*>(prob + a + 4 * g) = v;
+                mw[g] = bits;
+            }
+            u32x4 m4 = {mw[0], mw[1], mw[2], mw[3]};
+            *reinterpret_cast<u32x4*>(mask + a) = m4;
+        } else {
+            for (long e = max(a, p0); e < min(a + 16, p1); ++e) {
+                const float pr = (prob[e] - mn) / range;
+                prob[e] = pr;
+                mask[e] = pr > 0.5f ? 255 : 0;
+            }
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" int simseg_seg_select(const float* scores, int* cand_idx, float* cand_score, float* threshold, int64_t B, int64_t C,
@@ -412,5 +630,58 @@ extern "C" int simseg_seg_predict(const void* masks, const int* cand_idx, const 
                        static_cast<const unsigned char*>(masks), cand_idx, cand_score, static_cast<const unsigned char*>(labels), (int)ncand,
                        (int)Hm, (int)Wm, (int)H, (int)W, (int)C, (int)ignore_index, pred, static_cast<unsigned long long*>(hist));
     SS_LAUNCH_CHECK("seg_predict");
+    return 0;
+}
+
+extern "C" int simseg_slide_extract(const float* images, const int64_t* img_tab, const int64_t* win_tab, float* out, int64_t Nw, int64_t win,
+                                    void* stream) {
+    SS_CHECK(images && img_tab && win_tab && out, "slide_extract: null pointer");
+    SS_CHECK(Nw > 0 && win > 0 && win % 16 == 0, "slide_extract: Nw > 0 and win a positive multiple of 16");
+    SS_CHECK(((uintptr_t)out % 16) == 0, "slide_extract: out must be 16-byte aligned");
+    const long n4 = (long)Nw * 3 * win * win / 4;
+    long blocks = (n4 + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(slide_extract_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, images, img_tab, win_tab, out, n4, (int)win);
+    SS_LAUNCH_CHECK("slide_extract");
+    return 0;
+}
+
+extern "C" int simseg_slide_scores(const float* win_scores, const int64_t* img_tab, float* out, int64_t B, int64_t C, void* stream) {
+    SS_CHECK(win_scores && img_tab && out, "slide_scores: null pointer");
+    SS_CHECK(B > 0 && C > 0 && B * C < (1ll << 31), "slide_scores: bad shape");
+    hipLaunchKernelGGL(slide_scores_kernel, dim3((unsigned)((B * C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, win_scores, img_tab, out, (int)B,
+                       (int)C);
+    SS_LAUNCH_CHECK("slide_scores");
+    return 0;
+}
+
+extern "C" int64_t simseg_slide_stitch_workspace_bytes(int64_t B, int64_t ncand, int64_t max_h, int64_t max_w) {
+    if (B <= 0 || ncand <= 0 || max_h <= 0 || max_w <= 0) return -1;
+    return B * ncand * ((max_h + ST_T - 1) / ST_T) * ((max_w + ST_T - 1) / ST_T) * 2 * (int64_t)sizeof(float);
+}
+
+extern "C" int simseg_slide_stitch(const float* sim_w, const int64_t* img_tab, const int64_t* win_tab, const int* cand_idx, float* prob, void* mask,
+                                   float* minmax, float* workspace, int64_t B, int64_t ncand, int64_t n, int64_t C, int64_t win, int64_t max_h,
+                                   int64_t max_w, int64_t max_hw, void* stream) {
+    SS_CHECK(sim_w && img_tab && win_tab && cand_idx && prob && mask && minmax && workspace, "slide_stitch: null pointer");
+    SS_CHECK(B > 0 && B < 65536 && ncand >= 1 && ncand <= 8 && C > 0 && win > 0 && win % 16 == 0 && n == win / 16,
+             "slide_stitch: bad shape (n = win / 16, 1 <= ncand <= 8)");
+    SS_CHECK(max_h > 0 && max_w > 0 && max_h < (1 << 20) && max_w < (1 << 20) && max_hw >= 1 && max_hw <= max_h * max_w,
+             "slide_stitch: bad image extents");
+    SS_CHECK(((uintptr_t)prob % 16) == 0 && ((uintptr_t)mask % 16) == 0, "slide_stitch: prob and mask must be 16-byte aligned");
+    const long tiles = ((max_h + ST_T - 1) / ST_T) * ((max_w + ST_T - 1) / ST_T);
+    SS_CHECK(tiles < (1l << 31), "slide_stitch: image too large");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(slide_stitch_kernel, dim3((unsigned)tiles, (unsigned)ncand, (unsigned)B), dim3(256), 0, s, sim_w, img_tab, win_tab, cand_idx,
+                       (int)ncand, (int)C, (int)win, (int)n, (int)tiles, prob, workspace);
+    SS_LAUNCH_CHECK("slide_stitch");
+    hipLaunchKernelGGL(slide_minmax_kernel, dim3((unsigned)ncand, (unsigned)B), dim3(256), 0, s, img_tab, cand_idx, (int)ncand, (int)tiles, workspace,
+                       minmax);
+    SS_LAUNCH_CHECK("slide_stitch (min / max)");
+    long blocks = (max_hw / 16 + 2 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(slide_norm_kernel, dim3((unsigned)blocks, (unsigned)ncand, (unsigned)B), dim3(256), 0, s, img_tab, cand_idx, (int)ncand, minmax,
+                       prob, static_cast<unsigned char*>(mask));
+    SS_LAUNCH_CHECK("slide_stitch (normalise)");
     return 0;
 }

@@ -629,3 +629,88 @@ def dense_crf(rgb, prob, sxy_g=3.0, compat_g=3.0, sxy_b=40.0, srgb=13.0, compat_
     if single:
         return mask[0], (q[0] if want_q else None)
     return mask, q
+
+
+# ---- sliding windows over images of any size (segpost.slide_windows; include/simseg_hip.h simseg_slide_*) ---------------------------------
+def slide_plan(sizes, win, stride, device, ncand=5):
+    """Host geometry + device tables of a sliding-window pass over images of sizes [(H, W), ...]: windows at segpost.slide_windows offsets,
+    an image's windows consecutive.  -> dict(img_tab int64 [B,8], win_tab int64 [Nw,3] (device), windows [(image, y0, x0)], src_off, out_off
+    (element offsets of each image in the packed [3,H,W] images and in the [ncand,H,W] stitched planes), out_numel, sizes, win, ncand)."""
+    from .segpost import slide_windows
+    it, wt, src_off, out_off = [], [], [], []
+    s = o = 0
+    for b, (H, W) in enumerate(sizes):
+        offs = slide_windows(H, W, win, stride)
+        ny = len({y for y, _ in offs})
+        nx = len(offs) // ny
+        it.append([s, H, W, o, len(wt), ny, nx, 0])
+        wt.extend([b, y, x] for y, x in offs)
+        src_off.append(s); out_off.append(o)
+        s += 3 * H * W
+        o += (ncand * H * W + 15) // 16 * 16            # planes of the next image start 16-aligned (16-byte mask stores)
+    dev = torch.device(device)
+    return {"img_tab": to_device_async(it, dev), "win_tab": to_device_async(wt, dev),
+            "windows": [tuple(w) for w in wt], "src_off": src_off, "out_off": out_off, "out_numel": max(o, 16), "src_numel": s,
+            "sizes": [(int(H), int(W)) for H, W in sizes], "win": int(win), "stride": int(stride), "ncand": int(ncand)}
+
+
+def to_device_async(rows, device, dtype=torch.int64):
+    """A small host table -> device tensor without a host wait: a copy from pageable memory makes the host wait for the stream's queued
+    work (which would stall the evaluation pipeline's next encoder behind this batch), one from pinned memory does not."""
+    t = torch.tensor(rows, dtype=dtype)
+    return t.pin_memory().to(device, non_blocking=True) if torch.device(device).type == "cuda" else t
+
+
+def slide_extract(images_flat, plan, start=0, count=None):
+    """images_flat: the images' [3,H,W] fp32 pixels packed at plan['src_off'] -> windows start .. start+count-1 as [count, 3, win, win]
+    (zero past an image's border)."""
+    require_gpu(images_flat)
+    if images_flat.dtype != torch.float32 or images_flat.numel() != plan["src_numel"]:
+        raise ValueError(f"slide_extract: {plan['src_numel']} packed fp32 pixels expected, got {images_flat.numel()} {images_flat.dtype}")
+    count = len(plan["windows"]) - start if count is None else count
+    if count <= 0 or start < 0 or start + count > len(plan["windows"]):
+        raise ValueError(f"slide_extract: windows {start}..{start + count - 1} of {len(plan['windows'])}")
+    win = plan["win"]
+    out = torch.empty(count, 3, win, win, device=images_flat.device, dtype=torch.float32)
+    call("simseg_slide_extract", ptr(_c(images_flat)), ptr(plan["img_tab"]), ptr(plan["win_tab"][start:]), ptr(out), count, win, stream())
+    return out
+
+
+def slide_scores(win_scores, plan):
+    """win_scores [Nw, C] fp32 -> [B, C]: per image the mean of its windows' rows (fp32 sum in window order, divided once)."""
+    require_gpu(win_scores)
+    Nw, C = win_scores.shape
+    if win_scores.dtype != torch.float32 or Nw != len(plan["windows"]):
+        raise ValueError(f"slide_scores: fp32 [{len(plan['windows'])}, C] expected, got {tuple(win_scores.shape)} {win_scores.dtype}")
+    B = len(plan["sizes"])
+    out = torch.empty(B, C, device=win_scores.device, dtype=torch.float32)
+    call("simseg_slide_scores", ptr(_c(win_scores)), ptr(plan["img_tab"]), ptr(out), B, C, stream())
+    return out
+
+
+def slide_stitch(sim_w, plan, cand_idx):
+    """sim_w [Nw, n*n, C] fp32 per-window maps, cand_idx [B, ncand] -> (prob fp32, mask uint8, minmax [B, ncand, 2]): prob / mask flat,
+    image b's [ncand, H, W] planes at plan['out_off'][b] (slide_planes() cuts the views); visited slots only (the others stay zero)."""
+    require_gpu(sim_w, cand_idx)
+    Nw, N, C = sim_w.shape
+    win, K, B = plan["win"], plan["ncand"], len(plan["sizes"])
+    n = win // 16
+    if sim_w.dtype != torch.float32 or Nw != len(plan["windows"]) or N != n * n or tuple(cand_idx.shape) != (B, K):
+        raise ValueError(f"slide_stitch: fp32 [{len(plan['windows'])}, {n * n}, C] maps and [{B}, {K}] candidates expected, "
+                         f"got {tuple(sim_w.shape)} {sim_w.dtype}, {tuple(cand_idx.shape)}")
+    dev = sim_w.device
+    max_h = max(h for h, _ in plan["sizes"]); max_w = max(w for _, w in plan["sizes"]); max_hw = max(h * w for h, w in plan["sizes"])
+    prob = torch.zeros(plan["out_numel"], device=dev, dtype=torch.float32)
+    mask = torch.zeros(plan["out_numel"], device=dev, dtype=torch.uint8)
+    minmax = torch.zeros(B, K, 2, device=dev, dtype=torch.float32)
+    ws = torch.empty(raw("simseg_slide_stitch_workspace_bytes", B, K, max_h, max_w) // 4, device=dev, dtype=torch.float32)
+    call("simseg_slide_stitch", ptr(_c(sim_w)), ptr(plan["img_tab"]), ptr(plan["win_tab"]), ptr(_c(cand_idx)), ptr(prob), ptr(mask), ptr(minmax),
+         ptr(ws), B, K, n, C, win, max_h, max_w, max_hw, stream())
+    return prob, mask, minmax
+
+
+def slide_planes(flat, plan, b):
+    """Image b's [ncand, H, W] view of a flat slide_stitch output."""
+    H, W = plan["sizes"][b]
+    o = plan["out_off"][b]
+    return flat[o:o + plan["ncand"] * H * W].view(plan["ncand"], H, W)

@@ -185,6 +185,125 @@ def encode_batch_sliding(model, image, text, top_cls_num, win=512, stride=256, c
     return st
 
 
+# ---- sliding windows on images of ANY size (DESIGN.md "Sliding windows on any image size") ----------------------------------------------
+# Real evaluation images (COCO-Stuff ~640x480 resized to a short side of 512 -> 683x512) are not tiled exactly by 512-pixel windows at
+# stride 256.  Windows are then placed as mmseg's slide_inference does (the last one flush with the border, one window at (0, 0) padded with
+# zeros past the border of an image smaller than the window), the per-window maps are stitched at PIXEL resolution (the windows' offsets
+# need not share a patch grid) and any number of images of different sizes go through the towers together.  Where window_grid() accepts
+# an image the result is bit-identical to encode_batch_sliding + finish_batch.
+
+def slide_windows(H, W, win=512, stride=256):
+    """-> [(y0, x0), ...] row-major: ny = max(H - win + stride - 1, 0) // stride + 1 rows at y0(i) = min(i * stride, max(H - win, 0)), the
+    same for x.  H, W any positive sizes; win and stride multiples of the 16-pixel patch with 0 < stride <= win."""
+    if win % 16 or stride % 16 or stride <= 0 or stride > win or win <= 0:
+        raise ValueError(f"slide_windows: win {win} and stride {stride} must be multiples of the 16-pixel patch with 0 < stride <= win")
+    if H <= 0 or W <= 0:
+        raise ValueError(f"slide_windows: a {H}x{W} image")
+
+    def axis(L):
+        return [min(i * stride, max(L - win, 0)) for i in range(max(L - win + stride - 1, 0) // stride + 1)]
+    return [(y, x) for y in axis(H) for x in axis(W)]
+
+
+def encode_images_sliding(model, images, text, top_cls_num, win=512, stride=256, crf=True, mean=None, std=None, sim_dtype=None, window_batch=None):
+    """encode_batch_sliding() for images of any sizes: images = a list of [3, H_i, W_i] normalised fp32 tensors (or one [B,3,H,W] tensor).
+    All windows of all images (slide_windows offsets, ops.slide_extract) go through the towers together, at most `window_batch` per call;
+    image scores = the mean of an image's window scores (ops.slide_scores) -> candidate selection -> per visited slot the pixel-resolution
+    stitched map, min-max normalised, and its binary map (ops.slide_stitch).  Device work only (no host read).  finish_sliding() ends it."""
+    from .heads import patch_text_similarity
+    if torch.is_tensor(images):
+        B, _, H, W = images.shape
+        sizes, flat, groups = [(H, W)] * B, images.contiguous().reshape(-1), {(H, W): (list(range(B)), images)}
+    else:
+        images = [im.contiguous() for im in images]
+        sizes = [(im.shape[1], im.shape[2]) for im in images]
+        flat = images[0].reshape(-1) if len(images) == 1 else torch.cat([im.reshape(-1) for im in images])
+        groups = {}
+        for b, hw in enumerate(sizes):
+            groups.setdefault(hw, ([], None))[0].append(b)
+        groups = {hw: (bs, images[bs[0]][None] if len(bs) == 1 else torch.stack([images[b] for b in bs])) for hw, (bs, _) in groups.items()}
+    plan = ops.slide_plan(sizes, win, stride, flat.device)
+    Nw = len(plan["windows"])
+    wb = window_batch or Nw
+    sims, scores = [], []
+    for s in range(0, Nw, wb):
+        wins = ops.slide_extract(flat, plan, s, min(wb, Nw - s))
+        feats = model.forward_image_feature(wins)                     # [b, n*n, D]
+        pooled = model.forward_image_project(feats)                   # [b, 512]
+        sims.append(patch_text_similarity(model.image_projection(feats), text, compute_dtype=sim_dtype))
+        scores.append(ops.gemm(pooled.float(), text))
+    sim_w = sims[0] if len(sims) == 1 else torch.cat(sims)
+    sc_w = scores[0] if len(scores) == 1 else torch.cat(scores)
+    sc = ops.slide_scores(sc_w.float().contiguous(), plan)
+    cand_idx, cand_score, thr = ops.seg_select(sc, top_cls_num, plan["ncand"])
+    prob, masks, minmax = ops.slide_stitch(sim_w.float().contiguous(), plan, cand_idx)
+    raw = None
+    if crf:
+        # the de-normalised source images (tools/seg_evaluation.py:104), one [g, H, W, 3] tensor per image size
+        raw = {hw: (bs, (((x * std) + mean) * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()) for hw, (bs, x) in groups.items()}
+    return {"cand_idx": cand_idx, "cand_score": cand_score, "threshold": thr, "scores": sc, "prob": prob, "masks": masks, "minmax": minmax,
+            "plan": plan, "images_u8": raw, "num_classes": sim_w.shape[2]}
+
+
+def _crf_cached_size(device):
+    """(H, W) of the spatial lattice ops.dense_crf holds for the current stream, or None."""
+    sig = ops._CRF_SPATIAL.get((device, torch.cuda.current_stream().cuda_stream))
+    return None if sig is None else (sig[1], sig[2])
+
+
+def finish_sliding(st, labels, hist=None, num_classes=None, ignore_index=255, want_pred=False, closing=True):
+    """Second half of the any-size sliding-window evaluation: labels = a list of [Hl_i, Wl_i] uint8 tensors (or one [B,Hl,Wl] tensor).
+    Images are grouped by (H, W, label shape); per group: DenseCRF on the full-resolution prob maps (crf_masks(..., scale=1)) when
+    encode_images_sliding was given crf=True, else the binary maps; 7x7 closing; nearest resize to the labels + score-weighted argmax +
+    IoU histograms (ops.seg_predict, accumulated into `hist`).  Groups that share an image size run back to back, starting with the size
+    whose spatial lattice the CRF holds, so that lattice is rebuilt once per size.
+    -> dict(hist, cand_idx, cand_score, masks [per image: ncand x H x W uint8, after closing], pred [per image, or None])."""
+    plan = st["plan"]
+    sizes = plan["sizes"]
+    C = num_classes or st["num_classes"]
+    dev = st["cand_idx"].device
+    if hist is None:
+        hist = torch.zeros(3, C, device=dev, dtype=torch.int64)
+    labels = list(labels) if torch.is_tensor(labels) else labels
+    if len(labels) != len(sizes):
+        raise ValueError(f"finish_sliding: {len(labels)} label maps for {len(sizes)} images")
+    keys = {}
+    for b, (hw, lab) in enumerate(zip(sizes, labels)):
+        keys.setdefault(hw + tuple(lab.shape[-2:]), []).append(b)
+    order = sorted(keys)
+    raw = st.get("images_u8")
+    if raw is not None:
+        first = _crf_cached_size(dev)
+        order.sort(key=lambda k: (k[:2] != first, k))
+    out_masks, out_pred = [None] * len(sizes), [None] * len(sizes)
+
+    def take(t, rows):            # rows of a device tensor: a view for a contiguous run, else a gather (index copied without a host wait)
+        if rows == list(range(rows[0], rows[0] + len(rows))):
+            return t[rows[0]:rows[0] + len(rows)]
+        return t[ops.to_device_async(rows, dev)]
+
+    for key in order:
+        bs = keys[key]
+        cand, score = take(st["cand_idx"], bs), take(st["cand_score"], bs)
+        src = st["prob"] if raw is not None else st["masks"]
+        planes = [ops.slide_planes(src, plan, b) for b in bs]
+        maps = planes[0][None] if len(bs) == 1 else torch.stack(planes)
+        if raw is not None:
+            gb, u8 = raw[key[:2]]
+            img = take(u8, [gb.index(b) for b in bs])
+            maps = crf_masks(maps, cand, img, scale=1)
+        if closing:
+            maps = ops.close7(maps, cand.reshape(-1))
+        lab = labels[bs[0]][None] if len(bs) == 1 else torch.stack([labels[b] for b in bs])
+        pred, hist = ops.seg_predict(maps, cand, score, lab.contiguous(), C, ignore_index, hist=hist, want_pred=want_pred)
+        for j, b in enumerate(bs):
+            out_masks[b] = maps[j]
+            if want_pred:
+                out_pred[b] = pred[j]
+    return {"hist": hist, "cand_idx": st["cand_idx"], "cand_score": st["cand_score"], "threshold": st["threshold"], "masks": out_masks,
+            "pred": out_pred if want_pred else None}
+
+
 def shard_batches(batches, rank, world):
     """Round-robin shard of an iterable of batches: rank r takes batches r, r + world, ... (independent units, no data-path collective)."""
     for i, b in enumerate(batches):
@@ -201,7 +320,8 @@ def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=
     tensor ends the evaluation (simseg/utils/metrics.py:85-97 sums the same three vectors over the images).  Every rank still ITERATES the
     whole iterable (a batch it skips is produced and dropped): when producing a batch is expensive, hand in this rank's share only - a loader
     over a dataset sharded with the same i % world == rank rule - and say presharded=True (tools/seg_eval_device.py does).  slide = (win, stride): the
-    sliding-window form (encode_batch_sliding); None: one network input per image (encode_batch).
+    sliding-window form (encode_batch_sliding); None: one network input per image (encode_batch).  A batch whose image and label elements are
+    LISTS (images [3,H_i,W_i] of any sizes, labels [Hl_i,Wl_i]) takes the any-size sliding-window path (encode_images_sliding + finish_sliding).
     -> dict(iou [C] float64, miou, hist [3,C] int64 (global), images (global count), images_local)."""
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
@@ -212,18 +332,29 @@ def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=
     hist = torch.zeros(3, C, device=dev, dtype=torch.int64)
 
     def encode(image, label):
+        if isinstance(image, (list, tuple)):        # images of any sizes: the any-size sliding-window path
+            return encode_images_sliding(model, image, text, top_cls_num, win=slide[0], stride=slide[1], crf=crf, mean=mean, std=std,
+                                         sim_dtype=sim_dtype, window_batch=window_batch)
         if slide is not None:
             return encode_batch_sliding(model, image, text, top_cls_num, win=slide[0], stride=slide[1], crf=crf, mean=mean, std=std,
                                         sim_dtype=sim_dtype, window_batch=window_batch)
         return encode_batch(model, image, text, top_cls_num, crf=crf, mean=mean, std=std, sim_dtype=sim_dtype)
 
     def finish(st, image, label):
+        if isinstance(image, (list, tuple)):
+            return finish_sliding(st, label, hist=hist, num_classes=C)
         return finish_batch(st, label, hist=hist)
 
     count = 0
     pipe = EvalPipeline(dev, encode, finish, pipelined=crf if pipelined is None else pipelined)
     with torch.no_grad():
         for image, label in (batches if presharded else shard_batches(batches, rank, world)):      # presharded: `batches` is already this rank's share
+            if isinstance(image, (list, tuple)):
+                if slide is None:
+                    raise ValueError("evaluate_sharded: batches of image lists need slide=(win, stride)")
+                pipe.submit([x.to(dev, non_blocking=True) for x in image], [y.to(dev, non_blocking=True) for y in label])
+                count += len(image)
+                continue
             pipe.submit(image.to(dev, non_blocking=True), label.to(dev, non_blocking=True))
             count += image.shape[0]
         pipe.flush()

@@ -14,6 +14,19 @@ how the work is laid out, not in what is computed:
 
     python tools/seg_eval_device.py --cfg configs/clip/simseg.vit-b.yaml --ckpt_path ckpts/simseg.vit-b.pth
     python tools/seg_eval_device.py --cfg configs/clip/simseg.vit-s.yaml --synthetic 64        # no data / checkpoint needed
+
+Sliding windows (`--slide WIN,STRIDE`) take images of ANY size: windows are placed as mmseg's slide_inference does (the last one flush
+with the border; an image smaller than a window gets one zero-padded window) and `--batch` consecutive images of different sizes go
+through the towers together as lists (segpost.encode_images_sliding); a batch of equal-sized images that the windows tile exactly keeps
+the exact-tiling route (segpost.encode_batch_sliding).  Images of different sizes cannot be collated, so the loader must yield one image
+per batch (data.batch_size_val=1, as the shipped configs set).  The recommended COCO-Stuff run resizes the short side to 512 (bicubic)
+and slides 512-pixel windows at stride 256:
+
+    python tools/seg_eval_device.py --cfg configs/clip/simseg.vit-b.yaml --ckpt_path ckpts/simseg.vit-b.pth --slide 512,256 \
+        transforms.input_size=512 transforms.valid_transforms=[resize_bicubic] data.valid_name=[coco_stuff]
+    python tools/seg_eval_device.py --cfg configs/clip/simseg.vit-s.yaml --synthetic 8 --synthetic-sizes 96x150,80x80,131x257 --slide 96,48 \
+        transforms.input_size=96 model.image_encoder.tag=vit_test_patch16 model.image_encoder.embedding_dim=128 \
+        model.text_encoder.tag=bert-test model.text_encoder.embedding_dim=128      # ragged images, no data / checkpoint needed
 """
 import argparse
 import os
@@ -37,7 +50,8 @@ def parse_args():
     ap.add_argument("--host-crf", action="store_true", help="DenseCRF with pydensecrf on the host instead of the device kernels")
     ap.add_argument("--slide", default="", help="WIN,STRIDE: sliding-window evaluation (BASELINE configs[3]): images are fed at their loader size, cut into "
                                                 "WIN-pixel windows at STRIDE, per-window similarity maps overlap-averaged (segpost.encode_batch_sliding); "
-                                                "transforms.input_size must be WIN")
+                                                "transforms.input_size must be WIN; images of any size (see the module docstring)")
+    ap.add_argument("--synthetic-sizes", default="", help="H1xW1,H2xW2,...: sizes of the synthetic images, cycled over them (with --slide)")
     return ap.parse_known_args()
 
 
@@ -112,12 +126,42 @@ def main():
             for i, l in group:
                 yield i, l
 
+    slide = tuple(int(v) for v in args.slide.split(",")) if args.slide else None
+    syn_sizes = [tuple(int(v) for v in s.split("x")) for s in args.synthetic_sizes.split(",")] if args.synthetic_sizes else None
+    if syn_sizes and not slide:
+        raise SystemExit("--synthetic-sizes needs --slide WIN,STRIDE (images of other sizes go through sliding windows)")
+
+    def _tiles(hw):
+        try:
+            segpost.window_grid(int(hw[0]), int(hw[1]), *slide)
+            return True
+        except ValueError:
+            return False
+
+    def _emit_slide(group):
+        """--slide: `--batch` one-image items -> one batch; tensors when they share one size that the windows tile exactly (the existing
+        route), else lists of [3,H,W] images and [Hl,Wl] labels (segpost.encode_images_sliding)."""
+        if len({(tuple(i.shape), tuple(l.shape)) for i, l in group}) == 1 and _tiles(group[0][0].shape[-2:]):
+            yield torch.cat([i for i, _ in group]), torch.cat([l for _, l in group])
+        else:
+            yield [i[0] for i, _ in group], [l[0] for _, l in group]
+
     def batches(name, shard=None):
         """shard = (rank, world): only THIS rank's batches are produced (batch i goes to rank i % world - evaluate_sharded's rule), i.e. a
         rank decodes and transforms 1 / world of the images instead of all of them (the reference's loader gives every rank every image,
         simseg/datasets/seg/seg_dataset.py:67-81).  Batches are formed from `--batch` consecutive dataset items; an item whose label shape
         differs from its batch's ends the batch early in the unsharded form only - the sharded form cuts fixed groups of `--batch` items and
         splits a group with mixed shapes into single-image batches."""
+        if args.synthetic and syn_sizes:
+            g = torch.Generator().manual_seed(1)
+            for i, s in enumerate(range(0, args.synthetic, args.batch)):
+                group = []
+                for j in range(s, min(s + args.batch, args.synthetic)):
+                    hw = syn_sizes[j % len(syn_sizes)]
+                    group.append((torch.randn(1, 3, *hw, generator=g), torch.randint(0, 21, (1, *hw), generator=g, dtype=torch.int64).to(torch.uint8)))
+                if shard is None or i % shard[1] == shard[0]:
+                    yield from _emit_slide(group)
+            return
         if args.synthetic:
             g = torch.Generator().manual_seed(1)
             for i, s in enumerate(range(0, args.synthetic, args.batch)):
@@ -130,6 +174,9 @@ def main():
             return
         from simseg.datasets.seg.seg_dataset import build_torch_valid_loader
         loader = build_torch_valid_loader(cfg, name, mode="valid")
+        if slide and cfg.data.batch_size_val != 1:
+            raise SystemExit(f"--slide needs one image per loader batch (images of different sizes cannot be collated): "
+                             f"set data.batch_size_val=1 (got {cfg.data.batch_size_val})")
         if shard is not None and shard[1] > 1:
             # the same loader over a Subset holding this rank's groups of `--batch` consecutive items
             ds = loader.dataset
@@ -140,10 +187,20 @@ def main():
             for image, label in loader:
                 group.append((image, label.to(torch.uint8)))
                 if len(group) == args.batch:
-                    yield from _emit_group(group)
+                    yield from (_emit_slide(group) if slide else _emit_group(group))
                     group = []
             if group:
-                yield from _emit_group(group)
+                yield from (_emit_slide(group) if slide else _emit_group(group))
+            return
+        if slide:
+            group = []
+            for image, label in loader:
+                group.append((image, label.to(torch.uint8)))
+                if len(group) == args.batch:
+                    yield from _emit_slide(group)
+                    group = []
+            if group:
+                yield from _emit_slide(group)
             return
         imgs, labs = [], []
         for image, label in loader:                       # reference loader: batch size 1, labels at raw resolution
@@ -197,7 +254,6 @@ def main():
         else:
             # the product loop: batches dealt round-robin to the ranks of the process group (one rank when launched plainly; N under
             # `python -m torch.distributed.run --nproc-per-node N tools/seg_eval_device.py ...`), ONE all-reduce of the [3, C] area histograms
-            slide = tuple(int(v) for v in args.slide.split(",")) if args.slide else None
             # (each rank's loader produces only its own batches; evaluate_sharded then sees a one-rank deal of them and still ends with the
             #  all-reduce of the histograms over the world)
             on = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
