@@ -323,6 +323,20 @@ int64_t simseg_slide_stitch_workspace_bytes(int64_t B, int64_t ncand, int64_t ma
 int simseg_slide_stitch(const float* sim_w, const int64_t* img_tab, const int64_t* win_tab, const int* cand_idx, float* prob, void* mask,
                         float* minmax, float* workspace, int64_t B, int64_t ncand, int64_t n, int64_t C, int64_t win, int64_t max_h,
                         int64_t max_w, int64_t max_hw, void* stream);
+/* Image preprocessing (simseg_amd/preproc.py, DESIGN.md "Device-side image preprocessing"): B decoded uint8 [H, W, 3] images packed in
+ * `src` -> Pillow's uint8 resize (its integer arithmetic, bit for bit) restricted to an output rectangle -> out fp32 [3, OH, OW] planes
+ * = lut [3, 256] at the resized byte; optionally (out_u8 != NULL) also the resized bytes as [OH, OW, 3].  ONE launch for the batch.
+ * img_tab int64 [B, 16] = (src byte offset, H, W, out element offset, OH, OW, crop top, crop left, offset and ksize of the horizontal
+ * axis table, offset and ksize of the vertical one, resized RH, RW, out_u8 byte offset, first tile = the sum over the earlier images of
+ * ceil(OW / 64) * ceil(OH / 32)); an axis table at int32 offset `off` of `tab` = bounds [out, 2] (xmin, n) then coefficients
+ * [out, ksize] (22 fractional bits), out = RW / RH.  img_tab_host and tab_host are HOST copies of the two device tables: every offset,
+ * extent and bound is checked on them (offsets in range, OH, OW > 0, 1 <= n <= ksize, xmin + n <= in, monotone bounds, no int32
+ * overflow) and an error returned before anything is launched.  The kernel reads the DEVICE tables and nothing compares the two: the
+ * CALLER GUARANTEES that each host copy holds exactly what its device table holds (or will hold once the copies queued before this call
+ * on `stream`, or made visible to it, have run) - simseg_amd.preproc.plan builds both from one array. */
+int simseg_image_preprocess(const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
+                            const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, float* out,
+                            int64_t out_numel, void* out_u8, int64_t u8_bytes, void* stream);
 /* cv2.dilate / cv2.erode with a 7x7 ones kernel, ONE iteration (the third positional argument in :156-157 is `dst`, not
  * `iterations`), default border (never wins) on byte images [M,H,W]; erode = 0 dilate, 1 erode.  out must not alias in. */
 int simseg_morph7(const void* in, void* out, int64_t M, int64_t H, int64_t W, int erode, void* stream);

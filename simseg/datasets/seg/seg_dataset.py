@@ -8,7 +8,7 @@ import torch
 from PIL import Image
 
 from simseg.datasets.builder import DATALOADER
-from simseg.transforms import build_transforms
+from simseg.transforms import build_device_transforms, build_transforms
 
 __all__ = ["SegDataset", "build_torch_valid_loader", "seg"]
 
@@ -51,8 +51,22 @@ class SegDataset(torch.utils.data.Dataset):
         return self.length
 
 
-def build_torch_valid_loader(cfg, name, mode="valid", **kwargs):
-    """Not distributed, like the reference (every rank sees the whole set, seg_dataset.py:74-80)."""
+def _collate_lists(items):
+    """Raw images differ in size: a batch is a list of uint8 [H, W, 3] images and a list of [Hl, Wl] labels."""
+    return [i for i, _ in items], [l for _, l in items]
+
+
+def build_torch_valid_loader(cfg, name, mode="valid", device_preproc=False, **kwargs):
+    """Not distributed, like the reference (every rank sees the whole set, seg_dataset.py:74-80).  device_preproc=True: the dataset
+    only decodes (items are the raw uint8 [H, W, 3] image and the label) and batches are lists; resize, crop and normalisation then run
+    on the device from `loader.preproc_spec` (simseg_amd.preproc.preprocess)."""
+    if device_preproc:
+        host_op, spec = build_device_transforms(cfg, mode=mode)
+        ds = SegDataset(cfg=cfg, dataset_name=name, data_path=cfg.data.data_path, transforms=host_op)
+        loader = torch.utils.data.DataLoader(ds, batch_size=cfg.data.batch_size_val, num_workers=cfg.data.num_workers, pin_memory=False,
+                                             drop_last=False, collate_fn=_collate_lists)
+        loader.preproc_spec = spec
+        return loader
     ds = SegDataset(cfg=cfg, dataset_name=name, data_path=cfg.data.data_path, transforms=build_transforms(cfg, mode=mode))
     return torch.utils.data.DataLoader(ds, batch_size=cfg.data.batch_size_val, num_workers=cfg.data.num_workers, pin_memory=True,
                                        drop_last=False)

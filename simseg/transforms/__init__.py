@@ -1,6 +1,7 @@
 """Eval-time image transforms with the reference's builder API (simseg/transforms/mml/transforms.py:74-93) but without
 torchvision (absent here): PIL resampling + torch tensors.  Training-time augmentations (autoaug, random_resize_crop,
-color ops, random erasing) are host-side data prep outside the accelerated path and are not provided."""
+color ops, random erasing) are host-side data prep outside the accelerated path and are not provided.  build_device_transforms is the
+eval-time route that leaves only the decode on the host: resize, crop and normalisation run on the device (simseg_amd/preproc.py)."""
 import numpy as np
 import torch
 from PIL import Image
@@ -8,7 +9,7 @@ from PIL import Image
 from simseg.utils import logger
 from simseg.utils.registry import Registry
 
-__all__ = ["TRANSFORMS", "build_transforms"]
+__all__ = ["TRANSFORMS", "build_transforms", "build_device_transforms"]
 
 TRANSFORMS = Registry("TRANSFORMS")
 
@@ -88,3 +89,37 @@ def build_transforms(cfg, mode="train"):
     t = Compose(ops)
     logger.emph(f"{mode} image transform is composed of:", t)
     return t
+
+
+def _to_u8(img):
+    a = np.asarray(img.convert("RGB"), dtype=np.uint8)
+    return torch.from_numpy(a.copy())
+
+
+def build_device_transforms(cfg, mode="valid"):
+    """-> (host_op, spec) of the device route: host_op maps a PIL image to its uint8 [H, W, 3] tensor and nothing else; spec
+    (simseg_amd.preproc.make_spec) names the resize, the optional centre crop and the normalisation that simseg_amd.preproc.preprocess
+    applies on the device, with results bit-identical to build_transforms(cfg, mode)."""
+    from simseg_amd.preproc import make_spec
+    names = list(cfg.transforms.train_transforms if mode == "train" else cfg.transforms.valid_transforms)
+    for name in names:
+        if TRANSFORMS.get(name) is None:
+            raise NotImplementedError(f"transform {name!r} is a training-time augmentation outside the accelerated path; "
+                                      f"available: {sorted(TRANSFORMS.obj_dict)}")
+    crop = None
+    if names and names[-1] == "center_crop":
+        crop = cfg.transforms.center_crop.size
+        names = names[:-1]
+    if names == ["resize"]:
+        kind, size, filt = "square", cfg.transforms.resize.size, "bilinear"
+    elif names == ["resize_bicubic"]:
+        kind, size, filt = "short", cfg.transforms.resize_bicubic.size, "bicubic"
+    else:
+        raise NotImplementedError(f"the device route takes one resize (resize | resize_bicubic) and an optional center_crop after it, "
+                                  f"got {list(cfg.transforms.train_transforms if mode == 'train' else cfg.transforms.valid_transforms)}")
+    # the 256 byte values through the host route's own tensor arithmetic: the table IS that route's result per byte
+    lut = TRANSFORMS.get("normalize")(cfg)(_to_tensor(np.arange(256, dtype=np.uint8).reshape(1, 256, 1).repeat(3, axis=2)))
+    spec = make_spec(kind, size, filt, crop=crop, mean=list(cfg.transforms.normalize.mean), std=list(cfg.transforms.normalize.std),
+                     lut=lut.reshape(3, 256).contiguous())
+    logger.emph(f"{mode} image transform on the device:", {k: v for k, v in spec.items() if k != "lut"})
+    return _to_u8, spec

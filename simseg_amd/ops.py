@@ -714,3 +714,24 @@ def slide_planes(flat, plan, b):
     H, W = plan["sizes"][b]
     o = plan["out_off"][b]
     return flat[o:o + plan["ncand"] * H * W].view(plan["ncand"], H, W)
+
+
+# ---- image preprocessing on the device (simseg_amd/preproc.py; include/simseg_hip.h simseg_image_preprocess) ----------------------------------
+def image_preprocess(src, plan, lut, want_u8=False):
+    """src: the batch's uint8 [H, W, 3] images packed at plan['src_off'] (preproc.plan) -> (fp32 flat, image b's [3, OH, OW] planes at
+    plan['out_off'][b]; uint8 flat with its [OH, OW, 3] bytes at the same offset, or None).  The tables are checked on their host copies
+    before the launch."""
+    require_gpu(src, lut, plan["img_tab"], plan["tab"])
+    if src.dtype != torch.uint8 or src.numel() != plan["src_bytes"]:
+        raise ValueError(f"image_preprocess: {plan['src_bytes']} packed uint8 bytes expected, got {src.numel()} {src.dtype}")
+    if lut.dtype != torch.float32 or tuple(lut.shape) != (3, 256):
+        raise ValueError(f"image_preprocess: fp32 [3, 256] look-up table expected, got {tuple(lut.shape)} {lut.dtype}")
+    it, th = plan["img_tab_host"], plan["tab_host"]
+    if it.dtype != "int64" or th.dtype != "int32" or not it.flags.c_contiguous or not th.flags.c_contiguous or \
+            tuple(plan["img_tab"].shape) != it.shape or plan["tab"].numel() != th.size:
+        raise ValueError("image_preprocess: the host copies of the tables are contiguous int64 [B, 16] / int32 arrays of the device tables' sizes")
+    out = torch.empty(plan["out_numel"], device=src.device, dtype=torch.float32)
+    u8 = torch.empty(plan["out_numel"], device=src.device, dtype=torch.uint8) if want_u8 else None
+    call("simseg_image_preprocess", ptr(_c(src)), src.numel(), ptr(plan["img_tab"]), it.ctypes.data, it.shape[0], ptr(plan["tab"]), th.ctypes.data,
+         th.size, ptr(_c(lut)), ptr(out), out.numel(), ptr(u8), 0 if u8 is None else u8.numel(), stream())
+    return out, u8

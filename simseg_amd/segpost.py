@@ -205,13 +205,30 @@ def slide_windows(H, W, win=512, stride=256):
     return [(y, x) for y in axis(H) for x in axis(W)]
 
 
-def encode_images_sliding(model, images, text, top_cls_num, win=512, stride=256, crf=True, mean=None, std=None, sim_dtype=None, window_batch=None):
-    """encode_batch_sliding() for images of any sizes: images = a list of [3, H_i, W_i] normalised fp32 tensors (or one [B,3,H,W] tensor).
+def encode_images_sliding(model, images, text, top_cls_num, win=512, stride=256, crf=True, mean=None, std=None, sim_dtype=None, window_batch=None,
+                          sizes=None):
+    """encode_batch_sliding() for images of any sizes: images = a list of [3, H_i, W_i] normalised fp32 tensors (or one [B,3,H,W] tensor),
+    or - with sizes = [(H_i, W_i), ...] - the flat fp32 buffer that already holds them back to back (what preproc.preprocess writes: taken
+    as it is, nothing is concatenated).
     All windows of all images (slide_windows offsets, ops.slide_extract) go through the towers together, at most `window_batch` per call;
     image scores = the mean of an image's window scores (ops.slide_scores) -> candidate selection -> per visited slot the pixel-resolution
     stitched map, min-max normalised, and its binary map (ops.slide_stitch).  Device work only (no host read).  finish_sliding() ends it."""
     from .heads import patch_text_similarity
-    if torch.is_tensor(images):
+    if sizes is not None:
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        flat = images.contiguous().reshape(-1)
+        if flat.dtype != torch.float32 or flat.numel() != sum(3 * h * w for h, w in sizes):
+            raise ValueError(f"encode_images_sliding: a packed fp32 buffer of {sum(3 * h * w for h, w in sizes)} elements expected for sizes {sizes}, "
+                             f"got {flat.numel()} {flat.dtype}")
+        groups, at = {}, 0
+        for b, (h, w) in enumerate(sizes):
+            bs, views = groups.setdefault((h, w), ([], []))
+            bs.append(b)
+            views.append(flat[at:at + 3 * h * w].view(3, h, w))
+            at += 3 * h * w
+        if crf:
+            groups = {hw: (bs, v[0][None] if len(v) == 1 else torch.stack(v)) for hw, (bs, v) in groups.items()}
+    elif torch.is_tensor(images):
         B, _, H, W = images.shape
         sizes, flat, groups = [(H, W)] * B, images.contiguous().reshape(-1), {(H, W): (list(range(B)), images)}
     else:
@@ -312,7 +329,7 @@ def shard_batches(batches, rank, world):
 
 
 def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=None, slide=None, crf=True, mean=None, std=None, sim_dtype=None,
-                     device=None, pipelined=None, window_batch=None, presharded=False):
+                     device=None, pipelined=None, window_batch=None, presharded=False, preprocess=None):
     """The zero-shot segmentation evaluation over `batches` = an iterable of (image [b,3,H,W], label [b,Hl,Wl] uint8) - the SAME iterable on
     every rank - data-parallel over the ranks of `group` (default: the world, or a single process when torch.distributed is not
     initialised): batches are dealt round-robin (shard_batches; the reference's loader gives every rank every image,
@@ -322,6 +339,10 @@ def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=
     over a dataset sharded with the same i % world == rank rule - and say presharded=True (tools/seg_eval_device.py does).  slide = (win, stride): the
     sliding-window form (encode_batch_sliding); None: one network input per image (encode_batch).  A batch whose image and label elements are
     LISTS (images [3,H_i,W_i] of any sizes, labels [Hl_i,Wl_i]) takes the any-size sliding-window path (encode_images_sliding + finish_sliding).
+    preprocess: a callable for batches whose image element is a list of RAW uint8 [H, W, 3] images (host or device): it turns the list into
+    the network input - a [b,3,S,S] tensor, or the dict of simseg_amd.preproc.preprocess, whose packed buffer the any-size path takes as it
+    is - and is called inside the encoder stage, on the encoder stream of EvalPipeline: the preprocessing kernel is queued with the batch it
+    feeds and the raw bytes stay referenced as long as the batch does.  Labels of such a batch are a list ([Hl_i, Wl_i], any sizes).
     -> dict(iou [C] float64, miou, hist [3,C] int64 (global), images (global count), images_local)."""
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
@@ -332,6 +353,21 @@ def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=
     hist = torch.zeros(3, C, device=dev, dtype=torch.int64)
 
     def encode(image, label):
+        if preprocess is not None:
+            res = preprocess(image)
+            # (the state keeps what preprocess returned - packed buffer, plan, tables - referenced for as long as EvalPipeline keeps the batch)
+            if isinstance(res, dict) and slide is not None:
+                st = encode_images_sliding(model, res["packed"], text, top_cls_num, win=slide[0], stride=slide[1], crf=crf, mean=mean, std=std,
+                                           sim_dtype=sim_dtype, window_batch=window_batch, sizes=res["sizes"])
+                st["preprocessed"] = res
+                return st
+            image = res["images"] if isinstance(res, dict) else res
+            if not torch.is_tensor(image):
+                raise ValueError("evaluate_sharded: without slide=(win, stride) the preprocessed images of a batch must share one size")
+            if slide is None:
+                st = encode_batch(model, image, text, top_cls_num, crf=crf, mean=mean, std=std, sim_dtype=sim_dtype)
+                st["preprocessed"] = res
+                return st
         if isinstance(image, (list, tuple)):        # images of any sizes: the any-size sliding-window path
             return encode_images_sliding(model, image, text, top_cls_num, win=slide[0], stride=slide[1], crf=crf, mean=mean, std=std,
                                          sim_dtype=sim_dtype, window_batch=window_batch)
@@ -341,21 +377,29 @@ def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=
         return encode_batch(model, image, text, top_cls_num, crf=crf, mean=mean, std=std, sim_dtype=sim_dtype)
 
     def finish(st, image, label):
-        if isinstance(image, (list, tuple)):
+        if "plan" in st:                            # the any-size path's state (encode_images_sliding)
             return finish_sliding(st, label, hist=hist, num_classes=C)
+        if isinstance(label, (list, tuple)):        # raw-size labels of a preprocessed batch: one seg_predict per label size
+            return _finish_by_label_size(st, label, hist)
         return finish_batch(st, label, hist=hist)
 
     count = 0
     pipe = EvalPipeline(dev, encode, finish, pipelined=crf if pipelined is None else pipelined)
     with torch.no_grad():
         for image, label in (batches if presharded else shard_batches(batches, rank, world)):      # presharded: `batches` is already this rank's share
+            if preprocess is not None:
+                # raw images stay where they are: preprocess packs host ones into one pinned buffer and copies that once
+                pipe.submit(list(image), [y.to(dev, non_blocking=True) for y in label] if isinstance(label, (list, tuple)) else label.to(dev, non_blocking=True))
+                count += len(image)
+                continue
             if isinstance(image, (list, tuple)):
                 if slide is None:
                     raise ValueError("evaluate_sharded: batches of image lists need slide=(win, stride)")
                 pipe.submit([x.to(dev, non_blocking=True) for x in image], [y.to(dev, non_blocking=True) for y in label])
                 count += len(image)
                 continue
-            pipe.submit(image.to(dev, non_blocking=True), label.to(dev, non_blocking=True))
+            pipe.submit(image.to(dev, non_blocking=True),
+                        [y.to(dev, non_blocking=True) for y in label] if isinstance(label, (list, tuple)) else label.to(dev, non_blocking=True))
             count += image.shape[0]
         pipe.flush()
     n_img = torch.tensor([count], device=dev, dtype=torch.int64)
@@ -364,6 +408,30 @@ def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=
         dist.all_reduce(n_img, op=dist.ReduceOp.SUM, group=group)
     iou, miou = iou_from_hist(hist)
     return {"iou": iou, "miou": miou, "hist": hist, "images": int(n_img), "images_local": count, "rank": rank, "world": world}
+
+
+PER_IMAGE_KEYS = ("cand_idx", "cand_score", "threshold", "masks", "prob", "images_u8")      # the entries of encode_batch's state with one row per image
+
+
+def _finish_by_label_size(st, labels, hist):
+    """finish_batch() for a batch whose labels are a list of [Hl_i, Wl_i] maps: images that share a label size finish together (the
+    histogram sums are independent of the grouping).  The rows of the PER_IMAGE_KEYS entries are taken per group; everything else in the
+    state is passed on as it is."""
+    keys = {}
+    for b, lab in enumerate(labels):
+        keys.setdefault(tuple(lab.shape[-2:]), []).append(b)
+    if len(keys) == 1:
+        return finish_batch(st, labels[0][None].contiguous() if len(labels) == 1 else torch.stack(list(labels)), hist=hist)
+    dev = st["cand_idx"].device
+    for k in PER_IMAGE_KEYS:
+        if st.get(k) is not None and st[k].shape[0] != len(labels):
+            raise ValueError(f"_finish_by_label_size: state entry {k!r} has {st[k].shape[0]} rows for {len(labels)} labels")
+    out = None
+    for bs in keys.values():
+        idx = ops.to_device_async(bs, dev)
+        sub = {k: (v[idx] if k in PER_IMAGE_KEYS and v is not None else v) for k, v in st.items()}
+        out = finish_batch(sub, torch.stack([labels[b] for b in bs]), hist=hist)
+    return out
 
 
 def finish_batch(st, label, hist=None, refine=None, want_pred=False):

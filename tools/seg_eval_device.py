@@ -27,8 +27,17 @@ and slides 512-pixel windows at stride 256:
     python tools/seg_eval_device.py --cfg configs/clip/simseg.vit-s.yaml --synthetic 8 --synthetic-sizes 96x150,80x80,131x257 --slide 96,48 \
         transforms.input_size=96 model.image_encoder.tag=vit_test_patch16 model.image_encoder.embedding_dim=128 \
         model.text_encoder.tag=bert-test model.text_encoder.embedding_dim=128      # ragged images, no data / checkpoint needed
+
+`--device-preproc` leaves only the decode on the host: the loader yields raw uint8 images, and resize, crop and normalisation run on the
+device in one launch per batch (simseg_amd.preproc; bit-identical to the host transforms, so the histogram digest printed next to the
+mIoU is the same on both routes).  `--synthetic-raw H1xW1,...` makes seeded raw uint8 images and raw-size labels for runs without a
+dataset; without `--device-preproc` they go through PIL + build_transforms on the host:
+
+    python tools/seg_eval_device.py --cfg configs/clip/simseg.vit-b.yaml --synthetic 2048 --synthetic-raw 375x500,500x375,333x500 \
+        --device-preproc transforms.input_size=512 transforms.resize.size=512
 """
 import argparse
+import hashlib
 import os
 import sys
 import time
@@ -52,6 +61,10 @@ def parse_args():
                                                 "WIN-pixel windows at STRIDE, per-window similarity maps overlap-averaged (segpost.encode_batch_sliding); "
                                                 "transforms.input_size must be WIN; images of any size (see the module docstring)")
     ap.add_argument("--synthetic-sizes", default="", help="H1xW1,H2xW2,...: sizes of the synthetic images, cycled over them (with --slide)")
+    ap.add_argument("--device-preproc", action="store_true", help="resize / crop / normalise on the device from raw uint8 images (simseg_amd.preproc) "
+                                                                  "instead of PIL + torch on the host; same results bit for bit")
+    ap.add_argument("--synthetic-raw", default="", help="H1xW1,H2xW2,...: sizes of seeded synthetic RAW uint8 images (and their labels), cycled over "
+                                                        "them and sent through the config's valid transforms on the host or, with --device-preproc, on the device")
     return ap.parse_known_args()
 
 
@@ -146,12 +159,85 @@ def main():
         else:
             yield [i[0] for i, _ in group], [l[0] for _, l in group]
 
+    raw_sizes = [tuple(int(v) for v in s.split("x")) for s in args.synthetic_raw.split(",")] if args.synthetic_raw else None
+    if raw_sizes and not args.synthetic:
+        raise SystemExit("--synthetic-raw needs --synthetic N")
+    if args.device_preproc and args.synthetic and not raw_sizes:
+        raise SystemExit("--device-preproc with --synthetic needs --synthetic-raw H1xW1,... (raw images to preprocess)")
+    if args.device_preproc and args.host_crf and not args.no_crf:
+        raise SystemExit("--device-preproc is not wired to --host-crf")
+    preprocess = None
+    if args.device_preproc:
+        from simseg.transforms import build_device_transforms
+        from simseg_amd import preproc
+        _, spec = build_device_transforms(cfg, "valid")
+
+        def preprocess(raws):
+            return preproc.preprocess(raws, spec, device=ENV.device)
+
+    def raw_batches(shard):
+        """--synthetic-raw: seeded raw uint8 [H, W, 3] images with raw-size labels, `--batch` per batch.  Device route: the raw lists as they
+        are.  Host route: Image.fromarray + build_transforms(cfg, "valid") per image, stacked when the plain route takes them."""
+        import numpy as np
+        from PIL import Image
+        from simseg.transforms import build_transforms
+        tf = None if args.device_preproc else build_transforms(cfg, "valid")
+        pool = {}
+
+        def raw_item(j):
+            # (a pool of 8 distinct images per size, made once: generating pixels is not part of either route)
+            k = j % (8 * len(raw_sizes))
+            if k not in pool:
+                H, W = raw_sizes[k % len(raw_sizes)]
+                rng = np.random.default_rng(1000 + k)
+                # smooth colour fields plus noise: something for the resampling filters to do
+                yy, xx = np.mgrid[0:H, 0:W]
+                base = np.stack([128 + 100 * np.sin(yy / (7.0 + c) + k) * np.cos(xx / (11.0 - c)) for c in range(3)], -1)
+                pool[k] = (np.clip(base + rng.normal(0, 25, (H, W, 3)), 0, 255).astype(np.uint8), torch.from_numpy(rng.integers(0, 21, (H, W), dtype=np.uint8)))
+            return pool[k]
+        for i, s in enumerate(range(0, args.synthetic, args.batch)):
+            if shard is not None and i % shard[1] != shard[0]:
+                continue
+            imgs, labs = [], []
+            for j in range(s, min(s + args.batch, args.synthetic)):
+                raw, lab = raw_item(j)
+                labs.append(lab)
+                imgs.append(torch.from_numpy(raw) if tf is None else tf(Image.fromarray(raw)))
+            if tf is None or slide:
+                yield imgs, labs
+            else:
+                yield torch.stack(imgs), labs
+
+    def device_loader_batches(name, shard):
+        """--device-preproc on a dataset: the loader only decodes; `--batch` consecutive raw images and labels per batch, as lists."""
+        from simseg.datasets.seg.seg_dataset import build_torch_valid_loader
+        loader = build_torch_valid_loader(cfg, name, mode="valid", device_preproc=True)
+        if shard is not None and shard[1] > 1:
+            ds = loader.dataset
+            idx = [i for i in range(len(ds)) if (i // args.batch) % shard[1] == shard[0]]
+            loader = torch.utils.data.DataLoader(torch.utils.data.Subset(ds, idx), batch_size=1, shuffle=False, num_workers=getattr(loader, "num_workers", 0),
+                                                 collate_fn=loader.collate_fn)
+        imgs, labs = [], []
+        for image, label in loader:
+            imgs += list(image); labs += [l.to(torch.uint8) for l in label]
+            while len(imgs) >= args.batch:
+                yield imgs[:args.batch], labs[:args.batch]
+                imgs, labs = imgs[args.batch:], labs[args.batch:]
+        if imgs:
+            yield imgs, labs
+
     def batches(name, shard=None):
         """shard = (rank, world): only THIS rank's batches are produced (batch i goes to rank i % world - evaluate_sharded's rule), i.e. a
         rank decodes and transforms 1 / world of the images instead of all of them (the reference's loader gives every rank every image,
         simseg/datasets/seg/seg_dataset.py:67-81).  Batches are formed from `--batch` consecutive dataset items; an item whose label shape
         differs from its batch's ends the batch early in the unsharded form only - the sharded form cuts fixed groups of `--batch` items and
         splits a group with mixed shapes into single-image batches."""
+        if args.synthetic and raw_sizes:
+            yield from raw_batches(shard)
+            return
+        if args.device_preproc:
+            yield from device_loader_batches(name, shard)
+            return
         if args.synthetic and syn_sizes:
             g = torch.Generator().manual_seed(1)
             for i, s in enumerate(range(0, args.synthetic, args.batch)):
@@ -259,13 +345,15 @@ def main():
             on = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
             shard = (dist.get_rank(), dist.get_world_size()) if on else None
             res = segpost.evaluate_sharded(model, batches(name, shard), text, top_cls_num, slide=slide, crf=not args.no_crf, mean=mean, std=std,
-                                           device=ENV.device, presharded=on)
+                                           device=ENV.device, presharded=on, preprocess=preprocess)
             torch.cuda.synchronize()
-            iou, miou, count = res["iou"], res["miou"], res["images"]
+            iou, miou, count, hist = res["iou"], res["miou"], res["images"], res["hist"]
         dt = time.perf_counter() - t0
         print(f"---------------- {count} samples evaluated ({name}, {count / dt:.1f} images/s). ----------------")
         logger.emph("multi class iou:", iou)
         logger.emph("final mean iou:", miou)
+        print(f"histogram sha256 {hashlib.sha256(hist.cpu().numpy().tobytes()).hexdigest()} mean iou {float(miou)!r} "
+              f"({'device' if args.device_preproc else 'host'} preprocessing)")
 
 
 if __name__ == "__main__":
