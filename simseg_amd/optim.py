@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from .lib import call, note_half, ptr, stream
-from .towers import drop_split_copy, register_w16
+from .towers import drop_qscaled_copy, drop_split_copy, register_w16
 
 CHUNK = 1 << 16
 RING = 4
@@ -89,7 +89,7 @@ class AdamW(torch.optim.Optimizer):
         for t, p in enumerate(params):
             st = self.state[p]
             static[t, 0], static[t, 2], static[t, 3], static[t, 4] = p.data_ptr(), st["m"].data_ptr(), st["v"].data_ptr(), st["p16"].data_ptr()
-        plan = dict(ids=ids, m=m, v=v, p16=p16, static=static,
+        plan = dict(ids=ids, m=m, v=v, p16=p16, static=static, p16_filled=False,
                     sizes=torch.tensor([p.numel() for p in params], dtype=torch.int64, device=dev),
                     tid=torch.tensor(tid, dtype=torch.int32, device=dev), coff=torch.tensor(coff, dtype=torch.int64, device=dev),
                     ring=[torch.empty(len(params), 6, dtype=torch.int64).pin_memory() for _ in range(RING)],
@@ -135,6 +135,12 @@ class AdamW(torch.optim.Optimizer):
             hyper[:, 1] = [it[2] for it in items]
             host[:, 5] = hyper.view(np.int64)[:, 0]
             with (torch.cuda.stream(plan["stream"]) if plan["stream"] is not None else contextlib.nullcontext()):
+                if not plan["p16_filled"]:
+                    # a new plan's 16-bit copies start as the masters' values: a skipped AMP step (overflow) writes nothing, yet step()
+                    # hands the copies to the towers.  Once per plan, on the stream the kernel is launched on (ordered before its writes).
+                    for p in params:
+                        self.state[p]["p16"].copy_(p.detach())
+                    plan["p16_filled"] = True
                 plan["table"].copy_(plan["ring"][slot], non_blocking=True)      # (on the stream the kernel is launched on)
                 ev = torch.cuda.Event()
                 ev.record()
@@ -198,6 +204,7 @@ class AdamW(torch.optim.Optimizer):
               for p in params:                 # same stream as the next forward: the copies are current when it runs
                   register_w16(p, self.state[p]["p16"])
                   drop_split_copy(p)           # the exact-mode split-bf16 copy of the OLD value (raw-pointer update: _version did not move)
+                  drop_qscaled_copy(p)         # the same for the folded q-scaled qkv copy (weight and bias)
         if amp and ready:
             self._amp_calls += 1             # (several buckets: every launch of this call read the same slot and wrote the other; a call
                                              #  with no gradient at all launched nothing - the other slot was not written, so do not flip)

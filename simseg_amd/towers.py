@@ -34,12 +34,22 @@ def drop_split_copy(param):
     _W3.pop(id(param), None)
 
 
+def drop_qscaled_copy(param):
+    """Forget the folded q-scaled qkv copy (_wt_qscaled) made from a parameter - weight or bias - the optimizer's kernel has just rewritten
+    through raw pointers (same blindness as drop_split_copy).  O(1): the entry's key is found through _WQS_OF, not by a scan."""
+    for key in _WQS_OF.pop(id(param), ()):
+        _WQS.pop(key, None)
+
+
 def invalidate_weight_cache():
-    """Drop every cached bf16 weight copy.  Needed only after writes torch cannot see (in-place ops on `param.data`, which
-    carry their own version counter); load_state_dict / copy_ / optimizers / .to() are detected without it."""
+    """Drop every cached derived copy of the parameters: the 16-bit copies (_W16), the concatenated BERT q / k / v copies (_CAT), the
+    split-bf16 copies (_W3) and the folded q-scaled qkv copies (_WQS).  Needed only after writes torch cannot see (in-place ops on
+    `param.data`, which carry their own version counter); load_state_dict / copy_ / optimizers / .to() are detected without it."""
     _W16.clear()
     _CAT.clear()
     _W3.clear()
+    _WQS.clear()
+    _WQS_OF.clear()
 
 
 def _wt(w, adt):
@@ -92,7 +102,8 @@ def _wt_split(w):
     return w3
 
 
-_WQS = {}
+_WQS = {}     # (id(weight), id(bias)) -> (weakref(weight), weakref(bias), versions and data pointers, 16-bit weight, fp32 bias)
+_WQS_OF = {}  # id(weight) / id(bias) -> the _WQS keys made from it (drop_qscaled_copy)
 
 
 def _wt_qscaled(w, b, adt, D):
@@ -112,9 +123,13 @@ def _wt_qscaled(w, b, adt, D):
     w16 = ops.cast(ws.contiguous(), adt)
     if isinstance(w, torch.nn.Parameter):
         if len(_WQS) > 1024:
-            for k in [k for k, e in _WQS.items() if e[0]() is None]:
+            for k in [k for k, e in _WQS.items() if e[0]() is None or e[1]() is None]:
                 del _WQS[k]
+            for k in [k for k, keys in _WQS_OF.items() if not any(kk in _WQS for kk in keys)]:
+                del _WQS_OF[k]
         _WQS[key] = (weakref.ref(w), weakref.ref(b), (w._version, b._version, w.data_ptr(), b.data_ptr()), w16, bs)
+        _WQS_OF.setdefault(id(w), set()).add(key)
+        _WQS_OF.setdefault(id(b), set()).add(key)
     return w16, bs
 
 

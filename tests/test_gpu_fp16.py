@@ -193,6 +193,24 @@ def test_trainer_fp16_amp_with_live_gradscaler(golden, tmp_path):
     tr2 = Trainer(m2, m2.cfg, steps_per_epoch=40, amp_dtype="fp16")
     tr2.load_checkpoint(ck)
     assert tr2.scaler.get_scale() == 2.0 ** 39
+    # the resumed trainer's first step overflows at that scale and is skipped; it is also the first step of the optimizer's new launch plan,
+    # whose 16-bit weight copies the skipped kernel never writes: the resumed model must still evaluate bit for bit as the one it came from
+    n2 = tr2.optimizer.steps_taken()
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()                                          # a NaN block of the copy buffer's size, freed: the plan's buffer
+    nan = torch.full((sum(p.numel() for p in m2.parameters()),), float("nan"), device="cuda", dtype=torch.float16)    # gets it, so an
+    torch.cuda.synchronize()                                          # unwritten copy cannot happen to hold matching bytes
+    del nan
+    tr2.train_step(batch)
+    assert tr2.scaler.get_scale() == 2.0 ** 38
+    assert tr2.optimizer.steps_taken() == n2
+    assert all(torch.equal(a.detach(), b.detach()) for a, b in zip(m.parameters(), m2.parameters()))
+    m2.eval()
+    for p in m2.parameters():
+        assert torch.equal(tr2.optimizer.state[p]["p16"], p.detach().to(torch.float16))
+    with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
+        e1, e2 = m(batch, embeddings="all"), m2(batch, embeddings="all")
+    assert all(torch.equal(a, b) for a, b in zip(e1, e2))
     # no host synchronisation anywhere in the AMP iteration (forward, scaled backward, overflow check, unscale + update / skip, scale update);
     # the scale has come down to where steps are taken again, so this also covers a TAKEN step with either scaler
     for scaler in (GradScaler("cuda", init_scale=2.0 ** 14), torch.amp.GradScaler("cuda", init_scale=2.0 ** 14)):
