@@ -337,6 +337,20 @@ int simseg_slide_stitch(const float* sim_w, const int64_t* img_tab, const int64_
 int simseg_image_preprocess(const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
                             const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, float* out,
                             int64_t out_numel, void* out_u8, int64_t u8_bytes, void* stream);
+/* Training augmentation (simseg_amd/augment.py, DESIGN.md "Device-side training augmentation"): B decoded uint8 [H, W, 3] images packed
+ * in `src` -> crop box -> Pillow's bilinear uint8 resize to S x S -> op1, op2 of the AutoAugment set (Pillow's arithmetic, bit for bit)
+ * -> out fp32 [B, 3, S, S] = lut [3, 256] at the final byte; optionally (out_u8 != NULL) also the final bytes as [B, S, S, 3].  TWO
+ * launches for the batch, 32 <= S <= 384.  img_tab int64 [B, 30] = (src byte offset, H, W, crop top, crop left, crop h, crop w, offset
+ * and ksize of the horizontal axis table (crop w -> S), offset and ksize of the vertical one (crop h -> S), 0, op1 code, op2 code,
+ * 8 parameter slots of op1, 8 of op2); op codes 0 none, 1 posterize (mask), 2 solarize (bytes below the threshold kept), 3 invert,
+ * 4 autocontrast, 5 equalize, 6 color, 7 contrast, 8 sharpness (float bits of the blend factor), 9 rotate (16.16 fixed-point a0, a1,
+ * a3, a4, x start, y start), 10 shearX (double bits of the affine a0..a5); the axis tables are preproc's (simseg_image_preprocess).
+ * scratch: at least simseg_train_augment_scratch_bytes(B, S) device bytes.  Every offset, extent, table and parameter is checked on
+ * the HOST copies before anything is launched; the caller guarantees that they hold what the device tables hold. */
+int64_t simseg_train_augment_scratch_bytes(int64_t B, int64_t S);
+int simseg_train_augment(const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
+                         const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S, void* scratch,
+                         int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes, void* stream);
 /* cv2.dilate / cv2.erode with a 7x7 ones kernel, ONE iteration (the third positional argument in :156-157 is `dst`, not
  * `iterations`), default border (never wins) on byte images [M,H,W]; erode = 0 dilate, 1 erode.  out must not alias in. */
 int simseg_morph7(const void* in, void* out, int64_t M, int64_t H, int64_t W, int erode, void* stream);

@@ -1,7 +1,9 @@
 """Eval-time image transforms with the reference's builder API (simseg/transforms/mml/transforms.py:74-93) but without
-torchvision (absent here): PIL resampling + torch tensors.  Training-time augmentations (autoaug, random_resize_crop,
-color ops, random erasing) are host-side data prep outside the accelerated path and are not provided.  build_device_transforms is the
-eval-time route that leaves only the decode on the host: resize, crop and normalisation run on the device (simseg_amd/preproc.py)."""
+torchvision (absent here): PIL resampling + torch tensors.  build_transforms / build_device_transforms do not provide the training-time
+augmentations (autoaug, random_resize_crop, random erasing) and raise for them; build_train_augmentation is their route: the host decodes,
+the parameters are sampled on the host, and crop, resize, AutoAugment and normalisation run on the device (simseg_amd/augment.py).
+build_device_transforms is the eval-time route that leaves only the decode on the host: resize, crop and normalisation run on the device
+(simseg_amd/preproc.py)."""
 import numpy as np
 import torch
 from PIL import Image
@@ -9,7 +11,7 @@ from PIL import Image
 from simseg.utils import logger
 from simseg.utils.registry import Registry
 
-__all__ = ["TRANSFORMS", "build_transforms", "build_device_transforms"]
+__all__ = ["TRANSFORMS", "build_transforms", "build_device_transforms", "build_train_augmentation"]
 
 TRANSFORMS = Registry("TRANSFORMS")
 
@@ -123,3 +125,25 @@ def build_device_transforms(cfg, mode="valid"):
                      lut=lut.reshape(3, 256).contiguous())
     logger.emph(f"{mode} image transform on the device:", {k: v for k, v in spec.items() if k != "lut"})
     return _to_u8, spec
+
+
+def _normalize_lut(cfg):
+    """The 256 byte values through the host route's own tensor arithmetic: the table IS that route's result per byte."""
+    lut = TRANSFORMS.get("normalize")(cfg)(_to_tensor(np.arange(256, dtype=np.uint8).reshape(1, 256, 1).repeat(3, axis=2)))
+    return lut.reshape(3, 256).contiguous()
+
+
+def build_train_augmentation(cfg):
+    """-> (host_op, augment) of the training route: host_op maps a PIL image to its uint8 [H, W, 3] tensor and nothing else; augment
+    (simseg_amd.augment.TrainAugment), given a batch of those tensors and a numpy Generator, samples RandomResizedCrop and AutoAugment
+    parameters on the host and returns the augmented, normalised fp32 [B, 3, S, S] batch from the device.  Accepts train_transforms
+    [random_resize_crop, autoaug] or [random_resize_crop]."""
+    from simseg_amd.augment import TrainAugment
+    names = list(cfg.transforms.train_transforms)
+    if names not in (["random_resize_crop", "autoaug"], ["random_resize_crop"]):
+        raise NotImplementedError(f"the training augmentation route takes train_transforms [random_resize_crop, autoaug] or "
+                                  f"[random_resize_crop], got {names}")
+    rrc = cfg.transforms.random_resize_crop
+    aug = TrainAugment(rrc.size, tuple(rrc.scale), autoaug=len(names) == 2, lut=_normalize_lut(cfg))
+    logger.emph("train image augmentation on the device:", aug)
+    return _to_u8, aug

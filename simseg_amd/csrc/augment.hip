@@ -1,0 +1,428 @@
+// Training augmentation on the device: decoded uint8 [H, W, 3] images -> RandomResizedCrop (Pillow's bilinear uint8 resize of a crop
+// box) -> up to two AutoAugment ops -> normalised fp32 [3, S, S], bit-identical to the same parameters applied with Pillow
+// (simseg_amd/augment.py apply_pil).  TWO launches per batch, whatever its size and whichever ops were drawn.  DESIGN.md "Device-side
+// training augmentation" states every op's arithmetic.
+//
+// Launch 1 (augment_resize_kernel): preproc.hip's resample with a source row pitch - a workgroup of 256 threads owns a 64 x 32 output
+// tile, the input rows it needs pass through LDS in chunks after the horizontal pass, the vertical pass accumulates in registers - writing
+// packed uint8 [S, S, 3] into a scratch slot per image (slots 16-byte aligned).
+// Launch 2 (augment_ops_kernel): one workgroup of 1024 threads per image.  With S <= AG_LDS_MAX_S the image is copied into LDS (150,528
+// bytes at S = 224) and every op works there; larger images are worked on in their scratch slot, with a second slot as the target of the
+// geometric ops.  Point ops (posterize, solarize, invert, autocontrast, equalize) build a per-channel [3, 256] byte table (the last two
+// from per-channel histograms) and map every byte; colour and contrast blend each pixel with its degenerate value; sharpness, rotate and
+// shearX read neighbours or other pixels, so each thread first writes all its results to global memory (the image's own scratch slot
+// once the image is in LDS), the workgroup waits at a barrier, and the results are copied back.  The normalised output goes through the
+// host-filled [3, 256] fp32 table.
+//
+// Exactness: the blends, the 3x3 smoothing, autocontrast's scale and the bicubic shear must round as Pillow's C code does, so floating-
+// point contraction is off for this file (build.py compiles with -O3 and the default contraction, which would form FMAs).
+#pragma clang fp contract(off)
+#include <math.h>
+
+#include <vector>
+
+#include "common.h"
+
+constexpr int AG_COLS = 30, AG_SLOTS = 8;
+enum { AG_SRC = 0, AG_H, AG_W, AG_TOP, AG_LEFT, AG_CH, AG_CW, AG_HOFF, AG_HKS, AG_VOFF, AG_VKS, AG_RSV, AG_OP1, AG_OP2, AG_P1 };
+enum { OP_NONE = 0, OP_POSTERIZE, OP_SOLARIZE, OP_INVERT, OP_AUTOCONTRAST, OP_EQUALIZE, OP_COLOR, OP_CONTRAST, OP_SHARPNESS, OP_ROTATE,
+       OP_SHEARX, OP_COUNT };
+constexpr int AG_MIN_S = 32, AG_MAX_S = 384;
+constexpr int AG_THREADS = 1024;
+constexpr int AG_LDS_MAX_S = 230;                                   // 230 * 230 * 3 = 158,700 bytes + the static LDS below <= 160 KiB
+constexpr int RZ_TW = 64, RZ_TH = 32, RZ_CR = 48, RZ_RPT = RZ_TH / 4, RZ_BITS = 22;
+constexpr uint32_t AG_FILL = 128u | (128u << 8) | (128u << 16);
+
+__host__ __device__ inline int64_t ag_slot_bytes(int64_t S) { return (3 * S * S + 15) / 16 * 16; }
+static inline bool ag_in_lds(int64_t S) { return S <= AG_LDS_MAX_S; }
+
+// ---- launch 1: crop + resize -------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int rz_clip8(int acc) { return min(max(acc >> RZ_BITS, 0), 255); }
+
+__global__ __launch_bounds__(256) void augment_resize_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ img_tab,
+                                                             const int* __restrict__ tab, uint8_t* __restrict__ scratch, int S,
+                                                             int tiles_per_image) {
+    __shared__ uint32_t hbuf[RZ_CR * RZ_TW];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int b = blockIdx.x / tiles_per_image, tile = blockIdx.x % tiles_per_image;
+    const int64_t* it = img_tab + (long)b * AG_COLS;
+    const long src_off = it[AG_SRC];
+    const long pitch = it[AG_W];
+    const int top = (int)it[AG_TOP], left = (int)it[AG_LEFT], hks = (int)it[AG_HKS], vks = (int)it[AG_VKS];
+    const int* __restrict__ hb = tab + it[AG_HOFF];               // bounds [S, 2] inside the crop, then coefficients [S, hks]
+    const int* __restrict__ hk = hb + 2 * (long)S;
+    const int* __restrict__ vb = tab + it[AG_VOFF];
+    const int* __restrict__ vk = vb + 2 * (long)S;
+    const int tiles_x = (S + RZ_TW - 1) / RZ_TW;
+    const int x0 = (tile % tiles_x) * RZ_TW, y0 = (tile / tiles_x) * RZ_TH;
+    const int nx = min(RZ_TW, S - x0), ny = min(RZ_TH, S - y0);
+    const bool xin = lane < nx;
+    const int X = x0 + lane;
+    const int hx = xin ? hb[2 * X] : 0, hn = xin ? hb[2 * X + 1] : 0;
+    const int* __restrict__ hkx = hk + (long)(xin ? X : 0) * hks;
+    const int rmin = vb[2 * y0], rmax = vb[2 * (y0 + ny - 1)] + vb[2 * (y0 + ny - 1) + 1];
+    int acc[RZ_RPT][3];
+#pragma unroll
+    for (int r = 0; r < RZ_RPT; ++r) acc[r][0] = acc[r][1] = acc[r][2] = 1 << (RZ_BITS - 1);
+    for (int r0 = rmin; r0 < rmax; r0 += RZ_CR) {
+        const int rows = min(RZ_CR, rmax - r0);
+        for (int rr = wave; rr < rows; rr += 4) {
+            const uint8_t* __restrict__ p = src + src_off + ((long)(top + r0 + rr) * pitch + left + hx) * 3;
+            int a0 = 1 << (RZ_BITS - 1), a1 = a0, a2 = a0;
+            for (int i = 0; i < hn; ++i) {
+                const int k = hkx[i];
+                a0 += (int)p[3 * i] * k;
+                a1 += (int)p[3 * i + 1] * k;
+                a2 += (int)p[3 * i + 2] * k;
+            }
+            hbuf[rr * RZ_TW + lane] = (uint32_t)rz_clip8(a0) | ((uint32_t)rz_clip8(a1) << 8) | ((uint32_t)rz_clip8(a2) << 16);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int r = 0; r < RZ_RPT; ++r) {
+            const int yy = wave + 4 * r;
+            if (yy < ny) {
+                const int Y = y0 + yy;
+                const int ymin = vb[2 * Y], yn = vb[2 * Y + 1];
+                const int* __restrict__ vky = vk + (long)Y * vks;
+                const int jlo = max(ymin, r0), jhi = min(ymin + yn, r0 + rows);
+                for (int j = jlo; j < jhi; ++j) {
+                    const int k = vky[j - ymin];
+                    const uint32_t v = hbuf[(j - r0) * RZ_TW + lane];
+                    acc[r][0] += (int)(v & 255u) * k;
+                    acc[r][1] += (int)((v >> 8) & 255u) * k;
+                    acc[r][2] += (int)((v >> 16) & 255u) * k;
+                }
+            }
+        }
+        __syncthreads();
+    }
+    if (!xin) return;
+    uint8_t* __restrict__ dst = scratch + b * ag_slot_bytes(S);
+#pragma unroll
+    for (int r = 0; r < RZ_RPT; ++r) {
+        const int yy = wave + 4 * r;
+        if (yy < ny) {
+            uint8_t* q = dst + ((long)(y0 + yy) * S + x0 + lane) * 3;
+            q[0] = (uint8_t)rz_clip8(acc[r][0]); q[1] = (uint8_t)rz_clip8(acc[r][1]); q[2] = (uint8_t)rz_clip8(acc[r][2]);
+        }
+    }
+}
+
+// ---- launch 2: the ops ------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t ag_px(const uint8_t* buf, int p) {
+    return (uint32_t)buf[3 * p] | ((uint32_t)buf[3 * p + 1] << 8) | ((uint32_t)buf[3 * p + 2] << 16);
+}
+__device__ __forceinline__ void ag_put(uint8_t* buf, int p, uint32_t v) {
+    buf[3 * p] = (uint8_t)v; buf[3 * p + 1] = (uint8_t)(v >> 8); buf[3 * p + 2] = (uint8_t)(v >> 16);
+}
+// Image.blend(degenerate, image, f) on one byte: float32 deg + f * (im - deg), truncated, clamped
+__device__ __forceinline__ uint32_t ag_blend(int deg, int im, float f) {
+    const int v = (int)((float)deg + f * (float)(im - deg));
+    return (uint32_t)min(max(v, 0), 255);
+}
+__device__ __forceinline__ int ag_luma(uint32_t v) {            // convert("L"): ITU-R 601-2 in 16-bit fixed point
+    return (int)((19595u * (v & 255u) + 38470u * ((v >> 8) & 255u) + 7471u * ((v >> 16) & 255u) + 0x8000u) >> 16);
+}
+__device__ __forceinline__ double ag_cubic(double v1, double v2, double v3, double v4, double d) {   // Pillow's BICUBIC, a = -1
+    const double p1 = v2;
+    const double p2 = -v1 + v3;
+    const double p3 = 2 * (v1 - v2) + v3 - v4;
+    const double p4 = -v1 + v2 - v3 + v4;
+    return p1 + d * (p2 + d * (p3 + d * p4));
+}
+__device__ __forceinline__ double ag_f64(int64_t bits) { return __longlong_as_double((long long)bits); }
+__device__ __forceinline__ float ag_f32(int64_t bits) { return __int_as_float((int)bits); }
+
+// Every pixel through f(p) -> packed RGB, all reads before any write: the results go to `alt` (global memory), the workgroup waits, and
+// then the LDS path copies them back into LDS (16-byte pieces) while the global path makes `alt` the image.  (Keeping them in registers
+// instead - 52 pixels per thread at S = 230 - spills the bicubic's working set at 1024 threads.)
+template <bool LDS, class F>
+__device__ __forceinline__ void ag_gather(uint8_t*& buf, uint8_t*& alt, int n, long slot, F f) {
+    const int tid = threadIdx.x;
+    for (int p = tid; p < n; p += AG_THREADS) ag_put(alt, p, f(p));
+    __syncthreads();
+    if constexpr (LDS) {
+        const uint4* s4 = reinterpret_cast<const uint4*>(alt);
+        uint4* d4 = reinterpret_cast<uint4*>(buf);
+        for (int i = tid; i < (int)(slot / 16); i += AG_THREADS) d4[i] = s4[i];
+    } else {
+        uint8_t* t = buf; buf = alt; alt = t;
+    }
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(AG_THREADS) void augment_ops_kernel(const int64_t* __restrict__ img_tab, uint8_t* __restrict__ scratch,
+                                                                 uint8_t* __restrict__ scratch2, int S, const float* __restrict__ lut,
+                                                                 float* __restrict__ out, uint8_t* __restrict__ out_u8) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t ag_lds[];
+    __shared__ int hist[3][256];
+    __shared__ uint8_t tlut[3][256];
+    __shared__ int lsum;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int64_t* it = img_tab + (long)b * AG_COLS;
+    const int n = S * S;
+    const long slot = ag_slot_bytes(S);
+    uint8_t* buf;
+    uint8_t* alt = nullptr;
+    if constexpr (LDS) {
+        buf = ag_lds;
+        alt = scratch + b * slot;                                // free once copied: the target of the geometric ops
+        const uint4* s4 = reinterpret_cast<const uint4*>(scratch + b * slot);
+        uint4* d4 = reinterpret_cast<uint4*>(ag_lds);
+        for (int i = tid; i < (int)(slot / 16); i += AG_THREADS) d4[i] = s4[i];
+    } else {
+        buf = scratch + b * slot;
+        alt = scratch2 + b * slot;
+    }
+    for (int k = 0; k < 2; ++k) {
+        const int op = (int)it[AG_OP1 + k];
+        const int64_t* P = it + AG_P1 + k * AG_SLOTS;
+        __syncthreads();                                         // the image as the last step left it
+        if (op == OP_NONE) continue;
+        if (op <= OP_EQUALIZE) {
+            // ---- byte -> byte tables per channel
+            if (op == OP_AUTOCONTRAST || op == OP_EQUALIZE) {
+                for (int i = tid; i < 768; i += AG_THREADS) (&hist[0][0])[i] = 0;
+                __syncthreads();
+                for (int p = tid; p < n; p += AG_THREADS) {
+                    atomicAdd(&hist[0][buf[3 * p]], 1);
+                    atomicAdd(&hist[1][buf[3 * p + 1]], 1);
+                    atomicAdd(&hist[2][buf[3 * p + 2]], 1);
+                }
+                __syncthreads();
+                if (tid < 3) {
+                    const int c = tid;
+                    bool ident = false;
+                    if (op == OP_AUTOCONTRAST) {                 // ImageOps.autocontrast(cutoff = 0): scale and offset in double
+                        int lo = 0, hi = 255;
+                        while (lo < 255 && !hist[c][lo]) ++lo;
+                        while (hi > 0 && !hist[c][hi]) --hi;
+                        if (hi <= lo) {
+                            ident = true;
+                        } else {
+                            const double scale = 255.0 / (double)(hi - lo);
+                            const double offset = (double)(-lo) * scale;
+                            for (int i = 0; i < 256; ++i) {
+                                const int v = (int)((double)i * scale + offset);
+                                tlut[c][i] = (uint8_t)min(max(v, 0), 255);
+                            }
+                        }
+                    } else {                                     // ImageOps.equalize: integer arithmetic, the table clipped to 255
+                        int cnt = 0, last = 0;
+                        long sum = 0;
+                        for (int i = 0; i < 256; ++i) {
+                            const int h = hist[c][i];
+                            if (h) { ++cnt; sum += h; last = h; }
+                        }
+                        const long step = cnt <= 1 ? 0 : (sum - last) / 255;
+                        if (step == 0) {
+                            ident = true;
+                        } else {
+                            long acc = step / 2;
+                            for (int i = 0; i < 256; ++i) {
+                                tlut[c][i] = (uint8_t)(acc / step < 255 ? acc / step : 255);
+                                acc += hist[c][i];
+                            }
+                        }
+                    }
+                    if (ident)
+                        for (int i = 0; i < 256; ++i) tlut[c][i] = (uint8_t)i;
+                }
+            } else {
+                const int a = (int)P[0];
+                for (int i = tid; i < 768; i += AG_THREADS) {
+                    const int v = i & 255;
+                    (&tlut[0][0])[i] = (uint8_t)(op == OP_POSTERIZE ? (v & a) : op == OP_SOLARIZE ? (v < a ? v : 255 - v) : 255 - v);
+                }
+            }
+            __syncthreads();
+            for (int p = tid; p < n; p += AG_THREADS) {
+                buf[3 * p] = tlut[0][buf[3 * p]];
+                buf[3 * p + 1] = tlut[1][buf[3 * p + 1]];
+                buf[3 * p + 2] = tlut[2][buf[3 * p + 2]];
+            }
+        } else if (op == OP_COLOR) {                             // blend with the image's L replicated
+            const float f = ag_f32(P[0]);
+            for (int p = tid; p < n; p += AG_THREADS) {
+                const uint32_t v = ag_px(buf, p);
+                const int L = ag_luma(v);
+                ag_put(buf, p, ag_blend(L, v & 255u, f) | (ag_blend(L, (v >> 8) & 255u, f) << 8) | (ag_blend(L, (v >> 16) & 255u, f) << 16));
+            }
+        } else if (op == OP_CONTRAST) {                          // blend with the L mean, int(sum / n + 0.5)
+            const float f = ag_f32(P[0]);
+            if (tid == 0) lsum = 0;
+            __syncthreads();
+            int s = 0;
+            for (int p = tid; p < n; p += AG_THREADS) s += ag_luma(ag_px(buf, p));
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+            if ((tid & 63) == 0) atomicAdd(&lsum, s);
+            __syncthreads();
+            const int mean = (int)((double)lsum / (double)n + 0.5);
+            for (int p = tid; p < n; p += AG_THREADS) {
+                const uint32_t v = ag_px(buf, p);
+                ag_put(buf, p, ag_blend(mean, v & 255u, f) | (ag_blend(mean, (v >> 8) & 255u, f) << 8) | (ag_blend(mean, (v >> 16) & 255u, f) << 16));
+            }
+        } else if (op == OP_SHARPNESS) {                         // blend with ImageFilter.SMOOTH (border pixels copied)
+            const float f = ag_f32(P[0]);
+            constexpr float k1 = 1.0f / 13.0f, k5 = 5.0f / 13.0f;
+            const uint8_t* img = buf;
+            ag_gather<LDS>(buf, alt, n, slot, [&](int p) -> uint32_t {
+                const int y = p / S, x = p - y * S;
+                const uint32_t v = ag_px(img, p);
+                if (x == 0 || y == 0 || x == S - 1 || y == S - 1) return v;
+                uint32_t r = 0;
+#pragma unroll 1
+                for (int c = 0; c < 3; ++c) {
+                    float acc = 0.0f;
+                    for (int dy = -1; dy <= 1; ++dy)
+                        for (int dx = -1; dx <= 1; ++dx)
+                            acc = acc + (dx == 0 && dy == 0 ? k5 : k1) * (float)img[3 * ((y + dy) * S + x + dx) + c];
+                    const int deg = acc <= 0.0f ? 0 : acc >= 255.0f ? 255 : (int)((double)acc + 0.5);
+                    r |= ag_blend(deg, (v >> (8 * c)) & 255u, f) << (8 * c);
+                }
+                return r;
+            });
+        } else if (op == OP_ROTATE) {                            // Image.rotate, NEAREST: Pillow's 16.16 fixed-point coordinates
+            const long a0 = P[0], a1 = P[1], a3 = P[2], a4 = P[3], xo = P[4], yo = P[5];
+            const uint8_t* img = buf;
+            ag_gather<LDS>(buf, alt, n, slot, [&](int p) -> uint32_t {
+                const int y = p / S, x = p - y * S;
+                const long xs = (xo + a0 * x + a1 * y) >> 16, ys = (yo + a3 * x + a4 * y) >> 16;
+                return (xs >= 0 && xs < S && ys >= 0 && ys < S) ? ag_px(img, (int)ys * S + (int)xs) : AG_FILL;
+            });
+        } else if (op == OP_SHEARX) {                            // Image.transform(AFFINE, BICUBIC), fill outside the image
+            const double a0 = ag_f64(P[0]), a1 = ag_f64(P[1]), a2 = ag_f64(P[2]), a3 = ag_f64(P[3]), a4 = ag_f64(P[4]), a5 = ag_f64(P[5]);
+            const uint8_t* img = buf;
+            ag_gather<LDS>(buf, alt, n, slot, [&](int p) -> uint32_t {
+                const int y = p / S, x = p - y * S;
+                double xin = a0 * (x + 0.5) + a1 * (y + 0.5) + a2;
+                double yin = a3 * (x + 0.5) + a4 * (y + 0.5) + a5;
+                if (!(xin >= 0.0 && xin < (double)S && yin >= 0.0 && yin < (double)S)) return AG_FILL;
+                xin -= 0.5;
+                yin -= 0.5;
+                const int xf = (int)floor(xin), yf = (int)floor(yin);
+                const double dx = xin - xf, dy = yin - yf;
+                int xs[4], ys[4];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    xs[j] = min(max(xf - 1 + j, 0), S - 1);
+                    ys[j] = min(max(yf - 1 + j, 0), S - 1) * S;
+                }
+                uint32_t r = 0;
+#pragma unroll 1
+                for (int c = 0; c < 3; ++c) {
+                    double row[4];
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const uint8_t* q = img + 3 * ys[j] + c;
+                        row[j] = ag_cubic(q[3 * xs[0]], q[3 * xs[1]], q[3 * xs[2]], q[3 * xs[3]], dx);
+                    }
+                    const double v = ag_cubic(row[0], row[1], row[2], row[3], dy);
+                    r |= (uint32_t)(v <= 0.0 ? 0 : v >= 255.0 ? 255 : (int)v) << (8 * c);
+                }
+                return r;
+            });
+        }
+    }
+    __syncthreads();
+    float* __restrict__ o = out + (long)b * 3 * n;
+    uint8_t* __restrict__ q = out_u8 ? out_u8 + (long)b * 3 * n : nullptr;
+    for (int p = tid; p < n; p += AG_THREADS) {
+        const uint32_t v = ag_px(buf, p);
+        const int c0 = v & 255u, c1 = (v >> 8) & 255u, c2 = (v >> 16) & 255u;
+        o[p] = lut[c0];
+        o[n + p] = lut[256 + c1];
+        o[2 * n + p] = lut[512 + c2];
+        if (q) ag_put(q, p, v);
+    }
+}
+
+// ---- C entry points -----------------------------------------------------------------------------------------------------------------------
+const char* pp_check_axis(const int32_t* tab_host, int64_t tab_numel, int64_t off, int64_t ks, int64_t n_in, int64_t n_out);
+
+extern "C" int64_t simseg_train_augment_scratch_bytes(int64_t B, int64_t S) {
+    if (B < 1 || S < AG_MIN_S || S > AG_MAX_S) return 0;
+    return B * ag_slot_bytes(S) * (ag_in_lds(S) ? 1 : 2);
+}
+
+static bool ag_finite(double v) { return v == v && v - v == 0.0; }
+
+extern "C" int simseg_train_augment(const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
+                                    const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S,
+                                    void* scratch, int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes,
+                                    void* stream) {
+    SS_CHECK(src && img_tab && img_tab_host && tab && tab_host && lut && out && scratch, "train_augment: null pointer");
+    SS_CHECK(B >= 1 && B < (1 << 20) && src_bytes > 0 && tab_numel > 0, "train_augment: bad sizes");
+    SS_CHECK(S >= AG_MIN_S && S <= AG_MAX_S, "train_augment: the output size is %d .. %d, got %ld", AG_MIN_S, AG_MAX_S, (long)S);
+    SS_CHECK(out_numel == B * 3 * S * S, "train_augment: out holds %ld floats, expected %ld", (long)out_numel, (long)(B * 3 * S * S));
+    SS_CHECK(!out_u8 || u8_bytes == B * 3 * S * S, "train_augment: out_u8 holds %ld bytes, expected %ld", (long)u8_bytes, (long)(B * 3 * S * S));
+    SS_CHECK(scratch_bytes >= simseg_train_augment_scratch_bytes(B, S), "train_augment: scratch of %ld bytes, %ld needed", (long)scratch_bytes,
+             (long)simseg_train_augment_scratch_bytes(B, S));
+    const int64_t lim = 1ll << 30;
+    struct Axis { int64_t off, ks, n_in; };
+    std::vector<Axis> seen;                                      // axes checked already (a batch shares few)
+    auto axis = [&](int64_t off, int64_t ks, int64_t n_in) -> const char* {
+        for (const Axis& a : seen)
+            if (a.off == off && a.ks == ks && a.n_in == n_in) return nullptr;
+        const char* e = pp_check_axis(tab_host, tab_numel, off, ks, n_in, S);
+        if (!e) seen.push_back({off, ks, n_in});
+        return e;
+    };
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t* it = img_tab_host + b * AG_COLS;
+        const int64_t H = it[AG_H], W = it[AG_W], top = it[AG_TOP], left = it[AG_LEFT], ch = it[AG_CH], cw = it[AG_CW];
+        SS_CHECK(H > 0 && W > 0 && H < lim && W < lim && H * W < lim, "train_augment: image %ld: bad source extent %ld x %ld", (long)b, (long)H, (long)W);
+        SS_CHECK(it[AG_SRC] >= 0 && it[AG_SRC] + H * W * 3 <= src_bytes, "train_augment: image %ld: source offset out of range", (long)b);
+        SS_CHECK(top >= 0 && left >= 0 && ch > 0 && cw > 0 && top + ch <= H && left + cw <= W,
+                 "train_augment: image %ld: the crop box does not lie inside the image", (long)b);
+        const char* e = axis(it[AG_HOFF], it[AG_HKS], cw);
+        SS_CHECK(!e, "train_augment: image %ld, horizontal: %s", (long)b, e);
+        e = axis(it[AG_VOFF], it[AG_VKS], ch);
+        SS_CHECK(!e, "train_augment: image %ld, vertical: %s", (long)b, e);
+        for (int k = 0; k < 2; ++k) {
+            const int64_t op = it[AG_OP1 + k];
+            const int64_t* P = it + AG_P1 + k * AG_SLOTS;
+            SS_CHECK(op >= 0 && op < OP_COUNT, "train_augment: image %ld: op %d has code %ld", (long)b, k + 1, (long)op);
+            if (op == OP_POSTERIZE) SS_CHECK(P[0] >= 0 && P[0] <= 255, "train_augment: image %ld: posterize mask %ld", (long)b, (long)P[0]);
+            if (op == OP_SOLARIZE) SS_CHECK(P[0] >= 0 && P[0] <= 256, "train_augment: image %ld: solarize threshold %ld", (long)b, (long)P[0]);
+            if (op == OP_COLOR || op == OP_CONTRAST || op == OP_SHARPNESS) {
+                float f;
+                const int32_t bits = (int32_t)P[0];
+                memcpy(&f, &bits, 4);
+                SS_CHECK(P[0] == bits && ag_finite(f), "train_augment: image %ld: the blend factor is not a finite float", (long)b);
+            }
+            if (op == OP_ROTATE)
+                for (int i = 0; i < 6; ++i)
+                    SS_CHECK(P[i] > -(1ll << 40) && P[i] < (1ll << 40), "train_augment: image %ld: rotate coefficient %d out of range", (long)b, i);
+            if (op == OP_SHEARX)
+                for (int i = 0; i < 6; ++i) {
+                    double v;
+                    memcpy(&v, &P[i], 8);
+                    SS_CHECK(ag_finite(v) && fabs(v) < 1e6, "train_augment: image %ld: affine coefficient %d is not finite and small", (long)b, i);
+                }
+        }
+    }
+    const int tiles = ((int)S + RZ_TW - 1) / RZ_TW * (((int)S + RZ_TH - 1) / RZ_TH);
+    hipLaunchKernelGGL(augment_resize_kernel, dim3((unsigned)(B * tiles)), dim3(256), 0, (hipStream_t)stream, static_cast<const uint8_t*>(src),
+                       img_tab, tab, static_cast<uint8_t*>(scratch), (int)S, tiles);
+    SS_LAUNCH_CHECK("train_augment (resize)");
+    uint8_t* s1 = static_cast<uint8_t*>(scratch);
+    if (ag_in_lds(S)) {
+        static bool attr = false;
+        if (!attr) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(augment_ops_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               (int)ag_slot_bytes(AG_LDS_MAX_S));
+            SS_CHECK(e == hipSuccess, "train_augment: hipFuncSetAttribute: %s", hipGetErrorString(e));
+            attr = true;
+        }
+        hipLaunchKernelGGL(augment_ops_kernel<true>, dim3((unsigned)B), dim3(AG_THREADS), (size_t)ag_slot_bytes(S), (hipStream_t)stream,
+                           img_tab, s1, nullptr, (int)S, lut, out, static_cast<uint8_t*>(out_u8));
+    } else {
+        hipLaunchKernelGGL(augment_ops_kernel<false>, dim3((unsigned)B), dim3(AG_THREADS), 0, (hipStream_t)stream, img_tab, s1,
+                           s1 + B * ag_slot_bytes(S), (int)S, lut, out, static_cast<uint8_t*>(out_u8));
+    }
+    SS_LAUNCH_CHECK("train_augment (ops)");
+    return 0;
+}

@@ -124,8 +124,8 @@ __global__ __launch_bounds__(256) void image_preprocess_kernel(const uint8_t* __
 }
 
 // One axis table on the host copy: bounds inside the input, n <= ksize, monotone (the kernel takes a tile's input span from its first and
-// last row), and 255 * sum|k| + 2^21 inside int32.
-static const char* pp_check_axis(const int32_t* tab_host, int64_t tab_numel, int64_t off, int64_t ks, int64_t n_in, int64_t n_out) {
+// last row), and 255 * sum|k| + 2^21 inside int32.  Also used by augment.hip.
+const char* pp_check_axis(const int32_t* tab_host, int64_t tab_numel, int64_t off, int64_t ks, int64_t n_in, int64_t n_out) {
     if (off < 0 || ks < 1 || n_out < 1 || n_in < 1 || ks > (1 << 24) || off + n_out * (2 + ks) > tab_numel) return "axis table out of range";
     const int32_t* b = tab_host + off;
     const int32_t* k = b + 2 * n_out;

@@ -735,3 +735,26 @@ def image_preprocess(src, plan, lut, want_u8=False):
     call("simseg_image_preprocess", ptr(_c(src)), src.numel(), ptr(plan["img_tab"]), it.ctypes.data, it.shape[0], ptr(plan["tab"]), th.ctypes.data,
          th.size, ptr(_c(lut)), ptr(out), out.numel(), ptr(u8), 0 if u8 is None else u8.numel(), stream())
     return out, u8
+
+
+# ---- training augmentation on the device (simseg_amd/augment.py; include/simseg_hip.h simseg_train_augment) ---------------------------------
+def train_augment(src, plan, lut, want_u8=False):
+    """src: the batch's uint8 [H, W, 3] images packed at plan['src_off'] (augment.plan) -> (fp32 [B, 3, S, S], uint8 [B, S, S, 3] or
+    None).  Two launches; the tables and parameters are checked on their host copies before them."""
+    require_gpu(src, lut, plan["img_tab"], plan["tab"])
+    if src.dtype != torch.uint8 or src.numel() != plan["src_bytes"]:
+        raise ValueError(f"train_augment: {plan['src_bytes']} packed uint8 bytes expected, got {src.numel()} {src.dtype}")
+    if lut.dtype != torch.float32 or tuple(lut.shape) != (3, 256):
+        raise ValueError(f"train_augment: fp32 [3, 256] look-up table expected, got {tuple(lut.shape)} {lut.dtype}")
+    it, th = plan["img_tab_host"], plan["tab_host"]
+    if it.dtype != "int64" or th.dtype != "int32" or not it.flags.c_contiguous or not th.flags.c_contiguous or it.ndim != 2 or \
+            tuple(plan["img_tab"].shape) != it.shape or plan["tab"].numel() != th.size:
+        raise ValueError("train_augment: the host copies of the tables are contiguous int64 [B, 30] / int32 arrays of the device tables' sizes")
+    B, S = it.shape[0], plan["size"]
+    dev = src.device
+    scratch = torch.empty(max(raw("simseg_train_augment_scratch_bytes", B, S), 16), device=dev, dtype=torch.uint8)
+    out = torch.empty(B, 3, S, S, device=dev, dtype=torch.float32)
+    u8 = torch.empty(B, S, S, 3, device=dev, dtype=torch.uint8) if want_u8 else None
+    call("simseg_train_augment", ptr(_c(src)), src.numel(), ptr(plan["img_tab"]), it.ctypes.data, B, ptr(plan["tab"]), th.ctypes.data, th.size,
+         ptr(_c(lut)), S, ptr(scratch), scratch.numel(), ptr(out), out.numel(), ptr(u8), 0 if u8 is None else u8.numel(), stream())
+    return out, u8
