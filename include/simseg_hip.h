@@ -230,6 +230,23 @@ int simseg_retrieval_rank_cols(const float* sim, const int64_t* row_gid, const i
 int simseg_recall_counts(const int32_t* has_match, const int32_t* rank, int64_t M, int b0, int b1, int b2, int32_t* counts4,
                          void* stream);
 
+/* Fused top-K retrieval search (search.hip): score[m, j] = the j-th largest <q[m,:], g[n,:]> over n, idx[m, j] = n + index_offset, rows
+ * ordered by descending score and equal scores by ascending index - the first K columns of a stable descending argsort of q @ g^T
+ * (EmbANN._ann, simseg/tasks/clip/hooks/utils.py) - without the M x N matrix: the score tiles stay in MFMA accumulators and only values
+ * that beat a row's running K-th best leave them (into a per-row candidate list in LDS).  q [M, D] / g [N, D] row-major with leading
+ * dimensions ldq / ldg (elements), both in `dtype`: 0 = fp32 operands and products, 1 = bf16 operands, exact products, fp32 accumulation
+ * (always bf16: this entry point has no fp16 flavour).  1 <= K <= 128, D % 8 == 0, 16-byte aligned rows.  N < K: the tail slots hold
+ * -inf / -1.  Inputs are taken to be finite; -0.0 scores are returned as +0.0.  When M has too few row tiles to fill the chip the gallery
+ * is split over blocks and the partial lists (in `workspace`, simseg_topk_search_workspace_bytes: 8 * M * K bytes per column split, 0
+ * when there is one) are merged by a second launch.  Bit-reproducible: the result does not depend on the order in which lanes append. */
+int64_t simseg_topk_search_workspace_bytes(int64_t M, int64_t N, int64_t D, int K, int dtype);
+int simseg_topk_search(const void* q, const void* g, int dtype, int64_t M, int64_t N, int64_t D, int64_t ldq, int64_t ldg, int K,
+                       int64_t index_offset, float* score, int32_t* idx, void* workspace, int64_t workspace_bytes, void* stream);
+/* The same merge for two finished lists [M, K] (score descending, idx < 0 = empty slot): the K best of their union under the same order.
+ * A gallery larger than memory goes through simseg_topk_search in chunks with index_offset and is reduced with this. */
+int simseg_topk_merge(const float* score_a, const int32_t* idx_a, const float* score_b, const int32_t* idx_b, float* score, int32_t* idx,
+                      int64_t M, int K, void* stream);
+
 /* torch.optim.AdamW (configs/clip/simseg.vit-b.yaml:31-36) over a flat fp32 segment; refreshes the bf16 compute copy. */
 int simseg_adamw_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2,
                       float eps, float weight_decay, int64_t step, float grad_scale, void* stream);

@@ -51,6 +51,22 @@ class EmbANN:
         matched = right_sorted == leftemb.group_idx.to(order.device).unsqueeze(1)
         return right_sorted, matched
 
+    def topk(self, leftemb: IndexedEmbInfo, rightemb: IndexedEmbInfo, k: int):
+        """(right_sorted[:, :k], matched[:, :k]): the first k columns of what `_ann` returns, without its M x N matrices.  On the GPU the
+        fused search kernel (simseg_amd.retrieval.search: fp32 products, equal scores by ascending column like the stable argsort of
+        `_ann`); on CPU tensors plain torch.  k is clipped to the number of right rows."""
+        a, b = leftemb.emb_mat, rightemb.emb_mat
+        k = min(int(k), b.shape[0])
+        if a.is_cuda:
+            from simseg_amd.retrieval import search
+            _, order = search(a, b, k)
+        else:
+            sim = a.float() @ b.float().T
+            order = torch.argsort(sim, dim=1, descending=True, stable=True)[:, :k]
+        right_sorted = rightemb.group_idx.to(order.device)[order]
+        matched = right_sorted == leftemb.group_idx.to(order.device).unsqueeze(1)
+        return right_sorted, matched
+
     def __call__(self, leftemb: IndexedEmbInfo, rightemb: IndexedEmbInfo):
         if self.chunk_size is None:
             return self._ann(leftemb, rightemb)

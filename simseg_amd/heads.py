@@ -311,6 +311,22 @@ def retrieval_recalls_both(left, left_gid, right, right_gid, bounds=(1, 5, 10)):
 
 
 @torch.no_grad()
+def zero_shot_topk(image_emb, class_emb, labels=None, ks=(1, 5), compute_dtype=F32):
+    """Zero-shot classification of image embeddings [B, P] against the classifier of class_text_embeddings [C, P]: the max(ks) best class
+    ids per image [B, max(ks)] (int64, best first, equal scores by ascending class id) from the fused search kernel - the [B, C] logits
+    are never written.  With labels [B] also an int32 device tensor [len(ks)]: the number of images whose label is among their first k
+    predictions, for every k of ks.  No host read (like ops.recall_counts): the caller divides by B after its own sync."""
+    from .retrieval import search
+    kmax = max(int(k) for k in ks)
+    _, pred = search(image_emb, class_emb, kmax, compute_dtype=compute_dtype)
+    if labels is None:
+        return pred
+    hit = pred == labels.to(pred.device).long().unsqueeze(1)          # [B, kmax]; -1 in an empty slot matches no label
+    counts = torch.stack([hit[:, :int(k)].any(dim=1).sum() for k in ks]).to(torch.int32)
+    return pred, counts
+
+
+@torch.no_grad()
 def class_text_embeddings(model, input_ids, attention_mask, chunk=2048):
     """Zero-shot classifier weights (tools/seg_evaluation.py:57-75) as batched calls: input_ids / attention_mask are
     [C, P, L] (C classes x P prompt templates); the text tower runs over C*P captions in chunks and one kernel reduces the

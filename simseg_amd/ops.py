@@ -501,6 +501,67 @@ def recall_counts(has, rank, bounds=(1, 5, 10)):
     return counts
 
 
+TOPK_MAX = 128                 # simseg_topk_search / simseg_topk_merge: 1 <= K <= 128
+
+
+def _search_operand(t, dtype):
+    """[rows, D] operand of topk_search in `dtype` (fp32 or bf16): unit stride along D, any leading dimension that keeps rows 16-byte aligned."""
+    if t.dim() != 2:
+        raise ValueError("topk_search: operands are [rows, D] matrices")
+    if t.dtype != dtype:
+        if dtype == torch.bfloat16 and t.dtype == torch.float32:
+            t = cast(t.contiguous(), torch.bfloat16)
+        elif dtype == torch.float32 and t.dtype in HALF_TYPES:
+            t = t.float()
+        else:
+            raise TypeError(f"topk_search: cannot take {t.dtype} operands as {dtype}")
+    epc = 16 // t.element_size()
+    if t.stride(1) != 1 or (t.shape[0] > 1 and (t.stride(0) < t.shape[1] or t.stride(0) % epc)):
+        t = t.contiguous()
+    if t.data_ptr() % 16:
+        t = t.clone(memory_format=torch.contiguous_format)
+    return t
+
+
+def topk_search(q, g, k, index_offset=0, dtype=None):
+    """The k best rows of g [N, D] for every row of q [M, D] by inner product, fused (no M x N matrix): (score [M, k] fp32 descending,
+    idx [M, k] int32 = gallery row + index_offset); equal scores by ascending index, the order of a stable descending argsort; N < k
+    leaves -inf / -1 in the tail.  dtype: torch.float32 (fp32 products) or torch.bfloat16 (exact bf16 products, fp32 accumulation);
+    None takes q's.  D % 8 == 0."""
+    require_gpu(q, g)
+    dtype = dtype or q.dtype
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"topk_search: fp32 or bf16 operands, got {dtype}")
+    q, g = _search_operand(q, dtype), _search_operand(g, dtype)
+    M, D = q.shape
+    N = g.shape[0]
+    if g.shape[1] != D:
+        raise ValueError(f"topk_search: inner dims differ ({D} vs {g.shape[1]})")
+    k = int(k)
+    code = F32 if dtype == torch.float32 else BF16
+    score = torch.empty(M, k, device=q.device, dtype=torch.float32)
+    idx = torch.empty(M, k, device=q.device, dtype=torch.int32)
+    nbytes = raw("simseg_topk_search_workspace_bytes", M, N, D, k, code) if 1 <= k <= TOPK_MAX else 0
+    ws = torch.empty(nbytes // 8, device=q.device, dtype=torch.int64) if nbytes else None
+    ldq = q.stride(0) if M > 1 else D
+    ldg = g.stride(0) if N > 1 else D
+    call("simseg_topk_search", ptr(q), ptr(g), code, M, N, D, ldq, ldg, k, int(index_offset), ptr(score), ptr(idx), ptr(ws), nbytes, stream())
+    return score, idx
+
+
+def topk_merge(score_a, idx_a, score_b, idx_b):
+    """The k best of the union of two finished lists [M, k] of topk_search (same order, idx < 0 = empty slot)."""
+    require_gpu(score_a, idx_a, score_b, idx_b)
+    if not (score_a.shape == idx_a.shape == score_b.shape == idx_b.shape) or score_a.dim() != 2:
+        raise ValueError("topk_merge: four [M, k] tensors")
+    if score_a.dtype != torch.float32 or score_b.dtype != torch.float32 or idx_a.dtype != torch.int32 or idx_b.dtype != torch.int32:
+        raise TypeError("topk_merge: fp32 scores and int32 indices")
+    M, k = score_a.shape
+    score, idx = torch.empty_like(score_a), torch.empty_like(idx_a)
+    call("simseg_topk_merge", ptr(_c(score_a)), ptr(_c(idx_a)), ptr(_c(score_b)), ptr(_c(idx_b)), ptr(score), ptr(idx), M, k, stream())
+    return score, idx
+
+
 def adamw_step(p, g, m, v, p16, lr, betas, eps, weight_decay, step, grad_scale=1.0):
     call("simseg_adamw_step", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), p.numel(), float(lr), float(betas[0]), float(betas[1]),
          float(eps), float(weight_decay), int(step), float(grad_scale), stream())

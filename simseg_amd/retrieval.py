@@ -43,6 +43,35 @@ def gather_retrieval_sets(shard, group=None):
     return {k: v[valid] for k, v in full.items()}
 
 
+def search(queries, gallery, k, gallery_ids=None, compute_dtype=torch.float32):
+    """The k best gallery rows of every query row by inner product, on the device and without the M x N score matrix (ops.topk_search):
+    (scores [M, k] fp32 descending, index [M, k] int64); equal scores by ascending index, i.e. the first k columns of the stable descending
+    argsort EmbANN._ann takes of the full matrix.  Fewer than k gallery rows leave -inf / -1 in the tail.
+
+    gallery: a [N, D] tensor, or an iterable of (chunk [n_i, D], offset) pairs - chunk row j is gallery row offset + j - which is reduced
+    chunk by chunk with ops.topk_merge, so the gallery never has to be resident at once.
+    gallery_ids: optional [N] ids of the gallery rows (any integer dtype, on any device); the ids of the hits [M, k] are returned as a
+    third tensor, -1 in empty slots.
+    compute_dtype: torch.float32 (fp32 products) or torch.bfloat16 (operands rounded to bf16, exact products, fp32 accumulation)."""
+    from . import ops
+    if torch.is_tensor(gallery):
+        score, idx = ops.topk_search(queries, gallery, k, 0, compute_dtype)
+    else:
+        score = idx = None
+        q = ops._search_operand(queries, compute_dtype)          # converted once, not per chunk
+        for chunk, offset in gallery:
+            s, i = ops.topk_search(q, chunk, k, int(offset), compute_dtype)
+            score, idx = (s, i) if score is None else ops.topk_merge(score, idx, s, i)
+        if score is None:
+            raise ValueError("search: the gallery iterable is empty")
+    index = idx.long()
+    if gallery_ids is None:
+        return score, index
+    gid = gallery_ids.to(index.device)
+    ids = torch.where(index >= 0, gid[index.clamp_min(0)], torch.full_like(index, -1).to(gid.dtype))
+    return score, index, ids
+
+
 def retrieval_metrics(collection, name="coco"):
     """The rank-0 body of calcaulate_retrieval_metrics_and_log (:25-63) for the image-text datasets: unique images vs all captions,
     both directions, percentages + RSUM.  Returns the summary dict."""
