@@ -3,9 +3,9 @@
 // (simseg_amd/augment.py apply_pil).  TWO launches per batch, whatever its size and whichever ops were drawn.  DESIGN.md "Device-side
 // training augmentation" states every op's arithmetic.
 //
-// Launch 1 (augment_resize_kernel): preproc.hip's resample with a source row pitch - a workgroup of 256 threads owns a 64 x 32 output
-// tile, the input rows it needs pass through LDS in chunks after the horizontal pass, the vertical pass accumulates in registers - writing
-// packed uint8 [S, S, 3] into a scratch slot per image (slots 16-byte aligned).
+// Launch 1 (augment_resize_kernel): resample.h's pp_resample_tile, one 256-thread workgroup per output tile, on the crop box of the source
+// image (a source pointer at the box's origin and the image's row pitch), writing packed uint8 [S, S, 3] into a scratch slot per image
+// (slots 16-byte aligned).
 // Launch 2 (augment_ops_kernel): one workgroup of 1024 threads per image.  With S <= AG_LDS_MAX_S the image is copied into LDS (150,528
 // bytes at S = 224) and every op works there; larger images are worked on in their scratch slot, with a second slot as the target of the
 // geometric ops.  Point ops (posterize, solarize, invert, autocontrast, equalize) build a per-channel [3, 256] byte table (the last two
@@ -19,9 +19,7 @@
 #pragma clang fp contract(off)
 #include <math.h>
 
-#include <vector>
-
-#include "common.h"
+#include "resample.h"
 
 constexpr int AG_COLS = 30, AG_SLOTS = 8;
 enum { AG_SRC = 0, AG_H, AG_W, AG_TOP, AG_LEFT, AG_CH, AG_CW, AG_HOFF, AG_HKS, AG_VOFF, AG_VKS, AG_RSV, AG_OP1, AG_OP2, AG_P1 };
@@ -30,84 +28,30 @@ enum { OP_NONE = 0, OP_POSTERIZE, OP_SOLARIZE, OP_INVERT, OP_AUTOCONTRAST, OP_EQ
 constexpr int AG_MIN_S = 32, AG_MAX_S = 384;
 constexpr int AG_THREADS = 1024;
 constexpr int AG_LDS_MAX_S = 230;                                   // 230 * 230 * 3 = 158,700 bytes + the static LDS below <= 160 KiB
-constexpr int RZ_TW = 64, RZ_TH = 32, RZ_CR = 48, RZ_RPT = RZ_TH / 4, RZ_BITS = 22;
 constexpr uint32_t AG_FILL = 128u | (128u << 8) | (128u << 16);
 
 __host__ __device__ inline int64_t ag_slot_bytes(int64_t S) { return (3 * S * S + 15) / 16 * 16; }
 static inline bool ag_in_lds(int64_t S) { return S <= AG_LDS_MAX_S; }
 
 // ---- launch 1: crop + resize -------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int rz_clip8(int acc) { return min(max(acc >> RZ_BITS, 0), 255); }
-
 __global__ __launch_bounds__(256) void augment_resize_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ img_tab,
                                                              const int* __restrict__ tab, uint8_t* __restrict__ scratch, int S,
                                                              int tiles_per_image) {
-    __shared__ uint32_t hbuf[RZ_CR * RZ_TW];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    __shared__ uint32_t hbuf[PP_CR * PP_TW];
     const int b = blockIdx.x / tiles_per_image, tile = blockIdx.x % tiles_per_image;
     const int64_t* it = img_tab + (long)b * AG_COLS;
-    const long src_off = it[AG_SRC];
     const long pitch = it[AG_W];
-    const int top = (int)it[AG_TOP], left = (int)it[AG_LEFT], hks = (int)it[AG_HKS], vks = (int)it[AG_VKS];
     const int* __restrict__ hb = tab + it[AG_HOFF];               // bounds [S, 2] inside the crop, then coefficients [S, hks]
-    const int* __restrict__ hk = hb + 2 * (long)S;
     const int* __restrict__ vb = tab + it[AG_VOFF];
-    const int* __restrict__ vk = vb + 2 * (long)S;
-    const int tiles_x = (S + RZ_TW - 1) / RZ_TW;
-    const int x0 = (tile % tiles_x) * RZ_TW, y0 = (tile / tiles_x) * RZ_TH;
-    const int nx = min(RZ_TW, S - x0), ny = min(RZ_TH, S - y0);
-    const bool xin = lane < nx;
-    const int X = x0 + lane;
-    const int hx = xin ? hb[2 * X] : 0, hn = xin ? hb[2 * X + 1] : 0;
-    const int* __restrict__ hkx = hk + (long)(xin ? X : 0) * hks;
-    const int rmin = vb[2 * y0], rmax = vb[2 * (y0 + ny - 1)] + vb[2 * (y0 + ny - 1) + 1];
-    int acc[RZ_RPT][3];
-#pragma unroll
-    for (int r = 0; r < RZ_RPT; ++r) acc[r][0] = acc[r][1] = acc[r][2] = 1 << (RZ_BITS - 1);
-    for (int r0 = rmin; r0 < rmax; r0 += RZ_CR) {
-        const int rows = min(RZ_CR, rmax - r0);
-        for (int rr = wave; rr < rows; rr += 4) {
-            const uint8_t* __restrict__ p = src + src_off + ((long)(top + r0 + rr) * pitch + left + hx) * 3;
-            int a0 = 1 << (RZ_BITS - 1), a1 = a0, a2 = a0;
-            for (int i = 0; i < hn; ++i) {
-                const int k = hkx[i];
-                a0 += (int)p[3 * i] * k;
-                a1 += (int)p[3 * i + 1] * k;
-                a2 += (int)p[3 * i + 2] * k;
-            }
-            hbuf[rr * RZ_TW + lane] = (uint32_t)rz_clip8(a0) | ((uint32_t)rz_clip8(a1) << 8) | ((uint32_t)rz_clip8(a2) << 16);
-        }
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < RZ_RPT; ++r) {
-            const int yy = wave + 4 * r;
-            if (yy < ny) {
-                const int Y = y0 + yy;
-                const int ymin = vb[2 * Y], yn = vb[2 * Y + 1];
-                const int* __restrict__ vky = vk + (long)Y * vks;
-                const int jlo = max(ymin, r0), jhi = min(ymin + yn, r0 + rows);
-                for (int j = jlo; j < jhi; ++j) {
-                    const int k = vky[j - ymin];
-                    const uint32_t v = hbuf[(j - r0) * RZ_TW + lane];
-                    acc[r][0] += (int)(v & 255u) * k;
-                    acc[r][1] += (int)((v >> 8) & 255u) * k;
-                    acc[r][2] += (int)((v >> 16) & 255u) * k;
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (!xin) return;
+    const int tiles_x = (S + PP_TW - 1) / PP_TW;
+    const int x0 = (tile % tiles_x) * PP_TW, y0 = (tile / tiles_x) * PP_TH;
     uint8_t* __restrict__ dst = scratch + b * ag_slot_bytes(S);
-#pragma unroll
-    for (int r = 0; r < RZ_RPT; ++r) {
-        const int yy = wave + 4 * r;
-        if (yy < ny) {
-            uint8_t* q = dst + ((long)(y0 + yy) * S + x0 + lane) * 3;
-            q[0] = (uint8_t)rz_clip8(acc[r][0]); q[1] = (uint8_t)rz_clip8(acc[r][1]); q[2] = (uint8_t)rz_clip8(acc[r][2]);
-        }
-    }
+    pp_resample_tile(hbuf, src + it[AG_SRC] + (it[AG_TOP] * pitch + it[AG_LEFT]) * 3, pitch, hb, hb + 2 * (long)S, (int)it[AG_HKS], vb,
+                     vb + 2 * (long)S, (int)it[AG_VKS], x0, y0, min(PP_TW, S - x0), min(PP_TH, S - y0),
+                     [=](int yy, int lane, int c0, int c1, int c2) {
+        uint8_t* q = dst + ((long)(y0 + yy) * S + x0 + lane) * 3;
+        q[0] = (uint8_t)c0; q[1] = (uint8_t)c1; q[2] = (uint8_t)c2;
+    });
 }
 
 // ---- launch 2: the ops ------------------------------------------------------------------------------------------------------------------
@@ -340,8 +284,6 @@ __global__ __launch_bounds__(AG_THREADS) void augment_ops_kernel(const int64_t* 
 }
 
 // ---- C entry points -----------------------------------------------------------------------------------------------------------------------
-const char* pp_check_axis(const int32_t* tab_host, int64_t tab_numel, int64_t off, int64_t ks, int64_t n_in, int64_t n_out);
-
 extern "C" int64_t simseg_train_augment_scratch_bytes(int64_t B, int64_t S) {
     if (B < 1 || S < AG_MIN_S || S > AG_MAX_S) return 0;
     return B * ag_slot_bytes(S) * (ag_in_lds(S) ? 1 : 2);
@@ -360,26 +302,17 @@ extern "C" int simseg_train_augment(const void* src, int64_t src_bytes, const in
     SS_CHECK(!out_u8 || u8_bytes == B * 3 * S * S, "train_augment: out_u8 holds %ld bytes, expected %ld", (long)u8_bytes, (long)(B * 3 * S * S));
     SS_CHECK(scratch_bytes >= simseg_train_augment_scratch_bytes(B, S), "train_augment: scratch of %ld bytes, %ld needed", (long)scratch_bytes,
              (long)simseg_train_augment_scratch_bytes(B, S));
-    const int64_t lim = 1ll << 30;
-    struct Axis { int64_t off, ks, n_in; };
-    std::vector<Axis> seen;                                      // axes checked already (a batch shares few)
-    auto axis = [&](int64_t off, int64_t ks, int64_t n_in) -> const char* {
-        for (const Axis& a : seen)
-            if (a.off == off && a.ks == ks && a.n_in == n_in) return nullptr;
-        const char* e = pp_check_axis(tab_host, tab_numel, off, ks, n_in, S);
-        if (!e) seen.push_back({off, ks, n_in});
-        return e;
-    };
+    PpAxisCache axes{tab_host, tab_numel};                       // (a batch shares few axes)
     for (int64_t b = 0; b < B; ++b) {
         const int64_t* it = img_tab_host + b * AG_COLS;
         const int64_t H = it[AG_H], W = it[AG_W], top = it[AG_TOP], left = it[AG_LEFT], ch = it[AG_CH], cw = it[AG_CW];
-        SS_CHECK(H > 0 && W > 0 && H < lim && W < lim && H * W < lim, "train_augment: image %ld: bad source extent %ld x %ld", (long)b, (long)H, (long)W);
-        SS_CHECK(it[AG_SRC] >= 0 && it[AG_SRC] + H * W * 3 <= src_bytes, "train_augment: image %ld: source offset out of range", (long)b);
+        SS_CHECK(pp_extent_ok(H, W), "train_augment: image %ld: bad source extent %ld x %ld", (long)b, (long)H, (long)W);
+        SS_CHECK(pp_offset_ok(it[AG_SRC], H, W, src_bytes), "train_augment: image %ld: source offset out of range", (long)b);
         SS_CHECK(top >= 0 && left >= 0 && ch > 0 && cw > 0 && top + ch <= H && left + cw <= W,
                  "train_augment: image %ld: the crop box does not lie inside the image", (long)b);
-        const char* e = axis(it[AG_HOFF], it[AG_HKS], cw);
+        const char* e = axes.check(it[AG_HOFF], it[AG_HKS], cw, S);
         SS_CHECK(!e, "train_augment: image %ld, horizontal: %s", (long)b, e);
-        e = axis(it[AG_VOFF], it[AG_VKS], ch);
+        e = axes.check(it[AG_VOFF], it[AG_VKS], ch, S);
         SS_CHECK(!e, "train_augment: image %ld, vertical: %s", (long)b, e);
         for (int k = 0; k < 2; ++k) {
             const int64_t op = it[AG_OP1 + k];
@@ -404,7 +337,7 @@ extern "C" int simseg_train_augment(const void* src, int64_t src_bytes, const in
                 }
         }
     }
-    const int tiles = ((int)S + RZ_TW - 1) / RZ_TW * (((int)S + RZ_TH - 1) / RZ_TH);
+    const int tiles = ((int)S + PP_TW - 1) / PP_TW * (((int)S + PP_TH - 1) / PP_TH);
     hipLaunchKernelGGL(augment_resize_kernel, dim3((unsigned)(B * tiles)), dim3(256), 0, (hipStream_t)stream, static_cast<const uint8_t*>(src),
                        img_tab, tab, static_cast<uint8_t*>(scratch), (int)S, tiles);
     SS_LAUNCH_CHECK("train_augment (resize)");

@@ -777,20 +777,27 @@ def slide_planes(flat, plan, b):
     return flat[o:o + plan["ncand"] * H * W].view(plan["ncand"], H, W)
 
 
-# ---- image preprocessing on the device (simseg_amd/preproc.py; include/simseg_hip.h simseg_image_preprocess) ----------------------------------
+# ---- image preprocessing and training augmentation on the device (simseg_amd/preproc.py, augment.py; include/simseg_hip.h) -----------------------
+def _check_packed_batch(who, src, plan, lut, cols, need_2d=False):
+    """What image_preprocess and train_augment ask of their arguments: the packed source, the look-up table, and host copies of the
+    tables ([B, cols] image table) that the C entry point can read.  -> (img_tab_host, tab_host)."""
+    require_gpu(src, lut, plan["img_tab"], plan["tab"])
+    if src.dtype != torch.uint8 or src.numel() != plan["src_bytes"]:
+        raise ValueError(f"{who}: {plan['src_bytes']} packed uint8 bytes expected, got {src.numel()} {src.dtype}")
+    if lut.dtype != torch.float32 or tuple(lut.shape) != (3, 256):
+        raise ValueError(f"{who}: fp32 [3, 256] look-up table expected, got {tuple(lut.shape)} {lut.dtype}")
+    it, th = plan["img_tab_host"], plan["tab_host"]
+    if it.dtype != "int64" or th.dtype != "int32" or not it.flags.c_contiguous or not th.flags.c_contiguous or \
+            (need_2d and it.ndim != 2) or tuple(plan["img_tab"].shape) != it.shape or plan["tab"].numel() != th.size:
+        raise ValueError(f"{who}: the host copies of the tables are contiguous int64 [B, {cols}] / int32 arrays of the device tables' sizes")
+    return it, th
+
+
 def image_preprocess(src, plan, lut, want_u8=False):
     """src: the batch's uint8 [H, W, 3] images packed at plan['src_off'] (preproc.plan) -> (fp32 flat, image b's [3, OH, OW] planes at
     plan['out_off'][b]; uint8 flat with its [OH, OW, 3] bytes at the same offset, or None).  The tables are checked on their host copies
     before the launch."""
-    require_gpu(src, lut, plan["img_tab"], plan["tab"])
-    if src.dtype != torch.uint8 or src.numel() != plan["src_bytes"]:
-        raise ValueError(f"image_preprocess: {plan['src_bytes']} packed uint8 bytes expected, got {src.numel()} {src.dtype}")
-    if lut.dtype != torch.float32 or tuple(lut.shape) != (3, 256):
-        raise ValueError(f"image_preprocess: fp32 [3, 256] look-up table expected, got {tuple(lut.shape)} {lut.dtype}")
-    it, th = plan["img_tab_host"], plan["tab_host"]
-    if it.dtype != "int64" or th.dtype != "int32" or not it.flags.c_contiguous or not th.flags.c_contiguous or \
-            tuple(plan["img_tab"].shape) != it.shape or plan["tab"].numel() != th.size:
-        raise ValueError("image_preprocess: the host copies of the tables are contiguous int64 [B, 16] / int32 arrays of the device tables' sizes")
+    it, th = _check_packed_batch("image_preprocess", src, plan, lut, 16)
     out = torch.empty(plan["out_numel"], device=src.device, dtype=torch.float32)
     u8 = torch.empty(plan["out_numel"], device=src.device, dtype=torch.uint8) if want_u8 else None
     call("simseg_image_preprocess", ptr(_c(src)), src.numel(), ptr(plan["img_tab"]), it.ctypes.data, it.shape[0], ptr(plan["tab"]), th.ctypes.data,
@@ -798,19 +805,10 @@ def image_preprocess(src, plan, lut, want_u8=False):
     return out, u8
 
 
-# ---- training augmentation on the device (simseg_amd/augment.py; include/simseg_hip.h simseg_train_augment) ---------------------------------
 def train_augment(src, plan, lut, want_u8=False):
     """src: the batch's uint8 [H, W, 3] images packed at plan['src_off'] (augment.plan) -> (fp32 [B, 3, S, S], uint8 [B, S, S, 3] or
     None).  Two launches; the tables and parameters are checked on their host copies before them."""
-    require_gpu(src, lut, plan["img_tab"], plan["tab"])
-    if src.dtype != torch.uint8 or src.numel() != plan["src_bytes"]:
-        raise ValueError(f"train_augment: {plan['src_bytes']} packed uint8 bytes expected, got {src.numel()} {src.dtype}")
-    if lut.dtype != torch.float32 or tuple(lut.shape) != (3, 256):
-        raise ValueError(f"train_augment: fp32 [3, 256] look-up table expected, got {tuple(lut.shape)} {lut.dtype}")
-    it, th = plan["img_tab_host"], plan["tab_host"]
-    if it.dtype != "int64" or th.dtype != "int32" or not it.flags.c_contiguous or not th.flags.c_contiguous or it.ndim != 2 or \
-            tuple(plan["img_tab"].shape) != it.shape or plan["tab"].numel() != th.size:
-        raise ValueError("train_augment: the host copies of the tables are contiguous int64 [B, 30] / int32 arrays of the device tables' sizes")
+    it, th = _check_packed_batch("train_augment", src, plan, lut, 30, need_2d=True)
     B, S = it.shape[0], plan["size"]
     dev = src.device
     scratch = torch.empty(max(raw("simseg_train_augment_scratch_bytes", B, S), 16), device=dev, dtype=torch.uint8)

@@ -15,7 +15,7 @@ import torch
 PRECISION_BITS = 22
 FILTERS = {"bilinear": 1.0, "bicubic": 2.0}        # filter -> support
 IMG_COLS = 16                                      # int64 columns of the image table (include/simseg_hip.h simseg_image_preprocess)
-TILE_W, TILE_H = 64, 32                            # output tile of one workgroup (csrc/preproc.hip PP_TW, PP_TH)
+TILE_W, TILE_H = 64, 32                            # output tile of one workgroup (csrc/resample.h PP_TW, PP_TH)
 
 
 def _bilinear(x):

@@ -163,6 +163,21 @@ def test_plan_refuses_bad_input():
         A.plan([(80, 600)], A.explicit_params([(0, 0, 9, 10)], "rotate", 90.0), 224, "cpu")
 
 
+def test_shared_resample_cases_on_the_host():
+    """The (image, box) cases of tests/test_gpu_resample_shared.py without a GPU: augment.plan takes the four boxes, the preprocessing
+    plan of the four crops reads the very same axis tables, and Pillow's crop + resize is resample_ref of the crop."""
+    import test_gpu_resample_shared as T
+    from simseg_amd import augment as A, preproc
+    ap = A.plan([hw for hw, _ in T.CASES], A.explicit_params([box for _, box in T.CASES]), T.S, "cpu")
+    pp = T.crop_plan("cpu")
+    assert pp["out_sizes"] == [(T.S, T.S)] * len(T.CASES) and pp["tab_host"] is ap["tab_host"]
+    a, p = ap["img_tab_host"], pp["img_tab_host"]
+    assert np.array_equal(a[:, A.C_HOFF:A.C_VKS + 1], p[:, 8:12]) and np.array_equal(a[:, A.C_CH:A.C_CW + 1], p[:, 1:3])
+    raws = T._raws()
+    for raw, want, (_, (t, l, h, w)) in zip(raws, T.pillow_route(raws), T.CASES):
+        assert np.array_equal(preproc.resample_ref(np.ascontiguousarray(raw[t:t + h, l:l + w]), (T.S, T.S), "bilinear"), want)
+
+
 @pytest.mark.parametrize("path", ["configs/clip/simseg.vit-b.yaml", "configs/clip/simseg.vit-s.yaml"])
 def test_build_train_augmentation_on_shipped_configs(path):
     import torch
