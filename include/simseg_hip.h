@@ -368,6 +368,25 @@ int64_t simseg_train_augment_scratch_bytes(int64_t B, int64_t S);
 int simseg_train_augment(const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
                          const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S, void* scratch,
                          int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes, void* stream);
+/* Training transforms (simseg_amd/pipeline.py, DESIGN.md "Device-side training transforms"): the general chain behind
+ * simseg_train_augment's special case, on the same packed source, axis tables, look-up table and scratch rule, in TWO launches.  Per
+ * image: integer source box -> Pillow's uint8 resize of the box to RH x RW (either filter; RH = box h and RW = box w copy the box) ->
+ * the S x S output window of the resized image at (window top, window left), its columns mirrored when flip != 0 -> a chain of up to 5
+ * ops in order (the codes of simseg_train_augment plus 11 brightness: float bits of the blend factor with black) -> out fp32
+ * [B, 3, S, S] = lut at the final byte, EXCEPT inside the image's erase boxes (later boxes win), where the value is the fill of the
+ * mode: 0 const 0.0, 1 rand one normal per (image, box, channel), 2 pixel one normal per (image, box, channel, y, x).  A normal is
+ * sqrt(-2 ln u1) cos(2 pi u2), u1 = ((h1 >> 8) + 1) 2^-24, u2 = (h2 >> 8) 2^-24, h1 = hash_u32(seed, 2 i), h2 = hash_u32(seed, 2 i + 1),
+ * i = ((b * 4 + box) * 3 + channel) * 2^18 + y * 512 + x (y = x = 0 in mode 1; b = the image's row in the table).  out_u8 (optional)
+ * receives the bytes after the chain, before the look-up and the erasing.
+ * img_tab int64 [B, 81] = (0 src byte offset, 1 H, 2 W, 3..6 box top, left, h, w, 7..10 offset and ksize of the horizontal axis table
+ * (box w -> RW) and of the vertical one (box h -> RH), 11 RH, 12 RW, 13 window top, 14 window left, 15 flip, 16 number of ops,
+ * 17 number of erase boxes (0..4), 18 erase mode, 19 noise seed, 20..35 four erase boxes (top, left, h, w) in output coordinates,
+ * 36..40 op codes, 41..80 eight parameter slots per op).  Every field is checked on the HOST copies before anything is launched; the
+ * caller guarantees that they hold what the device tables hold. */
+int64_t simseg_train_transforms_scratch_bytes(int64_t B, int64_t S);
+int simseg_train_transforms(const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
+                            const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S, void* scratch,
+                            int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes, void* stream);
 /* cv2.dilate / cv2.erode with a 7x7 ones kernel, ONE iteration (the third positional argument in :156-157 is `dst`, not
  * `iterations`), default border (never wins) on byte images [M,H,W]; erode = 0 dilate, 1 erode.  out must not alias in. */
 int simseg_morph7(const void* in, void* out, int64_t M, int64_t H, int64_t W, int erode, void* stream);

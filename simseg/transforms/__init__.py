@@ -3,7 +3,10 @@ torchvision (absent here): PIL resampling + torch tensors.  build_transforms / b
 augmentations (autoaug, random_resize_crop, random erasing) and raise for them; build_train_augmentation is their route: the host decodes,
 the parameters are sampled on the host, and crop, resize, AutoAugment and normalisation run on the device (simseg_amd/augment.py).
 build_device_transforms is the eval-time route that leaves only the decode on the host: resize, crop and normalisation run on the device
-(simseg_amd/preproc.py)."""
+(simseg_amd/preproc.py).  build_train_pipeline is the general training route: every train_transforms list of the grammar
+list := geometry+ colour* (geometry: resize | resize_bicubic | random_resize_crop | center_crop | random_crop | random_flip; colour:
+autoaug | color_jitter), plus random erasing when transforms.random_erasing.reprob > 0, sampled on the host and applied on the device
+in two launches (simseg_amd/pipeline.py); the three other builders keep their behaviour."""
 import numpy as np
 import torch
 from PIL import Image
@@ -11,7 +14,7 @@ from PIL import Image
 from simseg.utils import logger
 from simseg.utils.registry import Registry
 
-__all__ = ["TRANSFORMS", "build_transforms", "build_device_transforms", "build_train_augmentation"]
+__all__ = ["TRANSFORMS", "build_transforms", "build_device_transforms", "build_train_augmentation", "build_train_pipeline"]
 
 TRANSFORMS = Registry("TRANSFORMS")
 
@@ -147,3 +150,14 @@ def build_train_augmentation(cfg):
     aug = TrainAugment(rrc.size, tuple(rrc.scale), autoaug=len(names) == 2, lut=_normalize_lut(cfg))
     logger.emph("train image augmentation on the device:", aug)
     return _to_u8, aug
+
+
+def build_train_pipeline(cfg):
+    """-> (host_op, pipeline) of the general training route: host_op maps a PIL image to its uint8 [H, W, 3] tensor and nothing else;
+    pipeline (simseg_amd.pipeline.TrainPipeline), given a batch of those tensors and a numpy Generator, samples every random choice of
+    cfg.transforms.train_transforms (and of random erasing, when its reprob > 0) on the host and returns the transformed, normalised fp32
+    [B, 3, S, S] batch from the device.  A list outside the grammar raises NotImplementedError naming the rule it breaks."""
+    from simseg_amd.pipeline import TrainPipeline, parse_chain
+    pipe = TrainPipeline(parse_chain(list(cfg.transforms.train_transforms), cfg, lut=_normalize_lut(cfg)))
+    logger.emph("train image transforms on the device:", pipe)
+    return _to_u8, pipe

@@ -116,18 +116,23 @@ def sample_params(sizes, rng, scale=(0.6, 1.0), autoaug=True):
         r = {"top": top, "left": left, "h": h, "w": w, "fallback": fb, "policy": -1, "op1": 0, "mag1": 0.0, "apply1": 0, "sign1": 1,
              "op2": 0, "mag2": 0.0, "apply2": 0, "sign2": 1}
         if autoaug:
-            k = int(rng.integers(0, len(POLICY)))
-            p1, o1, m1, p2, o2, m2 = POLICY[k]
-            r["policy"] = k
-            for j, (p, op, mi) in enumerate(((p1, o1, m1), (p2, o2, m2)), 1):
-                applied = rng.random() < p
-                r[f"op{j}"] = OP_CODE[op]
-                r[f"mag{j}"] = float(MAGNITUDES[op][mi])
-                r[f"apply{j}"] = int(applied)
-                if applied and op in SIGNED:
-                    r[f"sign{j}"] = 1 if rng.integers(0, 2) else -1
+            draw_autoaug(rng, r)
         rows.append(r)
     return _params(rows)
+
+
+def draw_autoaug(rng, r):
+    """One image's AutoAugment draws into its row r: the sub-policy, then per op the apply flag and (applied, signed) the sign."""
+    k = int(rng.integers(0, len(POLICY)))
+    p1, o1, m1, p2, o2, m2 = POLICY[k]
+    r["policy"] = k
+    for j, (p, op, mi) in enumerate(((p1, o1, m1), (p2, o2, m2)), 1):
+        applied = rng.random() < p
+        r[f"op{j}"] = OP_CODE[op]
+        r[f"mag{j}"] = float(MAGNITUDES[op][mi])
+        r[f"apply{j}"] = int(applied)
+        if applied and op in SIGNED:
+            r[f"sign{j}"] = 1 if rng.integers(0, 2) else -1
 
 
 def explicit_params(boxes, op1="none", mag1=0.0, sign1=1, op2="none", mag2=0.0, sign2=1):

@@ -14,6 +14,11 @@
 // once the image is in LDS), the workgroup waits at a barrier, and the results are copied back.  The normalised output goes through the
 // host-filled [3, 256] fp32 table.
 //
+// simseg_train_transforms (DESIGN.md "Device-side training transforms") is the general chain on the same two kernels, instantiated for
+// its wider table (WIDE): launch 1 resamples the source box with either filter to RH x RW, keeps the S x S output window and mirrors its
+// columns for a flip; launch 2 runs a chain of up to five ops (brightness added) and replaces the look-up value inside the image's erase
+// boxes by the fill of the mode.  The WIDE = false instances are simseg_train_augment's, as they were.
+//
 // Exactness: the blends, the 3x3 smoothing, autocontrast's scale and the bicubic shear must round as Pillow's C code does, so floating-
 // point contraction is off for this file (build.py compiles with -O3 and the default contraction, which would form FMAs).
 #pragma clang fp contract(off)
@@ -24,7 +29,11 @@
 constexpr int AG_COLS = 30, AG_SLOTS = 8;
 enum { AG_SRC = 0, AG_H, AG_W, AG_TOP, AG_LEFT, AG_CH, AG_CW, AG_HOFF, AG_HKS, AG_VOFF, AG_VKS, AG_RSV, AG_OP1, AG_OP2, AG_P1 };
 enum { OP_NONE = 0, OP_POSTERIZE, OP_SOLARIZE, OP_INVERT, OP_AUTOCONTRAST, OP_EQUALIZE, OP_COLOR, OP_CONTRAST, OP_SHARPNESS, OP_ROTATE,
-       OP_SHEARX, OP_COUNT };
+       OP_SHEARX, OP_COUNT, OP_BRIGHTNESS = OP_COUNT, OP_COUNT_WIDE };   // OP_COUNT: the AutoAugment set simseg_train_augment takes
+// the wider table of simseg_train_transforms: columns 0 .. AG_VKS as above, then
+constexpr int TT_COLS = 81, TT_MAX_OPS = 5, TT_MAX_ERASE = 4;
+enum { TT_RH = 11, TT_RW, TT_WTOP, TT_WLEFT, TT_FLIP, TT_NOPS, TT_NERASE, TT_MODE, TT_SEED, TT_BOX = 20, TT_OP = 36, TT_P = 41 };
+enum { ER_CONST = 0, ER_RAND, ER_PIXEL, ER_MODES };
 constexpr int AG_MIN_S = 32, AG_MAX_S = 384;
 constexpr int AG_THREADS = 1024;
 constexpr int AG_LDS_MAX_S = 230;                                   // 230 * 230 * 3 = 158,700 bytes + the static LDS below <= 160 KiB
@@ -34,22 +43,27 @@ __host__ __device__ inline int64_t ag_slot_bytes(int64_t S) { return (3 * S * S 
 static inline bool ag_in_lds(int64_t S) { return S <= AG_LDS_MAX_S; }
 
 // ---- launch 1: crop + resize -------------------------------------------------------------------------------------------------------------
+template <bool WIDE>
 __global__ __launch_bounds__(256) void augment_resize_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ img_tab,
                                                              const int* __restrict__ tab, uint8_t* __restrict__ scratch, int S,
                                                              int tiles_per_image) {
     __shared__ uint32_t hbuf[PP_CR * PP_TW];
     const int b = blockIdx.x / tiles_per_image, tile = blockIdx.x % tiles_per_image;
-    const int64_t* it = img_tab + (long)b * AG_COLS;
+    const int64_t* it = img_tab + (long)b * (WIDE ? TT_COLS : AG_COLS);
     const long pitch = it[AG_W];
-    const int* __restrict__ hb = tab + it[AG_HOFF];               // bounds [S, 2] inside the crop, then coefficients [S, hks]
+    const int* __restrict__ hb = tab + it[AG_HOFF];               // bounds [RW, 2] inside the crop, then coefficients [RW, hks]
     const int* __restrict__ vb = tab + it[AG_VOFF];
     const int tiles_x = (S + PP_TW - 1) / PP_TW;
     const int x0 = (tile % tiles_x) * PP_TW, y0 = (tile / tiles_x) * PP_TH;
     uint8_t* __restrict__ dst = scratch + b * ag_slot_bytes(S);
-    pp_resample_tile(hbuf, src + it[AG_SRC] + (it[AG_TOP] * pitch + it[AG_LEFT]) * 3, pitch, hb, hb + 2 * (long)S, (int)it[AG_HKS], vb,
-                     vb + 2 * (long)S, (int)it[AG_VKS], x0, y0, min(PP_TW, S - x0), min(PP_TH, S - y0),
+    // WIDE: the S x S window of the RH x RW resized box; a flip writes column x of the window to column S - 1 - x
+    const long RW = WIDE ? it[TT_RW] : S, RH = WIDE ? it[TT_RH] : S;
+    const int wx = WIDE ? (int)it[TT_WLEFT] : 0, wy = WIDE ? (int)it[TT_WTOP] : 0;
+    const int xs = WIDE && it[TT_FLIP] ? -1 : 1, xb = xs < 0 ? S - 1 - x0 : x0;
+    pp_resample_tile(hbuf, src + it[AG_SRC] + (it[AG_TOP] * pitch + it[AG_LEFT]) * 3, pitch, hb, hb + 2 * RW, (int)it[AG_HKS], vb,
+                     vb + 2 * RH, (int)it[AG_VKS], wx + x0, wy + y0, min(PP_TW, S - x0), min(PP_TH, S - y0),
                      [=](int yy, int lane, int c0, int c1, int c2) {
-        uint8_t* q = dst + ((long)(y0 + yy) * S + x0 + lane) * 3;
+        uint8_t* q = dst + ((long)(y0 + yy) * S + xb + xs * lane) * 3;
         q[0] = (uint8_t)c0; q[1] = (uint8_t)c1; q[2] = (uint8_t)c2;
     });
 }
@@ -79,6 +93,14 @@ __device__ __forceinline__ double ag_cubic(double v1, double v2, double v3, doub
 __device__ __forceinline__ double ag_f64(int64_t bits) { return __longlong_as_double((long long)bits); }
 __device__ __forceinline__ float ag_f32(int64_t bits) { return __int_as_float((int)bits); }
 
+// One standard normal of the erase noise: the counter-based hash of common.h through Box-Muller (the index is stated in
+// include/simseg_hip.h and restated in float64 by pipeline.erase_noise_ref).  u1 in (0, 1] and 2 u2 in [0, 2) are exact in fp32.
+__device__ __forceinline__ float ag_normal(uint64_t seed, uint64_t i) {
+    const float u1 = (float)((hash_u32(seed, 2 * i) >> 8) + 1u) * 0x1p-24f;
+    const float u2x2 = (float)(hash_u32(seed, 2 * i + 1) >> 8) * 0x1p-23f;
+    return sqrtf(-2.0f * logf(u1)) * cospif(u2x2);
+}
+
 // Every pixel through f(p) -> packed RGB, all reads before any write: the results go to `alt` (global memory), the workgroup waits, and
 // then the LDS path copies them back into LDS (16-byte pieces) while the global path makes `alt` the image.  (Keeping them in registers
 // instead - 52 pixels per thread at S = 230 - spills the bicubic's working set at 1024 threads.)
@@ -96,7 +118,7 @@ __device__ __forceinline__ void ag_gather(uint8_t*& buf, uint8_t*& alt, int n, l
     }
 }
 
-template <bool LDS>
+template <bool LDS, bool WIDE>
 __global__ __launch_bounds__(AG_THREADS) void augment_ops_kernel(const int64_t* __restrict__ img_tab, uint8_t* __restrict__ scratch,
                                                                  uint8_t* __restrict__ scratch2, int S, const float* __restrict__ lut,
                                                                  float* __restrict__ out, uint8_t* __restrict__ out_u8) {
@@ -105,9 +127,10 @@ __global__ __launch_bounds__(AG_THREADS) void augment_ops_kernel(const int64_t* 
     __shared__ uint8_t tlut[3][256];
     __shared__ int lsum;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int64_t* it = img_tab + (long)b * AG_COLS;
+    const int64_t* it = img_tab + (long)b * (WIDE ? TT_COLS : AG_COLS);
     const int n = S * S;
     const long slot = ag_slot_bytes(S);
+    const int nops = WIDE ? (int)it[TT_NOPS] : 2;
     uint8_t* buf;
     uint8_t* alt = nullptr;
     if constexpr (LDS) {
@@ -120,9 +143,9 @@ __global__ __launch_bounds__(AG_THREADS) void augment_ops_kernel(const int64_t* 
         buf = scratch + b * slot;
         alt = scratch2 + b * slot;
     }
-    for (int k = 0; k < 2; ++k) {
-        const int op = (int)it[AG_OP1 + k];
-        const int64_t* P = it + AG_P1 + k * AG_SLOTS;
+    for (int k = 0; k < nops; ++k) {
+        const int op = (int)it[(WIDE ? TT_OP : AG_OP1) + k];
+        const int64_t* P = it + (WIDE ? TT_P : AG_P1) + k * AG_SLOTS;
         __syncthreads();                                         // the image as the last step left it
         if (op == OP_NONE) continue;
         if (op <= OP_EQUALIZE) {
@@ -194,6 +217,9 @@ __global__ __launch_bounds__(AG_THREADS) void augment_ops_kernel(const int64_t* 
                 const int L = ag_luma(v);
                 ag_put(buf, p, ag_blend(L, v & 255u, f) | (ag_blend(L, (v >> 8) & 255u, f) << 8) | (ag_blend(L, (v >> 16) & 255u, f) << 16));
             }
+        } else if (WIDE && op == OP_BRIGHTNESS) {                // blend with black
+            const float f = ag_f32(P[0]);
+            for (int i = tid; i < 3 * n; i += AG_THREADS) buf[i] = (uint8_t)ag_blend(0, buf[i], f);
         } else if (op == OP_CONTRAST) {                          // blend with the L mean, int(sum / n + 0.5)
             const float f = ag_f32(P[0]);
             if (tid == 0) lsum = 0;
@@ -273,12 +299,39 @@ __global__ __launch_bounds__(AG_THREADS) void augment_ops_kernel(const int64_t* 
     __syncthreads();
     float* __restrict__ o = out + (long)b * 3 * n;
     uint8_t* __restrict__ q = out_u8 ? out_u8 + (long)b * 3 * n : nullptr;
+    const int nerase = WIDE ? (int)it[TT_NERASE] : 0;
+    if (nerase == 0) {
+        for (int p = tid; p < n; p += AG_THREADS) {
+            const uint32_t v = ag_px(buf, p);
+            const int c0 = v & 255u, c1 = (v >> 8) & 255u, c2 = (v >> 16) & 255u;
+            o[p] = lut[c0];
+            o[n + p] = lut[256 + c1];
+            o[2 * n + p] = lut[512 + c2];
+            if (q) ag_put(q, p, v);
+        }
+        return;
+    }
+    // random erasing, fused into the write: inside a box the fill replaces the look-up value, the last box that holds the pixel wins
+    // (moving this loop out of line did not bring the no-box path closer to simseg_train_augment's and cost the erased lists 4 %)
+    const int mode = (int)it[TT_MODE];
+    const uint64_t seed = (uint64_t)it[TT_SEED];
     for (int p = tid; p < n; p += AG_THREADS) {
         const uint32_t v = ag_px(buf, p);
-        const int c0 = v & 255u, c1 = (v >> 8) & 255u, c2 = (v >> 16) & 255u;
-        o[p] = lut[c0];
-        o[n + p] = lut[256 + c1];
-        o[2 * n + p] = lut[512 + c2];
+        const int y = p / S, x = p - y * S;
+        int box = -1;
+        for (int k = 0; k < nerase; ++k) {
+            const int64_t* e = it + TT_BOX + 4 * k;
+            if (y >= e[0] && y < e[0] + e[2] && x >= e[1] && x < e[1] + e[3]) box = k;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            float r = lut[256 * c + ((v >> (8 * c)) & 255u)];
+            if (box >= 0) {
+                const uint64_t i = (uint64_t)(((long)b * TT_MAX_ERASE + box) * 3 + c) << 18;
+                r = mode == ER_CONST ? 0.0f : ag_normal(seed, mode == ER_PIXEL ? i + (uint64_t)(y * 512 + x) : i);
+            }
+            o[c * n + p] = r;
+        }
         if (q) ag_put(q, p, v);
     }
 }
@@ -288,74 +341,116 @@ extern "C" int64_t simseg_train_augment_scratch_bytes(int64_t B, int64_t S) {
     if (B < 1 || S < AG_MIN_S || S > AG_MAX_S) return 0;
     return B * ag_slot_bytes(S) * (ag_in_lds(S) ? 1 : 2);
 }
+extern "C" int64_t simseg_train_transforms_scratch_bytes(int64_t B, int64_t S) { return simseg_train_augment_scratch_bytes(B, S); }
 
 static bool ag_finite(double v) { return v == v && v - v == 0.0; }
+
+// One op of image b's chain (its code, its slots) is one the kernel can run: 0, or what is wrong was reported under `who`.
+static int ag_check_op(const char* who, int64_t b, int k, int64_t op, const int64_t* P, int64_t count) {
+    SS_CHECK(op >= 0 && op < count, "%s: image %ld: op %d has code %ld", who, (long)b, k + 1, (long)op);
+    if (op == OP_POSTERIZE) SS_CHECK(P[0] >= 0 && P[0] <= 255, "%s: image %ld: posterize mask %ld", who, (long)b, (long)P[0]);
+    if (op == OP_SOLARIZE) SS_CHECK(P[0] >= 0 && P[0] <= 256, "%s: image %ld: solarize threshold %ld", who, (long)b, (long)P[0]);
+    if (op == OP_COLOR || op == OP_CONTRAST || op == OP_SHARPNESS || op == OP_BRIGHTNESS) {
+        float f;
+        const int32_t bits = (int32_t)P[0];
+        memcpy(&f, &bits, 4);
+        SS_CHECK(P[0] == bits && ag_finite(f), "%s: image %ld: the blend factor is not a finite float", who, (long)b);
+    }
+    if (op == OP_ROTATE)
+        for (int i = 0; i < 6; ++i)
+            SS_CHECK(P[i] > -(1ll << 40) && P[i] < (1ll << 40), "%s: image %ld: rotate coefficient %d out of range", who, (long)b, i);
+    if (op == OP_SHEARX)
+        for (int i = 0; i < 6; ++i) {
+            double v;
+            memcpy(&v, &P[i], 8);
+            SS_CHECK(ag_finite(v) && fabs(v) < 1e6, "%s: image %ld: affine coefficient %d is not finite and small", who, (long)b, i);
+        }
+    return 0;
+}
+
+// Both entry points: every field of the host copy is checked, then the two launches.  WIDE: the table of simseg_train_transforms.
+template <bool WIDE>
+static int ag_run(const char* who, const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
+                  const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S, void* scratch,
+                  int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes, void* stream) {
+    SS_CHECK(src && img_tab && img_tab_host && tab && tab_host && lut && out && scratch, "%s: null pointer", who);
+    SS_CHECK(B >= 1 && B < (1 << 20) && src_bytes > 0 && tab_numel > 0, "%s: bad sizes", who);
+    SS_CHECK(S >= AG_MIN_S && S <= AG_MAX_S, "%s: the output size is %d .. %d, got %ld", who, AG_MIN_S, AG_MAX_S, (long)S);
+    SS_CHECK(out_numel == B * 3 * S * S, "%s: out holds %ld floats, expected %ld", who, (long)out_numel, (long)(B * 3 * S * S));
+    SS_CHECK(!out_u8 || u8_bytes == B * 3 * S * S, "%s: out_u8 holds %ld bytes, expected %ld", who, (long)u8_bytes, (long)(B * 3 * S * S));
+    SS_CHECK(scratch_bytes >= simseg_train_augment_scratch_bytes(B, S), "%s: scratch of %ld bytes, %ld needed", who, (long)scratch_bytes,
+             (long)simseg_train_augment_scratch_bytes(B, S));
+    PpAxisCache axes{tab_host, tab_numel};                       // (a batch shares few axes)
+    for (int64_t b = 0; b < B; ++b) {
+        const int64_t* it = img_tab_host + b * (WIDE ? TT_COLS : AG_COLS);
+        const int64_t H = it[AG_H], W = it[AG_W], top = it[AG_TOP], left = it[AG_LEFT], ch = it[AG_CH], cw = it[AG_CW];
+        const int64_t RH = WIDE ? it[TT_RH] : S, RW = WIDE ? it[TT_RW] : S;
+        SS_CHECK(pp_extent_ok(H, W), "%s: image %ld: bad source extent %ld x %ld", who, (long)b, (long)H, (long)W);
+        SS_CHECK(pp_offset_ok(it[AG_SRC], H, W, src_bytes), "%s: image %ld: source offset out of range", who, (long)b);
+        SS_CHECK(top >= 0 && left >= 0 && ch > 0 && cw > 0 && top + ch <= H && left + cw <= W,
+                 "%s: image %ld: the crop box does not lie inside the image", who, (long)b);
+        if (WIDE) {
+            SS_CHECK(pp_extent_ok(RH, RW), "%s: image %ld: bad resized extent %ld x %ld", who, (long)b, (long)RH, (long)RW);
+            SS_CHECK(it[TT_WTOP] >= 0 && it[TT_WLEFT] >= 0 && it[TT_WTOP] + S <= RH && it[TT_WLEFT] + S <= RW,
+                     "%s: image %ld: the output window does not lie inside the resized %ld x %ld image", who, (long)b, (long)RH, (long)RW);
+            SS_CHECK(it[TT_FLIP] == 0 || it[TT_FLIP] == 1, "%s: image %ld: flip is 0 or 1, got %ld", who, (long)b, (long)it[TT_FLIP]);
+        }
+        const char* e = axes.check(it[AG_HOFF], it[AG_HKS], cw, RW);
+        SS_CHECK(!e, "%s: image %ld, horizontal: %s", who, (long)b, e);
+        e = axes.check(it[AG_VOFF], it[AG_VKS], ch, RH);
+        SS_CHECK(!e, "%s: image %ld, vertical: %s", who, (long)b, e);
+        const int64_t nops = WIDE ? it[TT_NOPS] : 2;
+        SS_CHECK(nops >= 0 && nops <= TT_MAX_OPS, "%s: image %ld: a chain of %ld ops, at most %d", who, (long)b, (long)nops, TT_MAX_OPS);
+        for (int k = 0; k < (int)nops; ++k)
+            if (int rc = ag_check_op(who, b, k, it[(WIDE ? TT_OP : AG_OP1) + k], it + (WIDE ? TT_P : AG_P1) + k * AG_SLOTS,
+                                     WIDE ? OP_COUNT_WIDE : OP_COUNT))
+                return rc;
+        if (WIDE) {
+            const int64_t ne = it[TT_NERASE];
+            SS_CHECK(ne >= 0 && ne <= TT_MAX_ERASE, "%s: image %ld: %ld erase boxes, at most %d", who, (long)b, (long)ne, TT_MAX_ERASE);
+            SS_CHECK(it[TT_MODE] >= 0 && it[TT_MODE] < ER_MODES, "%s: image %ld: erase mode %ld", who, (long)b, (long)it[TT_MODE]);
+            for (int k = 0; k < (int)ne; ++k) {
+                const int64_t* r = it + TT_BOX + 4 * k;
+                SS_CHECK(r[0] >= 0 && r[1] >= 0 && r[2] > 0 && r[3] > 0 && r[2] <= S && r[3] <= S && r[0] + r[2] <= S && r[1] + r[3] <= S,
+                         "%s: image %ld: erase box %d does not lie inside the %ld x %ld output", who, (long)b, k, (long)S, (long)S);
+            }
+        }
+    }
+    const int tiles = ((int)S + PP_TW - 1) / PP_TW * (((int)S + PP_TH - 1) / PP_TH);
+    hipLaunchKernelGGL(augment_resize_kernel<WIDE>, dim3((unsigned)(B * tiles)), dim3(256), 0, (hipStream_t)stream,
+                       static_cast<const uint8_t*>(src), img_tab, tab, static_cast<uint8_t*>(scratch), (int)S, tiles);
+    SS_LAUNCH_CHECK(WIDE ? "train_transforms (resize)" : "train_augment (resize)");
+    uint8_t* s1 = static_cast<uint8_t*>(scratch);
+    if (ag_in_lds(S)) {
+        static bool attr = false;                                // (one per instance of this template)
+        if (!attr) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(augment_ops_kernel<true, WIDE>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)ag_slot_bytes(AG_LDS_MAX_S));
+            SS_CHECK(e == hipSuccess, "%s: hipFuncSetAttribute: %s", who, hipGetErrorString(e));
+            attr = true;
+        }
+        hipLaunchKernelGGL((augment_ops_kernel<true, WIDE>), dim3((unsigned)B), dim3(AG_THREADS), (size_t)ag_slot_bytes(S), (hipStream_t)stream,
+                           img_tab, s1, nullptr, (int)S, lut, out, static_cast<uint8_t*>(out_u8));
+    } else {
+        hipLaunchKernelGGL((augment_ops_kernel<false, WIDE>), dim3((unsigned)B), dim3(AG_THREADS), 0, (hipStream_t)stream, img_tab, s1,
+                           s1 + B * ag_slot_bytes(S), (int)S, lut, out, static_cast<uint8_t*>(out_u8));
+    }
+    SS_LAUNCH_CHECK(WIDE ? "train_transforms (ops)" : "train_augment (ops)");
+    return 0;
+}
 
 extern "C" int simseg_train_augment(const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
                                     const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S,
                                     void* scratch, int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes,
                                     void* stream) {
-    SS_CHECK(src && img_tab && img_tab_host && tab && tab_host && lut && out && scratch, "train_augment: null pointer");
-    SS_CHECK(B >= 1 && B < (1 << 20) && src_bytes > 0 && tab_numel > 0, "train_augment: bad sizes");
-    SS_CHECK(S >= AG_MIN_S && S <= AG_MAX_S, "train_augment: the output size is %d .. %d, got %ld", AG_MIN_S, AG_MAX_S, (long)S);
-    SS_CHECK(out_numel == B * 3 * S * S, "train_augment: out holds %ld floats, expected %ld", (long)out_numel, (long)(B * 3 * S * S));
-    SS_CHECK(!out_u8 || u8_bytes == B * 3 * S * S, "train_augment: out_u8 holds %ld bytes, expected %ld", (long)u8_bytes, (long)(B * 3 * S * S));
-    SS_CHECK(scratch_bytes >= simseg_train_augment_scratch_bytes(B, S), "train_augment: scratch of %ld bytes, %ld needed", (long)scratch_bytes,
-             (long)simseg_train_augment_scratch_bytes(B, S));
-    PpAxisCache axes{tab_host, tab_numel};                       // (a batch shares few axes)
-    for (int64_t b = 0; b < B; ++b) {
-        const int64_t* it = img_tab_host + b * AG_COLS;
-        const int64_t H = it[AG_H], W = it[AG_W], top = it[AG_TOP], left = it[AG_LEFT], ch = it[AG_CH], cw = it[AG_CW];
-        SS_CHECK(pp_extent_ok(H, W), "train_augment: image %ld: bad source extent %ld x %ld", (long)b, (long)H, (long)W);
-        SS_CHECK(pp_offset_ok(it[AG_SRC], H, W, src_bytes), "train_augment: image %ld: source offset out of range", (long)b);
-        SS_CHECK(top >= 0 && left >= 0 && ch > 0 && cw > 0 && top + ch <= H && left + cw <= W,
-                 "train_augment: image %ld: the crop box does not lie inside the image", (long)b);
-        const char* e = axes.check(it[AG_HOFF], it[AG_HKS], cw, S);
-        SS_CHECK(!e, "train_augment: image %ld, horizontal: %s", (long)b, e);
-        e = axes.check(it[AG_VOFF], it[AG_VKS], ch, S);
-        SS_CHECK(!e, "train_augment: image %ld, vertical: %s", (long)b, e);
-        for (int k = 0; k < 2; ++k) {
-            const int64_t op = it[AG_OP1 + k];
-            const int64_t* P = it + AG_P1 + k * AG_SLOTS;
-            SS_CHECK(op >= 0 && op < OP_COUNT, "train_augment: image %ld: op %d has code %ld", (long)b, k + 1, (long)op);
-            if (op == OP_POSTERIZE) SS_CHECK(P[0] >= 0 && P[0] <= 255, "train_augment: image %ld: posterize mask %ld", (long)b, (long)P[0]);
-            if (op == OP_SOLARIZE) SS_CHECK(P[0] >= 0 && P[0] <= 256, "train_augment: image %ld: solarize threshold %ld", (long)b, (long)P[0]);
-            if (op == OP_COLOR || op == OP_CONTRAST || op == OP_SHARPNESS) {
-                float f;
-                const int32_t bits = (int32_t)P[0];
-                memcpy(&f, &bits, 4);
-                SS_CHECK(P[0] == bits && ag_finite(f), "train_augment: image %ld: the blend factor is not a finite float", (long)b);
-            }
-            if (op == OP_ROTATE)
-                for (int i = 0; i < 6; ++i)
-                    SS_CHECK(P[i] > -(1ll << 40) && P[i] < (1ll << 40), "train_augment: image %ld: rotate coefficient %d out of range", (long)b, i);
-            if (op == OP_SHEARX)
-                for (int i = 0; i < 6; ++i) {
-                    double v;
-                    memcpy(&v, &P[i], 8);
-                    SS_CHECK(ag_finite(v) && fabs(v) < 1e6, "train_augment: image %ld: affine coefficient %d is not finite and small", (long)b, i);
-                }
-        }
-    }
-    const int tiles = ((int)S + PP_TW - 1) / PP_TW * (((int)S + PP_TH - 1) / PP_TH);
-    hipLaunchKernelGGL(augment_resize_kernel, dim3((unsigned)(B * tiles)), dim3(256), 0, (hipStream_t)stream, static_cast<const uint8_t*>(src),
-                       img_tab, tab, static_cast<uint8_t*>(scratch), (int)S, tiles);
-    SS_LAUNCH_CHECK("train_augment (resize)");
-    uint8_t* s1 = static_cast<uint8_t*>(scratch);
-    if (ag_in_lds(S)) {
-        static bool attr = false;
-        if (!attr) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(augment_ops_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                               (int)ag_slot_bytes(AG_LDS_MAX_S));
-            SS_CHECK(e == hipSuccess, "train_augment: hipFuncSetAttribute: %s", hipGetErrorString(e));
-            attr = true;
-        }
-        hipLaunchKernelGGL(augment_ops_kernel<true>, dim3((unsigned)B), dim3(AG_THREADS), (size_t)ag_slot_bytes(S), (hipStream_t)stream,
-                           img_tab, s1, nullptr, (int)S, lut, out, static_cast<uint8_t*>(out_u8));
-    } else {
-        hipLaunchKernelGGL(augment_ops_kernel<false>, dim3((unsigned)B), dim3(AG_THREADS), 0, (hipStream_t)stream, img_tab, s1,
-                           s1 + B * ag_slot_bytes(S), (int)S, lut, out, static_cast<uint8_t*>(out_u8));
-    }
-    SS_LAUNCH_CHECK("train_augment (ops)");
-    return 0;
+    return ag_run<false>("train_augment", src, src_bytes, img_tab, img_tab_host, B, tab, tab_host, tab_numel, lut, S, scratch, scratch_bytes,
+                         out, out_numel, out_u8, u8_bytes, stream);
+}
+
+extern "C" int simseg_train_transforms(const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
+                                       const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S,
+                                       void* scratch, int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes,
+                                       void* stream) {
+    return ag_run<true>("train_transforms", src, src_bytes, img_tab, img_tab_host, B, tab, tab_host, tab_numel, lut, S, scratch,
+                        scratch_bytes, out, out_numel, out_u8, u8_bytes, stream);
 }

@@ -777,7 +777,7 @@ def slide_planes(flat, plan, b):
     return flat[o:o + plan["ncand"] * H * W].view(plan["ncand"], H, W)
 
 
-# ---- image preprocessing and training augmentation on the device (simseg_amd/preproc.py, augment.py; include/simseg_hip.h) -----------------------
+# ---- image preprocessing and training augmentation on the device (simseg_amd/preproc.py, augment.py, pipeline.py; include/simseg_hip.h) -----------------------
 def _check_packed_batch(who, src, plan, lut, cols, need_2d=False):
     """What image_preprocess and train_augment ask of their arguments: the packed source, the look-up table, and host copies of the
     tables ([B, cols] image table) that the C entry point can read.  -> (img_tab_host, tab_host)."""
@@ -816,4 +816,19 @@ def train_augment(src, plan, lut, want_u8=False):
     u8 = torch.empty(B, S, S, 3, device=dev, dtype=torch.uint8) if want_u8 else None
     call("simseg_train_augment", ptr(_c(src)), src.numel(), ptr(plan["img_tab"]), it.ctypes.data, B, ptr(plan["tab"]), th.ctypes.data, th.size,
          ptr(_c(lut)), S, ptr(scratch), scratch.numel(), ptr(out), out.numel(), ptr(u8), 0 if u8 is None else u8.numel(), stream())
+    return out, u8
+
+
+def train_transforms(src, plan, lut, want_u8=False):
+    """src: the batch's uint8 [H, W, 3] images packed at plan['src_off'] (pipeline.plan_pipeline) -> (fp32 [B, 3, S, S], uint8
+    [B, S, S, 3] = the bytes before normalisation and erasing, or None).  Two launches; every field of the table is checked on its host
+    copy before them."""
+    it, th = _check_packed_batch("train_transforms", src, plan, lut, 81, need_2d=True)
+    B, S = it.shape[0], plan["size"]
+    dev = src.device
+    scratch = torch.empty(max(raw("simseg_train_transforms_scratch_bytes", B, S), 16), device=dev, dtype=torch.uint8)
+    out = torch.empty(B, 3, S, S, device=dev, dtype=torch.float32)
+    u8 = torch.empty(B, S, S, 3, device=dev, dtype=torch.uint8) if want_u8 else None
+    call("simseg_train_transforms", ptr(_c(src)), src.numel(), ptr(plan["img_tab"]), it.ctypes.data, B, ptr(plan["tab"]), th.ctypes.data,
+         th.size, ptr(_c(lut)), S, ptr(scratch), scratch.numel(), ptr(out), out.numel(), ptr(u8), 0 if u8 is None else u8.numel(), stream())
     return out, u8
