@@ -340,6 +340,26 @@ int64_t simseg_slide_stitch_workspace_bytes(int64_t B, int64_t ncand, int64_t ma
 int simseg_slide_stitch(const float* sim_w, const int64_t* img_tab, const int64_t* win_tab, const int* cand_idx, float* prob, void* mask,
                         float* minmax, float* workspace, int64_t B, int64_t ncand, int64_t n, int64_t C, int64_t win, int64_t max_h,
                         int64_t max_w, int64_t max_hw, void* stream);
+/* Multi-scale and flip test-time augmentation over sliding windows (DESIGN.md "Multi-scale and flip test-time augmentation").
+ * extract_flip: simseg_slide_extract with a per-call flag; flip != 0 cuts the windows of win_tab from the left-to-right MIRRORED images:
+ * window (image, y0, x0), row i, column j reads source row y0 + i, column W - 1 - (x0 + j), zero where x0 + j >= W or y0 + i >= H. */
+int simseg_slide_extract_flip(const float* images, const int64_t* img_tab, const int64_t* win_tab, float* out, int64_t Nw, int64_t win, int flip,
+                              void* stream);
+/* stitch_multi: the fused map of P passes over the same B images, written in the layout of simseg_slide_stitch for the BASE image table
+ * img_tab (sizes H x W).  pass_tab (device, built on the host) int64 [P, 4] = (sim_w pointer, img_tab pointer, win_tab pointer, flip)
+ * per pass: the pass's per-window maps [Nw_p, n*n, C] fp32 and its own simseg_slide_* tables over its B images of sizes H_p x W_p, all with
+ * the same win.  S_p = the pass's pixel-resolution stitched map as simseg_slide_stitch defines it before its min-max step, un-mirrored
+ * (S_p(y', W_p - 1 - x')) when flip != 0.  Fused map at base pixel (y, x): nearest sampling with pixel centres in integers,
+ * y_p = min(((2y + 1) H_p) / (2H), H_p - 1), x_p likewise with W; F(y, x) = (sum over p in pass order, fp32, of S_p(y_p, x_p)) / P,
+ * divided once.  prob = F min-max normalised over the image, mask = prob > 0.5 ? 255 : 0, minmax [B, ncand, 2] = min and max of F, for
+ * visited slots (cand_idx [B, ncand] >= 0) at out_off + k*H*W; unvisited slots are not written.  With P = 1, H_p = H, W_p = W, flip = 0 the
+ * three outputs are simseg_slide_stitch's bit for bit.  At most 16 passes (1 <= P <= 16; a larger P is refused with an error before any launch);
+ * no limit on image sizes, scales or window counts; no host read.  max_h / max_w / max_hw: of the base images; workspace: fp32, of
+ * simseg_slide_stitch_multi_workspace_bytes(B, ncand, max_h, max_w) bytes. */
+int64_t simseg_slide_stitch_multi_workspace_bytes(int64_t B, int64_t ncand, int64_t max_h, int64_t max_w);
+int simseg_slide_stitch_multi(const int64_t* pass_tab, int64_t P, const int64_t* img_tab, const int* cand_idx, float* prob, void* mask,
+                              float* minmax, float* workspace, int64_t B, int64_t ncand, int64_t n, int64_t C, int64_t win, int64_t max_h,
+                              int64_t max_w, int64_t max_hw, void* stream);
 /* Image preprocessing (simseg_amd/preproc.py, DESIGN.md "Device-side image preprocessing"): B decoded uint8 [H, W, 3] images packed in
  * `src` -> Pillow's uint8 resize (its integer arithmetic, bit for bit) restricted to an output rectangle -> out fp32 [3, OH, OW] planes
  * = lut [3, 256] at the resized byte; optionally (out_u8 != NULL) also the resized bytes as [OH, OW, 3].  ONE launch for the batch.

@@ -550,6 +550,166 @@ __global__ __launch_bounds__(256) void slide_norm_kernel(const int64_t* __restri
     }
 }
 
+// ---- multi-scale / flip test-time augmentation over sliding windows (DESIGN.md "Multi-scale and flip test-time augmentation") --------
+// K21f extract from the MIRRORED image: window (image, y0, x0) column j reads source column W - 1 - (x0 + j); zero past the border of the
+// mirrored image (x0 + j >= W or y0 + i >= H).  The reads of a thread run backwards, so they are four scalar loads; the store is K21's.
+__global__ __launch_bounds__(256) void slide_extract_flip_kernel(const float* __restrict__ src, const int64_t* __restrict__ img_tab,
+                                                                 const int64_t* __restrict__ win_tab, float* __restrict__ out, long n4, int win) {
+    const int q = win >> 2;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < n4; e += (long)gridDim.x * 256) {
+        const int c4 = (int)(e % q);
+        long r = e / q;
+        const int row = (int)(r % win); r /= win;
+        const int ch = (int)(r % 3);
+        const long w = r / 3;
+        const int64_t* wt = win_tab + w * 3;
+        const int64_t* it = img_tab + wt[0] * SLIDE_IT;
+        const long H = it[1], W = it[2];
+        const long y = wt[1] + row, x = wt[2] + 4 * c4;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (y < H) {
+            const float* line = src + it[0] + (ch * H + y) * W;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (x + k < W) v[k] = line[W - 1 - (x + k)];
+        }
+        *reinterpret_cast<f32x4*>(out + e * 4) = v;
+    }
+}
+
+// K24 fused stitch of P passes, pass 1: one block per (64 x 64 pixel tile of the BASE image, candidate slot, image), visited slots only;
+// the thread-to-pixel map and the stores are K23's.  pass_tab int64 [P, SLIDE_PT] = (sim_w pointer, img_tab pointer, win_tab pointer, flip)
+// per pass.  Per pass the base pixel (y, x) samples the pass's stitched map at y_p = min(((2y + 1) H_p) / (2H), H_p - 1), x_p likewise
+// (integer division), mirrored to W_p - 1 - x_p for a flipped pass; that value is K23's: the sum over the covering windows in window
+// order of their cell, divided once by their count.  Only the windows touching the tile's sample rectangle are walked (their offsets
+// staged in LDS, SM_WCH at a time); the cells are read from global memory - neighbouring pixels share them, so a wave's 64 loads fall on
+// a handful of addresses - which puts no bound on the scale of a pass.  The pass values are summed in pass order and divided once by P.
+constexpr int SLIDE_MAXP = 16, SLIDE_PT = 4, SM_WCH = 64;
+__global__ __launch_bounds__(256) void slide_stitch_multi_kernel(const int64_t* __restrict__ pass_tab, int P, const int64_t* __restrict__ img_tab,
+                                                                 const int* __restrict__ cand_idx, int K, int C, int win, int n, int tiles_max,
+                                                                 float* __restrict__ prob, float* __restrict__ partial) {
+    __shared__ int meta[SM_WCH][2];                // y0, x0
+    __shared__ int range[4];                       // window rows i0..i1, columns j0..j1 touching the tile's sample rectangle
+    __shared__ float red[2][4];
+    const int t = blockIdx.x, k = blockIdx.y, b = blockIdx.z, tid = threadIdx.x;
+    const int idx = cand_idx[b * K + k];
+    if (idx < 0) return;
+    const int64_t* it = img_tab + (long)b * SLIDE_IT;
+    const int H = (int)it[1], W = (int)it[2];
+    const int tw = (W + ST_T - 1) / ST_T, th = (H + ST_T - 1) / ST_T;
+    if (t >= tw * th) return;
+    const int ty0 = (t / tw) * ST_T, tx0 = (t % tw) * ST_T;
+    const int ty1 = min(ty0 + ST_T, H), tx1 = min(tx0 + ST_T, W);
+    const int lx = 4 * (tid & 15), ly = tid >> 4;
+    const long nn = (long)n * n;
+    float tot[4][4];
+    for (int p = 0; p < P; ++p) {
+        const float* __restrict__ sim = reinterpret_cast<const float*>(pass_tab[p * SLIDE_PT]);
+        const int64_t* pit = reinterpret_cast<const int64_t*>(pass_tab[p * SLIDE_PT + 1]) + (long)b * SLIDE_IT;
+        const int64_t* __restrict__ win_tab = reinterpret_cast<const int64_t*>(pass_tab[p * SLIDE_PT + 2]);
+        const bool flip = pass_tab[p * SLIDE_PT + 3] != 0;
+        const long Hp = pit[1], Wp = pit[2];
+        const int ny = (int)pit[5], nx = (int)pit[6];
+        const long wstart = pit[4];
+        // this thread's sample rows / columns in the pass (pixels past the tile's border clamp into it: computed, never stored)
+        int sy[4], sx[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) sy[r] = (int)min(((2L * min(ty0 + ly + 16 * r, ty1 - 1) + 1) * Hp) / (2L * H), Hp - 1);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int xp = (int)min(((2L * min(tx0 + lx + q, tx1 - 1) + 1) * Wp) / (2L * W), Wp - 1);
+            sx[q] = flip ? (int)Wp - 1 - xp : xp;
+        }
+        // the tile's sample rectangle (inclusive): the index maps are monotone, so its corners are the tile's
+        const int ry0 = (int)min(((2L * ty0 + 1) * Hp) / (2L * H), Hp - 1), ry1 = (int)min(((2L * (ty1 - 1) + 1) * Hp) / (2L * H), Hp - 1);
+        const int xa = (int)min(((2L * tx0 + 1) * Wp) / (2L * W), Wp - 1), xb = (int)min(((2L * (tx1 - 1) + 1) * Wp) / (2L * W), Wp - 1);
+        const int rx0 = flip ? (int)Wp - 1 - xb : xa, rx1 = flip ? (int)Wp - 1 - xa : xb;
+        __syncthreads();                           // the previous pass has read range / meta
+        if (tid == 0) { range[0] = 0x7fffffff; range[1] = -1; range[2] = 0x7fffffff; range[3] = -1; }
+        __syncthreads();
+        for (int i = tid; i < ny; i += 256) {
+            const int y0 = (int)win_tab[(wstart + (long)i * nx) * 3 + 1];
+            if (y0 <= ry1 && y0 + win > ry0) { atomicMin(&range[0], i); atomicMax(&range[1], i); }
+        }
+        for (int j = tid; j < nx; j += 256) {
+            const int x0 = (int)win_tab[(wstart + j) * 3 + 2];
+            if (x0 <= rx1 && x0 + win > rx0) { atomicMin(&range[2], j); atomicMax(&range[3], j); }
+        }
+        __syncthreads();
+        const int i0 = range[0], nj = range[3] - range[2] + 1, j0 = range[2];
+        const int nwin = (range[1] - i0 + 1) * nj;
+        float acc[4][4];
+        int cnt[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) { acc[r][q] = 0.f; cnt[r][q] = 0; }
+        for (int c0 = 0; c0 < nwin; c0 += SM_WCH) {
+            const int m = min(SM_WCH, nwin - c0);
+            if (tid < m) {
+                const int wl = c0 + tid;
+                const long w = wstart + (long)(i0 + wl / nj) * nx + (j0 + wl % nj);
+                meta[tid][0] = (int)win_tab[w * 3 + 1]; meta[tid][1] = (int)win_tab[w * 3 + 2];
+            }
+            __syncthreads();
+            for (int wl = 0; wl < m; ++wl) {
+                const int y0 = meta[wl][0], x0 = meta[wl][1];
+                const float* col = sim + (wstart + (long)(i0 + (c0 + wl) / nj) * nx + (j0 + (c0 + wl) % nj)) * nn * C + idx;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int dy = sy[r] - y0;
+                    if (dy < 0 || dy >= win) continue;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        const int dx = sx[q] - x0;
+                        if (dx < 0 || dx >= win) continue;
+                        acc[r][q] += col[(long)((dy >> 4) * n + (dx >> 4)) * C];
+                        cnt[r][q] += 1;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float s = acc[r][q] / (float)cnt[r][q];
+                tot[r][q] = p == 0 ? s : tot[r][q] + s;
+            }
+    }
+    float mn = INFINITY, mx = -INFINITY;
+    float* plane = prob + it[3] + (long)k * H * W;
+    const float fp = (float)P;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int y = ty0 + ly + 16 * r, x = tx0 + lx;
+        if (y >= H || x >= W) continue;
+        f32x4 v;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            v[q] = tot[r][q] / fp;
+            if (x + q < W) { mn = fminf(mn, v[q]); mx = fmaxf(mx, v[q]); }
+        }
+        float* dst = plane + (long)y * W + x;
+        if (x + 3 < W && ((uintptr_t)dst & 15) == 0) {
+            *reinterpret_cast<f32x4*>(dst) = v;
+        } else {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (x + q < W) dst[q] = v[q];
+        }
+    }
+    mn = wave_min(mn); mx = wave_max(mx);
+    if ((tid & 63) == 0) { red[0][tid >> 6] = mn; red[1][tid >> 6] = mx; }
+    __syncthreads();
+    if (tid == 0) {
+        float* pp = partial + (((long)b * K + k) * tiles_max + t) * 2;
+        pp[0] = fminf(fminf(red[0][0], red[0][1]), fminf(red[0][2], red[0][3]));
+        pp[1] = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+    }
+}
+
 }  // namespace
 
 extern "C" int simseg_seg_select(const float* scores, int* cand_idx, float* cand_score, float* threshold, int64_t B, int64_t C,
@@ -683,5 +843,52 @@ extern "C" int simseg_slide_stitch(const float* sim_w, const int64_t* img_tab, c
     hipLaunchKernelGGL(slide_norm_kernel, dim3((unsigned)blocks, (unsigned)ncand, (unsigned)B), dim3(256), 0, s, img_tab, cand_idx, (int)ncand, minmax,
                        prob, static_cast<unsigned char*>(mask));
     SS_LAUNCH_CHECK("slide_stitch (normalise)");
+    return 0;
+}
+
+extern "C" int simseg_slide_extract_flip(const float* images, const int64_t* img_tab, const int64_t* win_tab, float* out, int64_t Nw, int64_t win,
+                                         int flip, void* stream) {
+    if (!flip) return simseg_slide_extract(images, img_tab, win_tab, out, Nw, win, stream);
+    SS_CHECK(images && img_tab && win_tab && out, "slide_extract_flip: null pointer");
+    SS_CHECK(Nw > 0 && win > 0 && win % 16 == 0, "slide_extract_flip: Nw > 0 and win a positive multiple of 16");
+    SS_CHECK(((uintptr_t)out % 16) == 0, "slide_extract_flip: out must be 16-byte aligned");
+    const long n4 = (long)Nw * 3 * win * win / 4;
+    long blocks = (n4 + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(slide_extract_flip_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, images, img_tab, win_tab, out, n4,
+                       (int)win);
+    SS_LAUNCH_CHECK("slide_extract_flip");
+    return 0;
+}
+
+extern "C" int64_t simseg_slide_stitch_multi_workspace_bytes(int64_t B, int64_t ncand, int64_t max_h, int64_t max_w) {
+    return simseg_slide_stitch_workspace_bytes(B, ncand, max_h, max_w);
+}
+
+extern "C" int simseg_slide_stitch_multi(const int64_t* pass_tab, int64_t P, const int64_t* img_tab, const int* cand_idx, float* prob, void* mask,
+                                         float* minmax, float* workspace, int64_t B, int64_t ncand, int64_t n, int64_t C, int64_t win,
+                                         int64_t max_h, int64_t max_w, int64_t max_hw, void* stream) {
+    SS_CHECK(P >= 1 && P <= SLIDE_MAXP, "slide_stitch_multi: %lld passes, 1 <= P <= %d", (long long)P, SLIDE_MAXP);
+    SS_CHECK(pass_tab && img_tab && cand_idx && prob && mask && minmax && workspace, "slide_stitch_multi: null pointer");
+    SS_CHECK(B > 0 && B < 65536 && ncand >= 1 && ncand <= 8 && C > 0 && win > 0 && win % 16 == 0 && n == win / 16,
+             "slide_stitch_multi: bad shape (n = win / 16, 1 <= ncand <= 8)");
+    SS_CHECK(max_h > 0 && max_w > 0 && max_h < (1 << 20) && max_w < (1 << 20) && max_hw >= 1 && max_hw <= max_h * max_w,
+             "slide_stitch_multi: bad image extents");
+    SS_CHECK(((uintptr_t)prob % 16) == 0 && ((uintptr_t)mask % 16) == 0, "slide_stitch_multi: prob and mask must be 16-byte aligned");
+    const long tiles = ((max_h + ST_T - 1) / ST_T) * ((max_w + ST_T - 1) / ST_T);
+    SS_CHECK(tiles < (1l << 31), "slide_stitch_multi: image too large");
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(slide_stitch_multi_kernel, dim3((unsigned)tiles, (unsigned)ncand, (unsigned)B), dim3(256), 0, s, pass_tab, (int)P, img_tab,
+                       cand_idx, (int)ncand, (int)C, (int)win, (int)n, (int)tiles, prob, workspace);
+    SS_LAUNCH_CHECK("slide_stitch_multi");
+    // passes 2 and 3 are K23's, on the base image table: the fused map lies where the single-pass stitch puts its own
+    hipLaunchKernelGGL(slide_minmax_kernel, dim3((unsigned)ncand, (unsigned)B), dim3(256), 0, s, img_tab, cand_idx, (int)ncand, (int)tiles, workspace,
+                       minmax);
+    SS_LAUNCH_CHECK("slide_stitch_multi (min / max)");
+    long blocks = (max_hw / 16 + 2 + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(slide_norm_kernel, dim3((unsigned)blocks, (unsigned)ncand, (unsigned)B), dim3(256), 0, s, img_tab, cand_idx, (int)ncand, minmax,
+                       prob, static_cast<unsigned char*>(mask));
+    SS_LAUNCH_CHECK("slide_stitch_multi (normalise)");
     return 0;
 }

@@ -777,6 +777,56 @@ def slide_planes(flat, plan, b):
     return flat[o:o + plan["ncand"] * H * W].view(plan["ncand"], H, W)
 
 
+# ---- multi-scale / flip test-time augmentation over sliding windows (segpost.encode_images_multiscale; include/simseg_hip.h) ------------
+def slide_extract_flip(images_flat, plan, start=0, count=None, flip=True):
+    """slide_extract() on the left-to-right MIRRORED images (flip=True): the windows of `plan` cut from torch.flip(image, [-1]) without
+    that copy being made; flip=False is slide_extract()."""
+    require_gpu(images_flat)
+    if images_flat.dtype != torch.float32 or images_flat.numel() != plan["src_numel"]:
+        raise ValueError(f"slide_extract_flip: {plan['src_numel']} packed fp32 pixels expected, got {images_flat.numel()} {images_flat.dtype}")
+    count = len(plan["windows"]) - start if count is None else count
+    if count <= 0 or start < 0 or start + count > len(plan["windows"]):
+        raise ValueError(f"slide_extract_flip: windows {start}..{start + count - 1} of {len(plan['windows'])}")
+    win = plan["win"]
+    out = torch.empty(count, 3, win, win, device=images_flat.device, dtype=torch.float32)
+    call("simseg_slide_extract_flip", ptr(_c(images_flat)), ptr(plan["img_tab"]), ptr(plan["win_tab"][start:]), ptr(out), count, win, int(bool(flip)),
+         stream())
+    return out
+
+
+def slide_stitch_multi(sims, plans, flips, base_plan, cand_idx):
+    """The fused map of P passes (DESIGN.md "Multi-scale and flip test-time augmentation"): sims[p] [Nw_p, n*n, C] fp32 = pass p's per-window
+    maps over its slide_plan plans[p] (the same images at the pass's scale, mirrored when flips[p]); base_plan: the slide_plan of the images
+    at their base sizes; cand_idx [B, ncand].  -> (prob, mask, minmax) in slide_stitch's layout for base_plan.  The number of passes is
+    bounded by the library (16), which refuses more before any launch."""
+    P = len(sims)
+    if P == 0 or len(plans) != P or len(flips) != P:
+        raise ValueError(f"slide_stitch_multi: {P} maps, {len(plans)} plans and {len(flips)} flip flags: one of each per pass expected")
+    require_gpu(cand_idx, *sims)
+    win, K, B = base_plan["win"], base_plan["ncand"], len(base_plan["sizes"])
+    n = win // 16
+    C = sims[0].shape[2] if sims[0].dim() == 3 else -1
+    if tuple(cand_idx.shape) != (B, K):
+        raise ValueError(f"slide_stitch_multi: [{B}, {K}] candidates expected, got {tuple(cand_idx.shape)}")
+    for p, (s, pl) in enumerate(zip(sims, plans)):
+        if len(pl["sizes"]) != B or pl["win"] != win:
+            raise ValueError(f"slide_stitch_multi: pass {p} has {len(pl['sizes'])} images and {pl['win']}-pixel windows, the base plan {B} and {win}")
+        if s.dtype != torch.float32 or s.dim() != 3 or tuple(s.shape) != (len(pl["windows"]), n * n, C):
+            raise ValueError(f"slide_stitch_multi: pass {p}: fp32 [{len(pl['windows'])}, {n * n}, {C}] maps expected, got {tuple(s.shape)} {s.dtype}")
+    dev = cand_idx.device
+    sims = [_c(s) for s in sims]                        # (kept until the launch is queued: the table below holds their addresses)
+    tab = to_device_async([[s.data_ptr(), pl["img_tab"].data_ptr(), pl["win_tab"].data_ptr(), int(bool(f))] for s, pl, f in zip(sims, plans, flips)], dev)
+    sizes = base_plan["sizes"]
+    max_h = max(h for h, _ in sizes); max_w = max(w for _, w in sizes); max_hw = max(h * w for h, w in sizes)
+    prob = torch.zeros(base_plan["out_numel"], device=dev, dtype=torch.float32)
+    mask = torch.zeros(base_plan["out_numel"], device=dev, dtype=torch.uint8)
+    minmax = torch.zeros(B, K, 2, device=dev, dtype=torch.float32)
+    ws = torch.empty(raw("simseg_slide_stitch_multi_workspace_bytes", B, K, max_h, max_w) // 4, device=dev, dtype=torch.float32)
+    call("simseg_slide_stitch_multi", ptr(tab), P, ptr(base_plan["img_tab"]), ptr(_c(cand_idx)), ptr(prob), ptr(mask), ptr(minmax), ptr(ws), B, K, n, C,
+         win, max_h, max_w, max_hw, stream())
+    return prob, mask, minmax
+
+
 # ---- image preprocessing and training augmentation on the device (simseg_amd/preproc.py, augment.py, pipeline.py; include/simseg_hip.h) -----------------------
 def _check_packed_batch(who, src, plan, lut, cols, need_2d=False):
     """What image_preprocess and train_augment ask of their arguments: the packed source, the look-up table, and host copies of the

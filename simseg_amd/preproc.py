@@ -264,6 +264,65 @@ def plan(sizes, spec, device):
             "out_sizes": out_sizes, "src_off": src_off, "out_off": out_off, "src_bytes": s, "out_numel": o, "tiles": tiles}
 
 
+def plan_extents(sizes, targets, filt, device):
+    """plan() for explicit per-image target extents: raw image i of sizes[i] = (H, W) is resized to targets[i] = (OH, OW) with `filt`, no
+    crop (the scaled passes of segpost.encode_images_multiscale).  Same dict, same tables, same kernel."""
+    from . import ops
+    if filt not in FILTERS:
+        raise ValueError(f"plan_extents: filter is one of {sorted(FILTERS)}, got {filt!r}")
+    if len(sizes) != len(targets):
+        raise ValueError(f"plan_extents: {len(sizes)} images and {len(targets)} target extents")
+    sizes = [(int(H), int(W)) for H, W in sizes]
+    targets = [(int(OH), int(OW)) for OH, OW in targets]
+    if any(min(hw) < 1 for hw in sizes + targets):
+        raise ValueError(f"plan_extents: extents must be positive, got {sizes} -> {targets}")
+    axes = set()
+    for (H, W), (OH, OW) in zip(sizes, targets):
+        axes.add((W, OW, filt))
+        axes.add((H, OH, filt))
+    ar = _arena(axes, device)
+    rows, src_off, out_off = [], [], []
+    s = o = tiles = 0
+    for (H, W), (OH, OW) in zip(sizes, targets):
+        hoff, hks = ar.where[(W, OW, filt)]
+        voff, vks = ar.where[(H, OH, filt)]
+        rows.append([s, H, W, o, OH, OW, 0, 0, hoff, hks, voff, vks, OH, OW, o, tiles])
+        src_off.append(s); out_off.append(o)
+        s += H * W * 3
+        o += 3 * OH * OW
+        tiles += -(-OW // TILE_W) * -(-OH // TILE_H)
+    host = np.asarray(rows, dtype=np.int64).reshape(-1, IMG_COLS)
+    return {"img_tab": ops.to_device_async(rows, device), "img_tab_host": host, "tab": ar.dev, "tab_host": ar.host, "sizes": sizes,
+            "out_sizes": targets, "src_off": src_off, "out_off": out_off, "src_bytes": s, "out_numel": o, "tiles": tiles}
+
+
+def preprocess_extents(images_u8, targets, spec, filt="bilinear", mean=None, std=None, device=None, src=None):
+    """preprocess() to explicit per-image extents targets = [(OH, OW), ...] with `filt`: the spec supplies the normalisation only.
+    src: the packed raw bytes of an earlier call on the same images (its 'src'), reused instead of being packed and copied again.
+    -> dict('packed', 'sizes', 'plan', 'src')."""
+    from . import ops
+    if not images_u8:
+        raise ValueError("preprocess_extents: an empty batch")
+    if device is None:
+        device = images_u8[0].device if images_u8[0].is_cuda else torch.device("cuda")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("simseg_amd.preproc.preprocess_extents runs on MI355X only; there is no CPU fallback (resample_ref is the host statement)")
+    lut = spec.get("lut")
+    if mean is not None or std is not None or lut is None:
+        m = spec["mean"] if mean is None else mean
+        s = spec["std"] if std is None else std
+        if m is None or s is None:
+            raise ValueError("preprocess_extents: the spec names no normalisation and none was given")
+        lut = make_lut(m, s)
+    lut_dev = _lut_on(lut, device)
+    pl = plan_extents([tuple(t.shape[:2]) for t in images_u8], targets, filt, device)
+    if src is None:
+        src = _pack(images_u8, pl, device)
+    packed, _ = ops.image_preprocess(src, pl, lut_dev)
+    return {"packed": packed, "sizes": pl["out_sizes"], "plan": pl, "src": src}
+
+
 def _pack(images_u8, pl, device):
     """The batch's [H, W, 3] uint8 images in one device buffer at pl['src_off']: host images go through ONE pinned buffer and ONE
     non-blocking copy, device images are packed on the device."""

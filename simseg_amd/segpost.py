@@ -262,6 +262,93 @@ def encode_images_sliding(model, images, text, top_cls_num, win=512, stride=256,
             "plan": plan, "images_u8": raw, "num_classes": sim_w.shape[2]}
 
 
+# ---- multi-scale and flip test-time augmentation (DESIGN.md "Multi-scale and flip test-time augmentation") ------------------------------
+# The evaluation protocol that goes with sliding windows: the same image at several scales and mirrored, every pass cut into windows
+# with the same win / stride, the passes' pixel-resolution maps fused on the device (ops.slide_stitch_multi) before candidate selection
+# and post-processing.  The reference has no such protocol (as it has no sliding window); tests/_tta_ref.py restates it in numpy.
+
+def tta_sizes(sizes, scales):
+    """-> per scale s the list [(H_p, W_p)] with H_p = max(1, floor(s * H + 0.5)), W_p likewise, for base sizes [(H, W), ...]."""
+    import math
+    out = []
+    for s in scales:
+        s = float(s)
+        if not s > 0 or not math.isfinite(s):
+            raise ValueError(f"tta_sizes: scales are positive numbers, got {s!r}")
+        out.append([(max(1, int(math.floor(s * int(H) + 0.5))), max(1, int(math.floor(s * int(W) + 0.5)))) for H, W in sizes])
+    return out
+
+
+def tta_nearest_index(i, L, Lp):
+    """Row (column) of a pass of extent Lp that base row (column) i of extent L samples: nearest with pixel centres, integers only."""
+    return min(((2 * i + 1) * Lp) // (2 * L), Lp - 1)
+
+
+def encode_images_multiscale(model, passes, text, top_cls_num, win=512, stride=256, crf=True, mean=None, std=None, sim_dtype=None,
+                             window_batch=None, base=0):
+    """encode_images_sliding() with test-time augmentation.  passes = [(flat, sizes, flip), ...]: per pass the flat fp32 buffer that holds
+    the batch's normalised [3, H_p, W_p] images back to back (what preproc.preprocess writes for that scale; NOT mirrored), their sizes,
+    and whether the pass runs on the mirrored images (the mirror is taken while the windows are cut: ops.slide_extract_flip).
+    passes[base] is the unflipped scale-1 pass: its sizes define the plan of the outputs and its pixels feed the CRF.  Every pass is cut
+    into windows with the same win / stride and goes through the towers at most `window_batch` windows per call (passes are not mixed in
+    a call).  Image scores: per pass the ops.slide_scores mean, summed over the passes in pass order in fp32 and divided once by their
+    number; candidates from the fused scores; prob / masks / minmax from ops.slide_stitch_multi.  -> the dict of encode_images_sliding
+    (plan = the base plan, scores = the fused scores): finish_sliding() ends it.  One pass (the base alone) gives encode_images_sliding's
+    result bit for bit."""
+    from .heads import patch_text_similarity
+    P = len(passes)
+    if P == 0 or not 0 <= base < P:
+        raise ValueError(f"encode_images_multiscale: {P} passes, base index {base}")
+    if passes[base][2]:
+        raise ValueError("encode_images_multiscale: the base pass is the unflipped scale-1 pass")
+    flats, plans, flips = [], [], []
+    B = len(passes[base][1])
+    for p, (buf, sizes, flip) in enumerate(passes):
+        sizes = [(int(h), int(w)) for h, w in sizes]
+        flat = buf.contiguous().reshape(-1)
+        if len(sizes) != B:
+            raise ValueError(f"encode_images_multiscale: pass {p} holds {len(sizes)} images, the base pass {B}")
+        if flat.dtype != torch.float32 or flat.numel() != sum(3 * h * w for h, w in sizes):
+            raise ValueError(f"encode_images_multiscale: pass {p}: a packed fp32 buffer of {sum(3 * h * w for h, w in sizes)} elements expected for "
+                             f"sizes {sizes}, got {flat.numel()} {flat.dtype}")
+        flats.append(flat); flips.append(bool(flip))
+        plans.append(ops.slide_plan(sizes, win, stride, flat.device))
+    plan = plans[base]
+    sims, sc = [], None
+    for flat, pl, flip in zip(flats, plans, flips):
+        Nw = len(pl["windows"])
+        wb = window_batch or Nw
+        sim_p, sc_p = [], []
+        for s in range(0, Nw, wb):
+            wins = ops.slide_extract_flip(flat, pl, s, min(wb, Nw - s), flip=flip)
+            feats = model.forward_image_feature(wins)                     # [b, n*n, D]
+            pooled = model.forward_image_project(feats)                   # [b, 512]
+            sim_p.append(patch_text_similarity(model.image_projection(feats), text, compute_dtype=sim_dtype))
+            sc_p.append(ops.gemm(pooled.float(), text))
+        sim_w = sim_p[0] if len(sim_p) == 1 else torch.cat(sim_p)
+        sc_w = sc_p[0] if len(sc_p) == 1 else torch.cat(sc_p)
+        sims.append(sim_w.float().contiguous())
+        one = ops.slide_scores(sc_w.float().contiguous(), pl)
+        sc = one if sc is None else sc + one
+    if P > 1:
+        sc = sc / float(P)
+    cand_idx, cand_score, thr = ops.seg_select(sc, top_cls_num, plan["ncand"])
+    prob, masks, minmax = ops.slide_stitch_multi(sims, plans, flips, plan, cand_idx)
+    raw = None
+    if crf:
+        # the de-normalised base images (tools/seg_evaluation.py:104), one [g, H, W, 3] tensor per image size
+        groups, at = {}, 0
+        for b, (h, w) in enumerate(plan["sizes"]):
+            bs, views = groups.setdefault((h, w), ([], []))
+            bs.append(b)
+            views.append(flats[base][at:at + 3 * h * w].view(3, h, w))
+            at += 3 * h * w
+        raw = {hw: (bs, (((x * std) + mean) * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous())
+               for hw, (bs, x) in ((hw, (bs, v[0][None] if len(v) == 1 else torch.stack(v))) for hw, (bs, v) in groups.items())}
+    return {"cand_idx": cand_idx, "cand_score": cand_score, "threshold": thr, "scores": sc, "prob": prob, "masks": masks, "minmax": minmax,
+            "plan": plan, "images_u8": raw, "num_classes": sims[0].shape[2]}
+
+
 def _crf_cached_size(device):
     """(H, W) of the spatial lattice ops.dense_crf holds for the current stream, or None."""
     sig = ops._CRF_SPATIAL.get((device, torch.cuda.current_stream().cuda_stream))
@@ -343,6 +430,8 @@ def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=
     the network input - a [b,3,S,S] tensor, or the dict of simseg_amd.preproc.preprocess, whose packed buffer the any-size path takes as it
     is - and is called inside the encoder stage, on the encoder stream of EvalPipeline: the preprocessing kernel is queued with the batch it
     feeds and the raw bytes stay referenced as long as the batch does.  Labels of such a batch are a list ([Hl_i, Wl_i], any sizes).
+    A preprocess that returns dict(passes=[(packed, sizes, flip), ...], base=index) with slide set takes the multi-scale / flip path
+    (encode_images_multiscale).
     -> dict(iou [C] float64, miou, hist [3,C] int64 (global), images (global count), images_local)."""
     import torch.distributed as dist
     on = dist.is_available() and dist.is_initialized()
@@ -356,6 +445,12 @@ def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=
         if preprocess is not None:
             res = preprocess(image)
             # (the state keeps what preprocess returned - packed buffer, plan, tables - referenced for as long as EvalPipeline keeps the batch)
+            if isinstance(res, dict) and slide is not None and "passes" in res:
+                # test-time augmentation: preprocess returned dict(passes=[(packed, sizes, flip), ...], base=index) (encode_images_multiscale)
+                st = encode_images_multiscale(model, res["passes"], text, top_cls_num, win=slide[0], stride=slide[1], crf=crf, mean=mean, std=std,
+                                              sim_dtype=sim_dtype, window_batch=window_batch, base=res["base"])
+                st["preprocessed"] = res
+                return st
             if isinstance(res, dict) and slide is not None:
                 st = encode_images_sliding(model, res["packed"], text, top_cls_num, win=slide[0], stride=slide[1], crf=crf, mean=mean, std=std,
                                            sim_dtype=sim_dtype, window_batch=window_batch, sizes=res["sizes"])

@@ -35,6 +35,15 @@ dataset; without `--device-preproc` they go through PIL + build_transforms on th
 
     python tools/seg_eval_device.py --cfg configs/clip/simseg.vit-b.yaml --synthetic 2048 --synthetic-raw 375x500,500x375,333x500 \
         --device-preproc transforms.input_size=512 transforms.resize.size=512
+
+`--scales S1,S2,...` and `--flip` add multi-scale / horizontal-flip test-time augmentation to `--slide` with `--device-preproc`: per batch one
+device resize per scale (1.0 = the config's own valid transform, which defines the base size (H, W); the others resize the raw image to
+max(1, floor(s H + 0.5)) x max(1, floor(s W + 0.5)), bilinear), every pass cut into the same windows, mirrored passes cut from the mirrored
+image, and the passes' pixel-resolution maps fused on the device before candidate selection (segpost.encode_images_multiscale; DESIGN.md
+"Multi-scale and flip test-time augmentation").  1.0 must be among the scales:
+
+    python tools/seg_eval_device.py --cfg configs/clip/simseg.vit-b.yaml --ckpt_path ckpts/simseg.vit-b.pth --slide 512,256 --device-preproc \
+        --scales 0.75,1.0,1.25 --flip transforms.input_size=512 transforms.valid_transforms=[resize_bicubic] data.valid_name=[coco_stuff]
 """
 import argparse
 import hashlib
@@ -65,7 +74,28 @@ def parse_args():
                                                                   "instead of PIL + torch on the host; same results bit for bit")
     ap.add_argument("--synthetic-raw", default="", help="H1xW1,H2xW2,...: sizes of seeded synthetic RAW uint8 images (and their labels), cycled over "
                                                         "them and sent through the config's valid transforms on the host or, with --device-preproc, on the device")
+    ap.add_argument("--scales", default="", help="S1,S2,...: multi-scale test-time augmentation (needs --slide and --device-preproc; 1.0 must be among them)")
+    ap.add_argument("--flip", action="store_true", help="add a horizontally mirrored pass per scale (needs --slide and --device-preproc)")
     return ap.parse_known_args()
+
+
+def tta_options(args):
+    """--scales / --flip -> (scales or None, flip); SystemExit with the reason when they do not fit the other options."""
+    if not args.scales and not args.flip:
+        return None, False
+    if not args.slide or not args.device_preproc:
+        raise SystemExit("--scales / --flip need --slide WIN,STRIDE and --device-preproc (the passes are resized on the device and fused over sliding windows)")
+    try:
+        scales = [float(v) for v in args.scales.split(",")] if args.scales else [1.0]
+    except ValueError:
+        raise SystemExit(f"--scales takes comma-separated numbers, got {args.scales!r}")
+    if any(not (v > 0 and v < float("inf")) for v in scales) or len(set(scales)) != len(scales):
+        raise SystemExit(f"--scales takes distinct positive numbers, got {args.scales!r}")
+    if 1.0 not in scales:
+        raise SystemExit(f"--scales must contain 1.0 (the base pass defines the output size), got {args.scales!r}")
+    if len(scales) * (2 if args.flip else 1) > 16:
+        raise SystemExit(f"--scales / --flip: {len(scales) * (2 if args.flip else 1)} passes, at most 16 are fused in one call")
+    return scales, bool(args.flip)
 
 
 def host_crf_refine(images_uint8):
@@ -93,6 +123,7 @@ def host_crf_refine(images_uint8):
 
 def main():
     args, overrides = parse_args()
+    tta_scales, tta_flip = tta_options(args)
     os.environ.setdefault("MASTER_ADDR", "127.0.0.1"); os.environ.setdefault("MASTER_PORT", "29511")
     os.environ.setdefault("RANK", "0"); os.environ.setdefault("WORLD_SIZE", "1")
     from simseg.core import cfg, init_device, update_cfg
@@ -174,6 +205,28 @@ def main():
 
         def preprocess(raws):
             return preproc.preprocess(raws, spec, device=ENV.device)
+
+        if tta_scales:
+            if spec["crop"] is not None:
+                raise SystemExit("--scales / --flip: the valid transform ends in a centre crop; test-time augmentation takes the whole resized image")
+            one_pass = preprocess
+
+            def preprocess(raws):
+                """One device resize per scale: the base pass through the config's transform, the others to tta_sizes of its extents."""
+                res = one_pass(raws)
+                passes, src = [], None
+                for s, target in zip(tta_scales, segpost.tta_sizes(res["sizes"], tta_scales)):
+                    if s == 1.0:
+                        packed, sizes = res["packed"], res["sizes"]
+                        res["base"] = len(passes)
+                    else:
+                        scaled = preproc.preprocess_extents(raws, target, spec, device=ENV.device, src=src)
+                        packed, sizes, src = scaled["packed"], scaled["sizes"], scaled["src"]
+                    passes.append((packed, sizes, False))
+                    if tta_flip:
+                        passes.append((packed, sizes, True))
+                res["passes"] = passes
+                return res
 
     def raw_batches(shard):
         """--synthetic-raw: seeded raw uint8 [H, W, 3] images with raw-size labels, `--batch` per batch.  Device route: the raw lists as they
