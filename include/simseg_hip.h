@@ -274,6 +274,27 @@ int simseg_adamw_multi_step_amp(const void* table, const int64_t* sizes, const i
 int simseg_grads_nonfinite(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off, int64_t n_chunks,
                            int chunk, float* found_inf, void* stream);
 
+/* Global-norm gradient clipping (torch.nn.utils.clip_grad_norm_, as the reference's OptimizerHook applies it: core/hooks/optimizer.py:45-47)
+ * over the same tensor table, without touching the gradients: a read-only norm pass, a one-block finish, and AdamW launches that multiply
+ * every gradient element by the coefficient the finish left on the device.  Nothing is read on the host.
+ * simseg_grads_norm_partials: partials[c] = sum of g^2 (norm_type 2, fp32) or max |g| (norm_type 0 = infinity) over chunk c, one block
+ * per chunk, one plain store per block, no atomics (bit-reproducible); inf / nan propagate.  The caller offsets `partials` per bucket.
+ * simseg_grads_norm_finish: reduces n_partials values in double precision.  out2[0] = total norm (sqrt of the sum for type 2), divided
+ * by loss_scale[0] when loss_scale is not null - the norm of the unscaled gradients; out2[1] = min(1, max_norm / (out2[0] + 1e-6)). */
+int simseg_grads_norm_partials(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off, int64_t n_chunks,
+                               int chunk, int norm_type, float* partials, void* stream);
+int simseg_grads_norm_finish(const float* partials, int64_t n_partials, int norm_type, float max_norm, const float* loss_scale, float* out2,
+                             void* stream);
+/* simseg_adamw_multi_step / simseg_adamw_multi_step_amp with every gradient element also multiplied by grad_coef[0] (a device scalar:
+ * out2 + 1 of simseg_grads_norm_finish), after grad_scale and after the division by the loss scale: unscale, clip, update. */
+int simseg_adamw_multi_step_clip(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
+                                 int64_t n_chunks, int chunk, float beta1, float beta2, float eps, int64_t step, float grad_scale,
+                                 const float* grad_coef, void* stream);
+int simseg_adamw_multi_step_amp_clip(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
+                                     int64_t n_chunks, int chunk, float beta1, float beta2, float eps, float grad_scale,
+                                     const float* loss_scale, const float* found_inf, const float* step_in, float* step_out,
+                                     const float* grad_coef, void* stream);
+
 int simseg_cast(const void* in, void* out, int64_t n, int to_bf16, void* stream);
 int simseg_transpose_f32(const float* in, float* out, int64_t R, int64_t C, void* stream);
 /* fp32 [rows, K] (row stride ld_in) -> bf16 [rows, 6 K]: the three round-to-nearest bf16 pieces hi / mid / lo of every element

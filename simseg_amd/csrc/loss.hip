@@ -282,10 +282,14 @@ static_assert(sizeof(AdamTensors) == 48, "table rows are six 8-byte words");
 // runs without the host read torch's scaler.step() makes for an optimizer that cannot skip by itself.  Bias corrections come from the device
 // counter (skipped steps do not count, as in torch's own fused Adam).
 struct AdamAmp { const float* scale; const float* found_inf; const float* step_in; float* step_out; };
+// CLIP (simseg_adamw_multi_step_clip / _amp_clip): every gradient element is also multiplied by coef[0], the global-norm clipping
+// coefficient simseg_grads_norm_finish left on the device - AFTER the unscale, the reference's order (core/hooks/optimizer.py:45-47:
+// scaler.unscale_ then clip_grad_norm_).  A template flag, not a multiply by 1.0f: the instantiation without it is the kernel as it was.
+template <bool CLIP>
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamTensors* __restrict__ table, const long* __restrict__ sizes,
                                                           const int* __restrict__ chunk_tid, const long* __restrict__ chunk_off,
                                                           int chunk, float b1, float b2, float eps, float bc1, float bc2_sqrt,
-                                                          float grad_scale, AdamAmp amp) {
+                                                          float grad_scale, AdamAmp amp, const float* __restrict__ coef) {
     const int c = blockIdx.x;
     if (amp.step_in) {
         const bool skip = amp.found_inf && amp.found_inf[0] != 0.f;
@@ -302,8 +306,10 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamTensors* __r
     const long hi = min(sizes[t], lo + chunk);
     const float decay = 1.0f - T.lr * T.wd;
     const float step_size = T.lr / bc1;
+    const float clip = CLIP ? coef[0] : 1.0f;
     auto one = [&](float g_, float& pi, float& mi, float& vi) {
-        const float gi = g_ * grad_scale;
+        float gi = g_ * grad_scale;
+        if (CLIP) gi *= clip;
         pi *= decay;
         mi = b1 * mi + (1.0f - b1) * gi;
         vi = b2 * vi + (1.0f - b2) * gi * gi;
@@ -367,6 +373,88 @@ __global__ __launch_bounds__(256) void grads_nonfinite_kernel(const AdamTensors*
     }
     for (long i = i0 + threadIdx.x; i < hi; i += 256) bad |= ((__float_as_uint(g[i]) & 0x7f800000u) == 0x7f800000u) ? 1u : 0u;
     if (__any(bad != 0) && (threadIdx.x & 63) == 0) found[0] = 1.0f;
+}
+
+// Global gradient norm, pass 1: partials[c] = sum of g^2 (norm_type 2) or max |g| (norm_type 0 = infinity) over chunk c of the table's
+// gradient tensors - the same read-only walk as grads_nonfinite_kernel (16 bytes per lane, streaming loads, scalar tail / unaligned
+// chunks).  fp32 sums: four independent accumulators per lane (<= 64 terms each for a 65536-element chunk), combined pairwise, a wave
+// butterfly, then LDS across the four waves in a fixed order; one plain store per block and no atomics, so a call is bit-reproducible.
+// inf and nan propagate through the sums by themselves.  The maximum is taken on the bit patterns of |g| as unsigned integers: for
+// non-negative floats that is the floating-point order, and every nan pattern lies above +inf, so a nan wins (fmaxf would drop it).
+__global__ __launch_bounds__(256) void grads_norm_partials_kernel(const AdamTensors* __restrict__ table, const long* __restrict__ sizes,
+                                                                  const int* __restrict__ chunk_tid, const long* __restrict__ chunk_off,
+                                                                  int chunk, int norm_type, float* __restrict__ partials) {
+    __shared__ float sh[4];
+    const int c = blockIdx.x;
+    const int t = chunk_tid[c];
+    const float* g = table[t].g;
+    const long lo = chunk_off[c];
+    const long hi = min(sizes[t], lo + chunk);
+    const bool vec = (uintptr_t)(g + lo) % 16 == 0;
+    const long n4 = vec ? (hi - lo) / 4 : 0;
+    const long i0 = lo + 4 * n4;
+    float r;
+    if (norm_type == 2) {
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+        for (long q = threadIdx.x; q < n4; q += 256) {
+            const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + lo + 4 * q));
+            a0 += v[0] * v[0]; a1 += v[1] * v[1]; a2 += v[2] * v[2]; a3 += v[3] * v[3];
+        }
+        for (long i = i0 + threadIdx.x; i < hi; i += 256) a0 += g[i] * g[i];
+        r = wave_sum((a0 + a1) + (a2 + a3));
+    } else {
+        unsigned m = 0;
+        for (long q = threadIdx.x; q < n4; q += 256) {
+            const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(g + lo + 4 * q));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) m = max(m, v[e] & 0x7fffffffu);
+        }
+        for (long i = i0 + threadIdx.x; i < hi; i += 256) m = max(m, __float_as_uint(g[i]) & 0x7fffffffu);
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
+        r = __uint_as_float(m);
+    }
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = r;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (norm_type == 2) r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+        else r = __uint_as_float(max(max(__float_as_uint(sh[0]), __float_as_uint(sh[1])), max(__float_as_uint(sh[2]), __float_as_uint(sh[3]))));
+        partials[c] = r;
+    }
+}
+
+// Pass 2, one block: the partials of every bucket reduced in double precision (fixed order: strided per lane, wave butterfly, LDS).
+// out2[0] = the total norm, divided by loss_scale[0] when given (the norm of the UNSCALED gradients, which is what the reference clips);
+// out2[1] = min(1, max_norm / (total_norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s coefficient (a nan norm gives a nan coefficient, as
+// torch's clamp does).  Everything stays on the device.
+__global__ __launch_bounds__(256) void grads_norm_finish_kernel(const float* __restrict__ partials, long n, int norm_type, float max_norm,
+                                                                const float* __restrict__ loss_scale, float* __restrict__ out2) {
+    __shared__ double shd[4];
+    double acc = 0.0;
+    if (norm_type == 2) {
+        for (long i = threadIdx.x; i < n; i += 256) acc += (double)partials[i];
+    } else {
+        unsigned m = 0;
+        for (long i = threadIdx.x; i < n; i += 256) m = max(m, __float_as_uint(partials[i]));
+        acc = (double)m;          // (exact: the bit patterns are ordered like the values; turned back into a float below)
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double other = __shfl_xor(acc, o, 64);
+        acc = norm_type == 2 ? acc + other : fmax(acc, other);
+    }
+    if ((threadIdx.x & 63) == 0) shd[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double total;
+        if (norm_type == 2) total = sqrt((shd[0] + shd[1]) + (shd[2] + shd[3]));
+        else total = (double)__uint_as_float((unsigned)fmax(fmax(shd[0], shd[1]), fmax(shd[2], shd[3])));
+        if (loss_scale) total /= (double)loss_scale[0];
+        double coef = (double)max_norm / (total + 1e-6);
+        if (coef > 1.0) coef = 1.0;
+        out2[0] = (float)total;
+        out2[1] = (float)coef;
+    }
 }
 
 }  // namespace
@@ -489,9 +577,27 @@ extern "C" int simseg_adamw_multi_step(const void* table, const int64_t* sizes, 
     if (n_chunks <= 0) return 0;
     const float bc1 = 1.0f - powf(beta1, (float)step);
     const float bc2 = 1.0f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
-                       (const int*)chunk_tid, (const long*)chunk_off, chunk, beta1, beta2, eps, bc1, sqrtf(bc2), grad_scale, AdamAmp{});
+    hipLaunchKernelGGL(adamw_multi_kernel<false>, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
+                       (const int*)chunk_tid, (const long*)chunk_off, chunk, beta1, beta2, eps, bc1, sqrtf(bc2), grad_scale, AdamAmp{},
+                       (const float*)nullptr);
     SS_LAUNCH_CHECK("adamw_multi_step");
+    return 0;
+}
+
+extern "C" int simseg_adamw_multi_step_clip(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
+                                            int64_t n_chunks, int chunk, float beta1, float beta2, float eps, int64_t step,
+                                            float grad_scale, const float* grad_coef, void* stream) {
+    SS_HALF_FWD(simseg_adamw_multi_step_clip, table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, step, grad_scale,
+                grad_coef, stream);
+    SS_CHECK(table && sizes && chunk_tid && chunk_off && grad_coef, "adamw_multi_step_clip: null pointer");
+    SS_CHECK(step >= 1 && chunk > 0, "adamw_multi_step_clip: bad step/chunk");
+    if (n_chunks <= 0) return 0;
+    const float bc1 = 1.0f - powf(beta1, (float)step);
+    const float bc2 = 1.0f - powf(beta2, (float)step);
+    hipLaunchKernelGGL(adamw_multi_kernel<true>, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
+                       (const int*)chunk_tid, (const long*)chunk_off, chunk, beta1, beta2, eps, bc1, sqrtf(bc2), grad_scale, AdamAmp{},
+                       grad_coef);
+    SS_LAUNCH_CHECK("adamw_multi_step_clip");
     return 0;
 }
 
@@ -504,9 +610,27 @@ extern "C" int simseg_adamw_multi_step_amp(const void* table, const int64_t* siz
     SS_CHECK(chunk > 0, "adamw_multi_step_amp: bad chunk");
     if (n_chunks <= 0) return 0;
     AdamAmp amp{loss_scale, found_inf, step_in, step_out};
-    hipLaunchKernelGGL(adamw_multi_kernel, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
-                       (const int*)chunk_tid, (const long*)chunk_off, chunk, beta1, beta2, eps, 1.0f, 1.0f, grad_scale, amp);
+    hipLaunchKernelGGL(adamw_multi_kernel<false>, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
+                       (const int*)chunk_tid, (const long*)chunk_off, chunk, beta1, beta2, eps, 1.0f, 1.0f, grad_scale, amp,
+                       (const float*)nullptr);
     SS_LAUNCH_CHECK("adamw_multi_step_amp");
+    return 0;
+}
+
+extern "C" int simseg_adamw_multi_step_amp_clip(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
+                                                int64_t n_chunks, int chunk, float beta1, float beta2, float eps, float grad_scale,
+                                                const float* loss_scale, const float* found_inf, const float* step_in, float* step_out,
+                                                const float* grad_coef, void* stream) {
+    SS_HALF_FWD(simseg_adamw_multi_step_amp_clip, table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, grad_scale,
+                loss_scale, found_inf, step_in, step_out, grad_coef, stream);
+    SS_CHECK(table && sizes && chunk_tid && chunk_off && step_in && step_out && step_in != step_out && grad_coef,
+             "adamw_multi_step_amp_clip: null / aliased pointer");
+    SS_CHECK(chunk > 0, "adamw_multi_step_amp_clip: bad chunk");
+    if (n_chunks <= 0) return 0;
+    AdamAmp amp{loss_scale, found_inf, step_in, step_out};
+    hipLaunchKernelGGL(adamw_multi_kernel<true>, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
+                       (const int*)chunk_tid, (const long*)chunk_off, chunk, beta1, beta2, eps, 1.0f, 1.0f, grad_scale, amp, grad_coef);
+    SS_LAUNCH_CHECK("adamw_multi_step_amp_clip");
     return 0;
 }
 
@@ -519,6 +643,28 @@ extern "C" int simseg_grads_nonfinite(const void* table, const int64_t* sizes, c
     hipLaunchKernelGGL(grads_nonfinite_kernel, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
                        (const int*)chunk_tid, (const long*)chunk_off, chunk, found_inf);
     SS_LAUNCH_CHECK("grads_nonfinite");
+    return 0;
+}
+
+extern "C" int simseg_grads_norm_partials(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
+                                          int64_t n_chunks, int chunk, int norm_type, float* partials, void* stream) {
+    SS_CHECK(table && sizes && chunk_tid && chunk_off && partials, "grads_norm_partials: null pointer");
+    SS_CHECK(chunk > 0 && (norm_type == 2 || norm_type == 0), "grads_norm_partials: chunk > 0, norm_type 2 or 0 (infinity)");
+    if (n_chunks <= 0) return 0;
+    hipLaunchKernelGGL(grads_norm_partials_kernel, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table,
+                       (const long*)sizes, (const int*)chunk_tid, (const long*)chunk_off, chunk, norm_type, partials);
+    SS_LAUNCH_CHECK("grads_norm_partials");
+    return 0;
+}
+
+extern "C" int simseg_grads_norm_finish(const float* partials, int64_t n_partials, int norm_type, float max_norm, const float* loss_scale,
+                                        float* out2, void* stream) {
+    SS_CHECK(out2 && (partials || n_partials <= 0), "grads_norm_finish: null pointer");
+    SS_CHECK(norm_type == 2 || norm_type == 0, "grads_norm_finish: norm_type 2 or 0 (infinity)");
+    SS_CHECK(max_norm >= 0.f, "grads_norm_finish: max_norm %g is negative (or nan)", (double)max_norm);
+    hipLaunchKernelGGL(grads_norm_finish_kernel, dim3(1), dim3(256), 0, STREAM, partials, (long)(n_partials > 0 ? n_partials : 0), norm_type,
+                       max_norm, loss_scale, out2);
+    SS_LAUNCH_CHECK("grads_norm_finish");
     return 0;
 }
 

@@ -12,15 +12,36 @@ training step launches no weight-cast kernels.
 Checkpoints use torch.optim.AdamW's state layout ({step, exp_avg, exp_avg_sq} per parameter), so the reference's optimizer
 checkpoints (core/hooks/checkpoint.py:14-45) load here and ours load there; the bias-correction step counter travels with them."""
 import contextlib
+import math
 
 import numpy as np
 import torch
+from torch.amp.grad_scaler import OptState
 
 from .lib import call, note_half, ptr, stream
 from .towers import drop_qscaled_copy, drop_split_copy, register_w16
 
 CHUNK = 1 << 16
 RING = 4
+
+
+def norm_type_code(norm_type):
+    """norm_type of torch.nn.utils.clip_grad_norm_ -> the kernels' code: 2 (Euclidean) or 0 (infinity).  Checked on the host, before any
+    device work."""
+    nt = float(norm_type)
+    if nt == 2.0:
+        return 2
+    if nt == math.inf:
+        return 0
+    raise NotImplementedError(f"norm_type {norm_type!r}: the fused gradient norm knows 2 and infinity (torch.nn.utils.clip_grad_norm_ has the others)")
+
+
+def live_scale(scaler):
+    """The loss scale of an enabled torch.amp.GradScaler as its float32 device tensor (what AdamW.clip_grad_norm_ takes as loss_scale);
+    None for a disabled scaler, for None, and before the scaler's first scale() call (the gradients are then unscaled anyway)."""
+    if scaler is None or not scaler.is_enabled():
+        return None
+    return scaler._scale
 
 
 class AdamW(torch.optim.Optimizer):
@@ -40,6 +61,9 @@ class AdamW(torch.optim.Optimizer):
         self._plans = {}
         self._prepared = None
         self._streams = {}                # id(parameter) -> stream its update is launched on (set_param_streams); default: the current stream
+        self._clip_coef = None            # armed by clip_grad_norm_: float32 [1] on the device, the coefficient the next step() multiplies in
+        self._norm_partials = None        # float32 [sum of the buckets' n_chunks]: one partial per chunk of the gradient-norm pass
+        self._norm_out = None             # float32 [2, 2]: {norm, coefficient} of clip_grad_norm_ (row 0) and of grad_norm (row 1)
 
     def set_param_streams(self, mapping):
         """mapping: {parameter: torch.cuda.Stream or None}.  The update of those parameters is launched on that stream instead of the current
@@ -160,6 +184,84 @@ class AdamW(torch.optim.Optimizer):
                  ptr(found_inf), stream())
         return found_inf
 
+    # ---- global gradient norm / clipping over the same tables ---------------------------------------------------------------
+    def _norm_pass(self, code, max_norm, loss_scale, row):
+        """One read-only launch per bucket into one partials buffer, one finish: _norm_out[row] = {norm, min(1, max_norm / (norm + 1e-6))}."""
+        ready = self._prepare(on_own=False)       # every bucket on the current stream: the norm needs them all
+        total = sum(plan["n_chunks"] for _, plan, _ in ready)
+        if self._norm_out is None or self._norm_partials.numel() < total:     # (with the plans: the first call, or a re-plan that grew)
+            dev = ready[0][1]["table"].device if ready else self.param_groups[0]["params"][0].device
+            self._norm_partials = torch.empty(max(total, 1), device=dev, dtype=torch.float32)
+            if self._norm_out is None:
+                self._norm_out = torch.zeros(2, 2, device=dev, dtype=torch.float32)
+        if loss_scale is not None and (loss_scale.dtype != torch.float32 or not loss_scale.is_cuda):
+            raise TypeError("loss_scale: a float32 tensor on the device (torch.amp.GradScaler's scale: optim.live_scale)")
+        first = 0
+        for key, plan, params in ready:
+            call("simseg_grads_norm_partials", ptr(plan["table"]), ptr(plan["sizes"]), ptr(plan["tid"]), ptr(plan["coff"]), plan["n_chunks"], CHUNK,
+                 code, ptr(self._norm_partials[first:]), stream())
+            first += plan["n_chunks"]
+        call("simseg_grads_norm_finish", ptr(self._norm_partials), first, code, float(max_norm), ptr(loss_scale), ptr(self._norm_out[row]), stream())
+        return ready
+
+    @torch.no_grad()
+    def clip_grad_norm_(self, max_norm, norm_type=2.0, error_if_nonfinite=False, loss_scale=None, materialize=False):
+        """torch.nn.utils.clip_grad_norm_ over this optimizer's parameters, fused into the next step(): one read-only pass over the
+        gradients (one launch per bucket over the step's own tensor tables, which the step() - and a GradScaler's overflow check - that
+        follows reuses: one upload), one finish, and the update kernel multiplies every gradient element by
+        min(1, max_norm / (total_norm + 1e-6)) as it reads it.  Returns the total norm, a 0-dim float32 device tensor (a view of a buffer
+        the next call overwrites: clone it to keep it).  No allocation after the first call and no host read: it adds to the step nothing
+        that a graph capture (simseg_amd/graph.py) or a sync-debug run would trip over.
+
+        * p.grad is left UNCLIPPED; only the update sees the clipped values.  materialize=True also scales p.grad in place (one small
+          launch per tensor) for callers that look at the gradients afterwards; step() then applies no coefficient.
+        * It arms the NEXT step() only - call it immediately before step() / scaler.step() - and step() disarms it; zero_grad() does too.
+          An armed step launches every bucket on the current stream (set_param_streams is ignored, as under a GradScaler).
+        * The gradients must be final: call it after any gradient exchange (parallel.GradSync.finish()).  Parameters whose grad is None
+          do not count, as in torch.
+        * loss_scale (a float32 device scalar: live_scale(scaler)) says the gradients still carry a GradScaler's loss scale: norm and
+          coefficient then refer to the UNSCALED gradients - the reference unscales before it clips (core/hooks/optimizer.py:45-47) -
+          while the gradients stay scaled until the update kernel divides the scale out.  GradScaler.clip_grad_norm_ passes it.
+        * norm_type: 2 or infinity.  error_if_nonfinite=True reads the norm on the host (the only path here that does)."""
+        code = norm_type_code(norm_type)
+        ready = self._norm_pass(code, max_norm, loss_scale, 0)
+        norm, coef = self._norm_out[0, 0], self._norm_out[0, 1:2]
+        if error_if_nonfinite and not bool(torch.isfinite(norm)):
+            self._prepared = None
+            raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it cannot be clipped.")
+        if materialize:
+            for key, plan, params in ready:
+                for p, g in zip(params, plan["keepalive"]):
+                    call("simseg_scale_by_scalar", ptr(g), ptr(coef), ptr(g), g.numel(), 1.0, stream())
+                    if g is not p.grad:               # (a non-contiguous gradient: the table addresses a contiguous copy)
+                        p.grad.copy_(g)
+            self._clip_coef = None
+        else:
+            self._clip_coef = coef
+        return norm
+
+    @torch.no_grad()
+    def grad_norm(self, norm_type=2.0):
+        """The total gradient norm (2 or infinity) as a 0-dim float32 device tensor, by the same read-only pass; arms nothing and leaves an
+        armed clip alone.  For logging: no host read; the value is overwritten by the next grad_norm() call.  The gradients must be
+        final (after any gradient exchange) and count as they are - under a GradScaler that is the SCALED norm.  It uploads tables of
+        its own (the step that follows prepares again)."""
+        code = norm_type_code(norm_type)
+        self._norm_pass(code, math.inf, None, 1)
+        self._prepared = None
+        return self._norm_out[1, 0]
+
+    def clip_coef(self):
+        """The coefficient min(1, max_norm / (total_norm + 1e-6)) of the last clip_grad_norm_ call: a 0-dim float32 device tensor (1 = the
+        clip did not bite), overwritten by the next call."""
+        if self._norm_out is None:
+            raise RuntimeError("clip_coef(): no clip_grad_norm_ call yet")
+        return self._norm_out[0, 1]
+
+    def zero_grad(self, set_to_none=True):
+        self._prepared, self._clip_coef = None, None      # tables and a coefficient of gradients that are going away
+        super().zero_grad(set_to_none=set_to_none)
+
     def steps_taken(self):
         """Updates actually applied (a host read of the device counter when a GradScaler drives this optimizer: skipped steps do not count)."""
         if self._step_dev is not None:
@@ -171,9 +273,11 @@ class AdamW(torch.optim.Optimizer):
         # torch.amp.GradScaler.step() sets these two attributes around the call (and deletes them afterwards)
         loss_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
         amp = loss_scale is not None or found_inf is not None
-        # param_streams=False (or a GradScaler-driven step, whose overflow flag is produced on the current stream): every launch on the
-        # current stream, whatever set_param_streams said - the caller's backward did not run on those streams this time
-        on_own = param_streams and not amp
+        coef, self._clip_coef = self._clip_coef, None      # clip_grad_norm_ armed this step only
+        # param_streams=False (or a GradScaler-driven step, whose overflow flag is produced on the current stream; or a clipped one, whose
+        # coefficient is): every launch on the current stream, whatever set_param_streams said - the caller's backward did not run on those
+        # streams this time
+        on_own = param_streams and not amp and coef is None
         ready = self._prepare(on_own)
         self._prepared = None
         if amp:
@@ -195,9 +299,14 @@ class AdamW(torch.optim.Optimizer):
               note_half(self.half_dtype)        # (the 16-bit copies are addressed through the table: tell the binding which flavour they are)
               if amp:
                   cur = self._amp_calls & 1
-                  call("simseg_adamw_multi_step_amp", ptr(plan["table"]), ptr(plan["sizes"]), ptr(plan["tid"]), ptr(plan["coff"]), plan["n_chunks"],
+                  tail = (ptr(coef), stream()) if coef is not None else (stream(),)
+                  call("simseg_adamw_multi_step_amp_clip" if coef is not None else "simseg_adamw_multi_step_amp", ptr(plan["table"]),
+                       ptr(plan["sizes"]), ptr(plan["tid"]), ptr(plan["coff"]), plan["n_chunks"],
                        CHUNK, key[0], key[1], key[2], float(grad_scale), ptr(loss_scale), ptr(found_inf), ptr(self._step_dev[cur:cur + 1]),
-                       ptr(self._step_dev[1 - cur:2 - cur]), stream())
+                       ptr(self._step_dev[1 - cur:2 - cur]), *tail)
+              elif coef is not None:
+                  call("simseg_adamw_multi_step_clip", ptr(plan["table"]), ptr(plan["sizes"]), ptr(plan["tid"]), ptr(plan["coff"]), plan["n_chunks"],
+                       CHUNK, key[0], key[1], key[2], self._step, float(grad_scale), ptr(coef), stream())
               else:
                   call("simseg_adamw_multi_step", ptr(plan["table"]), ptr(plan["sizes"]), ptr(plan["tid"]), ptr(plan["coff"]), plan["n_chunks"],
                        CHUNK, key[0], key[1], key[2], self._step, float(grad_scale), stream())
@@ -240,7 +349,7 @@ class AdamW(torch.optim.Optimizer):
             st["m"], st["v"] = st["m"].float().contiguous(), st["v"].float().contiguous()
             st.pop("p16", None)
         self._step = max(steps) if steps else 0
-        self._step_dev, self._amp_calls, self._prepared = None, 0, None
+        self._step_dev, self._amp_calls, self._prepared, self._clip_coef = None, 0, None, None
 
 
 class GradScaler(torch.amp.GradScaler):
@@ -260,3 +369,16 @@ class GradScaler(torch.amp.GradScaler):
         optimizer.found_inf_check(found_inf)
         self._per_optimizer_states[id(optimizer)]["found_inf_per_device"] = {_scale.device: found_inf}
         return self._per_optimizer_states[id(optimizer)]["found_inf_per_device"]
+
+    def clip_grad_norm_(self, optimizer, max_norm, norm_type=2.0, error_if_nonfinite=False, materialize=False):
+        """Between backward() and step(optimizer): clips a simseg_amd AdamW's gradients by their global norm, in the reference's order -
+        unscale, then clip (core/hooks/optimizer.py:45-47) - without unscaling them: AdamW.clip_grad_norm_ gets the live scale tensor, so
+        the norm it returns and the coefficient it arms for step() refer to the unscaled gradients, while the gradients stay scaled until
+        the update kernel divides the scale out.  Returns the (unscaled) total norm as a 0-dim device tensor."""
+        if not isinstance(optimizer, AdamW):
+            raise TypeError("GradScaler.clip_grad_norm_ drives a simseg_amd AdamW; for another optimizer: scaler.unscale_(optimizer), then "
+                            "torch.nn.utils.clip_grad_norm_")
+        # (after an explicit scaler.unscale_(optimizer) the gradients carry no scale any more, and step() gets none either)
+        unscaled = self.is_enabled() and self._per_optimizer_states[id(optimizer)]["stage"] is OptState.UNSCALED
+        return optimizer.clip_grad_norm_(max_norm, norm_type=norm_type, error_if_nonfinite=error_if_nonfinite,
+                                         loss_scale=None if unscaled else live_scale(self), materialize=materialize)

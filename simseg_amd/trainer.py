@@ -16,7 +16,12 @@ import time
 
 import torch
 
-from .optim import AdamW, GradScaler
+from .optim import AdamW, GradScaler, live_scale
+
+# cfg.optim.grad_clip with this package's AdamW: 1 (default) = the fused route - one read-only norm pass over the optimizer's tensor tables,
+# the coefficient applied inside the update kernel; 0 = the torch route (scaler.unscale_ + torch.nn.utils.clip_grad_norm_, what foreign
+# optimizers always get).  Read once, at import.
+FUSED_CLIP = os.environ.get("SIMSEG_AMD_FUSED_CLIP", "1") not in ("0", "")
 
 
 # ---- stateless learning-rate multipliers (functions of the global step only) -----------------------------------------
@@ -103,14 +108,30 @@ class Trainer:
             loss_dict, i2t_acc, t2i_acc = self.net(batch)
         loss = sum(loss_dict.values())
         self.scaler.scale(loss).backward()           # (disabled scaler: the loss itself)
+        out = {"loss": loss.detach(), "i2t_acc": i2t_acc, "t2i_acc": t2i_acc, "lr": lrs[0]}
         clip = dict(self.cfg.optim.grad_clip)
-        if clip:                                     # the reference clips BEFORE scaler.step (on the scaled gradients): core/hooks/optimizer.py:82-86
-            torch.nn.utils.clip_grad_norm_([p for p in self.model.parameters() if p.grad is not None], **clip)
+        if clip:                                     # the reference unscales, THEN clips, then scaler.step: core/hooks/optimizer.py:45-47, 82-86
+            out["grad_norm"] = self.clip_gradients(clip)
         self.scaler.step(self.optimizer)             # unscale_, skip the step on inf / nan (disabled: optimizer.step())
         self.scaler.update()
         self.step += 1
         self.inner_step += 1
-        return {"loss": loss.detach(), "i2t_acc": i2t_acc, "t2i_acc": t2i_acc, "lr": lrs[0]}
+        return out
+
+    def clip_gradients(self, clip):
+        """cfg.optim.grad_clip (the keyword arguments of torch.nn.utils.clip_grad_norm_) applied to the UNSCALED gradients, as the
+        reference's OptimizerHook does; -> the total norm, a 0-dim device tensor (no host read).
+        Fused route (this package's AdamW, norm type 2 or infinity, SIMSEG_AMD_FUSED_CLIP not 0): the gradients are neither unscaled nor
+        rescaled in memory - AdamW.clip_grad_norm_ measures them in one read-only pass and the update kernel applies loss scale and
+        coefficient as it reads them.  Torch route (any other optimizer or norm type, or the switch): scaler.unscale_ + torch's
+        clip_grad_norm_; torch's scaler remembers that it unscaled this optimizer and hands scaler.step no scale, so the fused unscale
+        of AdamW.step does not divide a second time."""
+        kw = {k: v for k, v in clip.items() if k != "foreach"}
+        if FUSED_CLIP and isinstance(self.optimizer, AdamW) and float(kw.get("norm_type", 2.0)) in (2.0, math.inf):
+            return self.optimizer.clip_grad_norm_(loss_scale=live_scale(self.scaler), **kw)
+        if self.scaler.is_enabled():
+            self.scaler.unscale_(self.optimizer)
+        return torch.nn.utils.clip_grad_norm_([p for p in self.model.parameters() if p.grad is not None], **clip)
 
     # ---- checkpoints in the reference's layout ---------------------------------------------------------------------
     def checkpoint(self, end_of_epoch=False):
