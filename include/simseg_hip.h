@@ -121,11 +121,14 @@ int64_t simseg_topk_pool_workspace_bytes(int64_t B, int64_t P, int k);
 int simseg_topk_pool_l2norm_bwd(const float* demb, const float* emb, const float* norm, const int32_t* idx, void* dtok,
                                 int dtype, int64_t B, int64_t N, int64_t P, int k, float eps, int normalize, void* stream);
 
-/* Kernel selection for benchmarking / tests (thread-local): 0 auto (bf16 sequences of <= 256 tokens run the "resident" kernels that hold a
- * whole head's K / V - or Q / dO - in LDS), 1 = always the streaming ring kernels (2 / 3: timing ablations). */
+/* Kernel selection for benchmarking / tests (thread-local, consumed by the host-side dispatch only): 0 auto (16-bit sequences of <= 256
+ * tokens run the "resident" kernels that hold a whole head's operands in LDS; unmasked ones of >= 512 tokens the 64-queries-per-wave
+ * forward), 1 = the streaming ring kernels wherever they apply, 6 / 7 = the 64-queries-per-wave forward with one / two query blocks per
+ * wave (unmasked sequences of >= 65 tokens).  Every value selects between production kernels; any other value is an error and leaves
+ * the previous selection in force. */
 int simseg_set_attention_variant(int v);
-int simseg_debug_attn_occupancy(int64_t T);
-/* debug (thread-local): the resident dK/dV kernel writes 3 x uint64 per block (start / operands landed / end, 100 MHz wall clock). */
+/* debug (thread-local): the one-kernel backward writes 4 x uint64 per block (start / operands landed / tile loop done / end, 100 MHz wall
+ * clock); NULL switches it off. */
 int simseg_debug_attn_trace(void* buf);
 /* debug (thread-local): the ping-pong GEMM kernel writes 5 x uint64 per block into buf (wall-clock stamps at 100 MHz of block start, K loop
  * start, K loop end, block end; HW_ID) - tools/dbg_gemm_trace.py; NULL switches it off. */

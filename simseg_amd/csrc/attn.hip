@@ -14,6 +14,8 @@
 #include "common.h"
 #include <type_traits>
 
+extern "C" int simseg_colsum_accum(const void* in, int in_dtype, float* out, int64_t rows, int64_t N, int64_t ld, void* stream);      // rowops.hip
+
 namespace {
 
 constexpr int KT = 64;            // keys per LDS tile
@@ -26,7 +28,6 @@ struct AttnParams {
     unsigned long long drop_seed; unsigned int drop_thresh; float drop_scale;
     // backward
     const void* dout; const float* delta; void* dqkv;
-    int dbg;            // resident kernels, benchmarking only: 2 = skip the K/V copy, 3 = skip the tile loop
     unsigned long long* trace;   // debugging (simseg_debug_attn_trace): per block {start, operands landed, end} wall-clock stamps
     int pack;           // resident kernels: rows past the last unmasked key of a sequence are neither read nor written (see attn_teff)
     float* colsum_ws;   // one-kernel backward: [B][3*H*64] per-sequence column sums of dqkv (the qkv bias gradient before the fold over B), or null
@@ -1243,16 +1244,10 @@ __global__ __launch_bounds__(256, NQB == 2 ? 2 : 3) void attn_fwd_w64_kernel(Att
 
 // host side.  Full blocks of 4 x 64 query rows (plus a partial one when more than half a block is left over); the rows behind them go to
 // key-split blocks of the same launch.  variant 6 (tools): one query block per wave throughout.
-thread_local int g_w64_extra_lds = 0;      // tools (attention variant 8): unused dynamic LDS per block, so that ONE block fits a CU
 template <int NQB, bool QS, bool DBG>
 static void launch_w64_grid(const AttnParams& p, hipStream_t stream, unsigned blocks) {
-    const int extra = g_w64_extra_lds;
-    if (extra) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_w64_kernel<NQB, false, QS, DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, extra);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_w64_kernel<NQB, true, QS, DBG>), hipFuncAttributeMaxDynamicSharedMemorySize, extra);
-    }
-    if ((p.T - 1) % 64) hipLaunchKernelGGL((attn_fwd_w64_kernel<NQB, true, QS, DBG>), dim3(blocks), dim3(256), extra, stream, p);
-    else hipLaunchKernelGGL((attn_fwd_w64_kernel<NQB, false, QS, DBG>), dim3(blocks), dim3(256), extra, stream, p);
+    if ((p.T - 1) % 64) hipLaunchKernelGGL((attn_fwd_w64_kernel<NQB, true, QS, DBG>), dim3(blocks), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((attn_fwd_w64_kernel<NQB, false, QS, DBG>), dim3(blocks), dim3(256), 0, stream, p);
 }
 
 template <bool DBG>
@@ -1296,7 +1291,7 @@ static void launch_w64(const AttnParams& p0, hipStream_t stream, int nqb) {
 constexpr int X3_STAGE = 6 * KT * 128;
 constexpr int X3_NS = 3;
 
-struct AttnX3Params { const bf16_t* qkv3; long plane; float* out; int B, T, H; float scale_log2e; int dbg; };
+struct AttnX3Params { const bf16_t* qkv3; long plane; float* out; int B, T, H; float scale_log2e; };
 
 __device__ __forceinline__ void kv_glds_x3(const bf16_t* base, long plane, long RS, int HD, int kv0, int T, char* stage, int wave, int nw, int per,
                                            int lane) {
@@ -1387,12 +1382,12 @@ __global__ __launch_bounds__(512) void attn_fwd_x3_kernel(AttnX3Params p) {
     auto tile = [&](int it, auto edge_tag) {
         constexpr bool EDGE = decltype(edge_tag)::value;
         const int kv0 = it * KT;
-        if (it > 0 && !(p.dbg & 16)) {
+        if (it > 0) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's copies of tile it + 1 (issued one iteration ago)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
         }
-        if (it + 2 < nt && !(p.dbg & 8)) {                  // every wave has left tile it - 1: its stage takes tile it + 2
+        if (it + 2 < nt) {                  // every wave has left tile it - 1: its stage takes tile it + 2
             int ns = cur + 2; ns = ns >= X3_NS ? ns - X3_NS : ns;
             kv_glds_x3(base, p.plane, RS, HD, kv0 + 2 * KT, T, lds + ns * X3_STAGE, wave, nw, per, lane);
         }
@@ -1404,9 +1399,9 @@ __global__ __launch_bounds__(512) void attn_fwd_x3_kernel(AttnX3Params p) {
         // every wave passes the tile barrier at the same instant, and with one order both waves of a SIMD held the matrix pipe together
         // and then the VALU together (MFMA time + VALU time per tile, measured).
         const bool first = wave < 4;
-        if (!EDGE && first && !(p.dbg & 4)) scores(lds + nx * X3_STAGE, sn);
+        if (!EDGE && first) scores(lds + nx * X3_STAGE, sn);
         __builtin_amdgcn_sched_barrier(0);
-        if (!(p.dbg & 1)) softmax_tile_lean<false, EDGE>(s, nullptr, h2, p.scale_log2e, m, lsum, o, T - kv0);
+        softmax_tile_lean<false, EDGE>(s, nullptr, h2, p.scale_log2e, m, lsum, o, T - kv0);
         // the fp32 probabilities as three exact bf16 pieces (index [piece][kb * 2 + s2])
         bf16x8 pp[3][4];
 #pragma unroll
@@ -1423,7 +1418,6 @@ __global__ __launch_bounds__(512) void attn_fwd_x3_kernel(AttnX3Params p) {
                     pp[1][kb * 2 + s2][e] = mid;
                     pp[2][kb * 2 + s2][e] = (bf16_t)(r1 - (float)mid);
                 }
-        if (!(p.dbg & 2))
 #pragma unroll
         for (int vc = 2; vc >= 0; --vc) {
             bf16x8 vf[8];
@@ -1446,7 +1440,7 @@ __global__ __launch_bounds__(512) void attn_fwd_x3_kernel(AttnX3Params p) {
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (!EDGE && !first && !(p.dbg & 4)) scores(lds + nx * X3_STAGE, sn);
+        if (!EDGE && !first) scores(lds + nx * X3_STAGE, sn);
         if (!EDGE) { s[0] = sn[0]; s[1] = sn[1]; }
         cur = cur + 1 == X3_NS ? 0 : cur + 1;
     };
@@ -1475,8 +1469,7 @@ __global__ __launch_bounds__(512) void attn_fwd_x3_kernel(AttnX3Params p) {
 // phase under the other blocks' compute.  (The ring kernel spent 8.3 k of its 22.5 k cycles per block staging the first
 // tile and ~660 cycles per tile in wait + barrier: profiles/r1_attn_timeline.txt.)
 // ------------------------------------------------------------------------------------------------
-constexpr int RES_MAXT = 256;
-constexpr int RES_AUTO_T = 256;          // measured (tools/dbg_attn_res.py): resident 56 vs ring 61 us at T=77, 20 vs 31 at T=25; at T=197 a tie in
+constexpr int RES_MAXT = 256;            // also the dispatcher's crossover.  Measured: resident 56 vs ring 61 us at T=77, 20 vs 31 at T=25; at T=197 a tie in
                                          // isolation (214 vs 209 us) and -0.3 ms per training step (same-box A/B), so resident wherever it fits
 
 // LDS of the resident kernels: [K rows8 x 128 B][V rows8 x 128 B][key bias], rows8 = T rounded up to 8 (rows T..rows8-1 repeat row
@@ -1527,7 +1520,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     float* kb_all = reinterpret_cast<float*>(ldsV + rows8 * 128);
 
     // K rows first (the first MFMAs need only K), then V rows; rows past T re-read row T-1
-    for (int piece = (p.dbg == 102 ? 2 * np : wave); piece < 2 * np; piece += nw) {
+    for (int piece = wave; piece < 2 * np; piece += nw) {
         const int isv = piece >= np;
         const int pp = isv ? piece - np : piece;
         const int r = pp * 8 + (lane >> 3);
@@ -1652,7 +1645,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 }
             }
         };
-        if (p.dbg != 103) {
+        // (this kernel scales q itself: pre-scaled operands, p.qscaled, belong to the w64 forward and never arrive here.  The test is
+        // always true; it is kept because a pass whose tile loops sit under a condition on a kernel argument is compiled with its
+        // invariants computed inside the pass.  Without it they are hoisted above the pass loop: 1 -> 3 and, with dropout, 15 -> 20
+        // spilled registers, and the T = 77 dropout forward measured 3.5 % slower - profiles/attn_prune.txt)
+        if (!p.qscaled) {
             for (int it = 0; it < nt - 1; ++it) tile(it, std::false_type{});
             tile(nt - 1, std::true_type{});            // (a full last tile goes through the masked form too: same result)
         }
@@ -1671,246 +1668,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
             if (p.lse && h2 == 0) p.lse[((long)b * p.H + h) * Tf + q] = m + log2f(ltot);
         }
     }
-}
-
-// ------------------------------------------------------------------------------------------------
-// bf16 forward, ViT-B training shape (128 < T <= 256, no mask, no dropout): PERSISTENT form with a loader wave (round 4).
-// The resident kernel above is one block per head: copy K / V (50 KB at T = 197) -> wait -> 2 query passes -> store, three such blocks per
-// CU at independent phases.  Measured (profiles/r2_attn_fwd_ablation.txt): its copies alone take 150 us, its tile loops alone 164 us, the
-// kernel 214 us - a block that computes has no copies in flight and a CU's HBM share is proportional to what it has in flight, so most
-// of one component is exposed.  Here ONE block per CU walks its heads: wave q32 only issues global -> LDS copies (the next head's K and V
-// into the other LDS stage, all 2 * rows8 / 8 pieces at once) and waits for them; waves 0 .. q32-1 own one 32-query tile each of the
-// CURRENT head - one pass instead of two, no second Q load, 7 of 8 waves busy instead of 7 of 8 passes - with the next head's Q rows
-// requested into a second register set at the start of the head.  One barrier per head hands the stages over.  A head's copies have the
-// whole tile loop of the previous head to land: the copy stream never stops, the matrix / VALU pipes never wait for it.
-// ------------------------------------------------------------------------------------------------
-constexpr int PERS_MAXT = 224;       // 7 compute waves + the loader = 8 waves = two per SIMD: the whole 256-register budget per wave
-
-__host__ __device__ inline int pers_stage_bytes(int T) { return 2 * ((T + 7) & ~7) * 128; }
-
-template <int DUMMY = 0>
-__global__ __launch_bounds__(512) void attn_fwd_bf16_pers_kernel(AttnParams p) {
-    extern __shared__ __attribute__((aligned(1024))) char lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h2 = lane >> 5, ql = lane & 31;
-    const int T = p.T;
-    const long RS = 3L * p.H * 64;
-    const int HD = p.H * 64;
-    const int nt = (T + KT - 1) / KT, q32 = (T + 31) / 32;
-    const int rows8 = res_rows8(T), np = rows8 >> 3;
-    const int stage_bytes = 2 * rows8 * 128;
-    const int nheads = p.B * p.H;
-    const int mine = (nheads - (int)blockIdx.x + (int)gridDim.x - 1) / (int)gridDim.x;      // heads blockIdx.x, + gridDim.x, ...
-    const bool loader = wave == q32;
-    const bf16_t* qkv = static_cast<const bf16_t*>(p.qkv);
-
-    auto issue = [&](int hd, int st) {             // the loader's: every piece of head hd's K (pieces 0..np-1) and V into stage st
-        const int b = hd / p.H, h = hd % p.H;
-        const bf16_t* base = qkv + (long)b * T * RS + h * 64;
-        char* dstK = lds + st * stage_bytes;
-        char* dstV = dstK + rows8 * 128;
-        for (int piece = 0; piece < 2 * np; ++piece) {
-            const int isv = piece >= np;
-            const int pp = isv ? piece - np : piece;
-            const int r = pp * 8 + (lane >> 3);
-            const int c = (lane & 7) ^ (isv ? v_swz(r) : k_swz(r));
-            const int key = r < T ? r : T - 1;
-            const bf16_t* src = base + (long)key * RS + (isv + 1) * HD + c * 8;
-            // (from inline asm: through the builtin the compiler knows that LDS writes are in flight somewhere in this kernel and puts
-            //  s_waitcnt vmcnt(0) in front of every transposed V read of the COMPUTE waves - draining their output stores and their Q
-            //  requests once per tile; the loader's own wait in front of the head barrier is the only one that is needed)
-            const unsigned d = __builtin_amdgcn_readfirstlane((unsigned)(unsigned long)(__attribute__((address_space(3))) char*)((isv ? dstV : dstK) + pp * 1024));
-            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(d) : "memory");
-        }
-    };
-    bf16x8 qr[4];
-    auto load_q = [&](int hd, bf16x8 (&dst)[4]) {  // a compute wave's: its 32 query rows of head hd (rows >= T: row T-1, never stored)
-        const int b = hd / p.H, h = hd % p.H;
-        const bf16_t* base = qkv + (long)b * T * RS + h * 64;
-        const int q = wave * 32 + ql;
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            // (plain loads: the compiler then puts s_waitcnt vmcnt(0) in front of the first MFMA that reads these registers, which also
-            //  drains the previous head's output stores.  Requesting them from inline asm instead - invisible to the wait counting, with
-            //  the loop's counted wait covering them - produced NaNs: the compiler believes an asm output is valid at once and moved
-            //  the registers before the data had landed.)
-            union { u32x4 v; bf16x8 hh; } u;
-            u.v = *reinterpret_cast<const u32x4*>(base + (long)min(q, T - 1) * RS + (2 * kk + h2) * 8);
-            dst[kk] = u.hh;
-        }
-    };
-    if (mine <= 0) return;
-    // (p.dbg: timing ablations with WRONG results - 41 = no tile loop, 42 = no K / V copies, 43 = no output stores: tools/attn_fwd_ab.py)
-    if (loader) { if (p.dbg != 42) issue(blockIdx.x, 0); }
-    else load_q(blockIdx.x, qr);
-
-    const int a16 = lane & 15, g16 = (lane >> 4) & 1;
-    const int krow = ql * 128, ksw = k_swz(ql);
-    const int vrow = (4 * h2 + (a16 >> 2)) * 128, vsw = v_swz(a16 >> 2);
-    const int vsub = ((a16 & 3) & 1) * 8, vch = g16 * 2 + ((a16 & 3) >> 1);
-
-#pragma unroll 1
-    for (int i = 0; i < mine; ++i) {
-        const int hd = blockIdx.x + i * gridDim.x;
-        const int st = i & 1;
-        // everything requested for head i (the loader's copies; this wave's Q rows) has landed before the barrier; behind it the other
-        // stage - head i-1's - is free
-        // (compute waves, from the second head on: the 4 Q requests are OLDER than the previous head's 8 output stores + 1 lse store, and
-        //  vmcnt retires in order - waiting for "at most 9 / 8 outstanding" leaves the stores in flight across the barrier.  A full drain here
-        //  exposed the stores' acknowledgement latency once per head: 228 vs 147 us for the layer, tools/attn_fwd_ab.py.)
-        if (loader || i == 0 || p.dbg == 43) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        else if (p.lse) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        __builtin_amdgcn_s_barrier();               // (the bare barrier: __syncthreads() is a fence + barrier and drains vmcnt again)
-        __builtin_amdgcn_sched_barrier(0);
-        if (loader) {
-            if (i + 1 < mine && p.dbg != 42) issue(hd + gridDim.x, st ^ 1);
-            continue;
-        }
-        const char* ldsK = lds + st * stage_bytes;
-        const char* ldsV = ldsK + rows8 * 128;
-        const int b = hd / p.H, h = hd % p.H;
-        const int q = wave * 32 + ql;
-        f32x16 o[2];
-#pragma unroll
-        for (int ii = 0; ii < 2; ++ii)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) o[ii][r] = 0.f;
-        float m = NEG, lsum = 0.f;
-        // Software pipeline over the key tiles (two score register sets): while the VALU works through tile it's softmax, the matrix pipe
-        // forms tile it+1's scores from fragments requested a stage earlier - a lone wave spent a third of its cycles in s_waitcnt (LDS round
-        // trips in front of the first score MFMA and behind the maximum's cross-lane exchange) and a quarter stalled at issue
-        // (profiles/r2_pmc_attn_fwd_resident.txt); with two waves per SIMD there is nobody else to fill those holes.
-        auto load_kf = [&](int it, bf16x8 (&kf)[8], auto edge_tag) {
-            constexpr bool EDGE = decltype(edge_tag)::value;
-            const int kv0 = it * KT;
-            const char* sk = ldsK + kv0 * 128;
-#pragma unroll
-            for (int ii = 0; ii < 8; ++ii) {
-                if (!EDGE) {
-                    kf[ii] = ld_bf16x8(sk + (ii >> 2) * 32 * 128 + krow + (((2 * (ii & 3) + h2) ^ ksw) << 4));
-                } else {
-                    int r = kv0 + (ii >> 2) * 32 + ql;
-                    r = r < rows8 ? r : rows8 - 1;
-                    kf[ii] = ld_bf16x8(ldsK + r * 128 + (((2 * (ii & 3) + h2) ^ k_swz(r)) << 4));
-                }
-            }
-        };
-        auto load_vf = [&](int it, bf16x8 (&vf)[8], auto edge_tag) {
-            constexpr bool EDGE = decltype(edge_tag)::value;
-            const int kv0 = it * KT;
-            const char* sv = ldsV + kv0 * 128;
-#pragma unroll
-            for (int ii = 0; ii < 8; ++ii) {     // ii = kb*4 + s2*2 + db
-                if (!EDGE) {
-                    const int roff = ((ii >> 2) * 32 + 16 * ((ii >> 1) & 1)) * 128 + vrow;
-                    const int coff = ((((ii & 1) * 4 + vch) ^ vsw) << 4) + vsub;
-                    vf[ii] = tr_frag(sv + roff + coff, 8 * 128);
-                } else {
-                    const int r0 = kv0 + (ii >> 2) * 32 + 16 * ((ii >> 1) & 1) + 4 * h2 + (a16 >> 2);
-                    const int ra = r0 < rows8 ? r0 : rows8 - 1, rb = r0 + 8 < rows8 ? r0 + 8 : rows8 - 1;
-                    const char* pa = ldsV + ra * 128 + ((((ii & 1) * 4 + vch) ^ v_swz(ra)) << 4) + vsub;
-                    const char* pb = ldsV + rb * 128 + ((((ii & 1) * 4 + vch) ^ v_swz(rb)) << 4) + vsub;
-                    union { struct { s16x4 lo, hi; } hh; bf16x8 v; } u;
-                    u.hh.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(pa));
-                    u.hh.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(pb));
-                    vf[ii] = u.v;
-                }
-            }
-        };
-        auto scores = [&](const bf16x8 (&kf)[8], f32x16 (&s)[2]) {      // (both 32-key blocks always: a branch per MFMA would end the scheduling region;
-#pragma unroll                                                          //  an all-padding block of the last tile costs four MFMAs once per head)
-            for (int kb = 0; kb < 2; ++kb)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                s[0] = SS_MFMA_32x32x16(kf[kk], qr[kk], s[0], 0, 0, 0);
-                s[1] = SS_MFMA_32x32x16(kf[4 + kk], qr[kk], s[1], 0, 0, 0);
-            }
-        };
-        auto pv = [&](const bf16x8 (&vf)[8], const f32x16 (&s)[2], bool two) {
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) {
-                if (kb == 1 && !two) break;
-#pragma unroll
-                for (int s2 = 0; s2 < 2; ++s2) {
-                    bf16x8 pf;
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) pf[e] = (bf16_t)s[kb][8 * s2 + e];
-#pragma unroll
-                    for (int db = 0; db < 2; ++db)
-                        o[db] = SS_MFMA_32x32x16(vf[kb * 4 + s2 * 2 + db], pf, o[db], 0, 0, 0);
-                }
-            }
-        };
-        const int kvl = (nt - 1) * KT;
-        const bool two_last = kvl + 32 < T;         // the last tile's second 32-key block holds keys
-        f32x16 sc[2], sn[2];
-        bf16x8 kf[8], vf[8];
-        if (nt == 1) load_kf(0, kf, std::true_type{}); else load_kf(0, kf, std::false_type{});
-        scores(kf, sc);
-        if (p.dbg != 41) {
-#pragma unroll 1
-        for (int it = 0; it + 2 < nt; ++it) {        // tiles it and it+1 interior: tile it+1's scores are formed beside tile it's softmax
-            load_vf(it, vf, std::false_type{});
-            load_kf(it + 1, kf, std::false_type{});
-            __builtin_amdgcn_sched_barrier(0);
-            scores(kf, sn);
-            softmax_tile_lean<false, false>(sc, nullptr, h2, p.scale_log2e, m, lsum, o, KT);
-            pv(vf, sc, true);
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) sc[kb] = sn[kb];
-        }
-        if (nt > 1) {                                 // tile nt-2 (interior) beside the scores of the last, partial tile
-            load_vf(nt - 2, vf, std::false_type{});
-            load_kf(nt - 1, kf, std::true_type{});
-            __builtin_amdgcn_sched_barrier(0);
-            scores(kf, sn);
-            softmax_tile_lean<false, false>(sc, nullptr, h2, p.scale_log2e, m, lsum, o, KT);
-            pv(vf, sc, true);
-#pragma unroll
-            for (int kb = 0; kb < 2; ++kb) sc[kb] = sn[kb];
-        }
-        }
-        // the head's last scores are formed: Q of the NEXT head replaces it (lands under the last tile's softmax / PV, the stores and the barrier)
-        if (i + 1 < mine) load_q(hd + gridDim.x, qr);
-        load_vf(nt - 1, vf, std::true_type{});
-        __builtin_amdgcn_sched_barrier(0);
-        softmax_tile_lean<false, true>(sc, nullptr, h2, p.scale_log2e, m, lsum, o, T - kvl, two_last);
-        pv(vf, sc, two_last);
-        const float ltot = lsum + __shfl_xor(lsum, 32, 64);
-        const float inv = 1.0f / ltot;
-        if (q < T && p.dbg != 43) {
-            bf16_t* orow = static_cast<bf16_t*>(p.out) + ((long)b * T + q) * HD + h * 64;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {
-                    const int d = db * 32 + 8 * r4 + 4 * h2;
-                    bf16x4 v = {(bf16_t)(o[db][4 * r4] * inv), (bf16_t)(o[db][4 * r4 + 1] * inv), (bf16_t)(o[db][4 * r4 + 2] * inv), (bf16_t)(o[db][4 * r4 + 3] * inv)};
-                    *reinterpret_cast<bf16x4*>(orow + d) = v;
-                }
-            if (p.lse && h2 == 0) p.lse[((long)b * p.H + h) * T + q] = m + log2f(ltot);
-        }
-    }
-}
-
-int launch_fwd_pers(const AttnParams& p, hipStream_t stream) {
-    static bool configured = false;
-    static int ncu = 256;
-    auto kern = attn_fwd_bf16_pers_kernel<0>;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * pers_stage_bytes(PERS_MAXT));
-        if (e != hipSuccess) return simseg_set_error("attention_fwd: cannot reserve LDS: %s", hipGetErrorString(e));
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
-        configured = true;
-    }
-    const int q32 = (p.T + 31) / 32;
-    const int nheads = p.B * p.H;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(nheads < ncu ? nheads : ncu)), dim3((q32 + 1) * 64), 2 * pers_stage_bytes(p.T), stream, p);
-    return 0;
 }
 
 __host__ int res_smem(int T, bool mask) { return 2 * ((T + 7) & ~7) * 128 + (mask ? ((T + KT - 1) / KT) * KT * 4 : 0); }
@@ -2276,13 +2033,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(AttnParams p) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// bf16 backward, short sequences (T <= 256): "resident" forms of the two passes.  The streaming kernels above move one
+// bf16 backward, short sequences (T <= 256): helpers of the one-kernel form below.  The streaming kernels above move one
 // 32-query (or 64-key) tile per iteration through LDS behind a register prefetch of ONE tile and a workgroup barrier: with ~600
 // cycles of MFMA work per iteration and 2-5 k cycles of global latency under load, every iteration waits for its tile (17 us per
-// block of 7 iterations at T = 197).  Here a block is one (batch, head); the operand that is walked - Q and dO for the dK/dV pass,
-// K and V for the dQ pass - is copied whole into LDS by global_load_lds once (rows padded to a multiple of 32 by repeating row
-// T-1: their lse = +inf / key bias = -inf makes every probability exactly 0), and each wave then runs over all tiles of it with no
-// barrier, no staging and no register prefetch in the loop.
+// block of 7 iterations at T = 197).  Here a block is one (batch, head); its operands are copied whole into LDS by global_load_lds
+// once (rows padded to a multiple of 32 by repeating row T-1: their lse = +inf / key bias = -inf makes every probability exactly
+// 0), and each wave then runs over all tiles with no staging and no register prefetch in the loop.
 // One swizzle serves both ways these tiles are read (k-contiguous b128 fragments AND transposed ds_read_b64_tr_b16 fragments of
 // the same image): 16-byte slot c of row r holds chunk c ^ ((3 * (r >> 1)) & 7): a bijection over eight consecutive row pairs
 // (conflict-free b128 reads of 32 consecutive rows) whose neighbouring row pairs differ in more than bit 0 (the 4-row blocks of a
@@ -2308,289 +2064,10 @@ __device__ __forceinline__ bf16x8 tr_frag2(const char* pa, const char* pb) {
     return u.v;
 }
 
-template <bool DROP>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dkv_res_kernel(AttnParams p) {
-    extern __shared__ __attribute__((aligned(1024))) char lds[];      // [Q rows32 x 128][dO rows32 x 128][lse rows32][delta rows32]
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h2 = lane >> 5, kl = lane & 31;
-    const int bh_ = blockIdx.x;
-    const int b = bh_ / p.H, h = bh_ % p.H;
-    const int Tf = p.T, T = attn_teff(p, b);          // Tf: the tensors' row count; T: the rows this block works on
-    if (p.trace && tid == 0) p.trace[(long)blockIdx.x * 4] = wall_clock64();
-    const long RS = 3L * p.H * 64, OS = (long)p.H * 64;
-    const bf16_t* base = static_cast<const bf16_t*>(p.qkv) + (long)b * Tf * RS + h * 64;
-    const bf16_t* gbase = static_cast<const bf16_t*>(p.dout) + (long)b * Tf * OS + h * 64;
-    const int nthr = blockDim.x, nw = nthr >> 6;
-    const int q32 = (T + 31) / 32, rows32 = q32 * 32;
-    char* ldsQ = lds;
-    char* ldsG = lds + rows32 * 128;
-    float* lse_l = reinterpret_cast<float*>(ldsG + rows32 * 128);
-    float* del_l = lse_l + rows32;
-    res_copy_rows(base, RS, T, rows32, ldsQ, wave, nw, lane);
-    res_copy_rows(gbase, OS, T, rows32, ldsG, wave, nw, lane);
-    for (int q = tid; q < rows32; q += nthr) {
-        lse_l[q] = q < T ? p.lse[((long)b * p.H + h) * Tf + q] : 1e30f;            // -> P = 0 for padded queries
-        del_l[q] = q < T ? p.delta[((long)b * p.H + h) * Tf + q] : 0.f;
-    }
-    const int a16 = lane & 15, g16 = (lane >> 4) & 1;
-    const float scale = p.scale_log2e * 0.6931471805599453f;
-    // fragment addressing inside a 32-query tile (tile start rows are multiples of 32: the swizzle terms depend on the lane only)
-    const int arow = kl * 128, asw = qd_swz(kl);                                   // A operand rows = queries, 16-byte chunk 2 kk + h2
-    const int trow = (4 * h2 + (a16 >> 2)) * 128, tsw = qd_swz(4 * h2 + (a16 >> 2));
-    const int tch = g16 * 2 + ((a16 & 3) >> 1), tsub = ((a16 & 3) & 1) * 8;       // transposed: chunk db * 4 + tch, 8-byte half tsub
-    bool landed = false;
-
-#pragma unroll 1
-    for (int kt = wave; kt < q32; kt += nw) {
-        const int key = kt * 32 + kl;
-        const bool kvalid = key < T;
-        const float kb_ = (kvalid && (!p.mask || p.mask[(long)b * Tf + key] != 0)) ? 0.f : NEG;
-        bf16x8 kr[4], vr[4];     // this lane's K and V row chunks: B operands of S = Q.K^T and dP = dO.V^T
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            union { u32x4 v; bf16x8 hh; } uk, uv;
-            uk.v = (u32x4){0u, 0u, 0u, 0u}; uv.v = uk.v;
-            if (kvalid) {
-                uk.v = *reinterpret_cast<const u32x4*>(base + (long)key * RS + p.H * 64 + (2 * kk + h2) * 8);
-                uv.v = *reinterpret_cast<const u32x4*>(base + (long)key * RS + 2 * p.H * 64 + (2 * kk + h2) * 8);
-            }
-            kr[kk] = uk.hh; vr[kk] = uv.hh;
-        }
-        if (!landed) {                  // first pass: the LDS image is complete once every wave's copies have landed
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            landed = true;
-            if (p.trace && tid == 0) p.trace[(long)blockIdx.x * 4 + 1] = wall_clock64();
-        }
-        f32x16 dk[2], dv[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { dk[i][r] = 0.f; dv[i][r] = 0.f; }
-        for (int qt = 0; qt < q32; ++qt) {
-            const int q0 = qt * 32;
-            const char* cq = ldsQ + q0 * 128;
-            const char* cg = ldsG + q0 * 128;
-            bf16x8 aq[4], ag[4];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const int off = arow + (((2 * kk + h2) ^ asw) << 4);
-                aq[kk] = ld_bf16x8(cq + off);
-                ag[kk] = ld_bf16x8(cg + off);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            f32x16 s, dp;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                s = SS_MFMA_32x32x16(aq[kk], kr[kk], s, 0, 0, 0);
-                dp = SS_MFMA_32x32x16(ag[kk], vr[kk], dp, 0, 0, 0);
-            }
-            // requested while the MFMAs run: lse / delta of this lane's 16 query rows, and the transposed dO / Q fragments
-            float4 l4[4], d4[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                l4[j] = *reinterpret_cast<const float4*>(lse_l + q0 + 8 * j + 4 * h2);
-                d4[j] = *reinterpret_cast<const float4*>(del_l + q0 + 8 * j + 4 * h2);
-            }
-            bf16x8 gf[4], qf[4];                              // index s2 * 2 + db
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int ro = (16 * (i >> 1)) * 128 + trow;
-                const int ca = ((((i & 1) * 4 + tch) ^ tsw) << 4) + tsub, cb = ((((i & 1) * 4 + tch) ^ tsw ^ 4) << 4) + tsub;
-                gf[i] = tr_frag2(cg + ro + ca, cg + ro + 8 * 128 + cb);      // dO^T fragment: [d][q-slots]
-                qf[i] = tr_frag2(cq + ro + ca, cq + ro + 8 * 128 + cb);      // Q^T fragment
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // lane: key column kl, rows q = (r%4) + 8*(r/4) + 4*h2
-            float pd[16], ds[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float lq = reinterpret_cast<const float*>(&l4[r >> 2])[r & 3];
-                const float dq_ = reinterpret_cast<const float*>(&d4[r >> 2])[r & 3];
-                const float pr = __builtin_amdgcn_exp2f(fminf(s[r] * p.scale_log2e + kb_ - lq, 0.f));
-                float keep = 1.f;
-                if (DROP) {
-                    const int qq = (r & 3) + 8 * (r >> 2) + 4 * h2;
-                    const unsigned idx = ((unsigned)bh_ * Tf + (q0 + qq)) * Tf + key;
-                    keep = dropout_keep32(seed_fold(p.drop_seed), idx, p.drop_thresh) ? p.drop_scale : 0.f;
-                }
-                pd[r] = pr * keep;                                   // dropped probabilities feed dV
-                ds[r] = pr * (dp[r] * keep - dq_) * scale;          // dS feeds dK
-            }
-            // dV^T[d][key] += dO^T[d][q] . P[q][key] ;  dK^T[d][key] += Q^T[d][q] . dS[q][key]
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                bf16x8 pf, df;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) { pf[e] = (bf16_t)pd[8 * s2 + e]; df[e] = (bf16_t)ds[8 * s2 + e]; }
-#pragma unroll
-                for (int db = 0; db < 2; ++db) {
-                    dv[db] = SS_MFMA_32x32x16(gf[s2 * 2 + db], pf, dv[db], 0, 0, 0);
-                    dk[db] = SS_MFMA_32x32x16(qf[s2 * 2 + db], df, dk[db], 0, 0, 0);
-                }
-            }
-        }
-        // dk/dv accumulators (transposed): column = this lane's key, rows d = db*32 + (r%4) + 8*(r/4) + 4*h2
-        if (kvalid) {
-            bf16_t* drow = static_cast<bf16_t*>(p.dqkv) + (long)b * Tf * RS + h * 64 + (long)key * RS;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {
-                    const int d = db * 32 + 8 * r4 + 4 * h2;
-                    store_bf16x4(drow + p.H * 64 + d, dk[db][4 * r4], dk[db][4 * r4 + 1], dk[db][4 * r4 + 2], dk[db][4 * r4 + 3]);
-                    store_bf16x4(drow + 2 * p.H * 64 + d, dv[db][4 * r4], dv[db][4 * r4 + 1], dv[db][4 * r4 + 2], dv[db][4 * r4 + 3]);
-                }
-        }
-    }
-    if (!landed) {       // a wave without a tile (short effective length): its share of the copies still has to land before the others read
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-    if (p.trace && tid == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); p.trace[(long)blockIdx.x * 4 + 2] = wall_clock64(); p.trace[(long)blockIdx.x * 4 + 3] = p.trace[(long)blockIdx.x * 4 + 2]; }
-}
-
-template <bool DROP>
-__global__ __launch_bounds__(256, 2) void attn_bwd_dq_res_kernel(AttnParams p) {
-    extern __shared__ __attribute__((aligned(1024))) char lds[];      // [K rows32 x 128][V rows32 x 128][key bias rows32]
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h2 = lane >> 5, ql = lane & 31;
-    const int bh_ = blockIdx.x;
-    const int b = bh_ / p.H, h = bh_ % p.H;
-    const int Tf = p.T, T = attn_teff(p, b);          // Tf: the tensors' row count; T: the rows this block works on
-    const long RS = 3L * p.H * 64, OS = (long)p.H * 64;
-    const bf16_t* base = static_cast<const bf16_t*>(p.qkv) + (long)b * Tf * RS + h * 64;
-    const bf16_t* gbase = static_cast<const bf16_t*>(p.dout) + (long)b * Tf * OS + h * 64;
-    const int nthr = blockDim.x, nw = nthr >> 6;
-    const int q32 = (T + 31) / 32, rows32 = q32 * 32;
-    char* ldsK = lds;
-    char* ldsV = lds + rows32 * 128;
-    float* kbias = reinterpret_cast<float*>(ldsV + rows32 * 128);
-    res_copy_rows(base + p.H * 64, RS, T, rows32, ldsK, wave, nw, lane);
-    res_copy_rows(base + 2 * p.H * 64, RS, T, rows32, ldsV, wave, nw, lane);
-    for (int key = tid; key < rows32; key += nthr)
-        kbias[key] = (key < T && (!p.mask || p.mask[(long)b * Tf + key] != 0)) ? 0.f : NEG;
-    const int a16 = lane & 15, g16 = (lane >> 4) & 1;
-    const float scale = p.scale_log2e * 0.6931471805599453f;
-    const int arow = ql * 128, asw = qd_swz(ql);
-    const int trow = (4 * h2 + (a16 >> 2)) * 128, tsw = qd_swz(4 * h2 + (a16 >> 2));
-    const int tch = g16 * 2 + ((a16 & 3) >> 1), tsub = ((a16 & 3) & 1) * 8;
-    bool landed = false;
-
-#pragma unroll 1
-    for (int qt = wave; qt < q32; qt += nw) {
-        const int q = qt * 32 + ql;
-        const bool qvalid = q < T;
-        bf16x8 qr[4], gr[4];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            union { u32x4 v; bf16x8 hh; } uq, ug;
-            uq.v = (u32x4){0u, 0u, 0u, 0u}; ug.v = uq.v;
-            if (qvalid) {
-                uq.v = *reinterpret_cast<const u32x4*>(base + (long)q * RS + (2 * kk + h2) * 8);
-                ug.v = *reinterpret_cast<const u32x4*>(gbase + (long)q * OS + (2 * kk + h2) * 8);
-            }
-            qr[kk] = uq.hh; gr[kk] = ug.hh;
-        }
-        const float lse = qvalid ? p.lse[((long)b * p.H + h) * Tf + q] : 1e30f;
-        // delta = rowsum(dO o O) of this lane's query, from the dO slices it already holds (this kernel runs FIRST and leaves delta for
-        // the dK / dV kernel: no separate pass over O and dO)
-        float del = 0.f;
-        if (qvalid) {
-            const bf16_t* obase = static_cast<const bf16_t*>(p.out) + (long)b * Tf * OS + h * 64 + (long)q * OS;
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const bf16x8 o8 = ld_bf16x8(obase + (2 * kk + h2) * 8);
-#pragma unroll
-                for (int e = 0; e < 8; ++e) del += (float)o8[e] * (float)gr[kk][e];
-            }
-        }
-        del += __shfl_xor(del, 32, 64);
-        if (qvalid && h2 == 0) const_cast<float*>(p.delta)[((long)b * p.H + h) * Tf + q] = del;
-        if (!landed) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            landed = true;
-        }
-        f32x16 dq[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) dq[i][r] = 0.f;
-        for (int kt = 0; kt < q32; ++kt) {
-            const int k0 = kt * 32;
-            const char* ck = ldsK + k0 * 128;
-            const char* cv = ldsV + k0 * 128;
-            // S^T[key][q], dP^T[key][q]: rows = keys (A from LDS), columns = queries (B = this lane's Q / dO row)
-            bf16x8 ak[4], av[4];
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const int off = arow + (((2 * kk + h2) ^ asw) << 4);
-                ak[kk] = ld_bf16x8(ck + off);
-                av[kk] = ld_bf16x8(cv + off);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            f32x16 s, dp;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                s = SS_MFMA_32x32x16(ak[kk], qr[kk], s, 0, 0, 0);
-                dp = SS_MFMA_32x32x16(av[kk], gr[kk], dp, 0, 0, 0);
-            }
-            float4 b4[4];                                 // key bias of this lane's 16 key rows
-#pragma unroll
-            for (int j = 0; j < 4; ++j) b4[j] = *reinterpret_cast<const float4*>(kbias + k0 + 8 * j + 4 * h2);
-            bf16x8 kf[4];                                 // K^T fragments [d][key-slots], index s2 * 2 + db
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int ro = (16 * (i >> 1)) * 128 + trow;
-                const int ca = ((((i & 1) * 4 + tch) ^ tsw) << 4) + tsub, cb = ((((i & 1) * 4 + tch) ^ tsw ^ 4) << 4) + tsub;
-                kf[i] = tr_frag2(ck + ro + ca, ck + ro + 8 * 128 + cb);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            float ds[16];
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const float kbv = reinterpret_cast<const float*>(&b4[r >> 2])[r & 3];
-                const float pr = __builtin_amdgcn_exp2f(fminf(s[r] * p.scale_log2e + kbv - lse, 0.f));
-                float keep = 1.f;
-                if (DROP) {
-                    const int kk_ = k0 + (r & 3) + 8 * (r >> 2) + 4 * h2;
-                    const unsigned idx = ((unsigned)bh_ * Tf + q) * Tf + kk_;
-                    keep = dropout_keep32(seed_fold(p.drop_seed), idx, p.drop_thresh) ? p.drop_scale : 0.f;
-                }
-                ds[r] = pr * (dp[r] * keep - del) * scale;
-            }
-            // dQ^T[d][q] += K^T[d][keys] . dS^T[keys][q]
-#pragma unroll
-            for (int s2 = 0; s2 < 2; ++s2) {
-                bf16x8 df;
-#pragma unroll
-                for (int e = 0; e < 8; ++e) df[e] = (bf16_t)ds[8 * s2 + e];
-#pragma unroll
-                for (int db = 0; db < 2; ++db) dq[db] = SS_MFMA_32x32x16(kf[s2 * 2 + db], df, dq[db], 0, 0, 0);
-            }
-        }
-        if (qvalid) {
-            bf16_t* drow = static_cast<bf16_t*>(p.dqkv) + (long)b * Tf * RS + h * 64 + (long)q * RS;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4)
-                    store_bf16x4(drow + db * 32 + 8 * r4 + 4 * h2, dq[db][4 * r4], dq[db][4 * r4 + 1], dq[db][4 * r4 + 2], dq[db][4 * r4 + 3]);
-        }
-    }
-    if (!landed) {       // a wave without a tile (short effective length): its share of the copies still has to land before the others read
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-    }
-}
-
 // ------------------------------------------------------------------------------------------------
-// bf16 backward, T <= 256 (ViT-B @224, every BERT caption): ONE kernel per (batch, head).  The two resident passes above each
-// recompute S = Q.K^T, dP = dO.V^T and the exponentials, and each reads Q/K/V/dO from HBM (7 tile products and ~300 KB per head at
-// T = 197).  Here wave w owns key tile w for dK / dV (K, V rows and the accumulators in registers, as in the dK/dV pass) AND query
+// bf16 backward, T <= 256 (ViT-B @224, every BERT caption): ONE kernel per (batch, head).  Two passes (dK / dV, then dQ: the
+// streaming kernels' split, and that of the resident two-pass form this kernel replaced) each recompute S = Q.K^T, dP = dO.V^T and
+// the exponentials, and each read Q/K/V/dO from HBM (7 tile products and ~300 KB per head at T = 197).  Here wave w owns key tile w for dK / dV (K, V rows and the accumulators in registers, as in the dK/dV pass) AND query
 // tile w for dQ.  It walks the query tiles in the order (w + j) mod n, j = 0..n-1, so at step j every wave holds the dS tile of a
 // DIFFERENT query tile.  dS comes out of the MFMA with the key on the lane; dQ contracts over keys, so the bf16 dS tile takes the
 // transposing trip of the GEMM epilogues anyway - staged [key][query], read back with ds_read_b64_tr_b16 as the B operand of
@@ -2616,7 +2093,7 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h2 = lane >> 5, kl = lane & 31;
     const int nthr = blockDim.x, nw = nthr >> 6;
     const int Tf = p.T;                               // the tensors' row count
-    // Measured and dropped (tools/attn_bwd_ab.py, tools/dbg_attn_trace.py; B = 512, T = 197):
+    // Measured and dropped (profiles/r2_attn_bwd_one_vs_two.txt, tools/dbg_attn_trace.py; B = 512, T = 197):
     //  - persistent blocks walking several heads, started a quarter period apart.  With one block per head the dispatcher keeps the CUs
     //    in step (all load, all compute, all store; a start offset on the first round is gone by the second); persistent blocks do keep
     //    their offsets, but a head's copies take ~5 us either way - 125 KB at the ~23 GB/s that one CU's outstanding requests sustain,
@@ -2650,8 +2127,8 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
     res_copy_rows(gbase, OS, T, rows32, ldsG, wave, nw, lane);
     res_copy_rows(base + HP, RS, T, rows32, ldsK, wave, nw, lane);
     // every global request of the head goes out before anything waits: the value loads below are consumed after the copies' wait
-    // (an LDS store of a loaded value right here would put a full s_waitcnt in front of the remaining requests: the resident passes
-    // above pay two to three memory round trips that way, most of their 7.6 us 'waiting for copies')
+    // (an LDS store of a loaded value right here would put a full s_waitcnt in front of the remaining requests: the resident two-pass
+    // form paid two to three memory round trips that way, most of its 7.6 us 'waiting for copies')
     // (unconditional requests from clamped addresses, selected afterwards: a request inside a divergent branch also gets its own wait)
     const float lse_ld = p.lse[((long)b * p.H + h) * Tf + min(tid, T - 1)];
     // delta = rowsum(dO o O): eight lanes per query row, one 16-byte chunk each; O is requested here, dO is read from its LDS image
@@ -2732,7 +2209,7 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
         const unsigned pad_ = __builtin_amdgcn_readfirstlane(
             (unsigned)(unsigned long)(__attribute__((address_space(3))) char*)(reinterpret_cast<char*>(del_l + rows32)) + wave * 256);
         const int groups_ = (Tf + 63) >> 6;                                       // wave-instructions per operand
-        const int nparts_ = p.dbg == 5 ? 3 : (p.dbg == 6 ? 2 : (p.dbg == 7 ? 4 : 5));      // (A/B: how much of the head fits beside everything else in L2)
+        constexpr int nparts_ = 5;                                                // q, k, v, dO, O
         for (int k = wave; k < nparts_ * groups_; k += nw) {
             const int part = k / groups_;
             const int r = min((k - part * groups_) * 64 + lane, Tf - 1);
@@ -2938,28 +2415,10 @@ int launch_bwd_one(const AttnParams& p, hipStream_t stream) {
         if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = -1;
     }
     AttnParams q = p;
-    // one block per CU is resident (LDS) for T > 128; shorter sequences fit two.  Variant 4 switches the next-head touches off (A/B runs).
+    // one block per CU is resident (LDS) for T > 128; shorter sequences fit two
     const int per_cu = one_smem(p.T) > 80 * 1024 ? 1 : 2;
-    q.pf_stride = (cus > 0 && p.dbg != 4 && per_cu == 1 && (long)p.B * p.H > (long)cus) ? cus : 0;      // (two blocks per CU - T = 77 - measured 9 % slower with them)
+    q.pf_stride = (cus > 0 && per_cu == 1 && (long)p.B * p.H > (long)cus) ? cus : 0;      // (two blocks per CU - T = 77 - measured 9 % slower with them)
     hipLaunchKernelGGL(attn_bwd_one_kernel<DROP>, dim3((unsigned)(p.B * p.H)), dim3(q32 * 64), one_smem(p.T), stream, q);
-    return 0;
-}
-
-template <bool DROP>
-int launch_bwd_res(const AttnParams& p, hipStream_t stream) {
-    const int q32 = (p.T + 31) / 32, rows32 = q32 * 32;
-    const int smem = 2 * rows32 * 128 + 2 * rows32 * 4;
-    static bool configured = false;
-    if (!configured) {
-        const int mx = 2 * RES_MAXT * 128 + 2 * RES_MAXT * 4;
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dkv_res_kernel<DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_dq_res_kernel<DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        if (e != hipSuccess) return simseg_set_error("attention_bwd: cannot reserve LDS: %s", hipGetErrorString(e));
-        configured = true;
-    }
-    const dim3 grid((unsigned)(p.B * p.H)), block((q32 < 4 ? q32 : 4) * 64);
-    hipLaunchKernelGGL(attn_bwd_dq_res_kernel<DROP>, grid, block, smem, stream, p);       // dQ; computes and writes delta
-    hipLaunchKernelGGL(attn_bwd_dkv_res_kernel<DROP>, grid, block, smem, stream, p);      // dK, dV (reads delta)
     return 0;
 }
 
@@ -2969,10 +2428,26 @@ int launch_bwd_res(const AttnParams& p, hipStream_t stream) {
 // for 6-wave blocks) - fewer waves per barrier and per staged K/V tile beat a perfectly filled last block.
 int attn_waves_per_block(int q32) { return q32 <= 4 ? q32 : 4; }
 
+// The 1-D grid of the ring kernels (attn_block_map): the row blocks of a (batch, head), the (batch, head) count padded to the 8 XCDs
+unsigned attn_ring_grid(int64_t B, int64_t T, int64_t H) {
+    const int q32 = (int)((T + 31) / 32), nw = attn_waves_per_block(q32);
+    return (unsigned)(((q32 + nw - 1) / nw) * (((B * H + 7) / 8) * 8));
+}
+
 thread_local unsigned long long* g_attn_trace = nullptr;
-thread_local int g_attn_variant = 0;   // tests / benchmarks (thread-local selector): 1 = always the streaming (ring) kernels, 3 = backward as the two
-                                       // resident passes, 4 = resident forward for every T <= 256; 102 / 103 = forward ablations (WRONG results:
-                                       // no operand copies / no tile loop - tools/dbg_attn_res.py only)
+// tests / benchmarks (thread-local selector, read by the host-side dispatch only): 0 = auto, 1 = the streaming (ring) kernels wherever they
+// apply, 6 / 7 = the w64 forward with one / two query blocks per wave wherever IT applies (unmasked, no dropout, T >= 65)
+thread_local int g_attn_variant = 0;
+
+// query blocks per wave the selector forces on the w64 forward; 0 = launch_w64's own choice
+int w64_forced_nqb() { return g_attn_variant == 6 ? 1 : (g_attn_variant == 7 ? 2 : 0); }
+
+// the resident forward's instantiation for p: dropout implies the key-bias form, as does a key mask
+int launch_fwd_res_for(const AttnParams& p, hipStream_t stream) {
+    if (p.drop_thresh) return launch_fwd_res<true, true>(p, stream);
+    if (p.mask) return launch_fwd_res<false, true>(p, stream);
+    return launch_fwd_res<false, false>(p, stream);
+}
 
 int fill_params(AttnParams& p, const void* qkv, const int64_t* mask, int64_t B, int64_t T, int64_t H, float scale,
                 uint64_t seed, float drop_p) {
@@ -2985,7 +2460,6 @@ int fill_params(AttnParams& p, const void* qkv, const int64_t* mask, int64_t B, 
     p.qkv = qkv; p.mask = (const long*)mask; p.B = (int)B; p.T = (int)T; p.H = (int)H;
     p.scale_log2e = scale * 1.4426950408889634f;
     p.rs = 3L * H * 64; p.ps = 64;          // the packed projection rows; the *_planes entry points overwrite these
-    p.dbg = g_attn_variant;
     p.trace = g_attn_trace;
     p.drop_seed = seed;
     p.drop_thresh = drop_p > 0.f ? (unsigned int)((double)drop_p * 4294967296.0) : 0u;
@@ -2993,24 +2467,28 @@ int fill_params(AttnParams& p, const void* qkv, const int64_t* mask, int64_t B, 
     return 0;
 }
 
+// The tail of the three 16-bit backward entry points for T <= ONE_MAXT: the one-kernel backward with the qkv bias gradient riding along -
+// per-sequence column sums from the kernel (workspace behind delta), folded over the batch by the column-sum kernel ([B, 3*H*64] fp32:
+// 4.7 MB at the training shape instead of a pass over the 465 MB of dqkv)
+int run_bwd_one(AttnParams& p, float* workspace, float* dqkv_colsum, const char* what, void* stream) {
+    p.colsum_ws = dqkv_colsum ? workspace + (long)p.B * p.H * p.T : nullptr;
+    if (int rc = p.drop_thresh ? launch_bwd_one<true>(p, (hipStream_t)stream) : launch_bwd_one<false>(p, (hipStream_t)stream)) return rc;
+    SS_LAUNCH_CHECK(what);
+    if (dqkv_colsum) return simseg_colsum_accum(p.colsum_ws, 0, dqkv_colsum, p.B, 3 * p.H * 64, 3 * p.H * 64, stream);
+    return 0;
+}
+
 }  // namespace
 
-// debug: resident blocks per CU the runtime predicts for the resident forward kernel at sequence length T
+// debug: per-block wall-clock stamps of the one-kernel backward into buf (AttnParams::trace); null = off
 extern "C" int simseg_debug_attn_trace(void* buf) { g_attn_trace = static_cast<unsigned long long*>(buf); return 0; }
-
-extern "C" int simseg_debug_attn_occupancy(int64_t T) {
-    int n = -1;
-    const int q32 = (int)((T + 31) / 32);
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, attn_fwd_bf16_res_kernel<false, false>, (q32 < 4 ? q32 : 4) * 64, res_smem((int)T, false));
-    return n;
-}
 
 extern "C" int simseg_set_attention_variant(int v) {
 #ifndef SS_HALF
-    simseg_set_attention_variant_h16(v);      // the fp16 flavour keeps its own (thread-local) selector
+    SS_CHECK(v == 0 || v == 1 || v == 6 || v == 7, "set_attention_variant: %d is not a kernel selection (0 = auto, 1 = ring kernels, 6 / 7 = w64 forward with one / two query blocks per wave)", v);
+    simseg_set_attention_variant_h16(v);      // the fp16 flavour keeps its own (thread-local) selector; v is checked here, once, for both
 #endif
-    g_w64_extra_lds = v == 8 ? 40000 : 0;     // 8 (tools/scratch/attn_w64_occ.py): the long-sequence forward at one block per CU
-    g_attn_variant = v == 8 ? 0 : v;
+    g_attn_variant = v;
     return 0;
 }
 
@@ -3026,31 +2504,20 @@ extern "C" int simseg_attention_fwd(const void* qkv, const int64_t* key_mask, vo
     SS_CHECK(dtype == 0 || !(key_mask || drop_p > 0.f) || T <= MAXT_BIAS, "attention_fwd: masked bf16 sequences are limited to %d keys", MAXT_BIAS);
     p.out = out; p.lse = lse;
     // one wave per 32 queries; a block holds up to 8 waves of the same (batch, head) so K/V tiles are staged once
-    const int q32 = (int)((T + 31) / 32);
-    const int nw = attn_waves_per_block(q32);
-    dim3 grid((unsigned)(((q32 + nw - 1) / nw) * (((B * H + 7) / 8) * 8)));      // 1-D, see attn_block_map
+    const dim3 grid(attn_ring_grid(B, T, H)), block(attn_waves_per_block((int)((T + 31) / 32)) * 64);
+    const bool ring = g_attn_variant == 1;
+    const int nqb = w64_forced_nqb();
+    // 64 queries per wave, four waves per block, every block of a (batch, head) on one XCD; forced (nqb > 0) also on short sequences
+    const bool w64 = !ring && !p.mask && !p.drop_thresh && T >= (nqb ? 65 : W64_MINT);
     if (dtype == 0)
-        hipLaunchKernelGGL(attn_fwd_f32_kernel, grid, dim3(nw * 64), 0, (hipStream_t)stream, p);
-    else if (T > 128 && T <= PERS_MAXT && !p.mask && !p.drop_thresh && !p.pack && (g_attn_variant == 4 || (g_attn_variant >= 40 && g_attn_variant <= 49))) {
-        // the persistent loader-wave kernel: OPT-IN (variant 4; 41-43 = its timing ablations).  Measured slower than the one-block-per-head
-        // resident kernel at the ViT-B training shape (223 vs 177 us, tools/attn_fwd_ab.py) - see the notes at the kernel
-        const int rc = launch_fwd_pers(p, (hipStream_t)stream);
-        if (rc) return rc;
-    } else if ((g_attn_variant == 6 || g_attn_variant == 7) && T >= 65 && !p.mask && !p.drop_thresh) {
-        launch_w64<false>(p, (hipStream_t)stream, g_attn_variant == 6 ? 1 : 2);      // tools: the long-sequence forward on a short sequence
-    } else if ((T <= RES_AUTO_T || (g_attn_variant >= 2 && T <= RES_MAXT)) && g_attn_variant != 1) {
-        int rc;
-        if (p.drop_thresh) rc = launch_fwd_res<true, true>(p, (hipStream_t)stream);
-        else if (p.mask) rc = launch_fwd_res<false, true>(p, (hipStream_t)stream);
-        else rc = launch_fwd_res<false, false>(p, (hipStream_t)stream);
-        if (rc) return rc;
-    } else if (T >= W64_MINT && !p.mask && !p.drop_thresh && g_attn_variant != 1) {
-        // 64 queries per wave, four waves per block, every block of a (batch, head) on one XCD
-        launch_w64<false>(p, (hipStream_t)stream, g_attn_variant == 6 ? 1 : (g_attn_variant == 7 ? 2 : 0));
-    } else
-        if (p.drop_thresh) hipLaunchKernelGGL((attn_fwd_bf16_kernel<true, true, false>), grid, dim3(nw * 64), 0, (hipStream_t)stream, p);
-        else if (p.mask) hipLaunchKernelGGL((attn_fwd_bf16_kernel<false, true, false>), grid, dim3(nw * 64), 0, (hipStream_t)stream, p);
-        else hipLaunchKernelGGL((attn_fwd_bf16_kernel<false, false, false>), grid, dim3(nw * 64), 0, (hipStream_t)stream, p);
+        hipLaunchKernelGGL(attn_fwd_f32_kernel, grid, block, 0, (hipStream_t)stream, p);
+    else if (T <= RES_MAXT && !ring && !(nqb && w64)) {          // (a forced 6 / 7 pre-empts the resident kernel where the w64 forward applies)
+        if (int rc = launch_fwd_res_for(p, (hipStream_t)stream)) return rc;
+    } else if (w64)
+        launch_w64<false>(p, (hipStream_t)stream, nqb);
+    else if (p.drop_thresh) hipLaunchKernelGGL((attn_fwd_bf16_kernel<true, true, false>), grid, block, 0, (hipStream_t)stream, p);
+    else if (p.mask) hipLaunchKernelGGL((attn_fwd_bf16_kernel<false, true, false>), grid, block, 0, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL((attn_fwd_bf16_kernel<false, false, false>), grid, block, 0, (hipStream_t)stream, p);
     SS_LAUNCH_CHECK("attention_fwd");
     return 0;
 }
@@ -3065,7 +2532,7 @@ extern "C" int simseg_attention_fwd_qscaled(const void* qkv, void* out, float* l
     SS_CHECK(out, "attention_fwd_qscaled: null out");
     SS_CHECK(T >= W64_MINT, "attention_fwd_qscaled: sequences of at least %d tokens", W64_MINT);
     p.out = out; p.lse = lse; p.qscaled = 1;
-    launch_w64<false>(p, (hipStream_t)stream, g_attn_variant == 6 ? 1 : (g_attn_variant == 7 ? 2 : 0));
+    launch_w64<false>(p, (hipStream_t)stream, w64_forced_nqb());
     SS_LAUNCH_CHECK("attention_fwd_qscaled");
     return 0;
 }
@@ -3085,7 +2552,6 @@ extern "C" int simseg_attention_fwd_x3(const void* qkv3, int64_t plane_elems, fl
     AttnX3Params p;
     p.qkv3 = static_cast<const bf16_t*>(qkv3); p.plane = (long)plane_elems; p.out = out; p.B = (int)B; p.T = (int)T; p.H = (int)H;
     p.scale_log2e = scale * 1.4426950408889634f;
-    p.dbg = g_attn_variant >= 200 ? g_attn_variant - 200 : 0;      // (timing ablations, WRONG results: tools/attn_x3_bench.py)
     // waves (32-query tiles) per block: 4..8, the count that leaves the fewest padding waves in a head's last block (33 tiles at
     // T = 1025: five blocks of 7; 11 at T = 325: two of 6); ties go to the larger block
     const int q32 = (int)((T + 31) / 32);
@@ -3107,13 +2573,11 @@ extern "C" int simseg_debug_attention_timeline(const void* qkv, void* out, float
     AttnParams p;
     if (int rc = fill_params(p, qkv, nullptr, B, T, H, 0.125f, 0, 0.f)) return rc;
     p.out = out; p.lse = lse; p.delta = reinterpret_cast<const float*>(dbg);
-    const int q32 = (int)((T + 31) / 32);
-    const int nw = attn_waves_per_block(q32);
-    dim3 grid((unsigned)(((q32 + nw - 1) / nw) * (((B * H + 7) / 8) * 8)));      // 1-D, see attn_block_map
     if (T >= W64_MINT && (T - 1) % 64 == 0 && g_attn_variant != 1)      // the w64 kernel's record layout: see the end of attn_fwd_w64_kernel
-        { p.qscaled = 1; launch_w64<true>(p, (hipStream_t)stream, g_attn_variant == 6 ? 1 : (g_attn_variant == 7 ? 2 : 0)); }      // (timing only: q taken as pre-scaled)
+        { p.qscaled = 1; launch_w64<true>(p, (hipStream_t)stream, w64_forced_nqb()); }      // (timing only: q taken as pre-scaled)
     else
-        hipLaunchKernelGGL((attn_fwd_bf16_kernel<false, false, true>), grid, dim3(nw * 64), 0, (hipStream_t)stream, p);
+        hipLaunchKernelGGL((attn_fwd_bf16_kernel<false, false, true>), dim3(attn_ring_grid(B, T, H)), dim3(attn_waves_per_block((int)((T + 31) / 32)) * 64), 0,
+                           (hipStream_t)stream, p);
     SS_LAUNCH_CHECK("attention_timeline");
     return 0;
 }
@@ -3123,8 +2587,6 @@ extern "C" int simseg_debug_attention_timeline(const void* qkv, void* out, float
 extern "C" int64_t simseg_attention_bwd_workspace_bytes(int64_t B, int64_t T, int64_t H) {
     return (B * H * T + B * 3 * H * 64) * (int64_t)sizeof(float);      // delta[B,H,T] + per-sequence column sums [B, 3*H*64]
 }
-
-extern "C" int simseg_colsum_accum(const void* in, int in_dtype, float* out, int64_t rows, int64_t N, int64_t ld, void* stream);
 
 extern "C" int simseg_attention_bwd(const void* qkv, const int64_t* key_mask, const void* out, const void* dout, const float* lse,
                                     float* workspace, void* dqkv, float* dqkv_colsum, int dtype, int64_t B, int64_t T, int64_t H, float scale,
@@ -3138,48 +2600,30 @@ extern "C" int simseg_attention_bwd(const void* qkv, const int64_t* key_mask, co
     SS_CHECK(dtype == 0 || dtype == 1, "attention_bwd: dtype must be 0 (fp32) or 1 (bf16)");
     p.out = const_cast<void*>(out); p.dout = dout; p.lse = const_cast<float*>(lse); p.delta = delta; p.dqkv = dqkv;
     hipStream_t s = (hipStream_t)stream;
+    const dim3 grid(attn_ring_grid(B, T, H)), block(attn_waves_per_block((int)((T + 31) / 32)) * 64);
     if (dtype == 0) {
         SS_CHECK(((uintptr_t)out % 16) == 0 && ((uintptr_t)dout % 16) == 0 && ((uintptr_t)dqkv % 16) == 0, "attention_bwd: operands must be 16-byte aligned");
-        const int q32 = (int)((T + 31) / 32);
-        const int nw = attn_waves_per_block(q32);
-        dim3 grid((unsigned)(((q32 + nw - 1) / nw) * (((B * H + 7) / 8) * 8)));      // 1-D, see attn_block_map
         if (p.drop_thresh) {
-            hipLaunchKernelGGL((attn_bwd_f32_kernel<false, true>), grid, dim3(nw * 64), 0, s, p);       // dQ, writes delta
-            hipLaunchKernelGGL((attn_bwd_f32_kernel<true, true>), grid, dim3(nw * 64), 0, s, p);        // dK, dV
+            hipLaunchKernelGGL((attn_bwd_f32_kernel<false, true>), grid, block, 0, s, p);       // dQ, writes delta
+            hipLaunchKernelGGL((attn_bwd_f32_kernel<true, true>), grid, block, 0, s, p);        // dK, dV
         } else {
-            hipLaunchKernelGGL((attn_bwd_f32_kernel<false, false>), grid, dim3(nw * 64), 0, s, p);
-            hipLaunchKernelGGL((attn_bwd_f32_kernel<true, false>), grid, dim3(nw * 64), 0, s, p);
+            hipLaunchKernelGGL((attn_bwd_f32_kernel<false, false>), grid, block, 0, s, p);
+            hipLaunchKernelGGL((attn_bwd_f32_kernel<true, false>), grid, block, 0, s, p);
         }
         SS_LAUNCH_CHECK("attention_bwd (fp32)");
         if (dqkv_colsum) return simseg_colsum_accum(dqkv, 0, dqkv_colsum, B * T, 3 * H * 64, 3 * H * 64, stream);
         return 0;
     }
+    if (T <= ONE_MAXT && g_attn_variant != 1) return run_bwd_one(p, workspace, dqkv_colsum, "attention_bwd", stream);
     const long groups = B * T * H;
-    const int q32 = (int)((T + 31) / 32);
-    const int nw = attn_waves_per_block(q32);
-    dim3 grid((unsigned)(((q32 + nw - 1) / nw) * (((B * H + 7) / 8) * 8)));      // 1-D, see attn_block_map
-    const bool resident = T <= RES_MAXT && g_attn_variant != 1;
-    if (!resident)       // (the resident dQ kernel forms delta itself)
-        hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((groups * 8 + 255) / 256)), dim3(256), 0, s, (const bf16_t*)out,
-                           (const bf16_t*)dout, delta, (int)B, (int)T, (int)H);
-    if (resident && T <= ONE_MAXT && g_attn_variant != 3) {       // (variant 3: the two resident passes, for A/B runs)
-        // the qkv bias gradient rides along: per-sequence column sums from the kernel, folded over the batch by the column-sum kernel
-        // ([B, 3*H*64] fp32: 4.7 MB at the training shape instead of a pass over the 465 MB of dqkv)
-        p.colsum_ws = dqkv_colsum ? workspace + B * H * T : nullptr;
-        if (int rc = p.drop_thresh ? launch_bwd_one<true>(p, s) : launch_bwd_one<false>(p, s)) return rc;
-        SS_LAUNCH_CHECK("attention_bwd");
-        if (dqkv_colsum) return simseg_colsum_accum(p.colsum_ws, 0, dqkv_colsum, B, 3 * H * 64, 3 * H * 64, stream);
-        return 0;
-    }
-    if (dqkv_colsum && p.pack) hipMemsetAsync(dqkv, 0, (size_t)B * T * 3 * H * 64 * 2, s);     // (rows these kernels leave untouched are summed below)
-    if (resident) {
-        if (int rc = p.drop_thresh ? launch_bwd_res<true>(p, s) : launch_bwd_res<false>(p, s)) return rc;
-    } else if (p.drop_thresh) {
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, grid, dim3(nw * 64), 0, s, p);
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, dim3(nw * 64), 0, s, p);
+    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((groups * 8 + 255) / 256)), dim3(256), 0, s, (const bf16_t*)out,
+                       (const bf16_t*)dout, delta, (int)B, (int)T, (int)H);
+    if (p.drop_thresh) {
+        hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, grid, block, 0, s, p);
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, block, 0, s, p);
     } else {
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, grid, dim3(nw * 64), 0, s, p);
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, dim3(nw * 64), 0, s, p);
+        hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, grid, block, 0, s, p);
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, block, 0, s, p);
     }
     SS_LAUNCH_CHECK("attention_bwd");
     if (dqkv_colsum) return simseg_colsum_accum(dqkv, 1, dqkv_colsum, B * T, 3 * H * 64, 3 * H * 64, stream);
@@ -3200,8 +2644,7 @@ extern "C" int simseg_attention_fwd_rows(const void* qkv, const int32_t* row_sta
     SS_CHECK(out && row_start, "attention_fwd_rows: null pointer");
     SS_CHECK(T <= RES_MAXT, "attention_fwd_rows: sequences of at most %d tokens (got %lld)", RES_MAXT, (long long)T);
     p.out = out; p.lse = lse; p.row_start = row_start;
-    int rc = p.drop_thresh ? launch_fwd_res<true, true>(p, (hipStream_t)stream) : launch_fwd_res<false, false>(p, (hipStream_t)stream);
-    if (rc) return rc;
+    if (int rc = launch_fwd_res_for(p, (hipStream_t)stream)) return rc;
     SS_LAUNCH_CHECK("attention_fwd_rows");
     return 0;
 }
@@ -3215,12 +2658,7 @@ extern "C" int simseg_attention_bwd_rows(const void* qkv, const int32_t* row_sta
     SS_CHECK(out && dout && lse && workspace && dqkv && row_start, "attention_bwd_rows: null pointer");
     SS_CHECK(T <= ONE_MAXT, "attention_bwd_rows: sequences of at most %d tokens (got %lld)", ONE_MAXT, (long long)T);
     p.out = const_cast<void*>(out); p.dout = dout; p.lse = const_cast<float*>(lse); p.delta = workspace; p.dqkv = dqkv; p.row_start = row_start;
-    hipStream_t s = (hipStream_t)stream;
-    p.colsum_ws = dqkv_colsum ? workspace + B * H * T : nullptr;
-    if (int rc = p.drop_thresh ? launch_bwd_one<true>(p, s) : launch_bwd_one<false>(p, s)) return rc;
-    SS_LAUNCH_CHECK("attention_bwd_rows");
-    if (dqkv_colsum) return simseg_colsum_accum(p.colsum_ws, 0, dqkv_colsum, B, 3 * H * 64, 3 * H * 64, stream);
-    return 0;
+    return run_bwd_one(p, workspace, dqkv_colsum, "attention_bwd_rows", stream);
 }
 
 // ---- plane-major projection operands (round 4) -----------------------------------------------------------------------------------
@@ -3237,8 +2675,7 @@ extern "C" int simseg_attention_fwd_planes(const void* qkv, int64_t plane_rows, 
     SS_CHECK(T <= RES_MAXT, "attention_fwd_planes: sequences of at most %d tokens (got %lld)", RES_MAXT, (long long)T);
     SS_CHECK(plane_rows >= (row_start ? 1 : B * T), "attention_fwd_planes: plane_rows %lld is smaller than the batch", (long long)plane_rows);
     p.out = out; p.lse = lse; p.row_start = row_start; p.rs = 64; p.ps = plane_rows * 64;
-    int rc = p.drop_thresh ? launch_fwd_res<true, true>(p, (hipStream_t)stream) : launch_fwd_res<false, false>(p, (hipStream_t)stream);
-    if (rc) return rc;
+    if (int rc = launch_fwd_res_for(p, (hipStream_t)stream)) return rc;
     SS_LAUNCH_CHECK("attention_fwd_planes");
     return 0;
 }
@@ -3254,10 +2691,5 @@ extern "C" int simseg_attention_bwd_planes(const void* qkv, int64_t plane_rows, 
     SS_CHECK(plane_rows >= (row_start ? 1 : B * T), "attention_bwd_planes: plane_rows %lld is smaller than the batch", (long long)plane_rows);
     p.out = const_cast<void*>(out); p.dout = dout; p.lse = const_cast<float*>(lse); p.delta = workspace; p.dqkv = dqkv; p.row_start = row_start;
     p.rs = 64; p.ps = plane_rows * 64;
-    hipStream_t s = (hipStream_t)stream;
-    p.colsum_ws = dqkv_colsum ? workspace + B * H * T : nullptr;
-    if (int rc = p.drop_thresh ? launch_bwd_one<true>(p, s) : launch_bwd_one<false>(p, s)) return rc;
-    SS_LAUNCH_CHECK("attention_bwd_planes");
-    if (dqkv_colsum) return simseg_colsum_accum(p.colsum_ws, 0, dqkv_colsum, B, 3 * H * 64, 3 * H * 64, stream);
-    return 0;
+    return run_bwd_one(p, workspace, dqkv_colsum, "attention_bwd_planes", stream);
 }

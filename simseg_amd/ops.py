@@ -46,11 +46,16 @@ def set_gemm_variant(v):
 
 def set_attention_variant(v):
     """0 auto (bf16 sequences of <= 256 tokens on the resident kernels, their backward as one kernel; unmasked 16-bit sequences of >= 512
-    tokens on the 64-queries-per-wave forward, small launches on its one-query-block form), 1 = always the streaming ring kernels, 3 = backward
-    as the two resident passes, 6 / 7 = the long-sequence forward with one / two query blocks per wave whatever the launch size, 8 = auto
-    with the long-sequence forward held to ONE block per CU (the occupancy probe tools/scratch/attn_w64_occ.py)  (tests / benchmarks only)."""
-    _VARIANT["attention"] = int(v)
-    _push_variant("attention")
+    tokens on the 64-queries-per-wave forward, small launches on its one-query-block form), 1 = the streaming ring kernels wherever they
+    apply, 6 / 7 = the long-sequence forward with one / two query blocks per wave whatever the launch size (unmasked sequences of >= 65
+    tokens).  Every value selects between production kernels; any other value raises and leaves the previous selection in force
+    (tests / benchmarks only)."""
+    old, _VARIANT["attention"] = _VARIANT["attention"], int(v)
+    try:
+        _push_variant("attention")
+    except Exception:
+        _VARIANT["attention"] = old     # a value the library rejects must not stay: every later launch would raise again
+        raise
 
 
 PROFILE = None   # bench.py sets this to a list to time every GEMM launch with events on the launch stream

@@ -740,8 +740,9 @@ def test_attention_deferred_rescale_branch(ops, T):
     """The online softmax raises its running maximum (and rescales O, l) only when a tile's maximum exceeds it by more than a
     threshold - a rare, data-dependent branch that bounded random scores never take after the first tile.  Force it: a few
     late keys are made collinear with a few queries so that those rows' maxima jump by far more than the threshold in the second,
-    third, ... tile, in some lanes of a wave only.  Forward (both kernels: resident for T <= 256, ring above / when forced) and the
-    log-sum-exp the backward consumes, against fp32 torch."""
+    third, ... tile, in some lanes of a wave only.  Forward - the dispatcher's choice (variant 0: the resident kernel for T <= 256, masked
+    at T = 77 and unmasked at T = 197, the 64-queries-per-wave kernel at T = 600) and the ring kernel (variant 1) - and the log-sum-exp
+    the backward consumes, against fp32 torch."""
     B, H = 2, 3
     qkv = _rand(B, T, 3 * H * 64, seed=T, scale=0.6, dtype=torch.bfloat16)
     v5 = qkv.view(B, T, 3, H, 64)
@@ -758,7 +759,7 @@ def test_attention_deferred_rescale_branch(ops, T):
         sc = sc.masked_fill(mask[:, None, None, :] == 0, -1e30)
     assert float(sc.max()) > 25.0                                   # the spikes are there (log2 units: > 36 >> 6)
     want_lse = torch.logsumexp(sc, -1) / math.log(2)
-    for variant in (4, 1):                                           # 4: resident kernel for every T <= 256, 1: ring kernel
+    for variant in (0, 1):                                           # 0: the dispatcher's choice, 1: ring kernel
         ops.set_attention_variant(variant)
         try:
             out, lse = ops.attention_fwd(qkv, H, mask, save_lse=True)
@@ -892,9 +893,10 @@ def test_attention_edge_lengths(ops, T):
 
 
 @pytest.mark.parametrize("T", [33, 77, 197, 224, 256])
-def test_attention_bwd_one_kernel_vs_two_passes(ops, T):
-    """bf16 backward for T <= 256: the one-kernel form (default) against the two resident passes (variant 3) and the fp32 reference, with a
-    ragged key mask and dropout; the one-kernel form hands dS tiles between waves in a fixed order, so two runs are bit-identical."""
+def test_attention_bwd_one_kernel(ops, T):
+    """bf16 backward for T <= 256 (the one-kernel form) with a ragged key mask and dropout against fp32 autograd on the same operands;
+    the dropout keep mask is regenerated with dropout_apply_ (linear index (bh * T + q) * T + key, as in test_attention_dropout) and
+    applied together with the key mask.  The kernel hands dS tiles between waves in a fixed order, so two runs are bit-identical."""
     B, H = 3, 2
     qkv = _rand(B, T, 3 * H * 64, seed=T + 11, scale=1.2, dtype=torch.bfloat16)
     dout = _rand(B, T, H * 64, seed=T + 12, dtype=torch.bfloat16)
@@ -907,17 +909,18 @@ def test_attention_bwd_one_kernel_vs_two_passes(ops, T):
         one = ops.attention_bwd(qkv, out, dout, lse, H, m, drop_seed=9, drop_p=p)
         again = ops.attention_bwd(qkv, out, dout, lse, H, m, drop_seed=9, drop_p=p)
         assert torch.equal(one, again)
-        ops.set_attention_variant(3)
-        try:
-            two = ops.attention_bwd(qkv, out, dout, lse, H, m, drop_seed=9, drop_p=p)
-        finally:
-            ops.set_attention_variant(0)
-        _close(one, two.float(), 6e-3, f"one kernel vs two passes T={T} mask={m is not None} p={p}")
+        x = qkv.float().requires_grad_(True)
         if p == 0.0:
-            x = qkv.float().requires_grad_(True)
             _attn_ref(x, H, m, 0.125).backward(dout.float())
-            _close(two, x.grad, 2e-2, f"two-pass attention bwd T={T}")
-            _close(one, x.grad, 2e-2, f"one-kernel attention bwd T={T}")
+            _close(one, x.grad, 2e-2, f"one-kernel attention bwd T={T} mask={m is not None}")
+        else:
+            keep = torch.ones(B * H * T * T, device="cuda")
+            ops.dropout_apply_(keep, 9, p)                      # kept entries carry 1 / (1 - p)
+            q, k, v = x.view(B, T, 3, H, 64).permute(2, 0, 3, 1, 4)
+            sc = (q @ k.transpose(-1, -2)) * 0.125 + (1.0 - m[:, None, None, :].float()) * -10000.0
+            ref = ((sc.softmax(-1) * keep.view(B, H, T, T)) @ v).transpose(1, 2).reshape(B, T, H * 64)
+            ref.backward(dout.float())
+            _close(one, x.grad, 2e-2, f"one-kernel attention bwd with dropout T={T}")
 
 
 @pytest.mark.parametrize("T", [25, 77, 197, 256, 300])
@@ -951,25 +954,22 @@ def test_attention_bwd_qkv_bias_gradient(ops, T):
             _close(cs, want, 2e-5, f"qkv bias gradient, ragged mask, skip_padded_rows={skip} T={T}")
 
 
-@pytest.mark.parametrize("B,T,H", [(3, 197, 4), (70, 145, 12), (40, 224, 3), (2, 130, 2)])
-def test_attention_fwd_persistent_loader_wave_kernel(ops, B, T, H):
-    """The opt-in persistent forward (attention variant 4: one block per CU walks its heads, a loader wave copies the next head's K / V
-    into the other LDS stage, the compute waves software-pipeline their key tiles) computes the bits of the default resident kernel - more
-    heads than blocks included - and both agree with the fp64 softmax attention."""
-    qkv = _rand(B, T, 3 * H * 64, seed=T, dtype=torch.bfloat16)
+@pytest.mark.parametrize("retired", [3, 4, 8, 41, 102, 205])
+def test_attention_variant_rejects_retired_values(ops, retired):
+    """set_attention_variant selects between production kernels only: a retired debug / ablation value raises the library's error, the
+    previous selection (here 1, the ring kernels, which auto dispatch does not use at T = 33) stays in force, in the library and in the
+    wrapper, and later launches on the thread run and compute the same bits as before the rejected call."""
+    qkv = _rand(2, 33, 3 * 2 * 64, seed=5, dtype=torch.bfloat16)
+    ops.set_attention_variant(1)
     try:
-        ops.set_attention_variant(4)
-        out4, lse4 = ops.attention_fwd(qkv, H, None, scale=0.125, save_lse=True)
-        ops.set_attention_variant(0)
-        out0, lse0 = ops.attention_fwd(qkv, H, None, scale=0.125, save_lse=True)
+        before, lse_before = ops.attention_fwd(qkv, 2, None, save_lse=True)
+        with pytest.raises(RuntimeError, match="not a kernel selection"):
+            ops.set_attention_variant(retired)
+        assert ops._VARIANT["attention"] == 1
+        after, lse_after = ops.attention_fwd(qkv, 2, None, save_lse=True)
+        assert torch.equal(before, after) and torch.equal(lse_before, lse_after)
     finally:
         ops.set_attention_variant(0)
-    assert torch.equal(lse4, lse0)
-    # (the persistent kernel forms all eight score MFMAs of the partial last tile; the masked block's probabilities are exactly 0 either way)
-    assert torch.equal(out4, out0)
-    q, k, v = [t.view(B, T, H, 64).transpose(1, 2).double() for t in qkv.chunk(3, -1)]
-    want = ((q @ k.transpose(-1, -2) * 0.125).softmax(-1) @ v).transpose(1, 2).reshape(B, T, H * 64)
-    assert float((out4.double() - want).abs().max()) < 2e-2
 
 
 @pytest.mark.parametrize("B,T,H,ragged,drop", [(5, 197, 12, False, 0.0), (9, 77, 4, True, 0.1), (3, 224, 2, False, 0.0), (6, 33, 3, True, 0.0)])

@@ -58,11 +58,6 @@ def main():
         for rnd in range(3):
             t = [timeit(f) for f in (fa, fb, ba, bb)]
             print(f"  {name} B={B} T={T}: fwd rows {t[0]:.1f} us  planes {t[1]:.1f} us | bwd rows {t[2]:.1f} us  planes {t[3]:.1f} us", flush=True)
-        for v, label in ((103, "no tile loop"), (102, "no copies")):
-            ops.set_attention_variant(v)
-            t = [timeit(f) for f in (fa, fb)]
-            print(f"  fwd ablation ({label}): rows {t[0]:.1f} us  planes {t[1]:.1f} us")
-        ops.set_attention_variant(0)
 
 
 if __name__ == "__main__":

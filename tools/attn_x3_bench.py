@@ -29,16 +29,5 @@ for B, T, H in ((63, 1025, 12), (16, 1025, 12), (64, 325, 6), (512, 197, 12)):
             fn()
         e1.record(); torch.cuda.synchronize()
         res[name] = e0.elapsed_time(e1) / 10
-    if T == 1025:
-        for dbg, what in ((8, "no copies in the loop"), (16, "no tile barrier"), (24, "neither"), (7, "barriers / copies only"), (15, "barriers only"), (31, "empty loop")):
-            ops.set_attention_variant(200 + dbg)
-            fn = lambda: call("simseg_attention_fwd_x3", ptr(planes), B * T * 3 * H * 64, ptr(out), B, T, H, 0.125, stream())
-            fn(); e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(10):
-                fn()
-            e1.record(); torch.cuda.synchronize()
-            print(f"   ablation {what}: {e0.elapsed_time(e1) / 10:.3f} ms")
-        ops.set_attention_variant(0)
     fl = 4.0 * T * T * 64 * B * H
     print(f"B={B} T={T} H={H}: fp32 kernel {res['fp32']:.3f} ms ({fl / res['fp32'] / 1e9:.0f} TF)   split-bf16 {res['x3']:.3f} ms ({fl / res['x3'] / 1e9:.0f} TF fp32-equivalent) = split pass {res['split']:.3f} + kernel {res['kernel']:.3f} ms ({6 * fl / res['kernel'] / 1e9:.0f} TF of bf16 MFMA work)")

@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Debug: a few launches of ONE attention configuration (for rocprofv3 --pmc runs).  argv: T variant [bwd]"""
+"""Debug: a few launches of ONE attention configuration (for rocprofv3 --pmc runs).  argv: T variant [bwd]
+variant: 0 = auto, 1 = ring kernels, 6 / 7 = the long-sequence forward with one / two query blocks per wave"""
 import os
 import sys
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Per-block timeline of the bf16 attention backward (single-kernel form; SIMSEG_ATTN_VARIANT=3: the resident dK/dV pass): how long a
+"""Per-block timeline of the bf16 attention backward (single-kernel form, T <= 256): how long a
 block waits for its operand copies, computes, and stores."""
 import os
 import sys

@@ -19,7 +19,7 @@ def t(fn, it=20):
 
 import os
 H = 12
-ops.set_attention_variant(int(os.environ.get("ATTN_VARIANT", "0")))
+ops.set_attention_variant(int(os.environ.get("ATTN_VARIANT", "0")))       # 0 auto, 6 / 7 = one / two query blocks per wave
 c = ops.attention_qscale(0.125)
 out = []
 for dtype in (torch.bfloat16, torch.float16):
