@@ -298,6 +298,42 @@ int simseg_adamw_multi_step_amp_clip(const void* table, const int64_t* sizes, co
                                      const float* loss_scale, const float* found_inf, const float* step_in, float* step_out,
                                      const float* grad_coef, void* stream);
 
+/* ---- linear-probe task (csrc/probe.hip; DESIGN.md "Linear probe") --------------------------------------------------------------
+ * Cross-entropy over integer class labels, top-k hits and the logit gradient in one pass over logits [B, C] (dt: 0 fp32, 1 the selected
+ * 16-bit type; labels int64 on the device): nn.CrossEntropyLoss(reduction='mean') + accuracy(topk=(1, 5)) of the reference's
+ * LinearProbModel.forward (simseg/models/pipelines/linear_prob.py:61-71, tasks/linear_prob/hooks/utils.py).  Per row i with label y, in fp32:
+ *   m = max_j x_j,  lse = m + log(sum_j exp(x_j - m)),  loss_rows[i] = lse - x_y,
+ *   ranks[i] = #{j : x_j > x_y} + #{j < y : x_j == x_y}      (equal logits rank by ascending class id, the order of simseg_topk_search),
+ *   write_grad: dlogits[i, j] = (exp(x_j - lse) - [j == y]) * gscale   (fp32 [B, C]; gscale = 1 / B for the mean loss).
+ * (lse is not rounded on its own: the loss is formed as log(sum) + (m - x_y) and the exponent as (x_j - m) - log(sum).)
+ * A label outside [0, C) never indexes the row: loss_rows[i] = NaN, ranks[i] = INT32_MAX (a miss at every k), gradient row zero.
+ * out3 = {mean of loss_rows, #{ranks < 1}, #{ranks < 5}} from a one-block second launch that adds the rows in index order in double
+ * precision (bit-reproducible, no atomics).  C <= 1024: one wave per row, the row held in registers; larger: one block per row.
+ * 1 <= C <= 65536, B >= 1; anything else is refused before a launch. */
+int simseg_ce_rows(const void* logits, int dt, const int64_t* labels, float* loss_rows, int32_t* ranks, float* dlogits, float* out3,
+                   int64_t B, int64_t C, float gscale, int write_grad, void* stream);
+/* LARS (simseg/core/optimizer/lars.py:86-127) as three launches over a tensor table, whatever the number of tensors.  table[t] = six
+ * 8-byte words {p, g, buf, p16, (float lr, float weight_decay), flags}: fp32 master, fp32 gradient, fp32 momentum buffer (0 when momentum
+ * is 0), the 16-bit compute copy to refresh (or 0), the tensor's learning rate and weight decay packed as two floats, flags bit 0 =
+ * lars_exclude, bit 1 = the tensor's first step (no momentum buffer yet).  sizes[t] elements; chunk c covers [chunk_off[c],
+ * chunk_off[c] + chunk) of tensor chunk_tid[c] (one block per chunk), a tensor's chunks are consecutive: [tensor_first[t],
+ * tensor_first[t + 1]).  The *_host arguments are HOST copies of the device tables of the same name: sizes, tensor ids, offsets and
+ * ranges are checked on them and an error returned before anything is launched; the caller guarantees that they hold what the device
+ * tables hold.
+ * norm_partials: partials[2c] = sum of p^2, partials[2c + 1] = sum of g^2 over chunk c (double; one plain store each; p, g read-only).
+ * finish: one block per tensor adds its partials in chunk order in double precision; local_lr[t] = eta * wn / (gn + weight_decay * wn
+ *   + eps) when wn != 0 and gn != 0, else 1; 1 for a lars_exclude tensor.  Nothing is read on the host.
+ * multi_step, per element: d = (g + weight_decay * p) * (local_lr[t] * lr); momentum != 0: buf = d on the tensor's first step, else
+ *   momentum * buf + (1 - dampening) * d, and d = nesterov ? d + momentum * buf : buf; p -= d; p16 = p rounded. */
+int simseg_lars_norm_partials(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
+                              const int64_t* sizes_host, const int32_t* chunk_tid_host, const int64_t* chunk_off_host, int64_t n_tensors,
+                              int64_t n_chunks, int chunk, double* partials, void* stream);
+int simseg_lars_finish(const void* table, const int32_t* tensor_first, const int32_t* tensor_first_host, const double* partials,
+                       int64_t n_tensors, int64_t n_chunks, float eta, float eps, float* local_lr, void* stream);
+int simseg_lars_multi_step(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
+                           const int64_t* sizes_host, const int32_t* chunk_tid_host, const int64_t* chunk_off_host, int64_t n_tensors,
+                           int64_t n_chunks, int chunk, const float* local_lr, float momentum, float dampening, int nesterov, void* stream);
+
 int simseg_cast(const void* in, void* out, int64_t n, int to_bf16, void* stream);
 int simseg_transpose_f32(const float* in, float* out, int64_t R, int64_t C, void* stream);
 /* fp32 [rows, K] (row stride ld_in) -> bf16 [rows, 6 K]: the three round-to-nearest bf16 pieces hi / mid / lo of every element

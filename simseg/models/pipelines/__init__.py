@@ -1,2 +1,3 @@
 from .builder import PIPELINE
 from . import clip
+from . import linear_prob

@@ -1,0 +1,511 @@
+// Linear-probe task (simseg/tasks/linear_prob, simseg/models/pipelines/linear_prob.py, simseg/core/optimizer/lars.py of the reference):
+// cross-entropy rows over integer class labels with top-1 / top-5 hits and the logit gradient in one pass, and LARS as three launches
+// over a tensor table.  Compiled ONCE: the 16-bit flavour (bf16 / fp16) is a template argument chosen from the calling thread's
+// simseg_set_half_type, so dtype code 1 means "the selected 16-bit type" as everywhere else in the ABI.
+#include <float.h>
+#include <limits.h>
+
+#include "common.h"
+
+namespace {
+
+// 16 bytes of a row as floats: 4 fp32 or 8 16-bit elements per lane and load.
+template <typename T>
+struct Chunk;
+template <>
+struct Chunk<float> {
+    static constexpr int VW = 4;
+    static __device__ __forceinline__ void load(const float* p, float* v) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = t[e];
+    }
+};
+template <typename H>
+struct Chunk16 {
+    static constexpr int VW = 8;
+    typedef H h8 __attribute__((ext_vector_type(8)));
+    static __device__ __forceinline__ void load(const H* p, float* v) {
+        const h8 t = *reinterpret_cast<const h8*>(p);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] = (float)t[e];
+    }
+};
+template <>
+struct Chunk<__bf16> : Chunk16<__bf16> {};
+template <>
+struct Chunk<_Float16> : Chunk16<_Float16> {};
+
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// Does column j with value x rank ahead of the label's column y with value xy?  Strictly larger, or equal with a smaller class id
+// (the order of search.hip: descending score, ascending index).
+__device__ __forceinline__ int ahead(float x, int j, float xy, int y) { return (x > xy || (x == xy && j < y)) ? 1 : 0; }
+
+constexpr int CE_WAVE_MAXC = 1024;      // up to here a row is 16 values per lane: one wave keeps it in registers and reads it once
+constexpr int CE_SLOTS = CE_WAVE_MAXC / 64;
+
+// One WAVE per row, four rows per block, C <= 1024: the row is loaded once into registers (16 bytes per lane and load when the rows are
+// 16-byte aligned: VEC), and max, sum of exponentials, rank count and the gradient all come from those registers; reductions are wave64
+// butterflies, no LDS and no barrier.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void ce_rows_wave_kernel(const T* __restrict__ logits, const long* __restrict__ labels,
+                                                           float* __restrict__ loss_rows, int* __restrict__ ranks,
+                                                           float* __restrict__ dlogits, int B, int C, float gscale, int write_grad) {
+    constexpr int VW = Chunk<T>::VW;
+    const int lane = threadIdx.x & 63;
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= B) return;                                  // (wave-uniform)
+    const T* row = logits + i * C;
+    float v[CE_SLOTS];
+    int col[CE_SLOTS];                                   // slot -> column (compile-time pattern, folded after unrolling)
+#pragma unroll
+    for (int s = 0; s < CE_SLOTS; ++s) col[s] = VEC ? ((s / VW) * 64 + lane) * VW + (s % VW) : s * 64 + lane;
+    if (VEC) {
+#pragma unroll
+        for (int k = 0; k < CE_SLOTS / VW; ++k) {
+            const int j0 = (k * 64 + lane) * VW;         // (C % VW == 0: a chunk is inside the row or outside it)
+            if (j0 < C) {
+                Chunk<T>::load(row + j0, v + k * VW);
+            } else {
+#pragma unroll
+                for (int e = 0; e < VW; ++e) v[k * VW + e] = -FLT_MAX;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < CE_SLOTS; ++s) v[s] = col[s] < C ? (float)row[col[s]] : -FLT_MAX;
+    }
+    const long y64 = labels[i];
+    const bool ok = y64 >= 0 && y64 < C;                 // a label outside [0, C) never indexes the row
+    const int y = ok ? (int)y64 : 0;
+    const float xy = ok ? (float)row[y] : 0.f;
+    float m = -FLT_MAX;
+#pragma unroll
+    for (int s = 0; s < CE_SLOTS; ++s) m = fmaxf(m, v[s]);
+    m = wave_max(m);
+    float se = 0.f;
+    int cnt = 0;
+#pragma unroll
+    for (int s = 0; s < CE_SLOTS; ++s) {
+        if (col[s] < C) {
+            se += expf(v[s] - m);
+            cnt += ahead(v[s], col[s], xy, y);
+        }
+    }
+    se = wave_sum(se);
+    cnt = wave_sum_int(cnt);
+    // lse = m + log(se) is never rounded on its own: loss = lse - x_y is formed as log(se) + (m - x_y) and exp(x_j - lse) as
+    // exp((x_j - m) - log(se)) - the same values without an error of half an ulp of |lse| in each (for the columns that carry the
+    // probability mass x_j - m is small and exact)
+    const float lsum = logf(se);
+    if (lane == 0) {
+        loss_rows[i] = ok ? lsum + (m - xy) : __int_as_float(0x7fc00000);
+        ranks[i] = ok ? cnt : INT_MAX;
+    }
+    if (!write_grad) return;
+    float* drow = dlogits + i * C;
+    float g[CE_SLOTS];
+#pragma unroll
+    for (int s = 0; s < CE_SLOTS; ++s) g[s] = ok ? (expf((v[s] - m) - lsum) - (col[s] == y ? 1.f : 0.f)) * gscale : 0.f;
+    if (VEC) {
+#pragma unroll
+        for (int k = 0; k < CE_SLOTS / VW; ++k) {
+            const int j0 = (k * 64 + lane) * VW;
+            if (j0 < C) {
+#pragma unroll
+                for (int q = 0; q < VW / 4; ++q) {
+                    const f32x4 o = {g[k * VW + 4 * q], g[k * VW + 4 * q + 1], g[k * VW + 4 * q + 2], g[k * VW + 4 * q + 3]};
+                    *reinterpret_cast<f32x4*>(drow + j0 + 4 * q) = o;
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int s = 0; s < CE_SLOTS; ++s)
+            if (col[s] < C) drow[col[s]] = g[s];
+    }
+}
+
+// One BLOCK per row, C > 1024: pass 1 reads the row once and keeps a running maximum and a sum of exponentials relative to it per lane
+// (rescaled when the maximum moves) beside the rank count; the lanes' pairs are merged against the block maximum in a fixed order (wave
+// butterfly, then the four waves through LDS).  Pass 2 (write_grad) re-reads the row - it was just read, so from cache - and writes the
+// gradient.
+template <typename T, bool VEC>
+__global__ __launch_bounds__(256) void ce_rows_block_kernel(const T* __restrict__ logits, const long* __restrict__ labels,
+                                                            float* __restrict__ loss_rows, int* __restrict__ ranks,
+                                                            float* __restrict__ dlogits, int C, float gscale, int write_grad) {
+    constexpr int VW = Chunk<T>::VW;
+    __shared__ float shf[4];
+    __shared__ int shi[4];
+    const int tid = threadIdx.x;
+    const long i = blockIdx.x;
+    const T* row = logits + i * C;
+    const long y64 = labels[i];
+    const bool ok = y64 >= 0 && y64 < C;
+    const int y = ok ? (int)y64 : 0;
+    const float xy = ok ? (float)row[y] : 0.f;
+    float m = -FLT_MAX, se = 0.f;
+    int cnt = 0;
+    if (VEC) {
+        for (int j0 = tid * VW; j0 < C; j0 += 256 * VW) {
+            float v[VW];
+            Chunk<T>::load(row + j0, v);
+            float vm = v[0];
+#pragma unroll
+            for (int e = 1; e < VW; ++e) vm = fmaxf(vm, v[e]);
+            if (vm > m) {
+                se *= expf(m - vm);
+                m = vm;
+            }
+#pragma unroll
+            for (int e = 0; e < VW; ++e) {
+                se += expf(v[e] - m);
+                cnt += ahead(v[e], j0 + e, xy, y);
+            }
+        }
+    } else {
+        for (int j = tid; j < C; j += 256) {
+            const float x = (float)row[j];
+            if (x > m) {
+                se *= expf(m - x);
+                m = x;
+            }
+            se += expf(x - m);
+            cnt += ahead(x, j, xy, y);
+        }
+    }
+    float bm = wave_max(m);
+    if ((tid & 63) == 0) shf[tid >> 6] = bm;
+    __syncthreads();
+    bm = fmaxf(fmaxf(shf[0], shf[1]), fmaxf(shf[2], shf[3]));
+    __syncthreads();
+    se = wave_sum(se * expf(m - bm));
+    cnt = wave_sum_int(cnt);
+    if ((tid & 63) == 0) {
+        shf[tid >> 6] = se;
+        shi[tid >> 6] = cnt;
+    }
+    __syncthreads();
+    se = (shf[0] + shf[1]) + (shf[2] + shf[3]);
+    cnt = (shi[0] + shi[1]) + (shi[2] + shi[3]);
+    const float lsum = logf(se);                         // (lse = bm + lsum is not rounded on its own: see the wave kernel)
+    if (tid == 0) {
+        loss_rows[i] = ok ? lsum + (bm - xy) : __int_as_float(0x7fc00000);
+        ranks[i] = ok ? cnt : INT_MAX;
+    }
+    if (!write_grad) return;
+    float* drow = dlogits + i * C;
+    if (VEC) {
+        for (int j0 = tid * VW; j0 < C; j0 += 256 * VW) {
+            float v[VW];
+            Chunk<T>::load(row + j0, v);
+#pragma unroll
+            for (int e = 0; e < VW; ++e) v[e] = ok ? (expf((v[e] - bm) - lsum) - (j0 + e == y ? 1.f : 0.f)) * gscale : 0.f;
+#pragma unroll
+            for (int q = 0; q < VW / 4; ++q) {
+                const f32x4 o = {v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]};
+                *reinterpret_cast<f32x4*>(drow + j0 + 4 * q) = o;
+            }
+        }
+    } else {
+        for (int j = tid; j < C; j += 256) drow[j] = ok ? (expf(((float)row[j] - bm) - lsum) - (j == y ? 1.f : 0.f)) * gscale : 0.f;
+    }
+}
+
+// One block: out3 = {mean loss, top-1 count, top-5 count}.  The loss rows are summed in INDEX order in double precision by one thread
+// (the block stages 1024 rows at a time in LDS for it), so the value is the same on every run and equals a sequential host sum; the
+// counts are integers, reduced by the whole block.
+__global__ __launch_bounds__(256) void ce_finish_kernel(const float* __restrict__ loss_rows, const int* __restrict__ ranks,
+                                                        float* __restrict__ out3, int B) {
+    __shared__ float stage[1024];
+    __shared__ int sh1[4], sh5[4];
+    const int tid = threadIdx.x;
+    int h1 = 0, h5 = 0;
+    double acc = 0.0;
+    for (int base = 0; base < B; base += 1024) {
+        const int n = min(1024, B - base);
+        for (int k = tid; k < n; k += 256) {
+            stage[k] = loss_rows[base + k];
+            const int r = ranks[base + k];
+            h1 += r < 1 ? 1 : 0;
+            h5 += r < 5 ? 1 : 0;
+        }
+        __syncthreads();
+        if (tid == 0)
+            for (int k = 0; k < n; ++k) acc += (double)stage[k];
+        __syncthreads();
+    }
+    h1 = wave_sum_int(h1);
+    h5 = wave_sum_int(h5);
+    if ((tid & 63) == 0) {
+        sh1[tid >> 6] = h1;
+        sh5[tid >> 6] = h5;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        out3[0] = (float)(acc / (double)B);
+        out3[1] = (float)((sh1[0] + sh1[1]) + (sh1[2] + sh1[3]));
+        out3[2] = (float)((sh5[0] + sh5[1]) + (sh5[2] + sh5[3]));
+    }
+}
+
+// ---- LARS over a tensor table ------------------------------------------------------------------------------------------------------
+// table[t] = six 8-byte words {p, g, buf, p16, (float lr, float weight_decay), flags}: fp32 master, fp32 gradient, fp32 momentum buffer
+// (0 when momentum == 0), the 16-bit compute copy to refresh (or 0), the tensor's learning rate and weight decay, and flags: bit 0 =
+// lars_exclude (local lr 1), bit 1 = first step of this tensor (no momentum buffer yet: buf = d).  Chunks as in the AdamW table: chunk c
+// covers [chunk_off[c], chunk_off[c] + chunk) of tensor chunk_tid[c], one block per chunk.
+struct LarsTensors { float* p; const float* g; float* buf; void* p16; float lr; float wd; long flags; };
+static_assert(sizeof(LarsTensors) == 48, "table rows are six 8-byte words");
+
+// partials[2c] = sum of p^2, partials[2c + 1] = sum of g^2 over chunk c.  Read-only on p and g; double accumulators (the pass is bound by
+// its 8 bytes per element, not by the FMAs), wave butterfly, the four waves through LDS in a fixed order, one plain store per sum.
+__global__ __launch_bounds__(256) void lars_norm_partials_kernel(const LarsTensors* __restrict__ table, const long* __restrict__ sizes,
+                                                                 const int* __restrict__ chunk_tid, const long* __restrict__ chunk_off,
+                                                                 int chunk, double* __restrict__ partials) {
+    __shared__ double sh[8];
+    const int c = blockIdx.x;
+    const int t = chunk_tid[c];
+    const float* p = table[t].p;
+    const float* g = table[t].g;
+    const long lo = chunk_off[c];
+    const long hi = min(sizes[t], lo + chunk);
+    const bool vec = (((uintptr_t)(p + lo) | (uintptr_t)(g + lo)) % 16) == 0;
+    const long n4 = vec ? (hi - lo) / 4 : 0;
+    double pp = 0.0, gg = 0.0;
+    for (long q = threadIdx.x; q < n4; q += 256) {
+        const f32x4 a = *reinterpret_cast<const f32x4*>(p + lo + 4 * q);
+        const f32x4 b = *reinterpret_cast<const f32x4*>(g + lo + 4 * q);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            pp = fma((double)a[e], (double)a[e], pp);
+            gg = fma((double)b[e], (double)b[e], gg);
+        }
+    }
+    for (long i = lo + 4 * n4 + threadIdx.x; i < hi; i += 256) {
+        pp = fma((double)p[i], (double)p[i], pp);
+        gg = fma((double)g[i], (double)g[i], gg);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        pp += __shfl_xor(pp, o, 64);
+        gg += __shfl_xor(gg, o, 64);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        sh[threadIdx.x >> 6] = pp;
+        sh[4 + (threadIdx.x >> 6)] = gg;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partials[2 * (long)c] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+        partials[2 * (long)c + 1] = (sh[4] + sh[5]) + (sh[6] + sh[7]);
+    }
+}
+
+// One block (one wave) per tensor: its chunks' partials, [tensor_first[t], tensor_first[t + 1]), are summed in CHUNK order in double
+// precision (the lanes fetch 64 at a time, the additions run in order), then
+//   local_lr[t] = eta * wn / (gn + weight_decay * wn + eps)   when wn != 0 and gn != 0, else 1;   1 for a lars_exclude tensor.
+// The reference reads both norms on the host (two .item() calls per tensor, lars.py:104-105); here nothing leaves the device.
+__global__ __launch_bounds__(64) void lars_finish_kernel(const LarsTensors* __restrict__ table, const int* __restrict__ tensor_first,
+                                                         const double* __restrict__ partials, float eta, float eps,
+                                                         float* __restrict__ local_lr) {
+    const int t = blockIdx.x, lane = threadIdx.x;
+    const int c0 = tensor_first[t], c1 = tensor_first[t + 1];
+    double sp = 0.0, sg = 0.0;
+    for (int base = c0; base < c1; base += 64) {
+        const int k = base + lane;
+        const double a = k < c1 ? partials[2 * (long)k] : 0.0;
+        const double b = k < c1 ? partials[2 * (long)k + 1] : 0.0;
+        const int n = min(64, c1 - base);
+        for (int j = 0; j < n; ++j) {
+            sp += __shfl(a, j, 64);
+            sg += __shfl(b, j, 64);
+        }
+    }
+    if (lane == 0) {
+        float out = 1.0f;
+        if (!(table[t].flags & 1)) {
+            const double wn = sqrt(sp), gn = sqrt(sg);
+            if (wn != 0.0 && gn != 0.0) out = (float)((double)eta * wn / (gn + (double)table[t].wd * wn + (double)eps));
+        }
+        local_lr[t] = out;
+    }
+}
+
+// The update, per element (lars.py:113-127 restated):
+//   d = (g + weight_decay * p) * (local_lr[t] * lr)
+//   momentum != 0:  buf = d on the tensor's first step, else momentum * buf + (1 - dampening) * d;   d = nesterov ? d + momentum * buf : buf
+//   p -= d;  p16 = p rounded to the 16-bit type
+// The arithmetic runs in double between the fp32 loads and stores (20 bytes of traffic per element: the kernel is bound by memory, and the
+// result is then the correctly rounded value of the law above rather than a chain of fp32 roundings); buf is rounded to fp32 BEFORE it
+// enters d, as the stored buffer is what the reference's update reads.
+template <typename H>
+__global__ __launch_bounds__(256) void lars_multi_kernel(const LarsTensors* __restrict__ table, const long* __restrict__ sizes,
+                                                         const int* __restrict__ chunk_tid, const long* __restrict__ chunk_off, int chunk,
+                                                         const float* __restrict__ local_lr, float momentum, float dampening,
+                                                         int nesterov) {
+    const int c = blockIdx.x;
+    const int t = chunk_tid[c];
+    const LarsTensors T = table[t];
+    H* p16 = reinterpret_cast<H*>(T.p16);
+    const long lo = chunk_off[c];
+    const long hi = min(sizes[t], lo + chunk);
+    const double scale = (double)local_lr[t] * (double)T.lr;
+    const double wd = (double)T.wd, mom = (double)momentum, keep = 1.0 - (double)dampening;
+    const bool first = (T.flags & 2) != 0;
+    const bool use_buf = momentum != 0.f && T.buf != nullptr;
+    auto one = [&](float g_, float& pi, float& bi) {
+        double d = ((double)g_ + wd * (double)pi) * scale;
+        if (use_buf) {
+            bi = (float)(first ? d : mom * (double)bi + keep * d);
+            d = nesterov ? d + mom * (double)bi : (double)bi;
+        }
+        pi = (float)((double)pi - d);
+    };
+    const bool vec = (((uintptr_t)(T.g + lo) | (uintptr_t)(T.p + lo)) % 16 == 0) && (!use_buf || (uintptr_t)(T.buf + lo) % 16 == 0) &&
+                     (!p16 || (uintptr_t)(p16 + lo) % 8 == 0);
+    long i0 = lo;
+    if (vec) {
+        typedef H h4 __attribute__((ext_vector_type(4)));
+        const long n4 = (hi - lo) / 4;
+        for (long q = threadIdx.x; q < n4; q += 256) {
+            const long i = lo + 4 * q;
+            const f32x4 g4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(T.g + i));
+            f32x4 p4 = *reinterpret_cast<const f32x4*>(T.p + i);
+            f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
+            if (use_buf && !first) b4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(T.buf + i));
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float pe = p4[e], be = b4[e];
+                one(g4[e], pe, be);
+                p4[e] = pe;
+                b4[e] = be;
+            }
+            *reinterpret_cast<f32x4*>(T.p + i) = p4;
+            if (use_buf) __builtin_nontemporal_store(b4, reinterpret_cast<f32x4*>(T.buf + i));
+            if (p16) {
+                const h4 o = {(H)p4[0], (H)p4[1], (H)p4[2], (H)p4[3]};
+                *reinterpret_cast<h4*>(p16 + i) = o;
+            }
+        }
+        i0 = lo + 4 * n4;
+    }
+    for (long i = i0 + threadIdx.x; i < hi; i += 256) {
+        float pi = T.p[i], bi = (use_buf && !first) ? T.buf[i] : 0.f;
+        one(T.g[i], pi, bi);
+        T.p[i] = pi;
+        if (use_buf) T.buf[i] = bi;
+        if (p16) p16[i] = (H)pi;
+    }
+}
+
+// The chunk tables as the HOST sees them, checked before anything is launched (the kernels index with them).
+int lars_check_tables(const char* who, const int64_t* sizes_host, const int32_t* chunk_tid_host, const int64_t* chunk_off_host,
+                      int64_t n_tensors, int64_t n_chunks, int chunk) {
+    SS_CHECK(sizes_host && chunk_tid_host && chunk_off_host, "%s: null host table", who);
+    SS_CHECK(n_tensors >= 1 && n_tensors < (1ll << 31) && n_chunks >= 0 && n_chunks < (1ll << 31) && chunk > 0,
+             "%s: bad table extents (%lld tensors, %lld chunks of %d)", who, (long long)n_tensors, (long long)n_chunks, chunk);
+    for (int64_t t = 0; t < n_tensors; ++t)
+        SS_CHECK(sizes_host[t] >= 0, "%s: tensor %lld has a negative size (%lld)", who, (long long)t, (long long)sizes_host[t]);
+    for (int64_t c = 0; c < n_chunks; ++c) {
+        const int64_t t = chunk_tid_host[c];
+        SS_CHECK(t >= 0 && t < n_tensors, "%s: chunk %lld names tensor id %lld, outside [0, %lld)", who, (long long)c, (long long)t,
+                 (long long)n_tensors);
+        SS_CHECK(chunk_off_host[c] >= 0 && chunk_off_host[c] < sizes_host[t], "%s: chunk offset %lld of chunk %lld is past the end of tensor %lld (%lld elements)",
+                 who, (long long)chunk_off_host[c], (long long)c, (long long)t, (long long)sizes_host[t]);
+    }
+    return 0;
+}
+
+}  // namespace
+
+#define STREAM ((hipStream_t)stream)
+
+template <typename T>
+static int ce_rows_launch(const void* logits, const int64_t* labels, float* loss_rows, int32_t* ranks, float* dlogits, int64_t B, int64_t C,
+                          float gscale, int write_grad, hipStream_t s) {
+    const bool vec = C % Chunk<T>::VW == 0 && ((uintptr_t)logits % 16) == 0 && (!write_grad || ((uintptr_t)dlogits % 16) == 0);
+    const T* x = (const T*)logits;
+    const long* y = (const long*)labels;
+    if (C <= CE_WAVE_MAXC) {
+        const dim3 grid((unsigned)((B + 3) / 4));
+        if (vec) hipLaunchKernelGGL((ce_rows_wave_kernel<T, true>), grid, dim3(256), 0, s, x, y, loss_rows, ranks, dlogits, (int)B, (int)C, gscale, write_grad);
+        else hipLaunchKernelGGL((ce_rows_wave_kernel<T, false>), grid, dim3(256), 0, s, x, y, loss_rows, ranks, dlogits, (int)B, (int)C, gscale, write_grad);
+    } else {
+        const dim3 grid((unsigned)B);
+        if (vec) hipLaunchKernelGGL((ce_rows_block_kernel<T, true>), grid, dim3(256), 0, s, x, y, loss_rows, ranks, dlogits, (int)C, gscale, write_grad);
+        else hipLaunchKernelGGL((ce_rows_block_kernel<T, false>), grid, dim3(256), 0, s, x, y, loss_rows, ranks, dlogits, (int)C, gscale, write_grad);
+    }
+    SS_LAUNCH_CHECK("ce_rows");
+    return 0;
+}
+
+extern "C" int simseg_ce_rows(const void* logits, int dt, const int64_t* labels, float* loss_rows, int32_t* ranks, float* dlogits,
+                              float* out3, int64_t B, int64_t C, float gscale, int write_grad, void* stream) {
+    SS_CHECK(logits && labels && loss_rows && ranks && out3, "ce_rows: null pointer");
+    SS_CHECK(!write_grad || dlogits, "ce_rows: write_grad needs dlogits");
+    SS_CHECK(dt == 0 || dt == 1, "ce_rows: dt must be 0 (fp32) or 1 (the selected 16-bit type), got %d", dt);
+    SS_CHECK(C >= 1 && C <= 65536, "ce_rows: need 1 <= C <= 65536 (got C=%lld)", (long long)C);
+    SS_CHECK(B >= 1 && B < (1ll << 31), "ce_rows: need 1 <= B < 2^31 (got B=%lld)", (long long)B);
+    SS_CHECK(((uintptr_t)logits % (dt == 0 ? 4 : 2)) == 0 && ((uintptr_t)labels % 8) == 0, "ce_rows: misaligned operand");
+    int rc;
+    if (dt == 0) rc = ce_rows_launch<float>(logits, labels, loss_rows, ranks, dlogits, B, C, gscale, write_grad, STREAM);
+    else if (g_ss_half == 2) rc = ce_rows_launch<_Float16>(logits, labels, loss_rows, ranks, dlogits, B, C, gscale, write_grad, STREAM);
+    else rc = ce_rows_launch<__bf16>(logits, labels, loss_rows, ranks, dlogits, B, C, gscale, write_grad, STREAM);
+    if (rc) return rc;
+    hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(256), 0, STREAM, loss_rows, ranks, out3, (int)B);
+    SS_LAUNCH_CHECK("ce_rows");
+    return 0;
+}
+
+extern "C" int simseg_lars_norm_partials(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
+                                         const int64_t* sizes_host, const int32_t* chunk_tid_host, const int64_t* chunk_off_host,
+                                         int64_t n_tensors, int64_t n_chunks, int chunk, double* partials, void* stream) {
+    SS_CHECK(table && sizes && chunk_tid && chunk_off && partials, "lars_norm_partials: null pointer");
+    if (int rc = lars_check_tables("lars_norm_partials", sizes_host, chunk_tid_host, chunk_off_host, n_tensors, n_chunks, chunk)) return rc;
+    if (n_chunks == 0) return 0;
+    hipLaunchKernelGGL(lars_norm_partials_kernel, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const LarsTensors*)table, (const long*)sizes,
+                       chunk_tid, (const long*)chunk_off, chunk, partials);
+    SS_LAUNCH_CHECK("lars_norm_partials");
+    return 0;
+}
+
+extern "C" int simseg_lars_finish(const void* table, const int32_t* tensor_first, const int32_t* tensor_first_host, const double* partials,
+                                  int64_t n_tensors, int64_t n_chunks, float eta, float eps, float* local_lr, void* stream) {
+    SS_CHECK(table && tensor_first && tensor_first_host && partials && local_lr, "lars_finish: null pointer");
+    SS_CHECK(n_tensors >= 1 && n_tensors < (1ll << 31) && n_chunks >= 0 && n_chunks < (1ll << 31), "lars_finish: bad table extents (%lld tensors, %lld chunks)",
+             (long long)n_tensors, (long long)n_chunks);
+    SS_CHECK(eta >= 0.f && eps >= 0.f, "lars_finish: eta %g / eps %g is negative (or nan)", (double)eta, (double)eps);
+    SS_CHECK(tensor_first_host[0] == 0 && tensor_first_host[n_tensors] == n_chunks, "lars_finish: the tensors' chunk ranges cover [%d, %d), not [0, %lld)",
+             tensor_first_host[0], tensor_first_host[n_tensors], (long long)n_chunks);
+    for (int64_t t = 0; t < n_tensors; ++t)
+        SS_CHECK(tensor_first_host[t] <= tensor_first_host[t + 1], "lars_finish: the chunk range of tensor %lld is reversed", (long long)t);
+    hipLaunchKernelGGL(lars_finish_kernel, dim3((unsigned)n_tensors), dim3(64), 0, STREAM, (const LarsTensors*)table, tensor_first, partials, eta, eps,
+                       local_lr);
+    SS_LAUNCH_CHECK("lars_finish");
+    return 0;
+}
+
+extern "C" int simseg_lars_multi_step(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
+                                      const int64_t* sizes_host, const int32_t* chunk_tid_host, const int64_t* chunk_off_host, int64_t n_tensors,
+                                      int64_t n_chunks, int chunk, const float* local_lr, float momentum, float dampening, int nesterov,
+                                      void* stream) {
+    SS_CHECK(table && sizes && chunk_tid && chunk_off && local_lr, "lars_multi_step: null pointer");
+    SS_CHECK(momentum >= 0.f, "lars_multi_step: momentum %g is negative (or nan)", (double)momentum);
+    SS_CHECK(!nesterov || (momentum > 0.f && dampening == 0.f), "lars_multi_step: Nesterov momentum requires a momentum and zero dampening");
+    if (int rc = lars_check_tables("lars_multi_step", sizes_host, chunk_tid_host, chunk_off_host, n_tensors, n_chunks, chunk)) return rc;
+    if (n_chunks == 0) return 0;
+    const dim3 grid((unsigned)n_chunks);
+    if (g_ss_half == 2)
+        hipLaunchKernelGGL(lars_multi_kernel<_Float16>, grid, dim3(256), 0, STREAM, (const LarsTensors*)table, (const long*)sizes, chunk_tid,
+                           (const long*)chunk_off, chunk, local_lr, momentum, dampening, nesterov);
+    else
+        hipLaunchKernelGGL(lars_multi_kernel<__bf16>, grid, dim3(256), 0, STREAM, (const LarsTensors*)table, (const long*)sizes, chunk_tid,
+                           (const long*)chunk_off, chunk, local_lr, momentum, dampening, nesterov);
+    SS_LAUNCH_CHECK("lars_multi_step");
+    return 0;
+}

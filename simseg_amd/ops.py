@@ -887,3 +887,58 @@ def train_transforms(src, plan, lut, want_u8=False):
     call("simseg_train_transforms", ptr(_c(src)), src.numel(), ptr(plan["img_tab"]), it.ctypes.data, B, ptr(plan["tab"]), th.ctypes.data,
          th.size, ptr(_c(lut)), S, ptr(scratch), scratch.numel(), ptr(out), out.numel(), ptr(u8), 0 if u8 is None else u8.numel(), stream())
     return out, u8
+
+
+# ---- linear-probe task (csrc/probe.hip) ------------------------------------------------------------------------------------------
+CE_MAX_CLASSES = 65536         # simseg_ce_rows: 1 <= C <= 65536
+
+
+def ce_rows(logits, labels, write_grad=True):
+    """Cross-entropy with integer class labels, top-1 / top-5 hits and the logit gradient of the MEAN loss in one pass over logits [B, C]
+    (fp32, bf16 or fp16; labels int64 [B] on the device).  -> (out3, loss_rows, ranks, dlogits): out3 fp32 [3] = {mean loss, top-1 count,
+    top-5 count}, loss_rows fp32 [B], ranks int32 [B] (how many classes rank ahead of the label's; equal logits by ascending class id),
+    dlogits fp32 [B, C] = (softmax - onehot) / B, or None when write_grad is False.  A label outside [0, C): NaN loss row, rank
+    2^31 - 1, zero gradient row (include/simseg_hip.h)."""
+    require_gpu(logits, labels)
+    if logits.dim() != 2 or labels.shape != logits.shape[:1]:
+        raise ValueError(f"ce_rows: logits [B, C] and labels [B], got {tuple(logits.shape)} and {tuple(labels.shape)}")
+    if labels.dtype != torch.int64:
+        raise TypeError(f"ce_rows: labels must be int64, got {labels.dtype}")
+    B, C = logits.shape
+    dev = logits.device
+    loss_rows = torch.empty(B, device=dev, dtype=torch.float32)
+    ranks = torch.empty(B, device=dev, dtype=torch.int32)
+    out3 = torch.empty(3, device=dev, dtype=torch.float32)
+    dlogits = torch.empty(B, C, device=dev, dtype=torch.float32) if write_grad else None
+    call("simseg_ce_rows", ptr(_c(logits)), dt(logits), ptr(_c(labels)), ptr(loss_rows), ptr(ranks), ptr(dlogits), ptr(out3), B, C,
+         1.0 / max(B, 1), int(bool(write_grad)), stream())
+    return out3, loss_rows, ranks, dlogits
+
+
+def _lars_tables(tab):
+    return (ptr(tab["table"]), ptr(tab["sizes"]), ptr(tab["tid"]), ptr(tab["coff"]), tab["sizes_host"].ctypes.data, tab["tid_host"].ctypes.data,
+            tab["coff_host"].ctypes.data, int(tab["n_tensors"]), int(tab["n_chunks"]), int(tab["chunk"]))
+
+
+def lars_norm_partials(tab, partials):
+    """partials float64 [n_chunks, 2] <- per chunk {sum p^2, sum g^2} of the tensor table `tab` (simseg_amd.optim.LARS._plan: device tables
+    table / sizes / tid / coff / first, their host copies *_host, n_tensors, n_chunks, chunk)."""
+    if partials.dtype != torch.float64 or partials.numel() < 2 * tab["n_chunks"]:
+        raise TypeError("lars_norm_partials: partials must be float64 [n_chunks, 2]")
+    call("simseg_lars_norm_partials", *_lars_tables(tab), ptr(partials), stream())
+    return partials
+
+
+def lars_finish(tab, partials, eta, eps, local_lr):
+    """local_lr fp32 [n_tensors] <- eta * |p| / (|g| + weight_decay * |p| + eps) per tensor (1 where a norm is zero or the tensor is
+    lars_exclude), from the partials of lars_norm_partials.  No host read."""
+    if local_lr.dtype != torch.float32 or local_lr.numel() < tab["n_tensors"]:
+        raise TypeError("lars_finish: local_lr must be fp32 [n_tensors]")
+    call("simseg_lars_finish", ptr(tab["table"]), ptr(tab["first"]), tab["first_host"].ctypes.data, ptr(partials), int(tab["n_tensors"]),
+         int(tab["n_chunks"]), float(eta), float(eps), ptr(local_lr), stream())
+    return local_lr
+
+
+def lars_multi_step(tab, local_lr, momentum, dampening, nesterov):
+    """The LARS update of every tensor of the table in one launch (masters, momentum buffers and 16-bit copies in place)."""
+    call("simseg_lars_multi_step", *_lars_tables(tab), ptr(local_lr), float(momentum), float(dampening), int(bool(nesterov)), stream())

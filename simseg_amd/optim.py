@@ -17,6 +17,7 @@ import math
 import numpy as np
 import torch
 from torch.amp.grad_scaler import OptState
+from torch.optim.optimizer import required
 
 from .lib import call, note_half, ptr, stream
 from .towers import drop_qscaled_copy, drop_split_copy, register_w16
@@ -382,3 +383,156 @@ class GradScaler(torch.amp.GradScaler):
         unscaled = self.is_enabled() and self._per_optimizer_states[id(optimizer)]["stage"] is OptState.UNSCALED
         return optimizer.clip_grad_norm_(max_norm, norm_type=norm_type, error_if_nonfinite=error_if_nonfinite,
                                          loss_scale=None if unscaled else live_scale(self), materialize=materialize)
+
+
+class LARS(torch.optim.Optimizer):
+    """Layer-wise adaptive rate scaling for SGD: the reference's simseg.core.optimizer.LARS (lars.py:36-127; same constructor arguments,
+    defaults and ValueErrors, the group key `lars_exclude`, the state key `momentum_buffer`) as THREE launches over a tensor table,
+    whatever the number of tensors: per-chunk sums of p^2 and g^2, one block per tensor that turns them into the local learning rate
+    eta * |p| / (|g| + weight_decay * |p| + eps) ON THE DEVICE (the reference reads both norms on the host: two .item() calls per tensor),
+    and the update itself, which also refreshes the 16-bit compute copies the towers read (as AdamW's kernel does).  Parameters are
+    bucketed by (momentum, dampening, nesterov, eta); lr, weight_decay and lars_exclude travel per tensor in the table.
+
+    The table is planned once per parameter set (the way AdamW._plan does it) and refreshed from a ring of pinned buffers each step
+    (gradient pointers, learning rates, first-step flags).  Optimizer checkpoints use torch's layout with `momentum_buffer`, so they load
+    into the reference's LARS and the reference's load here."""
+
+    def __init__(self, params, lr=required, momentum=0, weight_decay=0, dampening=0, eta=0.001, nesterov=False, eps=1e-8,
+                 half_dtype=torch.bfloat16):
+        if lr is not required and lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if eta < 0.0:
+            raise ValueError(f"Invalid LARS coefficient value: {eta}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if half_dtype not in (torch.bfloat16, torch.float16):
+            raise TypeError("half_dtype: torch.bfloat16 (the default) or torch.float16")
+        self.eps = eps
+        self.half_dtype = half_dtype
+        self._plans = {}
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov, eta=eta))
+
+    def __setstate__(self, state):
+        super().__setstate__(state)
+        for group in self.param_groups:
+            group.setdefault("nesterov", False)
+
+    # ---- launch plan: everything about a set of tensors that does not change from step to step ------------------------------
+    def _plan(self, key, params):
+        ids = tuple(id(p) for p in params)
+        plan = self._plans.get(key)
+        if plan is not None and plan["ids"] == ids and all(p.data_ptr() == a for p, a in zip(params, plan["static"][:, 0])):
+            return plan
+        dev = params[0].device
+        starts, o = [], 0
+        for p in params:                      # every tensor starts on a 16-byte boundary of the flat buffers (the kernels' 16-byte path)
+            starts.append(o)
+            o += (p.numel() + 3) // 4 * 4
+        total = max(o, 4)
+        use_buf = key[0] != 0.0
+        buf = torch.zeros(total, device=dev, dtype=torch.float32) if use_buf else None
+        p16 = torch.empty(total, device=dev, dtype=self.half_dtype)
+        views = []
+        for p, o in zip(params, starts):
+            st, n = self.state[p], p.numel()
+            if use_buf:
+                view = buf[o:o + n].view_as(p)
+                if "momentum_buffer" in st:       # keep the momentum across a re-plan / a loaded checkpoint
+                    view.copy_(st["momentum_buffer"])
+                    st["momentum_buffer"] = view
+                views.append(view)                # (handed to the state after the tensor's first step: the reference has no buffer before)
+            st["p16"] = p16[o:o + n].view_as(p)
+            st["p16"].copy_(p.detach())
+        tid, coff, first = [], [], [0]
+        for t, p in enumerate(params):
+            for c in range(0, p.numel(), CHUNK):
+                tid.append(t); coff.append(c)
+            first.append(len(tid))
+        static = np.zeros((len(params), 6), dtype=np.int64)
+        for t, p in enumerate(params):
+            static[t, 0], static[t, 3] = p.data_ptr(), self.state[p]["p16"].data_ptr()
+            static[t, 2] = views[t].data_ptr() if use_buf else 0
+        host = dict(sizes_host=np.array([p.numel() for p in params], dtype=np.int64), tid_host=np.array(tid, dtype=np.int32),
+                    coff_host=np.array(coff, dtype=np.int64), first_host=np.array(first, dtype=np.int32))
+        plan = dict(ids=ids, buf=buf, p16=p16, views=views, static=static, n_tensors=len(params), n_chunks=len(tid), chunk=CHUNK, **host,
+                    sizes=torch.from_numpy(host["sizes_host"]).to(dev), tid=torch.from_numpy(host["tid_host"]).to(dev),
+                    coff=torch.from_numpy(host["coff_host"]).to(dev), first=torch.from_numpy(host["first_host"]).to(dev),
+                    partials=torch.empty(max(len(tid), 1), 2, device=dev, dtype=torch.float64),
+                    local_lr=torch.empty(len(params), device=dev, dtype=torch.float32),
+                    ring=[torch.empty(len(params), 6, dtype=torch.int64).pin_memory() for _ in range(RING)], events=[None] * RING, slot=0,
+                    table=torch.empty(len(params), 6, dtype=torch.int64, device=dev))
+        self._plans[key] = plan
+        return plan
+
+    def local_lrs(self):
+        """{parameter: its local learning rate of the last step} as 0-dim fp32 device tensors (views; the next step overwrites them)."""
+        return {p: plan["local_lr"][t] for plan in self._plans.values() for t, p in enumerate(plan["params"])}
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        from . import ops
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        buckets = {}
+        for group in self.param_groups:
+            key = (float(group["momentum"]), float(group["dampening"]), bool(group["nesterov"]), float(group["eta"]))
+            exclude = bool(group.get("lars_exclude", False))
+            for p in group["params"]:
+                if p.grad is not None:
+                    buckets.setdefault(key, []).append((p, float(group["lr"]), float(group["weight_decay"]), exclude))
+        for key, items in buckets.items():
+            params = [it[0] for it in items]
+            if any(not p.is_contiguous() or p.dtype != torch.float32 or not p.is_cuda for p in params):
+                raise TypeError("simseg_amd LARS expects contiguous fp32 master parameters on the device")
+            plan = self._plan(key, params)
+            plan["params"] = params
+            grads = [p.grad if (p.grad.is_contiguous() and p.grad.dtype == torch.float32) else p.grad.float().contiguous() for p in params]
+            slot = plan["slot"]
+            plan["slot"] = (slot + 1) % RING
+            if plan["events"][slot] is not None:
+                plan["events"][slot].synchronize()          # the upload that last used this pinned buffer has executed (RING steps ago)
+            host = plan["ring"][slot].numpy()
+            host[:] = plan["static"]
+            host[:, 1] = [g.data_ptr() for g in grads]
+            hyper = np.empty((len(params), 2), dtype=np.float32)
+            hyper[:, 0] = [it[1] for it in items]
+            hyper[:, 1] = [it[2] for it in items]
+            host[:, 4] = hyper.view(np.int64)[:, 0]
+            use_buf = key[0] != 0.0
+            host[:, 5] = [int(it[3]) | (2 if (use_buf and "momentum_buffer" not in self.state[it[0]]) else 0) for it in items]
+            plan["table"].copy_(plan["ring"][slot], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            plan["events"][slot] = ev
+            plan["keepalive"] = grads            # the kernels read them asynchronously
+            ops.lars_norm_partials(plan, plan["partials"])
+            ops.lars_finish(plan, plan["partials"], key[3], self.eps, plan["local_lr"])
+            note_half(self.half_dtype)           # (the 16-bit copies are addressed through the table: tell the binding which flavour they are)
+            ops.lars_multi_step(plan, plan["local_lr"], key[0], key[1], key[2])
+            for t, p in enumerate(params):
+                if use_buf and "momentum_buffer" not in self.state[p]:
+                    self.state[p]["momentum_buffer"] = plan["views"][t]
+                register_w16(p, self.state[p]["p16"])
+                drop_split_copy(p)
+                drop_qscaled_copy(p)
+        return loss
+
+    # ---- checkpoints in the reference's layout ---------------------------------------------------------------------------
+    def state_dict(self):
+        sd = super().state_dict()
+        sd["state"] = {idx: {"momentum_buffer": st["momentum_buffer"].clone()} for idx, st in sd["state"].items() if "momentum_buffer" in st}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._plans.clear()                     # the buffers are re-packed (and the 16-bit copies rewritten) by the next step
+        for st in self.state.values():
+            st.pop("p16", None)
+            if "momentum_buffer" in st:
+                st["momentum_buffer"] = st["momentum_buffer"].float().contiguous()
