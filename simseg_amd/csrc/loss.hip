@@ -1,6 +1,7 @@
 // Row kernels behind the similarity matrices: InfoNCE cross-entropy rows (K13), retrieval first-match ranks (K16),
 // and the fused AdamW step over the flat parameter buffer.
 #include "common.h"
+#include "tensor_table.h"
 
 namespace {
 
@@ -269,10 +270,10 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
     }
 }
 
-// Multi-tensor form: one launch for every parameter tensor.  table[t] = {p, g, m, v, p16, lr, weight_decay}: five device pointers and
-// the tensor's own learning rate / weight decay (the reference builds one param group per parameter, tasks/clip/hooks/optimizer.py:18-36);
-// sizes[t] elements; chunk c of the launch covers elements [chunk_off[c], chunk_off[c] + chunk) of tensor chunk_tid[c].  p16 (may be
-// null) is the bf16 compute copy the next forward's GEMMs read: refreshed here, so no per-step cast kernels.
+// Multi-tensor form: one launch for every parameter tensor over a tensor table (tensor_table.h).  table[t] = {p, g, m, v, p16, lr,
+// weight_decay}: five device pointers and the tensor's own learning rate / weight decay (the reference builds one param group per
+// parameter, tasks/clip/hooks/optimizer.py:18-36).  p16 (may be null) is the bf16 compute copy the next forward's GEMMs read: refreshed
+// here, so no per-step cast kernels.
 struct AdamTensors { float* p; const float* g; float* m; float* v; bf16_t* p16; float lr; float wd; };
 static_assert(sizeof(AdamTensors) == 48, "table rows are six 8-byte words");
 // AMP form (round 4): the loss scale, the overflow flag and the count of steps actually taken live on the DEVICE (amp.scale / amp.found_inf:
@@ -300,10 +301,9 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamTensors* __r
         bc2_sqrt = sqrtf(1.0f - powf(b2, st));
         if (amp.scale) grad_scale /= amp.scale[0];
     }
-    const int t = chunk_tid[c];
-    const AdamTensors T = table[t];
-    const long lo = chunk_off[c];
-    const long hi = min(sizes[t], lo + chunk);
+    const auto ch = table_chunk(table, sizes, chunk_tid, chunk_off, chunk);
+    const AdamTensors T = ch.T;      // (plain locals, not structured bindings: with them the compiler emits the loops below differently)
+    const long lo = ch.lo, hi = ch.hi;
     const float decay = 1.0f - T.lr * T.wd;
     const float step_size = T.lr / bc1;
     const float clip = CLIP ? coef[0] : 1.0f;
@@ -355,11 +355,8 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamTensors* __r
 __global__ __launch_bounds__(256) void grads_nonfinite_kernel(const AdamTensors* __restrict__ table, const long* __restrict__ sizes,
                                                               const int* __restrict__ chunk_tid, const long* __restrict__ chunk_off,
                                                               int chunk, float* __restrict__ found) {
-    const int c = blockIdx.x;
-    const int t = chunk_tid[c];
-    const float* g = table[t].g;
-    const long lo = chunk_off[c];
-    const long hi = min(sizes[t], lo + chunk);
+    const auto [t, T, lo, hi] = table_chunk(table, sizes, chunk_tid, chunk_off, chunk);
+    const float* g = T.g;
     unsigned bad = 0;
     long i0 = lo;
     if ((uintptr_t)(g + lo) % 16 == 0) {
@@ -386,10 +383,8 @@ __global__ __launch_bounds__(256) void grads_norm_partials_kernel(const AdamTens
                                                                   int chunk, int norm_type, float* __restrict__ partials) {
     __shared__ float sh[4];
     const int c = blockIdx.x;
-    const int t = chunk_tid[c];
-    const float* g = table[t].g;
-    const long lo = chunk_off[c];
-    const long hi = min(sizes[t], lo + chunk);
+    const auto [t, T, lo, hi] = table_chunk(table, sizes, chunk_tid, chunk_off, chunk);
+    const float* g = T.g;
     const bool vec = (uintptr_t)(g + lo) % 16 == 0;
     const long n4 = vec ? (hi - lo) / 4 : 0;
     const long i0 = lo + 4 * n4;
@@ -568,20 +563,30 @@ extern "C" int simseg_recall_counts(const int32_t* has_match, const int32_t* ran
     return 0;
 }
 
+// The launch of the four simseg_adamw_multi_step* entry points: `step` is the host's count (bias corrections formed here), or the
+// device counter travels in `amp`; grad_coef selects CLIP.
+static int adamw_multi_launch(const char* who, const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
+                              int64_t n_chunks, int chunk, float beta1, float beta2, float eps, int64_t step, AdamAmp amp, float grad_scale,
+                              const float* grad_coef, void* stream) {
+    if (amp.step_in) SS_CHECK(chunk > 0, "%s: bad chunk", who);
+    else SS_CHECK(step >= 1 && chunk > 0, "%s: bad step/chunk", who);
+    if (n_chunks <= 0) return 0;
+    const float bc1 = amp.step_in ? 1.0f : 1.0f - powf(beta1, (float)step);
+    const float bc2_sqrt = amp.step_in ? 1.0f : sqrtf(1.0f - powf(beta2, (float)step));
+    const auto kernel = grad_coef ? adamw_multi_kernel<true> : adamw_multi_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
+                       (const int*)chunk_tid, (const long*)chunk_off, chunk, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, amp, grad_coef);
+    SS_LAUNCH_CHECK(who);
+    return 0;
+}
+
 extern "C" int simseg_adamw_multi_step(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
                                        int64_t n_chunks, int chunk, float beta1, float beta2, float eps, int64_t step,
                                        float grad_scale, void* stream) {
     SS_HALF_FWD(simseg_adamw_multi_step, table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, step, grad_scale, stream);
     SS_CHECK(table && sizes && chunk_tid && chunk_off, "adamw_multi_step: null pointer");
-    SS_CHECK(step >= 1 && chunk > 0, "adamw_multi_step: bad step/chunk");
-    if (n_chunks <= 0) return 0;
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2 = 1.0f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw_multi_kernel<false>, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
-                       (const int*)chunk_tid, (const long*)chunk_off, chunk, beta1, beta2, eps, bc1, sqrtf(bc2), grad_scale, AdamAmp{},
-                       (const float*)nullptr);
-    SS_LAUNCH_CHECK("adamw_multi_step");
-    return 0;
+    return adamw_multi_launch("adamw_multi_step", table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, step, AdamAmp{},
+                              grad_scale, nullptr, stream);
 }
 
 extern "C" int simseg_adamw_multi_step_clip(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
@@ -590,15 +595,8 @@ extern "C" int simseg_adamw_multi_step_clip(const void* table, const int64_t* si
     SS_HALF_FWD(simseg_adamw_multi_step_clip, table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, step, grad_scale,
                 grad_coef, stream);
     SS_CHECK(table && sizes && chunk_tid && chunk_off && grad_coef, "adamw_multi_step_clip: null pointer");
-    SS_CHECK(step >= 1 && chunk > 0, "adamw_multi_step_clip: bad step/chunk");
-    if (n_chunks <= 0) return 0;
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2 = 1.0f - powf(beta2, (float)step);
-    hipLaunchKernelGGL(adamw_multi_kernel<true>, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
-                       (const int*)chunk_tid, (const long*)chunk_off, chunk, beta1, beta2, eps, bc1, sqrtf(bc2), grad_scale, AdamAmp{},
-                       grad_coef);
-    SS_LAUNCH_CHECK("adamw_multi_step_clip");
-    return 0;
+    return adamw_multi_launch("adamw_multi_step_clip", table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, step, AdamAmp{},
+                              grad_scale, grad_coef, stream);
 }
 
 extern "C" int simseg_adamw_multi_step_amp(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
@@ -607,14 +605,8 @@ extern "C" int simseg_adamw_multi_step_amp(const void* table, const int64_t* siz
     SS_HALF_FWD(simseg_adamw_multi_step_amp, table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, grad_scale, loss_scale,
                 found_inf, step_in, step_out, stream);
     SS_CHECK(table && sizes && chunk_tid && chunk_off && step_in && step_out && step_in != step_out, "adamw_multi_step_amp: null / aliased pointer");
-    SS_CHECK(chunk > 0, "adamw_multi_step_amp: bad chunk");
-    if (n_chunks <= 0) return 0;
-    AdamAmp amp{loss_scale, found_inf, step_in, step_out};
-    hipLaunchKernelGGL(adamw_multi_kernel<false>, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
-                       (const int*)chunk_tid, (const long*)chunk_off, chunk, beta1, beta2, eps, 1.0f, 1.0f, grad_scale, amp,
-                       (const float*)nullptr);
-    SS_LAUNCH_CHECK("adamw_multi_step_amp");
-    return 0;
+    return adamw_multi_launch("adamw_multi_step_amp", table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, 0,
+                              AdamAmp{loss_scale, found_inf, step_in, step_out}, grad_scale, nullptr, stream);
 }
 
 extern "C" int simseg_adamw_multi_step_amp_clip(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
@@ -625,13 +617,8 @@ extern "C" int simseg_adamw_multi_step_amp_clip(const void* table, const int64_t
                 loss_scale, found_inf, step_in, step_out, grad_coef, stream);
     SS_CHECK(table && sizes && chunk_tid && chunk_off && step_in && step_out && step_in != step_out && grad_coef,
              "adamw_multi_step_amp_clip: null / aliased pointer");
-    SS_CHECK(chunk > 0, "adamw_multi_step_amp_clip: bad chunk");
-    if (n_chunks <= 0) return 0;
-    AdamAmp amp{loss_scale, found_inf, step_in, step_out};
-    hipLaunchKernelGGL(adamw_multi_kernel<true>, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
-                       (const int*)chunk_tid, (const long*)chunk_off, chunk, beta1, beta2, eps, 1.0f, 1.0f, grad_scale, amp, grad_coef);
-    SS_LAUNCH_CHECK("adamw_multi_step_amp_clip");
-    return 0;
+    return adamw_multi_launch("adamw_multi_step_amp_clip", table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, 0,
+                              AdamAmp{loss_scale, found_inf, step_in, step_out}, grad_scale, grad_coef, stream);
 }
 
 extern "C" int simseg_grads_nonfinite(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,

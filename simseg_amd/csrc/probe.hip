@@ -6,6 +6,7 @@
 #include <limits.h>
 
 #include "common.h"
+#include "tensor_table.h"
 
 namespace {
 
@@ -254,11 +255,10 @@ __global__ __launch_bounds__(256) void ce_finish_kernel(const float* __restrict_
     }
 }
 
-// ---- LARS over a tensor table ------------------------------------------------------------------------------------------------------
-// table[t] = six 8-byte words {p, g, buf, p16, (float lr, float weight_decay), flags}: fp32 master, fp32 gradient, fp32 momentum buffer
-// (0 when momentum == 0), the 16-bit compute copy to refresh (or 0), the tensor's learning rate and weight decay, and flags: bit 0 =
-// lars_exclude (local lr 1), bit 1 = first step of this tensor (no momentum buffer yet: buf = d).  Chunks as in the AdamW table: chunk c
-// covers [chunk_off[c], chunk_off[c] + chunk) of tensor chunk_tid[c], one block per chunk.
+// ---- LARS over a tensor table (tensor_table.h) ---------------------------------------------------------------------------------------
+// table[t] = {p, g, buf, p16, (float lr, float weight_decay), flags}: fp32 master, fp32 gradient, fp32 momentum buffer (0 when momentum
+// == 0), the 16-bit compute copy to refresh (or 0), the tensor's learning rate and weight decay, and flags: bit 0 = lars_exclude (local
+// lr 1), bit 1 = first step of this tensor (no momentum buffer yet: buf = d).
 struct LarsTensors { float* p; const float* g; float* buf; void* p16; float lr; float wd; long flags; };
 static_assert(sizeof(LarsTensors) == 48, "table rows are six 8-byte words");
 
@@ -269,11 +269,9 @@ __global__ __launch_bounds__(256) void lars_norm_partials_kernel(const LarsTenso
                                                                  int chunk, double* __restrict__ partials) {
     __shared__ double sh[8];
     const int c = blockIdx.x;
-    const int t = chunk_tid[c];
-    const float* p = table[t].p;
-    const float* g = table[t].g;
-    const long lo = chunk_off[c];
-    const long hi = min(sizes[t], lo + chunk);
+    const auto [t, T, lo, hi] = table_chunk(table, sizes, chunk_tid, chunk_off, chunk);
+    const float* p = T.p;
+    const float* g = T.g;
     const bool vec = (((uintptr_t)(p + lo) | (uintptr_t)(g + lo)) % 16) == 0;
     const long n4 = vec ? (hi - lo) / 4 : 0;
     double pp = 0.0, gg = 0.0;
@@ -348,12 +346,11 @@ __global__ __launch_bounds__(256) void lars_multi_kernel(const LarsTensors* __re
                                                          const int* __restrict__ chunk_tid, const long* __restrict__ chunk_off, int chunk,
                                                          const float* __restrict__ local_lr, float momentum, float dampening,
                                                          int nesterov) {
-    const int c = blockIdx.x;
-    const int t = chunk_tid[c];
-    const LarsTensors T = table[t];
+    const auto ch = table_chunk(table, sizes, chunk_tid, chunk_off, chunk);
+    const LarsTensors T = ch.T;      // (plain locals, as in adamw_multi_kernel)
+    const int t = ch.t;
+    const long lo = ch.lo, hi = ch.hi;
     H* p16 = reinterpret_cast<H*>(T.p16);
-    const long lo = chunk_off[c];
-    const long hi = min(sizes[t], lo + chunk);
     const double scale = (double)local_lr[t] * (double)T.lr;
     const double wd = (double)T.wd, mom = (double)momentum, keep = 1.0 - (double)dampening;
     const bool first = (T.flags & 2) != 0;

@@ -915,30 +915,25 @@ def ce_rows(logits, labels, write_grad=True):
     return out3, loss_rows, ranks, dlogits
 
 
-def _lars_tables(tab):
-    return (ptr(tab["table"]), ptr(tab["sizes"]), ptr(tab["tid"]), ptr(tab["coff"]), tab["sizes_host"].ctypes.data, tab["tid_host"].ctypes.data,
-            tab["coff_host"].ctypes.data, int(tab["n_tensors"]), int(tab["n_chunks"]), int(tab["chunk"]))
-
-
 def lars_norm_partials(tab, partials):
-    """partials float64 [n_chunks, 2] <- per chunk {sum p^2, sum g^2} of the tensor table `tab` (simseg_amd.optim.LARS._plan: device tables
-    table / sizes / tid / coff / first, their host copies *_host, n_tensors, n_chunks, chunk)."""
-    if partials.dtype != torch.float64 or partials.numel() < 2 * tab["n_chunks"]:
+    """partials float64 [n_chunks, 2] <- per chunk {sum p^2, sum g^2} of the tensor table `tab` (a simseg_amd.optim.TensorTable with
+    LARS's rows)."""
+    if partials.dtype != torch.float64 or partials.numel() < 2 * tab.n_chunks:
         raise TypeError("lars_norm_partials: partials must be float64 [n_chunks, 2]")
-    call("simseg_lars_norm_partials", *_lars_tables(tab), ptr(partials), stream())
+    call("simseg_lars_norm_partials", *tab.launch_args(host=True), ptr(partials), stream())
     return partials
 
 
 def lars_finish(tab, partials, eta, eps, local_lr):
     """local_lr fp32 [n_tensors] <- eta * |p| / (|g| + weight_decay * |p| + eps) per tensor (1 where a norm is zero or the tensor is
     lars_exclude), from the partials of lars_norm_partials.  No host read."""
-    if local_lr.dtype != torch.float32 or local_lr.numel() < tab["n_tensors"]:
+    if local_lr.dtype != torch.float32 or local_lr.numel() < tab.n_tensors:
         raise TypeError("lars_finish: local_lr must be fp32 [n_tensors]")
-    call("simseg_lars_finish", ptr(tab["table"]), ptr(tab["first"]), tab["first_host"].ctypes.data, ptr(partials), int(tab["n_tensors"]),
-         int(tab["n_chunks"]), float(eta), float(eps), ptr(local_lr), stream())
+    call("simseg_lars_finish", ptr(tab.table), ptr(tab.first), tab.first_host.ctypes.data, ptr(partials), tab.n_tensors, tab.n_chunks,
+         float(eta), float(eps), ptr(local_lr), stream())
     return local_lr
 
 
 def lars_multi_step(tab, local_lr, momentum, dampening, nesterov):
     """The LARS update of every tensor of the table in one launch (masters, momentum buffers and 16-bit copies in place)."""
-    call("simseg_lars_multi_step", *_lars_tables(tab), ptr(local_lr), float(momentum), float(dampening), int(bool(nesterov)), stream())
+    call("simseg_lars_multi_step", *tab.launch_args(host=True), ptr(local_lr), float(momentum), float(dampening), int(bool(nesterov)), stream())

@@ -1,15 +1,16 @@
-"""AdamW on the fused HIP kernel.  Same update rule and hyper-parameters as the reference's torch.optim.AdamW
-(configs/clip/simseg.vit-b.yaml:31-36); state (m, v) is fp32.
+"""The table-driven optimizers: AdamW (torch.optim.AdamW's update rule and hyper-parameters, configs/clip/simseg.vit-b.yaml:31-36; fp32
+state m, v) and LARS, each ONE update launch for every parameter tensor of every param group (the reference's ClipOptimizerHook builds
+one group per parameter, tasks/clip/hooks/optimizer.py:18-36, so "one launch per group" would be ~400 launches).
 
-ONE kernel launch updates every parameter tensor of every param group (the reference's ClipOptimizerHook builds one group per
-parameter, tasks/clip/hooks/optimizer.py:18-36, so "one launch per group" would be ~400 launches): a device table of
-{p, g, m, v, p16, lr, weight_decay} rows is refreshed from pinned host memory each step (gradient tensors are re-allocated by
-autograd, learning rates follow the schedule) without a host-device synchronisation.  The pinned staging buffers form a ring, each
-guarded by an event recorded after its upload, so the host never rewrites a buffer whose asynchronous copy has not executed yet.
-p16 is the bf16 compute copy of the parameter, written by the same kernel and handed to the towers (towers.register_w16), so a
-training step launches no weight-cast kernels.
+Both stand on one TensorTable (device contract: csrc/tensor_table.h): six 8-byte words per tensor - the fp32 master, its gradient, then
+the optimizer's own (state pointers, the 16-bit copy, the (lr, weight_decay) pair, flags) - plus the sizes and the list of CHUNK-element
+chunks, one block each.  The rows are completed in pinned host memory each step (gradient tensors are re-allocated by autograd, learning
+rates follow the schedule) and uploaded without a host-device synchronisation; the pinned buffers form a ring, each guarded by an event
+recorded after its upload, so the host never rewrites a buffer whose asynchronous copy has not executed yet.  The optimizers keep their
+bucketing key, their row layout, their flat state buffers and their launches.  p16 is the 16-bit compute copy of the parameter, written
+by the update kernel and handed to the towers (towers.weights_rewritten), so a training step launches no weight-cast kernels.
 
-Checkpoints use torch.optim.AdamW's state layout ({step, exp_avg, exp_avg_sq} per parameter), so the reference's optimizer
+AdamW checkpoints use torch.optim.AdamW's state layout ({step, exp_avg, exp_avg_sq} per parameter), so the reference's optimizer
 checkpoints (core/hooks/checkpoint.py:14-45) load here and ours load there; the bias-correction step counter travels with them."""
 import contextlib
 import math
@@ -20,10 +21,77 @@ from torch.amp.grad_scaler import OptState
 from torch.optim.optimizer import required
 
 from .lib import call, note_half, ptr, stream
-from .towers import drop_qscaled_copy, drop_split_copy, register_w16
+from .towers import weights_rewritten
 
 CHUNK = 1 << 16
 RING = 4
+
+
+def chunk_lists(sizes, chunk):
+    """-> (tid int32, coff int64, first int32 [len(sizes) + 1]): chunk c covers [coff[c], coff[c] + chunk) of tensor tid[c]; tensor t owns
+    the chunks first[t] .. first[t + 1] - 1 (none when it has no elements)."""
+    tid, coff, first = [], [], [0]
+    for t, n in enumerate(sizes):
+        for c in range(0, n, chunk):
+            tid.append(t); coff.append(c)
+        first.append(len(tid))
+    return np.array(tid, dtype=np.int32), np.array(coff, dtype=np.int64), np.array(first, dtype=np.int32)
+
+
+def pack_lr_wd(lr, wd):
+    """Per-tensor learning rates and weight decays -> the int64 table words that hold them as two float32 (lr in the low half)."""
+    hyper = np.empty((len(lr), 2), dtype=np.float32)
+    hyper[:, 0], hyper[:, 1] = lr, wd
+    return hyper.view(np.int64)[:, 0]
+
+
+class TensorTable:
+    """One bucket's launch plan: what does not change from step to step, and the ring through which each step's rows reach the device.
+    static: int64 [n, 6], the masters' addresses in column 0 and whatever else is fixed; the optimizers add their buffers as attributes."""
+
+    def __init__(self, params, static, chunk=CHUNK):
+        dev = params[0].device
+        self.params, self.ids, self.static = params, tuple(id(p) for p in params), static
+        self.sizes_host = np.array([p.numel() for p in params], dtype=np.int64)
+        self.tid_host, self.coff_host, self.first_host = chunk_lists(self.sizes_host.tolist(), chunk)
+        host = (self.sizes_host, self.tid_host, self.coff_host, self.first_host)
+        self.sizes, self.tid, self.coff, self.first = (torch.from_numpy(a).to(dev) for a in host)
+        self.n_tensors, self.n_chunks, self.chunk = len(params), len(self.tid_host), chunk
+        self.ring = [torch.empty(len(params), 6, dtype=torch.int64).pin_memory() for _ in range(RING)]
+        self.events, self.slot = [None] * RING, 0
+        self.table = torch.empty(len(params), 6, dtype=torch.int64, device=dev)
+
+    def __getitem__(self, name):
+        """plan["n_chunks"]: a field by name, as when the plans were dicts."""
+        return getattr(self, name)
+
+    def matches(self, params):
+        """The same parameter objects, and their storage where it was (.to() and a load with assign swap it)."""
+        return self.ids == tuple(id(p) for p in params) and all(p.data_ptr() == a for p, a in zip(params, self.static[:, 0]))
+
+    def upload(self, grads, columns, stream=None):
+        """This step's rows = static + the gradients' addresses (column 1) + columns {index: values}, copied on `stream` (default: the
+        current one) without a synchronisation.  grads are kept alive: the kernels read them asynchronously."""
+        slot = self.slot
+        self.slot = (slot + 1) % RING
+        if self.events[slot] is not None:
+            self.events[slot].synchronize()          # the upload that last used this pinned buffer has executed (RING steps ago)
+        host = self.ring[slot].numpy()
+        host[:] = self.static
+        host[:, 1] = [g.data_ptr() for g in grads]
+        for col, values in columns.items():
+            host[:, col] = values
+        with (torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext()):
+            self.table.copy_(self.ring[slot], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+        self.events[slot] = ev
+        self.keepalive = grads
+
+    def launch_args(self, host=False):
+        """The leading arguments of every entry point over the table (host=True: of those that check the host copies first)."""
+        mid = (self.sizes_host.ctypes.data, self.tid_host.ctypes.data, self.coff_host.ctypes.data, self.n_tensors) if host else ()
+        return (ptr(self.table), ptr(self.sizes), ptr(self.tid), ptr(self.coff)) + mid + (self.n_chunks, self.chunk)
 
 
 def norm_type_code(norm_type):
@@ -80,11 +148,10 @@ class AdamW(torch.optim.Optimizer):
         self._plans.clear()
         self._prepared = None
 
-    # ---- launch plan: everything about a set of tensors that does not change from step to step ------------------------------
+    # ---- launch plan: row = {p, g, m, v, p16, (lr, weight_decay)} ------------------------------------------------------------
     def _plan(self, key, params):
-        ids = tuple(id(p) for p in params)
         plan = self._plans.get(key)
-        if plan is not None and plan["ids"] == ids:
+        if plan is not None and plan.matches(params):
             return plan
         dev = params[0].device
         total = sum(p.numel() for p in params)
@@ -106,21 +173,12 @@ class AdamW(torch.optim.Optimizer):
             n = p.numel()
             self.state[p]["p16"] = p16[o:o + n].view_as(p)
             o += n
-        tid, coff = [], []
-        for t, p in enumerate(params):
-            for c in range(0, p.numel(), CHUNK):
-                tid.append(t); coff.append(c)
         static = np.zeros((len(params), 6), dtype=np.int64)
         for t, p in enumerate(params):
             st = self.state[p]
             static[t, 0], static[t, 2], static[t, 3], static[t, 4] = p.data_ptr(), st["m"].data_ptr(), st["v"].data_ptr(), st["p16"].data_ptr()
-        plan = dict(ids=ids, m=m, v=v, p16=p16, static=static, p16_filled=False,
-                    sizes=torch.tensor([p.numel() for p in params], dtype=torch.int64, device=dev),
-                    tid=torch.tensor(tid, dtype=torch.int32, device=dev), coff=torch.tensor(coff, dtype=torch.int64, device=dev),
-                    ring=[torch.empty(len(params), 6, dtype=torch.int64).pin_memory() for _ in range(RING)],
-                    events=[None] * RING, slot=0,
-                    table=torch.empty(len(params), 6, dtype=torch.int64, device=dev), n_chunks=len(tid))
-        self._plans[key] = plan
+        plan = self._plans[key] = TensorTable(params, static)
+        plan.m, plan.v, plan.p16, plan.p16_filled, plan.stream = m, v, p16, False, None
         return plan
 
     def _prepare(self, on_own=True):
@@ -143,34 +201,16 @@ class AdamW(torch.optim.Optimizer):
             if any(not p.is_contiguous() or p.dtype != torch.float32 for p in params):
                 raise TypeError("simseg_amd AdamW expects contiguous fp32 master parameters")
             plan = self._plan(key, params)
-            if any(p.data_ptr() != a for p, a in zip(params, plan["static"][:, 0])):       # storage swapped (.to(), load with assign)
-                self._plans.pop(key)
-                plan = self._plan(key, params)
             grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in params]
-            plan["stream"] = self._streams.get(id(params[0])) if (len(key) > 3 and on_own) else None      # where this step's upload + launch go
-            slot = plan["slot"]
-            plan["slot"] = (slot + 1) % RING
-            if plan["events"][slot] is not None:
-                plan["events"][slot].synchronize()          # the upload that last used this pinned buffer has executed (RING steps ago)
-            host = plan["ring"][slot].numpy()
-            host[:] = plan["static"]
-            host[:, 1] = [g.data_ptr() for g in grads]
-            hyper = np.empty((len(params), 2), dtype=np.float32)
-            hyper[:, 0] = [it[1] for it in items]
-            hyper[:, 1] = [it[2] for it in items]
-            host[:, 5] = hyper.view(np.int64)[:, 0]
-            with (torch.cuda.stream(plan["stream"]) if plan["stream"] is not None else contextlib.nullcontext()):
-                if not plan["p16_filled"]:
-                    # a new plan's 16-bit copies start as the masters' values: a skipped AMP step (overflow) writes nothing, yet step()
-                    # hands the copies to the towers.  Once per plan, on the stream the kernel is launched on (ordered before its writes).
+            plan.stream = self._streams.get(id(params[0])) if (len(key) > 3 and on_own) else None      # where this step's upload + launch go
+            if not plan.p16_filled:
+                # a new plan's 16-bit copies start as the masters' values: a skipped AMP step (overflow) writes nothing, yet step()
+                # hands the copies to the towers.  Once per plan, on the stream the kernel is launched on (ordered before its writes).
+                with (torch.cuda.stream(plan.stream) if plan.stream is not None else contextlib.nullcontext()):
                     for p in params:
                         self.state[p]["p16"].copy_(p.detach())
-                    plan["p16_filled"] = True
-                plan["table"].copy_(plan["ring"][slot], non_blocking=True)      # (on the stream the kernel is launched on)
-                ev = torch.cuda.Event()
-                ev.record()
-            plan["events"][slot] = ev
-            plan["keepalive"] = grads        # the kernels read them asynchronously
+                plan.p16_filled = True
+            plan.upload(grads, {5: pack_lr_wd([it[1] for it in items], [it[2] for it in items])}, plan.stream)
             ready.append((key, plan, params))
         self._prepared = (grads_now, ready)
         return ready
@@ -181,17 +221,16 @@ class AdamW(torch.optim.Optimizer):
         read-only launch per bucket over this optimizer's tensor table (simseg_amd.optim.GradScaler calls it instead of torch's
         read-modify-write pass over every gradient tensor)."""
         for key, plan, params in self._prepare(on_own=False):
-            call("simseg_grads_nonfinite", ptr(plan["table"]), ptr(plan["sizes"]), ptr(plan["tid"]), ptr(plan["coff"]), plan["n_chunks"], CHUNK,
-                 ptr(found_inf), stream())
+            call("simseg_grads_nonfinite", *plan.launch_args(), ptr(found_inf), stream())
         return found_inf
 
     # ---- global gradient norm / clipping over the same tables ---------------------------------------------------------------
     def _norm_pass(self, code, max_norm, loss_scale, row):
         """One read-only launch per bucket into one partials buffer, one finish: _norm_out[row] = {norm, min(1, max_norm / (norm + 1e-6))}."""
         ready = self._prepare(on_own=False)       # every bucket on the current stream: the norm needs them all
-        total = sum(plan["n_chunks"] for _, plan, _ in ready)
+        total = sum(plan.n_chunks for _, plan, _ in ready)
         if self._norm_out is None or self._norm_partials.numel() < total:     # (with the plans: the first call, or a re-plan that grew)
-            dev = ready[0][1]["table"].device if ready else self.param_groups[0]["params"][0].device
+            dev = ready[0][1].table.device if ready else self.param_groups[0]["params"][0].device
             self._norm_partials = torch.empty(max(total, 1), device=dev, dtype=torch.float32)
             if self._norm_out is None:
                 self._norm_out = torch.zeros(2, 2, device=dev, dtype=torch.float32)
@@ -199,9 +238,8 @@ class AdamW(torch.optim.Optimizer):
             raise TypeError("loss_scale: a float32 tensor on the device (torch.amp.GradScaler's scale: optim.live_scale)")
         first = 0
         for key, plan, params in ready:
-            call("simseg_grads_norm_partials", ptr(plan["table"]), ptr(plan["sizes"]), ptr(plan["tid"]), ptr(plan["coff"]), plan["n_chunks"], CHUNK,
-                 code, ptr(self._norm_partials[first:]), stream())
-            first += plan["n_chunks"]
+            call("simseg_grads_norm_partials", *plan.launch_args(), code, ptr(self._norm_partials[first:]), stream())
+            first += plan.n_chunks
         call("simseg_grads_norm_finish", ptr(self._norm_partials), first, code, float(max_norm), ptr(loss_scale), ptr(self._norm_out[row]), stream())
         return ready
 
@@ -232,7 +270,7 @@ class AdamW(torch.optim.Optimizer):
             raise RuntimeError(f"The total norm of order {float(norm_type)} for gradients from `parameters` is non-finite, so it cannot be clipped.")
         if materialize:
             for key, plan, params in ready:
-                for p, g in zip(params, plan["keepalive"]):
+                for p, g in zip(params, plan.keepalive):
                     call("simseg_scale_by_scalar", ptr(g), ptr(coef), ptr(g), g.numel(), 1.0, stream())
                     if g is not p.grad:               # (a non-contiguous gradient: the table addresses a contiguous copy)
                         p.grad.copy_(g)
@@ -283,7 +321,7 @@ class AdamW(torch.optim.Optimizer):
         self._prepared = None
         if amp:
             if self._step_dev is None:       # the device counter takes over from the host one
-                dev = ready[0][1]["table"].device if ready else torch.device("cuda")
+                dev = ready[0][1].table.device if ready else torch.device("cuda")
                 self._step_dev = torch.full((2,), float(self._step), device=dev, dtype=torch.float32)
                 self._amp_calls = 0
             for t in (loss_scale, found_inf):
@@ -294,27 +332,18 @@ class AdamW(torch.optim.Optimizer):
                 self._step = self.steps_taken()
                 self._step_dev = None
             self._step += 1
+        name = "simseg_adamw_multi_step" + ("_amp" if amp else "") + ("_clip" if coef is not None else "")
         for key, plan, params in ready:
-          own = plan.get("stream")
-          with (torch.cuda.stream(own) if own is not None else contextlib.nullcontext()):
-              note_half(self.half_dtype)        # (the 16-bit copies are addressed through the table: tell the binding which flavour they are)
-              if amp:
-                  cur = self._amp_calls & 1
-                  tail = (ptr(coef), stream()) if coef is not None else (stream(),)
-                  call("simseg_adamw_multi_step_amp_clip" if coef is not None else "simseg_adamw_multi_step_amp", ptr(plan["table"]),
-                       ptr(plan["sizes"]), ptr(plan["tid"]), ptr(plan["coff"]), plan["n_chunks"],
-                       CHUNK, key[0], key[1], key[2], float(grad_scale), ptr(loss_scale), ptr(found_inf), ptr(self._step_dev[cur:cur + 1]),
-                       ptr(self._step_dev[1 - cur:2 - cur]), *tail)
-              elif coef is not None:
-                  call("simseg_adamw_multi_step_clip", ptr(plan["table"]), ptr(plan["sizes"]), ptr(plan["tid"]), ptr(plan["coff"]), plan["n_chunks"],
-                       CHUNK, key[0], key[1], key[2], self._step, float(grad_scale), ptr(coef), stream())
-              else:
-                  call("simseg_adamw_multi_step", ptr(plan["table"]), ptr(plan["sizes"]), ptr(plan["tid"]), ptr(plan["coff"]), plan["n_chunks"],
-                       CHUNK, key[0], key[1], key[2], self._step, float(grad_scale), stream())
-              for p in params:                 # same stream as the next forward: the copies are current when it runs
-                  register_w16(p, self.state[p]["p16"])
-                  drop_split_copy(p)           # the exact-mode split-bf16 copy of the OLD value (raw-pointer update: _version did not move)
-                  drop_qscaled_copy(p)         # the same for the folded q-scaled qkv copy (weight and bias)
+            with (torch.cuda.stream(plan.stream) if plan.stream is not None else contextlib.nullcontext()):
+                note_half(self.half_dtype)        # (the 16-bit copies are addressed through the table: tell the binding which flavour they are)
+                if amp:
+                    cur = self._amp_calls & 1
+                    own = (float(grad_scale), ptr(loss_scale), ptr(found_inf), ptr(self._step_dev[cur:cur + 1]), ptr(self._step_dev[1 - cur:2 - cur]))
+                else:
+                    own = (self._step, float(grad_scale))
+                call(name, *plan.launch_args(), *key[:3], *own, *((ptr(coef),) if coef is not None else ()), stream())
+                for p in params:                 # same stream as the next forward: the copies are current when it runs
+                    weights_rewritten(p, self.state[p]["p16"])
         if amp and ready:
             self._amp_calls += 1             # (several buckets: every launch of this call read the same slot and wrote the other; a call
                                              #  with no gradient at all launched nothing - the other slot was not written, so do not flip)
@@ -393,9 +422,8 @@ class LARS(torch.optim.Optimizer):
     and the update itself, which also refreshes the 16-bit compute copies the towers read (as AdamW's kernel does).  Parameters are
     bucketed by (momentum, dampening, nesterov, eta); lr, weight_decay and lars_exclude travel per tensor in the table.
 
-    The table is planned once per parameter set (the way AdamW._plan does it) and refreshed from a ring of pinned buffers each step
-    (gradient pointers, learning rates, first-step flags).  Optimizer checkpoints use torch's layout with `momentum_buffer`, so they load
-    into the reference's LARS and the reference's load here."""
+    Each step refreshes the table's gradient pointers, learning rates and first-step flags.  Optimizer checkpoints use torch's layout
+    with `momentum_buffer`, so they load into the reference's LARS and the reference's load here."""
 
     def __init__(self, params, lr=required, momentum=0, weight_decay=0, dampening=0, eta=0.001, nesterov=False, eps=1e-8,
                  half_dtype=torch.bfloat16):
@@ -421,11 +449,10 @@ class LARS(torch.optim.Optimizer):
         for group in self.param_groups:
             group.setdefault("nesterov", False)
 
-    # ---- launch plan: everything about a set of tensors that does not change from step to step ------------------------------
+    # ---- launch plan: row = {p, g, momentum buffer, p16, (lr, weight_decay), flags} --------------------------------------------
     def _plan(self, key, params):
-        ids = tuple(id(p) for p in params)
         plan = self._plans.get(key)
-        if plan is not None and plan["ids"] == ids and all(p.data_ptr() == a for p, a in zip(params, plan["static"][:, 0])):
+        if plan is not None and plan.matches(params):
             return plan
         dev = params[0].device
         starts, o = [], 0
@@ -437,7 +464,8 @@ class LARS(torch.optim.Optimizer):
         buf = torch.zeros(total, device=dev, dtype=torch.float32) if use_buf else None
         p16 = torch.empty(total, device=dev, dtype=self.half_dtype)
         views = []
-        for p, o in zip(params, starts):
+        static = np.zeros((len(params), 6), dtype=np.int64)
+        for t, (p, o) in enumerate(zip(params, starts)):
             st, n = self.state[p], p.numel()
             if use_buf:
                 view = buf[o:o + n].view_as(p)
@@ -447,30 +475,16 @@ class LARS(torch.optim.Optimizer):
                 views.append(view)                # (handed to the state after the tensor's first step: the reference has no buffer before)
             st["p16"] = p16[o:o + n].view_as(p)
             st["p16"].copy_(p.detach())
-        tid, coff, first = [], [], [0]
-        for t, p in enumerate(params):
-            for c in range(0, p.numel(), CHUNK):
-                tid.append(t); coff.append(c)
-            first.append(len(tid))
-        static = np.zeros((len(params), 6), dtype=np.int64)
-        for t, p in enumerate(params):
-            static[t, 0], static[t, 3] = p.data_ptr(), self.state[p]["p16"].data_ptr()
-            static[t, 2] = views[t].data_ptr() if use_buf else 0
-        host = dict(sizes_host=np.array([p.numel() for p in params], dtype=np.int64), tid_host=np.array(tid, dtype=np.int32),
-                    coff_host=np.array(coff, dtype=np.int64), first_host=np.array(first, dtype=np.int32))
-        plan = dict(ids=ids, buf=buf, p16=p16, views=views, static=static, n_tensors=len(params), n_chunks=len(tid), chunk=CHUNK, **host,
-                    sizes=torch.from_numpy(host["sizes_host"]).to(dev), tid=torch.from_numpy(host["tid_host"]).to(dev),
-                    coff=torch.from_numpy(host["coff_host"]).to(dev), first=torch.from_numpy(host["first_host"]).to(dev),
-                    partials=torch.empty(max(len(tid), 1), 2, device=dev, dtype=torch.float64),
-                    local_lr=torch.empty(len(params), device=dev, dtype=torch.float32),
-                    ring=[torch.empty(len(params), 6, dtype=torch.int64).pin_memory() for _ in range(RING)], events=[None] * RING, slot=0,
-                    table=torch.empty(len(params), 6, dtype=torch.int64, device=dev))
-        self._plans[key] = plan
+            static[t, 0], static[t, 2], static[t, 3] = p.data_ptr(), (view.data_ptr() if use_buf else 0), st["p16"].data_ptr()
+        plan = self._plans[key] = TensorTable(params, static)
+        plan.buf, plan.p16, plan.views = buf, p16, views
+        plan.partials = torch.empty(max(plan.n_chunks, 1), 2, device=dev, dtype=torch.float64)
+        plan.local_lr = torch.empty(len(params), device=dev, dtype=torch.float32)
         return plan
 
     def local_lrs(self):
         """{parameter: its local learning rate of the last step} as 0-dim fp32 device tensors (views; the next step overwrites them)."""
-        return {p: plan["local_lr"][t] for plan in self._plans.values() for t, p in enumerate(plan["params"])}
+        return {p: plan.local_lr[t] for plan in self._plans.values() for t, p in enumerate(plan.params)}
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -491,36 +505,18 @@ class LARS(torch.optim.Optimizer):
             if any(not p.is_contiguous() or p.dtype != torch.float32 or not p.is_cuda for p in params):
                 raise TypeError("simseg_amd LARS expects contiguous fp32 master parameters on the device")
             plan = self._plan(key, params)
-            plan["params"] = params
             grads = [p.grad if (p.grad.is_contiguous() and p.grad.dtype == torch.float32) else p.grad.float().contiguous() for p in params]
-            slot = plan["slot"]
-            plan["slot"] = (slot + 1) % RING
-            if plan["events"][slot] is not None:
-                plan["events"][slot].synchronize()          # the upload that last used this pinned buffer has executed (RING steps ago)
-            host = plan["ring"][slot].numpy()
-            host[:] = plan["static"]
-            host[:, 1] = [g.data_ptr() for g in grads]
-            hyper = np.empty((len(params), 2), dtype=np.float32)
-            hyper[:, 0] = [it[1] for it in items]
-            hyper[:, 1] = [it[2] for it in items]
-            host[:, 4] = hyper.view(np.int64)[:, 0]
             use_buf = key[0] != 0.0
-            host[:, 5] = [int(it[3]) | (2 if (use_buf and "momentum_buffer" not in self.state[it[0]]) else 0) for it in items]
-            plan["table"].copy_(plan["ring"][slot], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record()
-            plan["events"][slot] = ev
-            plan["keepalive"] = grads            # the kernels read them asynchronously
-            ops.lars_norm_partials(plan, plan["partials"])
-            ops.lars_finish(plan, plan["partials"], key[3], self.eps, plan["local_lr"])
+            flags = [int(it[3]) | (2 if (use_buf and "momentum_buffer" not in self.state[it[0]]) else 0) for it in items]
+            plan.upload(grads, {4: pack_lr_wd([it[1] for it in items], [it[2] for it in items]), 5: flags})
+            ops.lars_norm_partials(plan, plan.partials)
+            ops.lars_finish(plan, plan.partials, key[3], self.eps, plan.local_lr)
             note_half(self.half_dtype)           # (the 16-bit copies are addressed through the table: tell the binding which flavour they are)
-            ops.lars_multi_step(plan, plan["local_lr"], key[0], key[1], key[2])
+            ops.lars_multi_step(plan, plan.local_lr, key[0], key[1], key[2])
             for t, p in enumerate(params):
                 if use_buf and "momentum_buffer" not in self.state[p]:
-                    self.state[p]["momentum_buffer"] = plan["views"][t]
-                register_w16(p, self.state[p]["p16"])
-                drop_split_copy(p)
-                drop_qscaled_copy(p)
+                    self.state[p]["momentum_buffer"] = plan.views[t]
+                weights_rewritten(p, self.state[p]["p16"])
         return loss
 
     # ---- checkpoints in the reference's layout ---------------------------------------------------------------------------

@@ -23,20 +23,14 @@ BF16, F32 = torch.bfloat16, torch.float32
 _W16 = {}      # id(parameter) -> (weakref(parameter), parameter._version, parameter.data_ptr(), bf16 copy)
 
 
-def register_w16(param, w16):
-    """The optimizer's kernel has just written `w16` = bf16(param) (raw-pointer update: param._version does not move)."""
+def weights_rewritten(param, w16):
+    """An optimizer's kernel has just rewritten `param` and its 16-bit copy `w16` through raw pointers, so neither `param._version` nor
+    `param.data_ptr()` moved and no cache here can see the update by itself: `w16` becomes the current 16-bit copy (_wt), and the copies
+    derived from the OLD value are forgotten - the split-bf16 one of exact-mode evaluation (_wt_split) and the folded q-scaled qkv ones
+    made from it as weight or bias (_wt_qscaled; O(1): their keys are found through _WQS_OF, not by a scan).  The one call an optimizer
+    makes per parameter after its update; a derived cache added here joins this function."""
     _W16[id(param)] = (weakref.ref(param), param._version, param.data_ptr(), w16)
-
-
-def drop_split_copy(param):
-    """Forget the split-bf16 (exact-mode evaluation) copy of a parameter the optimizer's kernel has just rewritten through raw pointers
-    (neither `_version` nor `data_ptr` moves, so `_wt_split`'s own check cannot see the update)."""
     _W3.pop(id(param), None)
-
-
-def drop_qscaled_copy(param):
-    """Forget the folded q-scaled qkv copy (_wt_qscaled) made from a parameter - weight or bias - the optimizer's kernel has just rewritten
-    through raw pointers (same blindness as drop_split_copy).  O(1): the entry's key is found through _WQS_OF, not by a scan."""
     for key in _WQS_OF.pop(id(param), ()):
         _WQS.pop(key, None)
 
@@ -55,7 +49,7 @@ def invalidate_weight_cache():
 def _wt(w, adt):
     """Weight in the activation dtype (bf16 compute copy of the fp32 master, like autocast's per-step cast).  The copy is
     cached per parameter object and reused while the parameter is untouched: torch-side writes bump `_version`, storage
-    swaps change `data_ptr`, and simseg_amd.optim.AdamW refreshes the copy in its own kernel (register_w16)."""
+    swaps change `data_ptr`, and simseg_amd.optim.AdamW refreshes the copy in its own kernel (weights_rewritten)."""
     if adt == F32:
         return w.detach()
     ent = _W16.get(id(w))
@@ -103,7 +97,7 @@ def _wt_split(w):
 
 
 _WQS = {}     # (id(weight), id(bias)) -> (weakref(weight), weakref(bias), versions and data pointers, 16-bit weight, fp32 bias)
-_WQS_OF = {}  # id(weight) / id(bias) -> the _WQS keys made from it (drop_qscaled_copy)
+_WQS_OF = {}  # id(weight) / id(bias) -> the _WQS keys made from it (weights_rewritten)
 
 
 def _wt_qscaled(w, b, adt, D):

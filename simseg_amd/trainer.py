@@ -146,7 +146,6 @@ class Trainer:
         missing, unexpected = self.model.load_state_dict(sd, strict=False)
         if load_optimizer and "optimizer" in state:
             self.optimizer.load_state_dict(state["optimizer"])
-            self.optimizer._plans.clear() if hasattr(self.optimizer, "_plans") else None
         if self.scaler.is_enabled() and state.get("scaler"):
             self.scaler.load_state_dict(state["scaler"])
         meta = state.get("meta", {})

@@ -5,6 +5,7 @@ Tolerances are never taken from the code under test.  Cross-entropy: ranks and c
 deviation of torch's own fp32 cross_entropy (on the device, same rounded inputs) from the float64 result, pooled over every case of this
 file and printed.  LARS: _lars_ref.LARS_TOL, 4 x the deviation of the reference's fp32 trajectories from the float64 restatement (fixed by
 tests/test_linear_probe_host.py).  Model: the same rule with torch's fp32 F.linear + cross_entropy head on the same features."""
+import copy
 import os
 
 import numpy as np
@@ -300,9 +301,9 @@ def test_corrupted_tables_are_refused():
     T, n = plan["n_tensors"], plan["n_chunks"]
 
     def broken(key, idx, val):
-        bad = dict(plan)
-        bad[key] = plan[key].copy()
-        bad[key][idx] = val
+        bad = copy.copy(plan)
+        setattr(bad, key, getattr(plan, key).copy())
+        getattr(bad, key)[idx] = val
         return bad
 
     for key, idx, val, what in [("tid_host", 0, T, "tensor id"), ("tid_host", n - 1, -1, "tensor id"), ("sizes_host", 2, -5, "negative size"),

@@ -113,9 +113,9 @@ def main():
     med = {}
     for name, _ in routes:
         dev = [d for d, _ in res[name]]
-        host = statistics.median(h for _, h in res[name])
+        host = [h for _, h in res[name]]
         med[name] = statistics.median(dev)
-        say(f"{name:38s} {med[name]:8.3f} ms [{min(dev):.3f} .. {max(dev):.3f}]   host {host:.3f} ms")
+        say(f"{name:38s} {med[name]:8.3f} ms [{min(dev):.3f} .. {max(dev):.3f}]   host {statistics.median(host):.3f} ms [{min(host):.3f} .. {max(host):.3f}]")
     (na, _), (nb, _), (nc, _) = routes
     say()
     say(f"(b) - (a) = {med[nb] - med[na]:.3f} ms: the norm pass and the finish ({4 * n / 1e6:.0f} MB read once: "

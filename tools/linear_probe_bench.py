@@ -141,9 +141,9 @@ def main():
     med = {}
     for name, _ in routes:
         dev = [d for d, _ in res[name]]
-        host = statistics.median(hh for _, hh in res[name])
+        host = [hh for _, hh in res[name]]
         med[name] = statistics.median(dev)
-        say(f"{name:40s} {med[name]:8.3f} ms [{min(dev):.3f} .. {max(dev):.3f}]   host {host:.3f} ms")
+        say(f"{name:40s} {med[name]:8.3f} ms [{min(dev):.3f} .. {max(dev):.3f}]   host {statistics.median(host):.3f} ms [{min(host):.3f} .. {max(host):.3f}]")
     names = [n for n, _ in routes]
     say()
     say(f"head: HIP {med[names[1]]:.3f} ms vs torch ops {med[names[3]]:.3f} ms;  LARS: HIP {med[names[2]]:.3f} ms vs torch loop {med[names[4]]:.3f} ms;  "
