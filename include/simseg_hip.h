@@ -71,6 +71,16 @@ int simseg_set_gemm_variant(int v);
 /* Which of those kernels (1 / 2 / 3 / 4) the calling thread's last simseg_gemm launched. */
 int simseg_gemm_last_variant(void);
 
+/* A transformer block's split-K weight gradients as ONE launch of the 256x256 ping-pong kernel: n (1..8) problems
+ * dW_i[out_i, in_i] += dY_i^T . X_i, dY_i [rows, out_i] and X_i [rows, in_i] in the selected 16-bit type, dW_i fp32 (zero-filled or holding
+ * a partial sum), all over the same `rows`, each cut into the same `slices` K-slices.  problems: n host-side records of 8 x int64
+ * {dY, X, dW, out, in, ld_dY, ld_X, ld_dW}.  Eligible when every out_i / in_i is a multiple of 256, rows % 64 == 0, the operands are
+ * 16-byte aligned and rows / 64 / slices >= 16; otherwise nothing is launched, the call still returns 0, and simseg_wgrad_group_last()
+ * reads 0 - the caller then issues per-problem simseg_gemm calls.  After a grouped launch simseg_gemm_last_variant() reads 3. */
+int simseg_gemm_wgrad_group(const int64_t* problems, int n, int64_t rows, int slices, void* stream);
+/* How many problems the calling thread's last simseg_gemm_wgrad_group launched as one group (0 = it fell back). */
+int simseg_wgrad_group_last(void);
+
 /* LayerNorm over the last dim of x[rows,D] (fp32 residual stream) -> y (out_dtype) and optionally a bf16 copy.
  * Saves mean/rstd when non-null.  Replaces nn.LayerNorm in timm Block.norm1/norm2/VisionTransformer.norm
  * (eps 1e-6) and HF Bert*Output.LayerNorm / BertEmbeddings.LayerNorm (eps 1e-12). */

@@ -21,6 +21,7 @@
 // LDS rows are padded (144 B pitch for k-contiguous tiles, 320 B for transposed tiles) so that the
 // ds_read_b128 / ds_read_b64_tr_b16 fragment fetches are bank-conflict free.
 #include "common.h"
+#include <type_traits>
 
 // Epilogue ablation switches of tools/dbg_fc1_epilogue.py (skip the GELU' store / the GELU itself / the output store through
 // simseg_debug_gemm_stagger(1001..1003)) exist only in builds made with -DSS_GEMM_ABLATE: in the shipped library a left-over debug value
@@ -1197,6 +1198,47 @@ __device__ __forceinline__ void pp_epilogue_f32_direct(const GemmParams& p, cons
     }
 }
 
+// Split-K partial of a full tile, added from the accumulators where they lie: one atomic instruction covers 32 consecutive floats of two
+// rows (a half-wave each), against 64 floats of one row on the staged path - the same number of instructions, without the LDS round trip.
+__device__ __forceinline__ void pp_epilogue_atomic_direct(const GemmParams& p, const f32x16 (&acc)[4][2], int m0, int c0, int c1, int grp, int lane) {
+    const int cl = lane & 31, h2 = lane >> 5;
+    float* Cf = reinterpret_cast<float*>(p.C);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        float* Cr = Cf + (long)(m0 + (i >> 1) * 128 + grp * 64 + (i & 1) * 32 + 4 * h2) * p.ldc + cl;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+            float* Ce = Cr + (long)((e & 3) + 8 * (e >> 2)) * p.ldc;
+            atomicAdd(Ce + c0, acc[i][0][e] * p.alpha);
+            atomicAdd(Ce + c1, acc[i][1][e] * p.alpha);
+        }
+    }
+}
+
+// ---- grouped split-K weight gradients --------------------------------------------------------------------------
+// The four weight gradients of a transformer block (dW_i[out_i, in_i] += dY_i^T . X_i) contract over the same rows on the same 256x256
+// tile, so a (tile, slice) block costs the same whichever matrix it belongs to: ONE launch walks the concatenated tile lists with one
+// common slice count.  For ViT-B / BERT-base that is 108 tiles x 7 slices = 756 blocks (2.95 rounds of 256) in place of four one-round
+// launches of ~250 blocks each: no launch boundary inside the group, at most 7 concurrent adders per output tile (proj had 28), and 756
+// instead of 999 accumulator tiles added per block.  Blocks are ordered problem-major, slice-major, tile-minor, so a slice's tiles still
+// sit next to each other in one XCD's chunk.  No flags, no spinning, no order between blocks.
+constexpr int WG_MAX = 8;
+struct WgradProblem {
+    const void* dy; const void* x; float* dw;      // dY [rows, out], X [rows, in] (16-bit), dW [out, in] (fp32)
+    long ld_dy, ld_x, ld_dw;
+    int out, in;
+};
+struct WgradGroupParams {
+    WgradProblem prob[WG_MAX];
+    int first[WG_MAX + 1];                          // first[i] = blocks before problem i = slices * (tiles of problems 0..i-1); first[n] = all
+    int n, rows, ksplit, nsplit;
+    unsigned long long* dbg_trace;
+};
+
+// the block's problem: the kernel argument itself, or the grouped launch's problem descriptor unpacked into `own`
+__device__ __forceinline__ const GemmParams& pp_params(const GemmParams& arg, const GemmParams&) { return arg; }
+__device__ __forceinline__ const GemmParams& pp_params(const WgradGroupParams&, const GemmParams& own) { return own; }
+
 // PP_LEAD: half-tiles in flight ahead of the phase that reads them (3..5; the ring of two K-tiles allows up to 6).  PRIO: 1 = raise the
 // wave priority around every MFMA cluster, 2 = static priority for the second group only, 0 = none.  Measured (tools/gemm_bench.py,
 // r2): LEAD 3 / 4 / 5 and PRIO 0 / 1 / 2 are all within run-to-run noise (+-2 %) on the training shapes and on 4096^3 / 8192^3.
@@ -1205,15 +1247,42 @@ __device__ __forceinline__ void pp_epilogue_f32_direct(const GemmParams& p, cons
 // phase Y reads A half 1 (8 reads), stages B half 0 / A half 0 / B half 1 of the K-tile after next (6 copies: those slots were last read
 // in phase X) and multiplies A half 1 by both B halves.  Every half-tile is requested two phases (one K-tile) before it is read;
 // vmcnt(8) in every phase.  Half as many barrier pairs per MFMA.
-template <typename TO, bool TA, bool TB, int PP_LEAD = 4, int PRIO = 1, int BIG = 0, int EK = 1>
-__global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p) {
+// GROUPED: the argument is a WgradGroupParams and only the front differs - the block finds its problem, then its (slice, tile) in it.
+// ATOMIC_DIRECT (grouped launches): the split-K adds of a full tile are issued from the accumulators in the MFMA layout
+// (pp_epilogue_atomic_direct) instead of through the staged epilogue.
+template <typename TO, bool TA, bool TB, int PP_LEAD = 4, int PRIO = 1, int BIG = 0, int EK = 1, bool GROUPED = false, bool ATOMIC_DIRECT = false>
+__global__ __launch_bounds__(512, 2) void gemm_pp_kernel(typename std::conditional<GROUPED, WgradGroupParams, GemmParams>::type arg) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
+    GemmParams own;
+    int gkz = 0, gt = 0;
+    if constexpr (GROUPED) {
+        const int gq = xcd_remap(blockIdx.x, gridDim.x);
+        if (gq >= arg.first[arg.n]) return;                          // (a padded grid: before the first barrier)
+        int i = 0;
+#pragma unroll
+        for (int j = 1; j < WG_MAX; ++j)
+            if (j < arg.n && gq >= arg.first[j]) i = j;
+        const WgradProblem& w = arg.prob[i];
+        own = GemmParams{};
+        own.A = w.dy; own.B = w.x; own.C = w.dw;
+        own.M = w.out; own.N = w.in; own.K = arg.rows;
+        own.lda = w.ld_dy; own.ldb = w.ld_x; own.ldc = w.ld_dw;
+        own.alpha = 1.0f;
+        own.accumulate = 1;
+        own.ksplit = arg.ksplit; own.nsplit = arg.nsplit;
+        own.dbg_trace = arg.dbg_trace;
+        const int gtiles = (w.out >> 8) * (w.in >> 8);
+        const int r = gq - arg.first[i];
+        gkz = r / gtiles;
+        gt = r - gkz * gtiles;
+    }
+    const GemmParams& p = pp_params(arg, own);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int grp = wave >> 2, wn = wave & 3;
     const int tiles_n = (p.N + 255) / 256;
     const int tiles = tiles_n * ((p.M + 255) / 256);
     const int q = xcd_remap(blockIdx.x, gridDim.x);
-    const int kz = q / tiles, t = q - kz * tiles;
+    const int kz = GROUPED ? gkz : q / tiles, t = GROUPED ? gt : q - kz * tiles;
     const int m0 = (t / tiles_n) * 256, n0 = (t % tiles_n) * 256;
     const int nk = p.K / 64;
     const int kt0 = kz * p.ksplit;
@@ -1421,6 +1490,18 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(GemmParams p) {
         if (direct) {
             pp_epilogue_f32_direct(p, acc, m0, c0, c1, grp, lane);
             if (pf_ok) wait_vm<63>();                                // 128 stores behind the tail's copies
+            if (p.dbg_trace && tid == 0) {
+                const unsigned long long tr3 = wall_clock64();
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                unsigned long long* d = p.dbg_trace + (long)blockIdx.x * 5;
+                d[0] = tr0; d[1] = tr1; d[2] = tr2; d[3] = wall_clock64(); d[4] = tr3;
+            }
+            return;
+        }
+    }
+    if constexpr (ATOMIC_DIRECT && sizeof(TO) == 4) {
+        if (atomic && !p.dbg_skip_epilogue && m0 + 256 <= p.M && n0 + 256 <= p.N) {
+            pp_epilogue_atomic_direct(p, acc, m0, c0, c1, grp, lane);
             if (p.dbg_trace && tid == 0) {
                 const unsigned long long tr3 = wall_clock64();
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2068,6 +2149,66 @@ extern "C" int simseg_patch_text_sim(const void* x, const void* text, float* out
 extern "C" int simseg_gemm_aux_blocked_ok(int64_t M, int64_t N, int64_t K) {
     if (M <= 0 || N <= 0 || K <= 0 || M % 256 || N % 256 || K % 64 || K < 768) return 0;
     return (M / 256) * (N / 256) >= 96;
+}
+
+// How many problems the calling thread's last simseg_gemm_wgrad_group launched as one group (0: not eligible, nothing launched).
+static thread_local int g_wgrad_group_last = 0;
+extern "C" int simseg_wgrad_group_last(void) {
+    SS_HALF_FWD(simseg_wgrad_group_last); return g_wgrad_group_last; }
+
+// n problems dW_i[out_i, in_i] += dY_i^T . X_i over the same `rows` in ONE split-K launch (gemm_pp_kernel<..., GROUPED>).  problems: n records of
+// 8 x int64 {dY, X, dW, out, in, ld_dY, ld_X, ld_dW} in host memory.  Returns 0 and launches nothing when the group is not eligible
+// (simseg_wgrad_group_last() then reads 0 and the caller issues per-problem simseg_gemm calls), -1 on a bad argument.
+extern "C" int simseg_gemm_wgrad_group(const int64_t* problems, int n, int64_t rows, int slices, void* stream) {
+    SS_HALF_FWD(simseg_gemm_wgrad_group, problems, n, rows, slices, stream);
+    g_wgrad_group_last = 0;
+    SS_CHECK(problems && n >= 1 && n <= WG_MAX, "simseg_gemm_wgrad_group: 1..%d problems", WG_MAX);
+    SS_CHECK(rows > 0 && rows < (1ll << 31) && slices >= 1, "simseg_gemm_wgrad_group: bad rows %lld / slices %d", (long long)rows, slices);
+    if (rows % 64 != 0) return 0;
+    const int nk = (int)(rows / 64);
+    if (nk / slices < 16) return 0;                                  // the minimum slice depth of the per-problem dispatch
+    WgradGroupParams g;
+    memset(&g, 0, sizeof(g));
+    g.ksplit = (nk + slices - 1) / slices;
+    g.nsplit = (nk + g.ksplit - 1) / g.ksplit;                       // (as launch_pp: no empty last slice)
+    long blocks = 0;
+    for (int i = 0; i < n; ++i) {
+        const int64_t* d = problems + 8 * i;
+        WgradProblem& w = g.prob[i];
+        SS_CHECK(d[0] && d[1] && d[2], "simseg_gemm_wgrad_group: null operand in problem %d", i);
+        const int64_t out = d[3], in = d[4];
+        if (out <= 0 || in <= 0 || out % 256 || in % 256 || out >= (1ll << 31) || in >= (1ll << 31)) return 0;
+        if (d[5] < out || d[6] < in || d[7] < in || d[5] % 8 || d[6] % 8 || d[7] % 4) return 0;
+        if ((uintptr_t)d[0] % 16 || (uintptr_t)d[1] % 16 || (uintptr_t)d[2] % 16) return 0;
+        // the kernel's per-lane operand offsets are 32-bit byte offsets inside one K-tile (64 rows)
+        if (64 * d[5] * 2 >= (1ll << 31) || 64 * d[6] * 2 >= (1ll << 31)) return 0;
+        w.dy = (const void*)(uintptr_t)d[0]; w.x = (const void*)(uintptr_t)d[1]; w.dw = (float*)(uintptr_t)d[2];
+        w.out = (int)out; w.in = (int)in; w.ld_dy = d[5]; w.ld_x = d[6]; w.ld_dw = d[7];
+        g.first[i] = (int)blocks;
+        blocks += (out / 256) * (in / 256) * g.nsplit;
+        if (blocks >= (1l << 24)) return 0;
+    }
+    for (int i = n; i <= WG_MAX; ++i) g.first[i] = (int)blocks;
+    g.n = n; g.rows = (int)rows;
+    g.dbg_trace = g_gemm_debug_trace;
+    // the adds from the accumulator layout (median block epilogue 9.1 against 23.9 us on the ViT-B block, 17.0 against 30.0 us on a 21 760-row
+    // text block: profiles/wgrad_group.txt); SIMSEG_GEMM_WGRAD_DIRECT=0: the staged epilogue (A/B runs; process-wide)
+    static const bool direct = !(getenv("SIMSEG_GEMM_WGRAD_DIRECT") && atoi(getenv("SIMSEG_GEMM_WGRAD_DIRECT")) == 0);
+    constexpr int SMEM = 9 * PP_HALF;
+    static bool configured = false;
+    if (!configured) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<float, true, true, 4, 1, 1, 1, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<float, true, true, 4, 1, 1, 1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+        if (e != hipSuccess) return simseg_set_error("simseg_gemm_wgrad_group: cannot reserve %d bytes of LDS: %s", SMEM, hipGetErrorString(e));
+        configured = true;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (direct) hipLaunchKernelGGL((gemm_pp_kernel<float, true, true, 4, 1, 1, 1, true, true>), dim3((unsigned)blocks, 1, 1), dim3(512), SMEM, s, g);
+    else hipLaunchKernelGGL((gemm_pp_kernel<float, true, true, 4, 1, 1, 1, true, false>), dim3((unsigned)blocks, 1, 1), dim3(512), SMEM, s, g);
+    SS_LAUNCH_CHECK("simseg_gemm_wgrad_group");
+    g_gemm_last_variant = 3;
+    g_wgrad_group_last = n;
+    return 0;
 }
 
 // dtype codes: 0 = fp32, 1 = bf16

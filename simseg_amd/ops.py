@@ -1,5 +1,6 @@
 """Tensor-level wrappers over the C ABI (include/simseg_hip.h).  PyTorch supplies device memory and the stream;
 all arithmetic runs in libsimseg_hip.so.  No autograd here (see autograd.py) and no CPU fallback."""
+import ctypes
 import os
 import threading
 
@@ -98,6 +99,83 @@ def gemm(a, b, *, trans_a=False, trans_b=False, out=None, out_dtype=None, alpha=
         kind += {1: "", 2: "_L", 3: "_P", 4: "_S", 5: "_R", 8: "_X", 9: "_Y", 10: "_Q"}[raw("simseg_gemm_last_variant")]      # the kernel the library actually launched
         PROFILE.append((kind, 2.0 * M * N * K, e0, e1))
     return out
+
+
+def gemm_last_variant():
+    return raw("simseg_gemm_last_variant")
+
+
+WGRAD_EPILOGUE_KTILES = 8      # a block's atomic epilogue in units of its K loop's time per K-tile (13-15 us against 1.6-1.8 us, profiles/r4_wgrad_block_timeline.txt)
+
+
+def wgrad_group_plan(tiles, nk, cus=256):
+    """Slice count of a grouped split-K weight-gradient launch: `tiles` = the 256x256 output tiles of each problem, nk = 64-row K-tiles of
+    the shared contraction.  The launch runs ceil(sum(tiles) * sk / cus) rounds of blocks, each ceil(nk / sk) K-tiles of K loop plus one
+    atomic epilogue: the sk that minimises rounds x (K-tiles + WGRAD_EPILOGUE_KTILES), among those that leave a slice at least 16
+    K-tiles (sk = 1 always allowed); ties go to the smaller sk.  (Without the epilogue term the count of K-tiles alone prefers many thin
+    slices - 26 at ViT-B's 1576 K-tiles, 671 against 678 K-tiles per CU - and pays for them with 26 adders per output tile.)"""
+    total = int(sum(tiles))
+    nk = int(nk)
+    best, best_cost = 1, None
+    for sk in range(1, max(1, nk // 16) + 1):
+        cost = -(-total * sk // cus) * (-(-nk // sk) + WGRAD_EPILOGUE_KTILES)
+        if best_cost is None or cost < best_cost:
+            best, best_cost = sk, cost
+    return best
+
+
+_WG_LAST = threading.local()
+
+
+def wgrad_group_last():
+    """How many problems this thread's last wgrad_group() launched as ONE kernel (0: it fell back to per-problem GEMMs)."""
+    return getattr(_WG_LAST, "n", 0)
+
+
+def wgrad_group(problems, slices=None):
+    """dW_i += dy_i^T . x_i for a list of (dy_i [rows, out_i], x_i [rows, in_i], dW_i [out_i, in_i] fp32) over the same rows - a
+    transformer block's weight gradients - as one split-K launch (simseg_gemm_wgrad_group); per-problem split-K GEMMs when the group is
+    not eligible.  slices=None: wgrad_group_plan's choice."""
+    problems = list(problems)
+    if not problems:
+        return
+    rows = problems[0][0].shape[0]
+    ok = 1 <= len(problems) <= 8
+    for dy, x, out in problems:
+        require_gpu(dy, x, out)
+        _c(dy); _c(x); _c(out)
+        if dy.dim() != 2 or x.dim() != 2 or dy.shape[0] != x.shape[0] or tuple(out.shape) != (dy.shape[1], x.shape[1]) or out.dtype != torch.float32:
+            raise ValueError("wgrad_group: need dy [rows, out], x [rows, in] and an fp32 dW [out, in]")
+        if dy.dtype != x.dtype:
+            raise TypeError(f"wgrad_group: operands of different types ({dy.dtype}, {x.dtype})")
+        ok = ok and dy.shape[0] == rows and dy.dtype in HALF_TYPES and dy.dtype == problems[0][0].dtype
+    nk = rows // 64
+    if slices is None:
+        slices = wgrad_group_plan([(dy.shape[1] // 256) * (x.shape[1] // 256) for dy, x, _ in problems], nk)
+    _push_variant("gemm")
+    if PROFILE is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    grouped = 0
+    if ok:
+        desc = []
+        for dy, x, out in problems:
+            desc += [ptr(dy), ptr(x), ptr(out), dy.shape[1], x.shape[1], dy.shape[1], x.shape[1], x.shape[1]]
+        call("simseg_gemm_wgrad_group", (ctypes.c_int64 * len(desc))(*desc), len(problems), rows, int(slices), stream())
+        grouped = raw("simseg_wgrad_group_last")
+    _WG_LAST.n = grouped
+    if not grouped:
+        for dy, x, out in problems:
+            t128 = -(-dy.shape[1] // 128) * -(-x.shape[1] // 128)       # (the slice count the per-problem dispatch is tuned for: 1024 blocks of 128x128)
+            sk = max(1, min(-(-dy.shape[0] // 64), -(-1024 // t128), 64))
+            if dy.dtype == torch.float32:        # (the fp32 kernel is row.row only)
+                gemm(transpose_f32(dy), transpose_f32(x), out=out, accumulate=True, splitk=sk)
+            else:
+                gemm(dy, x, trans_a=True, trans_b=True, out=out, accumulate=True, splitk=sk)
+        return
+    if PROFILE is not None:
+        e1.record()
+        PROFILE.append(("bf16_tn_o32_P", sum(2.0 * dy.shape[1] * x.shape[1] * rows for dy, x, _ in problems), e0, e1))
 
 
 _BLK_OK = {}

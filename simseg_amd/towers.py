@@ -328,6 +328,24 @@ def _wgrad_now(dy, x, out=None):
     return dw
 
 
+# A block's four weight gradients as ONE grouped split-K launch (ops.wgrad_group) after the block's last LayerNorm backward, instead of four
+# launches between the data-gradient kernels: same contraction, same tile, one common slice count - no launch boundary inside the group and
+# fewer concurrent adders per output tile.  16-bit compute with all four gradients wanted and the side stream off; everything else keeps
+# _wgrad.  SIMSEG_AMD_WGRAD_GROUP=0: the per-GEMM launches (A/B runs).
+_WG_GROUP = os.environ.get("SIMSEG_AMD_WGRAD_GROUP", "1") != "0"
+WGRAD_GROUPS = [0]    # grouped launches issued (tests assert that the fast path is the one that runs)
+
+
+def _wgrad_grouped(adt, needs):
+    return _WG_GROUP and not _WG_ON and adt != F32 and all(needs)
+
+
+def _wgrad_flush(group):
+    ops.wgrad_group(group)
+    if ops.wgrad_group_last():
+        WGRAD_GROUPS[0] += 1
+
+
 def _dgrad(d, w_, **kw):
     """dx = d . W for a weight stored [out, in] (nn.Linear layout), with the GEMM epilogue options in kw."""
     if d.dtype == F32:
@@ -583,26 +601,30 @@ class ViTBlockFn(_GradAwareFn):
         (df1b, df2w_z, df1w_z, dn2w, dn2b, dpb, dpw_z, dqw_z, dqb_z, dn1w, dn1b, dsum) = _zeros_or(
             dy.device, (None, tg[0], tg[1], None, None, None, tg[2], tg[3], None, None, None, None),
             (4 * D,), (D, 4 * D), (4 * D, D), (D,), (D,), (D,), (D, D), (3 * D, D), (3 * D,), (D,), (D,), (D,))
+        group = [] if _wgrad_grouped(adt, (need[13], need[11], need[7], need[5])) else None      # (dy, x, zeroed dW) of the deferred weight gradients
+        wg = _wgrad if group is None else (lambda d, x_, z: group.append((d, x_, z)) or z)
         # mlp
         dpre = _dgrad(dy16, f2w_, act=(4, 6, 8)[ctx.blk], aux=pre, colsum=df1b)
-        df2w = _wgrad(dy16, act, df2w_z) if need[13] else None
+        df2w = wg(dy16, act, df2w_z) if need[13] else None
         dln2 = _dgrad(dpre, f1w_)
-        df1w = _wgrad(dpre, ln2, df1w_z) if need[11] else None
+        df1w = wg(dpre, ln2, df1w_z) if need[11] else None
         r16 = adt != F32 and _RES16                           # between this block's two LayerNorm backward kernels: 16 bits only
         dx1_32, dx1_16 = _ln_bwd(adt, x1, mean2, rstd2, n2w, dn2w, dn2b, dln2, dres=None if res16 else dy, dres16=dy16 if res16 else None, dxsum=dpb,
                                  want32=not r16, y16=ln2, beta=n2b)
         # attention
         datt = _dgrad(dx1_16, pw_)
-        dpw = _wgrad(dx1_16, att.view(-1, D), dpw_z) if need[7] else None
+        dpw = wg(dx1_16, att.view(-1, D), dpw_z) if need[7] else None
         dqb = _zeros_like_bias(dqb_z, 3 * D, qkv.device) if need[6] else None       # the qkv bias gradient rides on the attention backward
         dqkv = ops.attention_bwd(qkv.view(B, T, 3 * D), att, datt.view(B, T, D), lse, ctx.heads, None, scale=64 ** -0.5,
                                  colsum=dqb if _FUSED_QKV_BIAS else None).view(-1, 3 * D)
         if dqb is not None and not _FUSED_QKV_BIAS:
             ops.colsum_accum(dqkv, dqb)
         dln1 = _dgrad(dqkv, qw_)
-        dqw = _wgrad(dqkv, ln1.view(-1, D), dqw_z) if need[5] else None
+        dqw = wg(dqkv, ln1.view(-1, D), dqw_z) if need[5] else None
         dx, dx16 = _ln_bwd(adt, x.view(-1, D), mean1, rstd1, n1w, dn1w, dn1b, dln1, dres=None if r16 else dx1_32, dres16=dx1_16 if r16 else None,
                            dxsum=dsum, want32=not ctx.lazy, y16=ln1, beta=n1b)
+        if group:
+            _wgrad_flush(group)
         if dx is None:
             dx = _lazy32((B, T, D), x.device, dx16, dsum)
         else:
@@ -863,16 +885,18 @@ class BertLayerFn(_GradAwareFn):
             (D,), (D,), (D,), (I,), (D, I), (I, D), (D,), (D,), (D,), (D, D), (3 * D, D), (3 * D,))
         ds2_32, d2 = _ln_bwd(adt, s2, mean_o, rstd_o, low, dlow, dlob, None if adt != F32 else dy, dy32=dy if adt != F32 else None,
                              dxsum=do2b, drop=(p, seed + 2))
+        group = [] if _wgrad_grouped(adt, (need[18], need[16], need[12], need[6] or need[8] or need[10])) else None
+        wg = _wgrad if group is None else (lambda d, x_, z: group.append((d, x_, z)) or z)
         dpre = _dgrad(d2, o2w_, act=(4, 6, 8)[ctx.blk], aux=pre, colsum=dib)
-        do2w = _wgrad(d2, act, do2w_z) if need[18] else None
+        do2w = wg(d2, act, do2w_z) if need[18] else None
         # gradient reaching LN_a's output: through the intermediate dense (da) + the residual branch (ds2_32); bf16 mode adds them
         # inside the LayerNorm kernel, exact mode in the GEMM's residual epilogue
         da = _dgrad(dpre, iw_) if adt != F32 else _dgrad(dpre, iw_, residual=ds2_32)
-        diw = _wgrad(dpre, aa, diw_z) if need[16] else None
+        diw = wg(dpre, aa, diw_z) if need[16] else None
         ds1_32, d1 = _ln_bwd(adt, s1, mean_a, rstd_a, law, dlaw, dlab, da, dy32=ds2_32 if adt != F32 else None, dxsum=dob,
                              drop=(p, seed + 1))
         datt = _dgrad(d1, ow_)
-        dow = _wgrad(d1, att.view(-1, D), dow_z) if need[12] else None
+        dow = wg(d1, att.view(-1, D), dow_z) if need[12] else None
         dbqkv = _zeros_like_bias(dbqkv_z, 3 * D, qkv.device) if (need[7] or need[9] or need[11]) else None
         if ctx.rows:                                                 # attention backward straight on the packed rows
             dqkv = ops.attention_bwd_rows(qkv, att, datt.contiguous(), lse, ctx.heads, cu, L, scale=64 ** -0.5, drop_seed=seed, drop_p=p,
@@ -890,7 +914,9 @@ class BertLayerFn(_GradAwareFn):
         if dbqkv is not None and not _FUSED_QKV_BIAS:
             ops.colsum_accum(dqkv, dbqkv)
         dx = _dgrad(dqkv, wqkv, residual=ds1_32, out_dtype=F32)
-        dwqkv = _wgrad(dqkv, xa, dwqkv_z) if (need[6] or need[8] or need[10]) else None
+        dwqkv = wg(dqkv, xa, dwqkv_z) if (need[6] or need[8] or need[10]) else None
+        if group:
+            _wgrad_flush(group)
         dws = [dwqkv[i * D:(i + 1) * D] if dwqkv is not None else None for i in range(3)]
         dbs = [dbqkv[i * D:(i + 1) * D] if dbqkv is not None else None for i in range(3)]
         return (dx if packed else dx.view(B, L, D), None, None, None, None, None, dws[0], dbs[0], dws[1], dbs[1], dws[2], dbs[2], dow, dob,
