@@ -199,7 +199,7 @@ int simseg_attention_bwd_planes(const void* qkv, int64_t plane_rows, const int32
                                 float scale, uint64_t drop_seed, float drop_p, void* stream);
 
 /* Prompt ensemble of the zero-shot classifier: out[s,:] = normalize(mean over the P prompt embeddings x[s,:,:]).
- * tools/seg_evaluation.py:71-73 (class_embeddings.mean(dim=0); /= norm()). */
+ * tools/seg_evaluation.py:71-73 (class_embeddings.mean(dim=0); /= norm()).  A zero mean yields NaN, as the reference's division does. */
 int simseg_segment_mean_l2norm(const float* x, float* out, int64_t S, int64_t P, int64_t D, void* stream);
 
 /* rnorm[r] = 1 / max(||x_r||_2, eps): the F.normalize of tools/seg_evaluation.py:112 as a GEMM row scale. */
@@ -208,6 +208,8 @@ int simseg_row_rnorm(const void* x, int dtype, float* rnorm, int64_t rows, int64
 /* InfoNCE rows over sims[N1,N2] = feat1 . feat2_global^T (fp32, from simseg_gemm): z = s / clamp(T,1e-3,0.5),
  * per-row cross-entropy against target column target0 + i with optional label smoothing and ignore weights, top-1
  * hit, and (write_grad) dLoss/ds written IN PLACE over sims.  out3 = {loss, top-1 acc, dLoss/dT}.
+ * Top-1 rule: the FIRST index attaining the row maximum is the prediction - a target tied with an earlier column is a miss, a target
+ * tied only with later columns is a hit.
  * simseg/models/criteria/losses/mml_loss.py:56,73-77,89-95 (+ :350-376 LabelSmoothingCrossEntropy,
  * simseg/utils/misc.py:462-478 calc_topk_accuracy). */
 int simseg_nce_rows(float* sims, const float* temperature, const float* ignore_mask, float* row_loss, float* row_correct,

@@ -32,6 +32,9 @@ __global__ __launch_bounds__(256) void nce_rows_kernel(float* __restrict__ sims,
                                                        float* __restrict__ row_correct, float* __restrict__ row_tdot,
                                                        int N1, int N2, int target0, float smoothing, int write_grad) {
     // (the pair form - simseg_nce_pair - launches 2 N1 blocks over two stacked [N1, N2] matrices: row i of matrix i / N1)
+    // Every pass forms z = s * inv_t as the SAME rounded product: contracted into the subtractions below, one pass would see the exact
+    // product and another the rounded one, and they would disagree about z - bmx by half an ulp of z.
+#pragma clang fp contract(off)
     __shared__ float sh[8];
     __shared__ int shi[8];
     const int i = blockIdx.x, tid = threadIdx.x;
@@ -64,10 +67,12 @@ __global__ __launch_bounds__(256) void nce_rows_kernel(float* __restrict__ sims,
     }
     se = block_reduce_sum(se, sh);
     sz = block_reduce_sum(sz, sh);
-    const float lse = bmx + __logf(se);
+    // lse = bmx + lg is never formed: where the target dominates its row (bmx = zt ~ 20, nll = lg = log(1 + 1e-5)) the rounding of that
+    // sum, half an ulp of 20, is a tenth of nll and of 1 - p_target.  Differences from the maximum first, then the small logarithm.
+    const float lg = __logf(se);
     const float zt = row[tgt] * inv_t;
-    const float nll = lse - zt;
-    const float smooth = lse - sz / N2;                 // -mean_j logp_ij
+    const float nll = (bmx - zt) + lg;
+    const float smooth = (bmx - sz / N2) + lg;          // -mean_j logp_ij
     const float w = ignore ? 1.0f - ignore[il] : 1.0f;
     const float loss = (1.0f - smoothing) * nll + smoothing * smooth;
     __syncthreads();
@@ -76,7 +81,7 @@ __global__ __launch_bounds__(256) void nce_rows_kernel(float* __restrict__ sims,
         const float c = w / N1;
         for (int j = tid; j < N2; j += 256) {
             const float s = row[j];
-            const float pj = __expf(s * inv_t - lse);
+            const float pj = __expf((s * inv_t - bmx) - lg);
             float dz = pj - smoothing / N2;
             if (j == tgt) dz -= (1.0f - smoothing);
             dz *= c;

@@ -1071,6 +1071,7 @@ extern "C" int simseg_vit_cls_rows(const float* cls, const float* pos, float* x,
 
 extern "C" int simseg_vit_cls_grad(const float* dx, float* dcls, int64_t B, int64_t T, int64_t D, void* stream) {
     SS_CHECK(dx && dcls, "vit_cls_grad: null pointer");
+    if (B <= 0 || D <= 0) return 0;
     hipLaunchKernelGGL(vit_cls_grad_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)((B + 15) / 16)), dim3(256), 0, STREAM, dx, dcls, (int)B, (int)T, (int)D);
     SS_LAUNCH_CHECK("vit_cls_grad");
     return 0;
