@@ -152,7 +152,10 @@ int simseg_debug_gemm_wgrad_blocks(int blocks);
  * key_mask[B,T] (1 = attend, 0 = padding; may be NULL) reproduces HF's additive key-padding mask; lse[B,H,T]
  * (log2 domain, optional) is saved for the backward.  dtype 0 = exact fp32 MFMA, 1 = bf16 MFMA.  drop_p > 0 applies
  * HF attention_probs dropout.  Replaces timm Attention.forward (q@k^T*scale, softmax, @v) and HF
- * BertSelfAttention.forward as reached through vit_builder.py:18 / huggingface_builder.py:16-17. */
+ * BertSelfAttention.forward as reached through vit_builder.py:18 / huggingface_builder.py:16-17.
+ * A sequence with NO unmasked key gets finite but otherwise unspecified out / lse / dqkv: the kernels add -1e30 to a masked score rather
+ * than HF's -10000, so in such a row the tile-padding keys behind T carry weight too (the reference's tokenizer never produces one: every
+ * caption has its [CLS]). */
 /* skip_padded_rows (bf16, T <= 256, with a key mask): the caller neither reads the outputs nor uses the gradients of the rows past a
  * sequence's last unmasked key (the packed text tower): the kernels then work on 1 + that key's index rows of each sequence only and
  * leave the other rows of out / lse / dqkv untouched. */
