@@ -327,6 +327,38 @@ int simseg_adamw_multi_step_amp_clip(const void* table, const int64_t* sizes, co
  * 1 <= C <= 65536, B >= 1; anything else is refused before a launch. */
 int simseg_ce_rows(const void* logits, int dt, const int64_t* labels, float* loss_rows, int32_t* ranks, float* dlogits, float* out3,
                    int64_t B, int64_t C, float gscale, int write_grad, void* stream);
+/* simseg_ce_rows against a two-label soft target (timm's mixup_target; with labels_a == labels_b the reference's
+ * LabelSmoothingCrossEntropy, mml_loss.py:350-376), still one pass and no dense [B, C] target.  Per row i with a = labels_a[i],
+ * b = labels_b[i], lam = lam[i] (fp32 on the device), eps = smoothing (0 <= eps < 1):
+ *   t_c = lam * s_c(a) + (1 - lam) * s_c(b),   s_c(y) = (1 - eps) * [c == y] + eps / C,
+ *   loss_rows[i] = -sum_c t_c log softmax(x)_c
+ *                = log(sum_j exp(x_j - m)) + (1 - eps) * (lam * (m - x_a) + (1 - lam) * (m - x_b)) - eps * mean_c(x_c - m)
+ *     (relative to the row maximum m, never through a rounded lse),
+ *   ranks[i] as in simseg_ce_rows for the label a (training accuracy is reported against the sample's own label),
+ *   write_grad: dlogits[i, c] = (softmax(x)_c - t_c) * gscale.
+ * With lam = 1 and eps = 0 every output equals simseg_ce_rows' on (logits, labels_a) bit for bit (the same kernels, instantiated with
+ * the soft terms).  A label outside [0, C) in EITHER vector: NaN loss row, rank INT32_MAX, zero gradient row.  out3, the limits on B and
+ * C and the two regimes as in simseg_ce_rows. */
+int simseg_soft_ce_rows(const void* logits, int dt, const int64_t* labels_a, const int64_t* labels_b, const float* lam, float smoothing,
+                        float* loss_rows, int32_t* ranks, float* dlogits, float* out3, int64_t B, int64_t C, float gscale, int write_grad,
+                        void* stream);
+/* Mixup / CutMix of a batch with its flipped self, in place and in ONE launch (csrc/mixup.hip; DESIGN.md "Mixup / CutMix").  images
+ * [B, C, H, W] contiguous (dt: 0 fp32, 1 the selected 16-bit type), B even; the partner of sample i is j = B - 1 - i.  table[i] = eight
+ * int32 words {kind, yl, yh, xl, xh, lam, om, 0} with lam and om (= float32(1.0 - double(lam)), formed by the caller) as fp32 bits.  With
+ * x the values before the call:
+ *   kind 0: sample i keeps its bits and is not written;
+ *   kind 1 (mixup): out_i = fl32(fl32(lam_i * x_i) + fl32(om_i * x_j)) - two rounded products and a rounded sum, no FMA: on fp32 storage
+ *           the bits of torch's x * lam + x.flip(0) * (1 - lam); on 16-bit storage the same fp32 arithmetic on the widened values,
+ *           rounded once (to nearest even) to the storage type;
+ *   kind 2 (cutmix): out_i = x_j inside rows [yl, yh) x columns [xl, xh) of every channel, x_i elsewhere (lam_i is not read; an empty
+ *           box is legal).
+ * out_i is formed from the partner's ORIGINAL values although the partner is rewritten by the same launch (also when i is a mixup row and
+ * j a cutmix row with another box): the unit of work is the pair.  Every element is read at most once and written at most once; a pair of
+ * cutmix rows moves only its boxes.  table_host is a HOST copy of table: before anything is launched an odd B, a kind outside 0..2, a
+ * box outside 0 <= yl <= yh <= H, 0 <= xl <= xh <= W, a lam or om that is not finite or outside [0, 1], and a null or misaligned pointer
+ * are refused with a message naming the sample. */
+int simseg_mix_batch(void* images, int dt, const int32_t* table, const int32_t* table_host, int64_t B, int64_t C, int64_t H, int64_t W,
+                     void* stream);
 /* LARS (simseg/core/optimizer/lars.py:86-127) as three launches over a tensor table, whatever the number of tensors.  table[t] = six
  * 8-byte words {p, g, buf, p16, (float lr, float weight_decay), flags}: fp32 master, fp32 gradient, fp32 momentum buffer (0 when momentum
  * is 0), the 16-bit compute copy to refresh (or 0), the tensor's learning rate and weight decay packed as two floats, flags bit 0 =

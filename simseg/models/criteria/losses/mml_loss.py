@@ -11,7 +11,7 @@ from simseg_amd.heads import ClipLossFn, NCEFn, all_gather_rows
 
 from .builder import LOSS
 
-__all__ = ["NCE"]
+__all__ = ["NCE", "LabelSmoothingCrossEntropy", "SoftTargetCrossEntropy"]
 
 
 @LOSS.register_obj
@@ -67,3 +67,50 @@ class NCE(nn.Module):
         l1, a1 = NCEFn.apply(feat1, feat2, self.temperature, None, None, 0, self.smoothing)
         l2, a2 = NCEFn.apply(feat2, feat1, self.temperature, None, None, 0, self.smoothing)
         return 0.5 * (l1 + l2), a1, a2
+
+
+def _reduce(rows, reduction):
+    if reduction == "mean":
+        return rows.mean()
+    return rows
+
+
+@LOSS.register_obj
+class LabelSmoothingCrossEntropy(nn.Module):
+    """NLL loss with label smoothing (mml_loss.py:350-376 of the reference): confidence * nll + smoothing * mean_c(-log softmax_c), which
+    is the cross-entropy against (1 - smoothing) * onehot(target) + smoothing / C - the two-label kernel with a = b = target and lam = 1
+    (simseg_amd.probe.SoftCEFn over ops.soft_ce_rows), one autograd node, no log-softmax tensor.  reduction="mean" returns the mean,
+    anything else the rows, as the reference does."""
+
+    def __init__(self, cfg, rank, smoothing=0.1, reduction="mean", **kwargs):
+        super().__init__()
+        if not smoothing < 1.0:
+            raise AssertionError("smoothing must be below 1")
+        self.smoothing, self.confidence, self.reduction = smoothing, 1.0 - smoothing, reduction
+
+    def forward(self, x, target):
+        from simseg_amd.probe import SoftCEFn
+        lam = torch.ones(target.shape[0], device=x.device, dtype=torch.float32)
+        return SoftCEFn.apply(x, target, target, lam, self.smoothing, self.reduction == "mean")
+
+
+@LOSS.register_obj
+class SoftTargetCrossEntropy(nn.Module):
+    """Cross-entropy against soft targets (mml_loss.py:379-391 of the reference).
+
+    forward(x, target) with a dense [B, C] target is the reference's three lines in torch ops - the UNFUSED form: it materialises the
+    log-softmax and the product beside the target, and also runs on the CPU.  A Mixup / CutMix target never has more than two
+    non-uniform entries per row, so forward(x, {"label", "label_b", "lam", "smoothing"}) - the dict simseg_amd.mixup.Mixup.apply returns
+    - takes the fused kernel instead (one autograd node, no dense tensor beside the logits)."""
+
+    def __init__(self, cfg, rank, reduction="mean", **kwargs):
+        super().__init__()
+        self.reduction = reduction
+
+    def forward(self, x, target):
+        if isinstance(target, dict):
+            from simseg_amd.probe import SoftCEFn
+            return SoftCEFn.apply(x, target["label"], target["label_b"], target["lam"], float(target.get("smoothing", 0.0)),
+                                  self.reduction == "mean")
+        loss = torch.sum(-target * torch.log_softmax(x, dim=-1), dim=-1)
+        return _reduce(loss, self.reduction)

@@ -7,7 +7,9 @@ state-dict keys: image_encoder.model.model.* (timm names; the same ImageEncoder 
 
 On the device the head is one autograd node, simseg_amd.probe.ProbeHeadFn: fp32 logits from the fp32 master weights, the fused
 cross-entropy / top-k / logit-gradient rows, fp32 weight and bias gradients.  Logits and gradients of the head are fp32 whatever 16-bit
-type the encoder computes in, so this task uses no loss scaling."""
+type the encoder computes in, so this task uses no loss scaling.  A Mixup / CutMix batch (simseg_amd.mixup.Mixup.apply: `label_b`, `lam`
+and `smoothing` beside `label`) takes the same head against its two-label soft target, SoftProbeHeadFn; the accuracies stay those against
+`label`, the samples' own labels."""
 import os
 
 import torch
@@ -56,8 +58,14 @@ class LinearProbModel(nn.Module):
         return feats
 
     def _head(self, batch):
-        from simseg_amd.probe import ProbeHeadFn
+        """A batch that carries `label_b` and `lam` (simseg_amd.mixup.Mixup.apply) takes the soft-target head with `smoothing` from the
+        batch (default 0); any other batch takes ProbeHeadFn, and the soft path is not even imported."""
         feats = self.forward_image_feature(batch["image"])
+        if "label_b" in batch and "lam" in batch:
+            from simseg_amd.probe import SoftProbeHeadFn
+            return SoftProbeHeadFn.apply(feats, self.classifier.weight, self.classifier.bias, batch["label"], batch["label_b"], batch["lam"],
+                                         float(batch.get("smoothing", 0.0)))
+        from simseg_amd.probe import ProbeHeadFn
         return ProbeHeadFn.apply(feats, self.classifier.weight, self.classifier.bias, batch["label"])
 
     def forward(self, batch, valid=False, **kwargs):

@@ -161,3 +161,19 @@ def build_train_pipeline(cfg):
     pipe = TrainPipeline(parse_chain(list(cfg.transforms.train_transforms), cfg, lut=_normalize_lut(cfg)))
     logger.emph("train image transforms on the device:", pipe)
     return _to_u8, pipe
+
+
+def build_mixup(cfg):
+    """-> simseg_amd.mixup.Mixup from cfg.transforms.{mixup, cutmix, cutmix_minmax, mixup_prob, mixup_switch_prob, mixup_mode},
+    cfg.loss.smoothing and cfg.model.classifier.num_classes (timm's Mixup arguments under the reference's key names), or None when both
+    alphas are 0.  Called explicitly by a data loop that wants mixing, as build_train_pipeline is: the task defaults carry mixup = 0.8 and
+    cutmix = 1.0, and nothing enables mixing from the config on its own."""
+    t = cfg.transforms
+    if not (t.mixup > 0 or t.cutmix > 0 or t.cutmix_minmax is not None):
+        return None
+    from simseg_amd.mixup import Mixup
+    minmax = None if t.cutmix_minmax is None else tuple(t.cutmix_minmax)
+    mix = Mixup(mixup_alpha=t.mixup, cutmix_alpha=t.cutmix, cutmix_minmax=minmax, prob=t.mixup_prob, switch_prob=t.mixup_switch_prob,
+                mode=t.mixup_mode, label_smoothing=cfg.loss.smoothing, num_classes=cfg.model.classifier.num_classes)
+    logger.emph("mixup / cutmix on the device:", mix)
+    return mix

@@ -993,6 +993,50 @@ def ce_rows(logits, labels, write_grad=True):
     return out3, loss_rows, ranks, dlogits
 
 
+def soft_ce_rows(logits, labels_a, labels_b, lam, smoothing=0.0, write_grad=True):
+    """ce_rows against the two-label soft target t = lam * s(a) + (1 - lam) * s(b), s(y) = (1 - smoothing) * onehot(y) + smoothing / C
+    (timm's mixup_target; a == b, lam = 1: label smoothing), with no dense target: labels_a / labels_b int64 [B], lam fp32 [B], all on the
+    device.  -> (out3, loss_rows, ranks, dlogits) laid out as ce_rows'; ranks and the two counts are those of labels_a; dlogits =
+    (softmax - t) / B.  lam = 1, smoothing = 0 gives ce_rows' bits.  A label outside [0, C) in either vector: NaN loss row, rank
+    2^31 - 1, zero gradient row (include/simseg_hip.h)."""
+    require_gpu(logits, labels_a, labels_b, lam)
+    if logits.dim() != 2 or labels_a.shape != logits.shape[:1] or labels_b.shape != logits.shape[:1] or lam.shape != logits.shape[:1]:
+        raise ValueError(f"soft_ce_rows: logits [B, C] and labels_a, labels_b, lam [B], got {tuple(logits.shape)}, {tuple(labels_a.shape)}, "
+                         f"{tuple(labels_b.shape)} and {tuple(lam.shape)}")
+    if labels_a.dtype != torch.int64 or labels_b.dtype != torch.int64:
+        raise TypeError(f"soft_ce_rows: labels must be int64, got {labels_a.dtype} and {labels_b.dtype}")
+    if lam.dtype != torch.float32:
+        raise TypeError(f"soft_ce_rows: lam must be fp32, got {lam.dtype}")
+    B, C = logits.shape
+    dev = logits.device
+    loss_rows = torch.empty(B, device=dev, dtype=torch.float32)
+    ranks = torch.empty(B, device=dev, dtype=torch.int32)
+    out3 = torch.empty(3, device=dev, dtype=torch.float32)
+    dlogits = torch.empty(B, C, device=dev, dtype=torch.float32) if write_grad else None
+    call("simseg_soft_ce_rows", ptr(_c(logits)), dt(logits), ptr(_c(labels_a)), ptr(_c(labels_b)), ptr(_c(lam)), float(smoothing), ptr(loss_rows),
+         ptr(ranks), ptr(dlogits), ptr(out3), B, C, 1.0 / max(B, 1), int(bool(write_grad)), stream())
+    return out3, loss_rows, ranks, dlogits
+
+
+# ---- Mixup / CutMix (csrc/mixup.hip; simseg_amd/mixup.py) --------------------------------------------------------------------------------
+def mix_batch(images, table_dev, table_host):
+    """Mixup / CutMix of images [B, C, H, W] (fp32, bf16 or fp16; contiguous; B even) with its flipped self, IN PLACE, one launch.
+    table_dev int32 [B, 8] on the device and table_host, its host copy (a contiguous int32 numpy array): per sample {kind, yl, yh, xl,
+    xh, lam bits, om bits, 0} (simseg_amd.mixup; include/simseg_hip.h).  The host copy is checked before the launch.  -> images."""
+    require_gpu(images, table_dev)
+    if images.dim() != 4:
+        raise ValueError(f"mix_batch: images [B, C, H, W] expected, got {tuple(images.shape)}")
+    B, C, H, W = images.shape
+    if table_dev.dtype != torch.int32 or tuple(table_dev.shape) != (B, 8):
+        raise ValueError(f"mix_batch: int32 [{B}, 8] device table expected, got {tuple(table_dev.shape)} {table_dev.dtype}")
+    if getattr(table_host, "dtype", None) != "int32" or table_host.shape != (B, 8) or not table_host.flags.c_contiguous:
+        raise ValueError(f"mix_batch: the host copy of the table is a contiguous int32 [{B}, 8] numpy array")
+    if not images.is_contiguous():
+        raise RuntimeError("mix_batch: the batch must be contiguous [B, C, H, W] (it is mixed in place)")
+    call("simseg_mix_batch", ptr(images), dt(images), ptr(_c(table_dev)), table_host.ctypes.data, B, C, H, W, stream())
+    return images
+
+
 def lars_norm_partials(tab, partials):
     """partials float64 [n_chunks, 2] <- per chunk {sum p^2, sum g^2} of the tensor table `tab` (a simseg_amd.optim.TensorTable with
     LARS's rows)."""

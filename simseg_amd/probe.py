@@ -1,6 +1,8 @@
 """The linear-probe task on the HIP path (the reference's simseg/tasks/linear_prob + simseg/models/pipelines/linear_prob.py):
 
   ProbeHeadFn          classifier + nn.CrossEntropyLoss + accuracy(topk=(1, 5)) as ONE autograd node
+  SoftProbeHeadFn      the same head against the two-label soft target of a Mixup / CutMix batch (simseg_amd.mixup), same backward
+  SoftCEFn             the soft-target rows alone as one node (LabelSmoothingCrossEntropy / SoftTargetCrossEntropy of the LOSS registry)
   LinearProbeTrainer   one training iteration / an evaluation pass / checkpoints, with the reference's semantics
                        (LinearProbRunner + ClipOptimizerHook + LinearEvalHook), as simseg_amd.trainer.Trainer is for the clip task
 
@@ -57,6 +59,58 @@ class ProbeHeadFn(_GradAwareFn):
         if ctx.needs_input_grad[0]:
             dx = ops.gemm(dl, ops.transpose_f32(w), out_dtype=F32).to(ctx.x_dtype)                 # [B, C] . [D, C]^T
         return dx, dw, db, None
+
+
+class SoftProbeHeadFn(ProbeHeadFn):
+    """(x [B, D], weight [C, D], bias [C], labels_a int64 [B], labels_b int64 [B], lam fp32 [B], smoothing) -> (loss, out3, logits).
+
+    ProbeHeadFn against the two-label soft target of a Mixup / CutMix batch, t = lam * s(a) + (1 - lam) * s(b) with s(y) = (1 - smoothing)
+    * onehot(y) + smoothing / C (ops.soft_ce_rows: the same single pass, no dense target): loss = mean of -sum_c t_c log softmax_c,
+    dlogits = (softmax - t) / B, and out3's counts are top-1 / top-5 hits against labels_a, the samples' own labels.  The backward is
+    ProbeHeadFn's: it only needs dlogits."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, labels_a, labels_b, lam, smoothing):
+        x32 = x.detach().to(F32).contiguous()
+        w = weight.detach().contiguous()
+        logits = ops.gemm(x32, w, bias=bias.detach().contiguous(), out_dtype=F32)
+        need = _saving(ctx)
+        out3, _, _, dlogits = ops.soft_ce_rows(logits, labels_a.contiguous(), labels_b.contiguous(), lam.detach().to(F32).contiguous(),
+                                               smoothing=float(smoothing), write_grad=need)
+        if need:
+            ctx.save_for_backward(x32, w, dlogits)
+        ctx.x_dtype = x.dtype
+        ctx.mark_non_differentiable(out3, logits)
+        return out3[0].clone(), out3, logits
+
+    @staticmethod
+    def backward(ctx, gloss, _g3, _glogits):
+        return ProbeHeadFn.backward(ctx, gloss, _g3, _glogits) + (None, None, None)
+
+
+class SoftCEFn(_GradAwareFn):
+    """(logits [B, C] fp32 / bf16 / fp16, labels_a, labels_b int64 [B], lam fp32 [B], smoothing, mean) -> the mean of the two-label
+    soft-target cross-entropy rows (mean=True) or the rows themselves, as ONE autograd node over ops.soft_ce_rows: the forward pass already
+    wrote (softmax - t) / B, the backward scales it by the upstream gradient on the device (per row, times B, for the rows)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels_a, labels_b, lam, smoothing, mean):
+        need = _saving(ctx)
+        out3, rows, _, dlogits = ops.soft_ce_rows(logits.detach().contiguous(), labels_a.contiguous(), labels_b.contiguous(),
+                                                  lam.detach().to(F32).contiguous(), smoothing=float(smoothing), write_grad=need)
+        if need:
+            ctx.save_for_backward(dlogits)
+        ctx.mean, ctx.dtype = bool(mean), logits.dtype
+        return out3[0].clone() if mean else rows
+
+    @staticmethod
+    def backward(ctx, g):
+        dlogits, = ctx.saved_tensors
+        if ctx.mean:
+            dl = ops.scale_by_scalar(dlogits, g.to(F32).reshape(1).contiguous())
+        else:
+            dl = ops.scale_rows(dlogits, g.to(F32).contiguous(), alpha=float(dlogits.shape[0]))
+        return dl.to(ctx.dtype), None, None, None, None, None
 
 
 def optimizer_class(name):
