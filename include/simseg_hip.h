@@ -64,11 +64,17 @@ int simseg_gemm_aux_blocked_ok(int64_t M, int64_t N, int64_t K);
 int simseg_patch_text_sim(const void* x, const void* text, float* out, int64_t M, int64_t C, int64_t K, int dtype, float eps,
                           int normalize, void* stream);
 
-/* Kernel selection for benchmarking / tests (thread-local; production callers never call it): 0 auto, 1 = 128x128 register-staged kernel, 2 = 256x256 direct-to-LDS ring kernel,
- * 3 = 256x256 ping-pong kernel, 4 = small-problem kernel (32x64 / 64x64 tiles, intra-block split-K) wherever it applies (+100: debug, epilogue skipped and a cycle-counter timeline written to C by
- * tools/dbg_gemm_timeline.py). */
+/* Kernel selection for benchmarking / tests (thread-local; production callers never call it).  Every value forces a choice among the
+ * kernels the automatic dispatch itself uses, where that kernel applies to the call; where it does not, the call is dispatched as under 0:
+ *   0  auto
+ *   1  128x128 register-staged kernel
+ *   3  256x256 ping-pong kernel, one tile per block (never the persistent kernel)
+ *   4  small-problem kernel (32x64 / 64x64 tiles, intra-block split-K) wherever it applies
+ *   5  128x128 tile on the four-stage direct-to-LDS ring (k-contiguous operands, K % 64 == 0, M, N >= 128, no split-K)
+ *   10 persistent 256x256 ping-pong kernel wherever it applies (full tiles, more than one round, the epilogue kinds auto puts on it)
+ * Any other value is an error and leaves the previous selection in force. */
 int simseg_set_gemm_variant(int v);
-/* Which of those kernels (1 / 2 / 3 / 4) the calling thread's last simseg_gemm launched. */
+/* Which of those kernels (1 / 3 / 4 / 5 / 10) the calling thread's last simseg_gemm launched. */
 int simseg_gemm_last_variant(void);
 
 /* A transformer block's split-K weight gradients as ONE launch of the 256x256 ping-pong kernel: n (1..8) problems
@@ -140,13 +146,10 @@ int simseg_set_attention_variant(int v);
 /* debug (thread-local): the one-kernel backward writes 4 x uint64 per block (start / operands landed / tile loop done / end, 100 MHz wall
  * clock); NULL switches it off. */
 int simseg_debug_attn_trace(void* buf);
-/* debug (thread-local): the ping-pong GEMM kernel writes 5 x uint64 per block into buf (wall-clock stamps at 100 MHz of block start, K loop
- * start, K loop end, block end; HW_ID) - tools/dbg_gemm_trace.py; NULL switches it off. */
+/* debug (thread-local): the per-tile ping-pong GEMM kernel writes 5 x uint64 per block into buf (wall-clock stamps at 100 MHz of block
+ * start, K loop start, K loop end, block end; HW_ID) - tools/dbg_gemm_trace.py, tools/dbg_wgrad_trace.py; NULL switches it off.  A traced
+ * call never runs on the persistent kernel. */
 int simseg_debug_gemm_trace(void* buf);
-int simseg_debug_gemm_stagger(int ticks);
-/* debug / experiments (thread-local): > 0 = the split-K weight-gradient GEMMs (transA, fp32 accumulate) use at most this many 256x256
- * blocks, i.e. CUs, instead of one round of all of them; 0 = default. */
-int simseg_debug_gemm_wgrad_blocks(int blocks);
 
 /* Fused softmax attention, head_dim 64, from the packed projection qkv[B,T,3,H,64] to ctx[B,T,H*64].
  * key_mask[B,T] (1 = attend, 0 = padding; may be NULL) reproduces HF's additive key-padding mask; lse[B,H,T]

@@ -1,7 +1,20 @@
 // MFMA GEMM with fused epilogues for the encoder hot path (K1, K4, K6-K8, K10, K13, K14, K16 of
-// SURVEY.md section 2.2).  One kernel template:
+// SURVEY.md section 2.2):
 //
 //     C[M,N] = epilogue( alpha * opA(A)[M,K] . opB(B)[K,N] )
+//
+// Five kernels, numbered as simseg_set_gemm_variant / simseg_gemm_last_variant number them; every instantiation in this file is one the
+// automatic dispatch (selector 0; dispatch_bf16 and the tail of simseg_gemm) reaches for some valid call:
+//    4  gemm_small_kernel   32x64 / 64x64 tiles, the K slab split between wave groups: k-contiguous fp32 or 16-bit problems that leave
+//                           the 128x128 tiling with fewer than 160 (fp32: 200) blocks - the batch-1 evaluation shapes
+//    3  gemm_pp_kernel      256x256 ping-pong kernel, one tile per block: 16-bit forward / dgrad problems of >= 96 tiles with a long
+//                           enough contraction, and the split-K weight gradients (one round of blocks; grouped: simseg_gemm_wgrad_group)
+//   10  gemm_pp2_kernel     the same tile and schedule, persistent (one block per CU walks a tile list): >= 600 full tiles with an
+//                           accumulator-layout epilogue
+//    5  gemm_large_kernel   128x128 tile on a four-stage direct-to-LDS ring: one round of tiles (160-256) of a k-contiguous 16-bit problem
+//    1  gemm_kernel         128x128 register-staged kernel, described below: fp32 operands and every 16-bit call the others do not take
+// (simmap_kernel, the fused patch x text similarity map, is separate: simseg_patch_text_sim.)  What was measured and dropped on the
+// way - other tile shapes, ring depths, schedules, CU partitioning - is in profiles/HISTORY.md.
 //
 //   * T = float  : v_mfma_f32_32x32x2_f32  (exact fp32, parity mode), operands k-contiguous only
 //   * T = bf16   : v_mfma_f32_32x32x16_bf16 (fp32 accumulate), operands k-contiguous or, for the
@@ -22,15 +35,6 @@
 // ds_read_b128 / ds_read_b64_tr_b16 fragment fetches are bank-conflict free.
 #include "common.h"
 #include <type_traits>
-
-// Epilogue ablation switches of tools/dbg_fc1_epilogue.py (skip the GELU' store / the GELU itself / the output store through
-// simseg_debug_gemm_stagger(1001..1003)) exist only in builds made with -DSS_GEMM_ABLATE: in the shipped library a left-over debug value
-// cannot silently produce wrong activations, and simseg_debug_gemm_stagger refuses values >= 1000.
-#ifdef SS_GEMM_ABLATE
-#define SS_ABL(v) (p.stagger == (v))
-#else
-#define SS_ABL(v) false
-#endif
 
 namespace {
 
@@ -62,14 +66,14 @@ struct GemmParams {
     int res_mod;             // residual row = 1 + r % G (pos_embed) instead of the output row
     int accumulate;          // C += result (fp32 output only; always set when split-K)
     unsigned long long* dbg_trace;   // debugging only (simseg_debug_gemm_trace): per block {start, K loop start, K loop end, end} wall-clock stamps + hardware id
-    int stagger;             // ping-pong kernel: first-round blocks start (slot % 4) * stagger wall-clock ticks (10 ns) late (see launch_pp)
-    int dbg_skip_epilogue;   // benchmarking only (simseg_set_gemm_variant(100 + v)): the accumulators are kept live but nothing is stored
+    int stagger;             // always 0: the first-round delay experiment is gone (profiles/HISTORY.md 7.8); the field and its branch stay so that the kernels remain byte-identical
+    int dbg_skip_epilogue;   // always 0 (its selector is retired); kept, with the branches that read it, for the same reason
     int ksplit;              // k-tiles per split-K slice
     int nsplit;              // number of split-K slices (grid = tiles * nsplit, slice-major so a slice's tiles share an XCD)
     // dropout on (acc*alpha + bias), before the residual:  keep iff hash(seed, row*N+col) >= thresh
     unsigned long long drop_seed; unsigned int drop_thresh; float drop_scale;
     float* colsum;           // optional [N]: += column sums of the stored output (bias gradient of the producing layer)
-    int pf_next;             // ping-pong kernel: the tail's copies fetch the next tile of this XCD (see gemm_pp_kernel)
+    int pf_next;             // always 1: the per-tile ping-pong kernel's tail copies fetch the next tile of this XCD (see gemm_pp_kernel); kept for the same reason
     int aux_blocked;         // act 3 / 4 on the ping-pong kernels: aux_out / aux is the tile-blocked accumulator image (simseg_gemm act codes 5 / 6)
 };
 
@@ -204,7 +208,7 @@ template <typename TO>
 __device__ __forceinline__ void epilogue_block(const GemmParams& p, const f32x16& accL, const f32x16& accR, float* wlds, int row0,
                                                int col0, int col1, int lane, bool atomic, bool vec_ok, float (&cs)[8]) {
     const int h2 = lane >> 5, cl = lane & 31;
-    if (p.dbg_skip_epilogue) {         // debug: epilogue skipped (keeps the accumulators live), for fixed-cost attribution
+    if (p.dbg_skip_epilogue) {         // never taken: dbg_skip_epilogue is always 0 (see GemmParams)
         if (accL[0] + accR[0] == 12345.678f) static_cast<TO*>(p.C)[0] = (TO)1.f;
         return;
     }
@@ -571,13 +575,14 @@ int launch(const GemmParams& p, int splitk, hipStream_t stream) {
 
 
 // =================================================================================================================
-// Large-tile bf16 kernel: 256x256 block tile, 8 waves (2 x 4), each wave 128x64 = 4x2 MFMA 32x32 accumulators.
+// Direct-to-LDS ring kernel (16-bit operands): a TM x TN block tile on WM_ x WN_ waves.  Its one instantiation is the 128x128 tile on
+// 2 x 2 waves (64x64 = 2x2 MFMA 32x32 accumulators each) with a ring of four 64-deep slabs, one block per CU.
 // Operand K-slabs go global -> LDS directly (global_load_lds_dwordx4, 1 KiB per wave-instruction, no VGPR staging) into
 // a ring of NSTAGE slabs of BKE k-elements each, so NSTAGE-1 slabs are in flight while one is consumed; one raw
 // s_barrier per slab and counted vmcnt waits (never a full drain in steady state).  The LDS image is lane-linear, so
 // the bank-conflict swizzle is applied to the per-lane SOURCE address and undone on the fragment read:
-//   k-contiguous slab  [256 rows][BKE*2 B]: 16-B slot s of row r holds k-chunk  s ^ f(r)
-//   transposed slab    [BKE k-rows][512 B]: 16-B slot s of k-row kr holds m-chunk s ^ ((kr & 3) << 2)
+//   k-contiguous slab  [TM rows][BKE*2 B]: 16-B slot s of row r holds k-chunk  s ^ f(r)
+//   transposed slab    [BKE k-rows][TM*2 B]: 16-B slot s of k-row kr holds m-chunk s ^ ((kr & 3) << 2)
 // Requirements: bf16 operands, K % BKE == 0, 16-byte aligned contiguous extents (else the 128x128 kernel is used).
 // =================================================================================================================
 
@@ -734,7 +739,7 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, MINW) void gemm_large_kernel(GemmPa
         if (FN > 2) flush_colsum(p, csb, cb, cb + 32, lane);
     }
     if (FN == 2) flush_colsum(p, cs, n0 + wn * 64, n0 + wn * 64 + 32, lane);
-    if (p.dbg_skip_epilogue && blockIdx.x == 0 && tid == 0) {    // debug timeline (cycle counter) of block 0 / wave 0
+    if (p.dbg_skip_epilogue && blockIdx.x == 0 && tid == 0) {    // never taken: dbg_skip_epilogue is always 0 (see GemmParams)
         unsigned long long* d = reinterpret_cast<unsigned long long*>(p.C);
         d[0] = dbg_t1 - dbg_t0; d[1] = dbg_t2 - dbg_t1; d[2] = dbg_t3 - dbg_t2; d[3] = __builtin_readcyclecounter() - dbg_t3;
     }
@@ -768,8 +773,8 @@ int launch_large(const GemmParams& p, int splitk, hipStream_t stream) {
 // =================================================================================================================
 // Ping-pong ("8-phase") bf16 kernel: 256x256 block tile, K-tiles of 64, 8 waves in two groups of four.
 //
-// The 256x256 direct-to-LDS kernel above moves all eight waves through "wait for the slab - read fragments - MFMA" in lockstep:
-// its K loop measures ~1000 TFLOP/s (MFMA pipe ~40 % busy; profiles/r1_gemm_vs_vendor.txt).  Here the two waves that share a SIMD
+// The 256x256 form of the ring kernel above (removed) moved all eight waves through "wait for the slab - read fragments - MFMA" in
+// lockstep: its K loop measured ~1000 TFLOP/s (MFMA pipe ~40 % busy; profiles/r1_gemm_vs_vendor.txt).  Here the two waves that share a SIMD
 // (wave w and w+4 = the two wave rows) run half a phase apart: while one issues its LDS fragment reads and global->LDS copies,
 // the other owns the matrix pipe with a cluster of 8 back-to-back MFMAs, and two workgroup barriers per phase keep the
 // alternation strict (cdna_hip_programming.md, "The 256^2 8-phase template").
@@ -777,7 +782,7 @@ int launch_large(const GemmParams& p, int splitk, hipStream_t stream) {
 //   * wave (g, wn) owns output rows {h*128 + g*64 + [0,64)} and columns {h*128 + wn*32 + [0,32)}, h = 0,1: one 64x32 quadrant per
 //     operand half, so every wave needs operand half 0 before half 1 and staging follows that order.
 //   * a K-tile is four 16 KiB half-tiles (B half 0, A half 0, B half 1, A half 1 - the order the fragment reads need them),
-//     staged one per phase with global_load_lds (2 per wave), PP_LEAD phases ahead of the phase that reads them, into a ring of
+//     staged with global_load_lds (2 per wave and half-tile), four half-tiles ahead of the phase that reads them, into a ring of
 //     two K-tiles (128 KiB).  Counted vmcnt only; a half-tile is waited for one phase before it is read, ahead of that phase's
 //     first barrier (both groups have then passed a barrier behind every wave's wait).
 //   * per phase a wave reads 8 (an A half) or 4 (a B half) fragments and runs one quadrant x K=64 = 8 MFMA 32x32x16; fragment
@@ -1023,17 +1028,16 @@ __device__ __forceinline__ void pp_epilogue_bf16(const GemmParams& p, const f32x
             for (int e = 0; e < 16; ++e) {           // the left / right element as one pair: packed fp32 arithmetic (common.h)
                 f32x2 d;
                 f32x2 y = __builtin_elementwise_fma((f32x2){acc[i][0][e], acc[i][1][e]}, (f32x2){p.alpha, p.alpha}, (f32x2){bL, bR});
-                if (!SS_ABL(1002)) y = gelu_poly_grad2(y, d); else d = y;
+                y = gelu_poly_grad2(y, d);
                 l[e] = y.x; r[e] = y.y;
                 dl.h[e] = (bf16_t)d.x; dr.h[e] = (bf16_t)d.y;
             }
-            if (!SS_ABL(1001))
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
                 *reinterpret_cast<u32x4*>(Bb + (i * 2) * 1024 + q * 8) = dl.v[q];
                 *reinterpret_cast<u32x4*>(Bb + (i * 2 + 1) * 1024 + q * 8) = dr.v[q];
             }
-            if (!SS_ABL(1003)) emit(l, r, Cb, m0 + (i >> 1) * 128 + grp * 64 + (i & 1) * 32);
+            emit(l, r, Cb, m0 + (i >> 1) * 128 + grp * 64 + (i & 1) * 32);
         }
     } else if (EK == 1 && p.act == 4) {
         // times the saved derivative (the dgrad through fc2) + column sums (fc1's bias gradient).  The saved tensor is row-major like the
@@ -1239,10 +1243,18 @@ struct WgradGroupParams {
 __device__ __forceinline__ const GemmParams& pp_params(const GemmParams& arg, const GemmParams&) { return arg; }
 __device__ __forceinline__ const GemmParams& pp_params(const WgradGroupParams&, const GemmParams& own) { return own; }
 
-// PP_LEAD: half-tiles in flight ahead of the phase that reads them (3..5; the ring of two K-tiles allows up to 6).  PRIO: 1 = raise the
-// wave priority around every MFMA cluster, 2 = static priority for the second group only, 0 = none.  Measured (tools/gemm_bench.py,
-// r2): LEAD 3 / 4 / 5 and PRIO 0 / 1 / 2 are all within run-to-run noise (+-2 %) on the training shapes and on 4096^3 / 8192^3.
-// BIG = 1 (round 3 experiment, variant 14): TWO phases per K-tile instead of four - 16 MFMAs between a phase's barriers.  Phase X reads A
+// debugging (simseg_debug_gemm_trace): thread 0 of a block writes its wall-clock stamps {start, K loop start, K loop end, end, last store issued}
+__device__ __forceinline__ void pp_trace_end(const GemmParams& p, int tid, unsigned long long tr0, unsigned long long tr1, unsigned long long tr2) {
+    if (p.dbg_trace && tid == 0) {
+        const unsigned long long tr3 = wall_clock64();               // every store of this wave is issued
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // ... and acknowledged
+        unsigned long long* d = p.dbg_trace + (long)blockIdx.x * 5;
+        d[0] = tr0; d[1] = tr1; d[2] = tr2; d[3] = wall_clock64(); d[4] = tr3;
+    }
+}
+
+// The K loop runs TWO phases per K-tile - 16 MFMAs between a phase's barriers, the wave priority raised around every MFMA cluster (the
+// four-phase schedule it replaced, and the lead / priority variants measured with it: profiles/HISTORY.md).  Phase X reads A
 // half 0 and both B halves (16 fragment reads), stages A half 1 of the next K-tile (2 copies) and multiplies A half 0 by both B halves;
 // phase Y reads A half 1 (8 reads), stages B half 0 / A half 0 / B half 1 of the K-tile after next (6 copies: those slots were last read
 // in phase X) and multiplies A half 1 by both B halves.  Every half-tile is requested two phases (one K-tile) before it is read;
@@ -1250,7 +1262,7 @@ __device__ __forceinline__ const GemmParams& pp_params(const WgradGroupParams&, 
 // GROUPED: the argument is a WgradGroupParams and only the front differs - the block finds its problem, then its (slice, tile) in it.
 // ATOMIC_DIRECT (grouped launches): the split-K adds of a full tile are issued from the accumulators in the MFMA layout
 // (pp_epilogue_atomic_direct) instead of through the staged epilogue.
-template <typename TO, bool TA, bool TB, int PP_LEAD = 4, int PRIO = 1, int BIG = 0, int EK = 1, bool GROUPED = false, bool ATOMIC_DIRECT = false>
+template <typename TO, bool TA, bool TB, int EK = 1, bool GROUPED = false, bool ATOMIC_DIRECT = false>
 __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(typename std::conditional<GROUPED, WgradGroupParams, GemmParams>::type arg) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     GemmParams own;
@@ -1296,10 +1308,10 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(typename std::condition
     // dummy slot.  They now read what the NEXT block of this XCD will want first - the first seven half-tiles of the tile 32 places on
     // in this XCD's run (one block per CU, 32 CUs per XCD: the tile that takes this round's place) - so that block's prologue finds its
     // operands in this XCD's L2 / the Infinity Cache instead of HBM.  A per-lane offset belongs to this tile's rows; the next tile's
-    // rows are a scalar distance away as long as both tiles are full.  p.pf_next = 0 switches it off (A/B).
+    // rows are a scalar distance away as long as both tiles are full.  (p.pf_next is always 1: see GemmParams.)
     long dA = 0, dB = 0;
     bool pf_ok = false;
-    if (BIG && p.pf_next && p.nsplit == 1) {
+    if (p.pf_next && p.nsplit == 1) {
         const int nb8 = (int)gridDim.x >> 3, rr8 = (int)gridDim.x & 7, xx = (int)blockIdx.x & 7, jj = (int)blockIdx.x >> 3;
         if (jj + 32 < nb8 + (xx < rr8 ? 1 : 0)) {
             const int tn_ = t + 32;                                  // (kz = 0: no split-K here)
@@ -1355,92 +1367,46 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(typename std::condition
 #define PP_READ_B(FB, PAR, HALF) \
     _Pragma("unroll") for (int kk_ = 0; kk_ < 4; ++kk_) FB[kk_] = frb.read(lds, ((PAR) * 2 + (HALF)) * PP_HALF, 0, kk_);
 #define PP_CLUSTER(RH, CH, FB)                                                                       \
-    if (PRIO == 1) __builtin_amdgcn_s_setprio(1);                                                    \
+    __builtin_amdgcn_s_setprio(1);                                                                   \
     _Pragma("unroll") for (int kk_ = 0; kk_ < 4; ++kk_)                                              \
         _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) mma<bf16_t>(acc[2 * (RH) + i_][CH], fa[i_ * 4 + kk_], FB[kk_]); \
-    if (PRIO == 1) __builtin_amdgcn_s_setprio(0);
+    __builtin_amdgcn_s_setprio(0);
 
-    if (p.stagger > 0 && blockIdx.x < 256) {                         // first round only: the phase offset then persists from round to round
+    if (p.stagger > 0 && blockIdx.x < 256) {                         // never taken: stagger is always 0 (see GemmParams)
         const unsigned long long until = wall_clock64() + (unsigned long long)(((blockIdx.x >> 3) & 3) * p.stagger);
         while (wall_clock64() < until) __builtin_amdgcn_s_sleep(8);
     }
     unsigned long long tr0 = 0, tr1 = 0, tr2 = 0;
     if (p.dbg_trace) tr0 = wall_clock64();
-    if constexpr (BIG) {
-        PP_STAGE(0, 0) PP_STAGE(1, 1) PP_STAGE(2, 2) PP_STAGE(3, 3) PP_STAGE(4, 0) PP_STAGE(5, 1) PP_STAGE(6, 2)
-        wait_vm<8>();                                               // half-tiles 0..2 (what phase X of the first K-tile reads)
-        __builtin_amdgcn_s_barrier();
-        __builtin_amdgcn_sched_barrier(0);
-        if (grp == 1) __builtin_amdgcn_s_barrier();                 // the second group runs one barrier behind the first
-        if (p.dbg_trace) tr1 = wall_clock64();
-#define PP_BIGPHASE(READS, STAGES, RH, CA, FA_, CB, FB_)                                       \
-    {                                                                                          \
-        READS                                                                                  \
-        STAGES                                                                                 \
-        wait_vm<8>();                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-        __builtin_amdgcn_s_barrier();                                                          \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-        PP_CLUSTER(RH, CA, FA_)                                                                \
-        PP_CLUSTER(RH, CB, FB_)                                                                \
-        asm volatile("" : "+v"(acc[2 * (RH)][0]), "+v"(acc[2 * (RH) + 1][0]), "+v"(acc[2 * (RH)][1]), "+v"(acc[2 * (RH) + 1][1])); \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-        __builtin_amdgcn_s_barrier();                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-    }
-        for (int tt = 0; tt < ntile; ++tt) {
-            PP_BIGPHASE(PP_READ_B(fb0, 0, 0) PP_READ_A(0, 0) PP_READ_B(fb1, 0, 1), PP_STAGE(4 * tt + 7, 3), 0, 0, fb0, 1, fb1)
-            frb.toggle(2 * PP_HALF);
-            PP_BIGPHASE(PP_READ_A(0, 1), PP_STAGE(4 * tt + 8, 0) PP_STAGE(4 * tt + 9, 1) PP_STAGE(4 * tt + 10, 2), 1, 1, fb1, 0, fb0)
-            fra.toggle(2 * PP_HALF);
-        }
-#undef PP_BIGPHASE
-    } else {
-    // ---- prologue: half-tiles 0..PP_LEAD on their way, 0 and 1 landed, B half 0 of the first K-tile in registers
-    PP_STAGE(0, 0) PP_STAGE(1, 1) PP_STAGE(2, 2) PP_STAGE(3, 3)
-    if (PP_LEAD >= 4) PP_STAGE(4, 0)
-    if (PP_LEAD >= 5) PP_STAGE(5, 1)
-    wait_vm<2 * (PP_LEAD - 1)>();                                   // half-tiles 0 and 1: the younger ones may be in flight
-    if (PRIO == 2 && grp == 1) __builtin_amdgcn_s_setprio(1);
+    PP_STAGE(0, 0) PP_STAGE(1, 1) PP_STAGE(2, 2) PP_STAGE(3, 3) PP_STAGE(4, 0) PP_STAGE(5, 1) PP_STAGE(6, 2)
+    wait_vm<8>();                                               // half-tiles 0..2 (what phase X of the first K-tile reads)
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
-    PP_READ_B(fb0, 0, 0)
-    if (grp == 1) __builtin_amdgcn_s_barrier();                     // the second group runs one barrier behind the first
+    if (grp == 1) __builtin_amdgcn_s_barrier();                 // the second group runs one barrier behind the first
     if (p.dbg_trace) tr1 = wall_clock64();
-
-    // phase m = 4 * tile + q: reads half-tile m + 1, stages half-tile m + 1 + PP_LEAD and waits for half-tile m + 2 (the
-    // PP_LEAD - 1 = 3 half-tiles staged after it may stay in flight)
-#define PP_PHASE(M_, Q, READS, RH, CH, FB)                                                     \
+#define PP_BIGPHASE(READS, STAGES, RH, CA, FA_, CB, FB_)                                       \
     {                                                                                          \
-        READS                                                                                  \
-        PP_STAGE((M_) + 1 + PP_LEAD, ((Q) + 1 + PP_LEAD) & 3)                                  \
-        wait_vm<2 * (PP_LEAD - 1)>();                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-        __builtin_amdgcn_s_barrier();                                                          \
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                     \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-        PP_CLUSTER(RH, CH, FB)                                                                 \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
-        __builtin_amdgcn_s_barrier();                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                     \
+    READS                                                                                  \
+    STAGES                                                                                 \
+    wait_vm<8>();                                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                                     \
+    __builtin_amdgcn_s_barrier();                                                          \
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                     \
+    __builtin_amdgcn_sched_barrier(0);                                                     \
+    PP_CLUSTER(RH, CA, FA_)                                                                \
+    PP_CLUSTER(RH, CB, FB_)                                                                \
+    asm volatile("" : "+v"(acc[2 * (RH)][0]), "+v"(acc[2 * (RH) + 1][0]), "+v"(acc[2 * (RH)][1]), "+v"(acc[2 * (RH) + 1][1])); \
+    __builtin_amdgcn_sched_barrier(0);                                                     \
+    __builtin_amdgcn_s_barrier();                                                          \
+    __builtin_amdgcn_sched_barrier(0);                                                     \
     }
-    // One K-tile per trip.  The ring parity is a bit of the fragment addresses (slot = parity * 32 KiB + half * 16 KiB inside each
-    // operand's 64 KiB region; the lane-dependent part stays below 16 KiB), toggled once per tile, so the loop body is the same
-    // for every tile and each accumulator lives in one set of registers.  B half 0 of the NEXT tile is read into fb1 during the
-    // fourth phase (fb1 is free after the third) and moved to fb0 behind that phase's MFMAs.
     for (int tt = 0; tt < ntile; ++tt) {
-        PP_PHASE(4 * tt + 0, 0, PP_READ_A(0, 0), 0, 0, fb0)
-        PP_PHASE(4 * tt + 1, 1, PP_READ_B(fb1, 0, 1), 0, 1, fb1)
-        PP_PHASE(4 * tt + 2, 2, PP_READ_A(0, 1), 1, 1, fb1)
+        PP_BIGPHASE(PP_READ_B(fb0, 0, 0) PP_READ_A(0, 0) PP_READ_B(fb1, 0, 1), PP_STAGE(4 * tt + 7, 3), 0, 0, fb0, 1, fb1)
         frb.toggle(2 * PP_HALF);
-        PP_PHASE(4 * tt + 3, 3, PP_READ_B(fb1, 0, 0), 1, 0, fb0)
+        PP_BIGPHASE(PP_READ_A(0, 1), PP_STAGE(4 * tt + 8, 0) PP_STAGE(4 * tt + 9, 1) PP_STAGE(4 * tt + 10, 2), 1, 1, fb1, 0, fb0)
         fra.toggle(2 * PP_HALF);
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) fb0[kk] = fb1[kk];
     }
-#undef PP_PHASE
-    }
+#undef PP_BIGPHASE
 #undef PP_STAGE
 #undef PP_READ_A
 #undef PP_READ_B
@@ -1470,12 +1436,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(typename std::condition
         if (fastep) {
             pp_epilogue_bf16<EK>(p, acc, reinterpret_cast<char*>(wlds), m0, c0, c1, grp, lane);
             if (pf_ok) wait_vm<16>();                                // >= 16 stores were issued after the tail's copies: those have landed
-            if (p.dbg_trace && tid == 0) {
-                const unsigned long long tr3 = wall_clock64();
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                unsigned long long* d = p.dbg_trace + (long)blockIdx.x * 5;
-                d[0] = tr0; d[1] = tr1; d[2] = tr2; d[3] = wall_clock64(); d[4] = tr3;
-            }
+            pp_trace_end(p, tid, tr0, tr1, tr2);
             return;
         }
     }
@@ -1490,24 +1451,14 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(typename std::condition
         if (direct) {
             pp_epilogue_f32_direct(p, acc, m0, c0, c1, grp, lane);
             if (pf_ok) wait_vm<63>();                                // 128 stores behind the tail's copies
-            if (p.dbg_trace && tid == 0) {
-                const unsigned long long tr3 = wall_clock64();
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                unsigned long long* d = p.dbg_trace + (long)blockIdx.x * 5;
-                d[0] = tr0; d[1] = tr1; d[2] = tr2; d[3] = wall_clock64(); d[4] = tr3;
-            }
+            pp_trace_end(p, tid, tr0, tr1, tr2);
             return;
         }
     }
     if constexpr (ATOMIC_DIRECT && sizeof(TO) == 4) {
         if (atomic && !p.dbg_skip_epilogue && m0 + 256 <= p.M && n0 + 256 <= p.N) {
             pp_epilogue_atomic_direct(p, acc, m0, c0, c1, grp, lane);
-            if (p.dbg_trace && tid == 0) {
-                const unsigned long long tr3 = wall_clock64();
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                unsigned long long* d = p.dbg_trace + (long)blockIdx.x * 5;
-                d[0] = tr0; d[1] = tr1; d[2] = tr2; d[3] = wall_clock64(); d[4] = tr3;
-            }
+            pp_trace_end(p, tid, tr0, tr1, tr2);
             return;
         }
     }
@@ -1522,19 +1473,14 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(typename std::condition
     }
     flush_colsum(p, cs, c0, c1, lane);
     if (pf_ok) wait_vm<0>();
-    if (p.dbg_trace && tid == 0) {
-        const unsigned long long tr3 = wall_clock64();               // every store of this wave is issued
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // ... and acknowledged
-        unsigned long long* d = p.dbg_trace + (long)blockIdx.x * 5;
-        d[0] = tr0; d[1] = tr1; d[2] = tr2; d[3] = wall_clock64(); d[4] = tr3;
-    }
+    pp_trace_end(p, tid, tr0, tr1, tr2);
 }
 
-template <typename TO, bool TA, bool TB, int LEAD = 4, int PRIO = 1, int BIG = 0, int EK = 1>
+template <typename TO, bool TA, bool TB, int EK = 1>
 int launch_pp(const GemmParams& p, int splitk, hipStream_t stream) {
     constexpr int SMEM = 9 * PP_HALF;
     static bool configured = false;
-    auto kern = gemm_pp_kernel<TO, TA, TB, LEAD, PRIO, BIG, EK>;
+    auto kern = gemm_pp_kernel<TO, TA, TB, EK>;
     if (!configured) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
         if (e != hipSuccess) return simseg_set_error("simseg_gemm: cannot reserve %d bytes of LDS: %s", SMEM, hipGetErrorString(e));
@@ -1594,10 +1540,9 @@ __device__ __forceinline__ PP2Item pp2_item(const GemmParams& p, int t, int tile
     return it;
 }
 
-// SCHED (where a phase's two global->LDS copies are issued; the load segment of a phase - fragment reads + copies + waits - measured
-// longer than the 8-MFMA segment it is supposed to hide under): 0 = both in the load segment (the per-tile kernel's order), 1 = both
-// inside the wave's own MFMA cluster, 2 = one and one, 3 = both in the load segment but ahead of the fragment reads.
-template <typename TO, bool TA, bool TB, int SCHED = 0, int EK = 1>
+// A phase's two global->LDS copies are issued in its load segment, behind the fragment reads (placing them inside the MFMA cluster or
+// ahead of the reads computed the same and measured no better: profiles/HISTORY.md).
+template <typename TO, bool TA, bool TB, int EK = 1>
 __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1661,13 +1606,11 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmParams p) {
 #define PP_READ_B(FB, HALF) \
     _Pragma("unroll") for (int kk_ = 0; kk_ < 4; ++kk_) FB[kk_] = frb.read(lds, (HALF) * PP_HALF, 0, kk_);
 #define PP_MMA(RH, CH, FB, KK, I) mma<bf16_t>(acc[2 * (RH) + (I)][CH], fa[(I) * 4 + (KK)], FB[KK]);
-    // the wave group's 8 MFMAs of a phase; copies placed inside the cluster go behind the 2nd / 5th MFMA (the matrix pipe has work queued)
-#define PP_CLUSTER(RH, CH, FB, KIND, PRE)                                                            \
+    // the wave group's 8 MFMAs of a phase
+#define PP_CLUSTER(RH, CH, FB)                                                                       \
     __builtin_amdgcn_s_setprio(1);                                                                   \
     PP_MMA(RH, CH, FB, 0, 0) PP_MMA(RH, CH, FB, 0, 1)                                                \
-    if (SCHED == 1) { __builtin_amdgcn_sched_barrier(0); PRE PP2_PIECE(KIND, 0) __builtin_amdgcn_sched_barrier(0); } \
     PP_MMA(RH, CH, FB, 1, 0) PP_MMA(RH, CH, FB, 1, 1) PP_MMA(RH, CH, FB, 2, 0)                       \
-    if (SCHED == 1 || SCHED == 2) { __builtin_amdgcn_sched_barrier(0); PP2_PIECE(KIND, 1) __builtin_amdgcn_sched_barrier(0); } \
     PP_MMA(RH, CH, FB, 2, 1) PP_MMA(RH, CH, FB, 3, 0) PP_MMA(RH, CH, FB, 3, 1)                       \
     /* the cluster's results are "used" here: without this the optimiser sinks the MFMAs (pure register operations) out of the */ \
     /* priority / barrier bracket into the next phase's load segment */                               \
@@ -1678,16 +1621,14 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmParams p) {
     // staging state's step to the next K-tile, ahead of the first copy of a B half 0.
 #define PP_PHASE(READS, KIND, PRE, RH, CH, FB)                                                 \
     {                                                                                          \
-        if (SCHED == 3) { PRE PP2_STAGE(KIND) }                                                \
         READS                                                                                  \
-        if (SCHED == 0) { PRE PP2_STAGE(KIND) }                                                \
-        if (SCHED == 2) { PRE PP2_PIECE(KIND, 0) }                                             \
-        wait_vm<SCHED == 1 ? 4 : (SCHED == 2 ? 5 : 6)>();                                      \
+        PRE PP2_STAGE(KIND)                                                                    \
+        wait_vm<6>();                                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                     \
         __builtin_amdgcn_s_barrier();                                                          \
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                                     \
         __builtin_amdgcn_sched_barrier(0);                                                     \
-        PP_CLUSTER(RH, CH, FB, KIND, PRE)                                                      \
+        PP_CLUSTER(RH, CH, FB)                                                                 \
         __builtin_amdgcn_sched_barrier(0);                                                     \
         __builtin_amdgcn_s_barrier();                                                          \
         __builtin_amdgcn_sched_barrier(0);                                                     \
@@ -1782,12 +1723,12 @@ bool pp2_ok(const GemmParams& p, int splitk) {
     return !p.aux && p.act == 0 && !p.colsum && !p.accumulate;
 }
 
-template <typename TO, bool TA, bool TB, int SCHED = 0, int EK = 1>
+template <typename TO, bool TA, bool TB, int EK = 1>
 int launch_pp2(const GemmParams& p, hipStream_t stream, int reserve = 0) {
     constexpr int SMEM = 9 * PP_HALF;
     static bool configured = false;
     static int blocks = 0;
-    auto kern = gemm_pp2_kernel<TO, TA, TB, SCHED, EK>;
+    auto kern = gemm_pp2_kernel<TO, TA, TB, EK>;
     if (!configured) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
         if (e != hipSuccess) return simseg_set_error("simseg_gemm: cannot reserve %d bytes of LDS: %s", SMEM, hipGetErrorString(e));
@@ -1799,7 +1740,7 @@ int launch_pp2(const GemmParams& p, hipStream_t stream, int reserve = 0) {
     }
     GemmParams q = p;
     q.ksplit = p.K / 64; q.nsplit = 1;
-    // reserve > 0 (variant 18): that many CUs are left to the kernels of the other stream - a persistent launch never hands a CU back, so
+    // reserve > 0 (SIMSEG_GEMM_PP2_RESERVE): that many CUs are left to the kernels of the other stream - a persistent launch never hands a CU back, so
     // without a reserve the other tower's kernels wait for whole GEMM launches (the -6.7 % of round 3's first half)
     const int nb = reserve > 0 ? ((blocks - reserve) & ~7) : blocks;
     hipLaunchKernelGGL(kern, dim3(nb < 8 ? 8 : nb, 1, 1), dim3(512), SMEM, stream, q);
@@ -1809,22 +1750,11 @@ int launch_pp2(const GemmParams& p, hipStream_t stream, int reserve = 0) {
 
 
 
-// Debug / benchmarking selectors.  Thread-local: the entry points are otherwise stateless and re-entrant, and a selector set by a
+// Test / benchmarking selectors.  Thread-local: the entry points are otherwise stateless and re-entrant, and a selector set by a
 // benchmark thread never changes what another caller's simseg_gemm launches.
-thread_local int g_gemm_debug_skip_epilogue = 0;
+thread_local int g_gemm_variant = 0;           // simseg_set_gemm_variant: 0 auto, 1 / 3 / 4 / 5 / 10 force one of the kernels below
+thread_local int g_gemm_last_variant = 0;      // the kernel the last call launched: 1 / 3 / 4 / 5 / 10 (same numbering)
 thread_local unsigned long long* g_gemm_debug_trace = nullptr;
-thread_local int g_gemm_stagger = 0;
-thread_local int g_gemm_wgrad_blocks = 0;      // > 0: the split-K weight gradients use at most this many 256x256 blocks (simseg_debug_gemm_wgrad_blocks)
-thread_local int g_gemm_last_variant = 0;      // 1 = 128x128 register-staged, 2 = 256x256 direct-to-LDS, 3 = 256x256 ping-pong
-// variant: 0 = auto, 1 = 128x128 register-staged, 2 = 256x256 direct-to-LDS (BK64, 2 stages).  Other points of the design
-// space were measured and dropped (profiles/r1_gemm_variants.txt): 256x256 with a 4-deep BK32 ring, 256x128 at 2 blocks/CU,
-// 128x128 with BK=128, 256x128 with a 3-deep BK32 ring at 2 blocks/CU (563 vs 741 TFLOP/s aggregate), a persistent 256x256 kernel with
-// cross-tile prefetch, an LDS-free epilogue on transposed accumulators (8-byte stores straight from registers: same time), a persistent
-// one-block-per-CU kernel that defers a tile's stores into the first eight K-slabs of the next tile (NT +1 %, NN slower), non-temporal
-// 16-byte output stores (same time; non-temporal 8-byte stores 30-50 % slower), four waves of 128x128 per block as the vendor library does (launch_large<..., 2, 2, 1>: 256 VGPR + 256 AGPR, no
-// spills, correct, but 556 vs 673 TFLOP/s aggregate with compiler scheduling at one wave per SIMD), 256x128 tiles on four 128x64 waves at two
-// blocks per CU so that one block's epilogue overlaps the other's K loop (launch_large<..., 32, 2|3, 256, 128, 2, 2, 2>: 630 vs 670), delaying the first round's blocks by 1/4..3/4 of a tile so the CUs' store bursts do not coincide (-1..-6 %), deeper BK32 rings (4 and 5 stages) and a
-// two-group ping-pong schedule of the 256x256 kernel (MFMA phase of one wave per SIMD against the load phase of the other).
 
 // =================================================================================================================
 // Small-problem kernel: the reference tool's batch-1 call pattern (tools/seg_evaluation.py:84-85, 109: one image per forward ->
@@ -1960,177 +1890,113 @@ int dispatch_small(const GemmParams& p, hipStream_t s) {
     return launch_small<T, TO, 1, 4>(p, s);
 }
 
-thread_local int g_gemm_variant = 0;
-
-// the persistent kernel's instantiation for this call's epilogue kind (see pp_epilogue_bf16: each heavy kind has kernels of its own)
-template <typename TO, bool TA, bool TB>
-int launch_pp2_ek(const GemmParams& p, hipStream_t s, int reserve) {
-    if constexpr (sizeof(TO) == 2) {      // (the kinds exist for 16-bit outputs only; the blocked image: fc1 forward = NT, dgrad through fc2 = NN)
-        if (p.act == 4 && !p.aux_blocked) return launch_pp2<TO, TA, TB, 0, 1>(p, s, reserve);
-        if constexpr (!TB) { if (p.act == 3 && p.aux_blocked == 1) return launch_pp2<TO, TA, TB, 0, 2>(p, s, reserve); }
-        if constexpr (TB) { if (p.act == 4 && p.aux_blocked == 1) return launch_pp2<TO, TA, TB, 0, 3>(p, s, reserve); }
-        if constexpr (!TB) { if (p.act == 3 && p.aux_blocked == 2) return launch_pp2<TO, TA, TB, 0, 4>(p, s, reserve); }
-        if constexpr (TB) { if (p.act == 4 && p.aux_blocked == 2) return launch_pp2<TO, TA, TB, 0, 5>(p, s, reserve); }
+// Calls f(std::integral_constant<int, EK>) with the epilogue kind (EK of pp_epilogue_bf16) of a ping-pong launch.  The blocked image is
+// saved by the fc1 forward (x . W^T: act 3, EK 2 / 4) and read by the dgrad through fc2 (d . W: act 4, EK 3 / 5), 16-bit outputs only.
+template <typename TO, bool TB, typename F>
+int with_pp_kind(const GemmParams& p, F&& f) {
+    if constexpr (sizeof(TO) == 2) {
+        if constexpr (!TB) {
+            if (p.act == 3 && p.aux_blocked == 1) return f(std::integral_constant<int, 2>{});
+            if (p.act == 3 && p.aux_blocked == 2) return f(std::integral_constant<int, 4>{});
+        } else {
+            if (p.act == 4 && p.aux_blocked == 1) return f(std::integral_constant<int, 3>{});
+            if (p.act == 4 && p.aux_blocked == 2) return f(std::integral_constant<int, 5>{});
+        }
+        if (!p.aux_blocked && p.act != 4) return f(std::integral_constant<int, 0>{});
     }
-    if (p.aux_blocked) return simseg_set_error("simseg_gemm: act 5 is a forward (x . W^T) epilogue, act 6 a dgrad (d . W) epilogue, both with 16-bit outputs");
-    return launch_pp2<TO, TA, TB, 0, 0>(p, s, reserve);
+    if (p.aux_blocked) return simseg_set_error("simseg_gemm: act 5 / 7 is a forward (x . W^T) epilogue, act 6 / 8 a dgrad (d . W) epilogue, both with 16-bit outputs");
+    return f(std::integral_constant<int, 1>{});      // times the row-major saved derivative; every fp32 output
 }
 
+// The 16-bit dispatch, in the order the kernels are tried: weight-gradient split-K and the forward / dgrad problems of many tiles on the
+// 256x256 ping-pong kernels (persistent or one tile per block), one round of 128x128 tiles on the direct-to-LDS ring, everything else on
+// the 128x128 register-staged kernel.  (The small-problem kernel is taken in simseg_gemm, ahead of this.)  A forced selector (sel != 0)
+// replaces a kernel's measured size rule, never its requirements; a call it does not apply to ends on the 128x128 kernel.
 template <typename TO, bool TA, bool TB>
 int dispatch_bf16(const GemmParams& p, int splitk, bool aligned, hipStream_t s) {
+    const int sel = g_gemm_variant;
     const bool big_ok = aligned && p.K % 64 == 0 && p.M >= 256 && p.N >= 128;
-    const bool four_phase = g_gemm_variant == 15;       // 15 = the automatic choice, ping-pong kernel on its four-phase schedule (A/B runs)
-    int v = (four_phase || g_gemm_variant == 16 || g_gemm_variant == 18) ? 0 : g_gemm_variant;
     const int nk64 = p.K / 64;
     const int kper = (nk64 + (splitk > 1 ? splitk : 1) - 1) / (splitk > 1 ? splitk : 1);   // 64-deep slabs per block
-    // measured (profiles/r1_gemm_variants.txt, after the epilogue was rolled to fit the instruction cache): the 256x256
-    // direct-to-LDS kernel wins for k-contiguous A from K >= 768 on when there is at least one tile per CU; split-K wgrad
-    // (transposed A) and small problems stay on the 128x128 kernel (3 blocks/CU, more blocks to spread)
     const int tiles256 = ((p.M + 255) / 256) * ((p.N + 255) / 256);
     if constexpr (TA && sizeof(TO) == 4) {
         // split-K weight gradient (accumulating into a zero-filled fp32 output): the caller's slice count targets the 128x128
         // kernel; for the 256x256 kernel pick the largest count that still fits ONE round of 256 blocks (a 288-block launch
         // runs two rounds, the second 12 % full)
-        if ((v == 0 || v == 6 || v == 3) && v != 7 && big_ok && p.accumulate && splitk > 1 && p.M % 256 == 0 && p.N % 256 == 0 && tiles256 <= 128) {
+        if ((sel == 0 || sel == 3) && big_ok && p.accumulate && splitk > 1 && p.M % 256 == 0 && p.N % 256 == 0 && tiles256 <= 128) {
             int sk = 256 / tiles256;
-            static const int env_blocks = getenv("SIMSEG_GEMM_WGRAD_BLOCKS") ? atoi(getenv("SIMSEG_GEMM_WGRAD_BLOCKS")) : 0;      // (process-wide: backward runs on autograd's threads)
-            const int wb = g_gemm_wgrad_blocks > 0 ? g_gemm_wgrad_blocks : env_blocks;
-            if (wb > 0) sk = wb / tiles256 > 0 ? wb / tiles256 : 1;      // (CU-partition experiments)
             if (nk64 / sk < 16 && nk64 >= 64) sk = nk64 / 16;        // short contraction (packed text rows): fewer, 16-deep slices
-            if (nk64 / sk >= 16 && tiles256 * sk >= 96 && (v == 3 || v == 0)) {
+            if (nk64 / sk >= 16 && tiles256 * sk >= 96) {
                 g_gemm_last_variant = 3;
-                return four_phase ? launch_pp<TO, TA, TB>(p, sk, s) : launch_pp<TO, TA, TB, 4, 1, 1>(p, sk, s);
+                return launch_pp<TO, TA, TB>(p, sk, s);
             }
-            if (nk64 / sk >= 16 && v == 6) { g_gemm_last_variant = 2; return launch_large<TO, TA, TB, 64, 2, 256, 256, 2, 4, 2>(p, sk, s); }
         }
-        if (v == 3) v = 0;
-        if (v == 6) v = 0;
-        if (v == 7) v = 1;
     }
-    // (measured, tools/gemm_mid_bench.py: the ping-pong kernel is ahead of the 128x128 one from ~96 of its tiles on - e.g. the packed text
-    //  tower's ~22 k x 768 problems, 255 tiles: 34 vs 52 us at K = 768, 98 vs 151 us at K = 3072)
-    // Round 5 (tools/gemm_vits_bench.py, the ViT-S forward shapes at M = 262400): a SHORT contraction (K = 384: six slabs) is still 22-26 %
-    // faster on the ping-pong kernel once the problem is many rounds of tiles (qkv 502 -> 373 us, fc1 671 -> 521 us); and a column count that
-    // leaves the last 256-wide tile mostly empty (N = 384: a third of the matrix work wasted) is better off on the 128x128 kernel up to K ~ 2500
-    // (fc2 at K = 1536: 653 -> 543 us; from K = 3072 on the long K loop wins again: 223 vs 177 us at M = 64575).
-    if (v == 0) {
+    if constexpr (!TA) {
+        // (measured, tools/gemm_mid_bench.py: the ping-pong kernel is ahead of the 128x128 one from ~96 of its tiles on - e.g. the packed text
+        //  tower's ~22 k x 768 problems, 255 tiles: 34 vs 52 us at K = 768, 98 vs 151 us at K = 3072)
+        // Round 5 (tools/gemm_vits_bench.py, the ViT-S forward shapes at M = 262400): a SHORT contraction (K = 384: six slabs) is still 22-26 %
+        // faster on the ping-pong kernel once the problem is many rounds of tiles (qkv 502 -> 373 us, fc1 671 -> 521 us); and a column count that
+        // leaves the last 256-wide tile mostly empty (N = 384: a third of the matrix work wasted) is better off on the 128x128 kernel up to K ~ 2500
+        // (fc2 at K = 1536: 653 -> 543 us; from K = 3072 on the long K loop wins again: 223 vs 177 us at M = 64575).
         const int pad_n = ((p.N + 255) / 256) * 256 - p.N;
         const bool n_fits = pad_n * 6 <= p.N || kper >= 40;               // <= 1/6 of the columns are padding - or a contraction long enough
                                                                             // (K >= 2560: the split-bf16 form of an fp32 product) to make up for it
-        v = (big_ok && !TA && tiles256 >= 96 && n_fits && (kper >= 12 || (kper >= 6 && tiles256 >= 1024))) ? 3 : 1;
-    }
-    if (v >= 10 && v <= 13 && !(big_ok && !TA)) v = 1;
-    // one round of 128x128 tiles (more than the small-problem kernel takes, at most a block per CU): the ring variant's three slabs in
-    // flight beat the register-staged kernel's one (14.7 vs 16.8 us on 1025 x 2304 x 768)
-    const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
-    if (v == 1 && (g_gemm_variant == 0 || g_gemm_variant >= 15) && !TA && !TB && splitk <= 1 && t128 >= 160 && t128 <= 256) v = 5;
-    if (v == 8 || v == 9) {      // experiments: 256x128 / 128x256 tiles, 4-wave blocks, two blocks per CU (one block's epilogue under the other's K loop)
-        if (aligned && p.K % 32 == 0 && p.M >= 256 && p.N >= 256) {
-            g_gemm_last_variant = v;
-            if (v == 8) return launch_large<TO, TA, TB, 32, 3, 256, 128, 2, 2, 2>(p, splitk, s);
-            return launch_large<TO, TA, TB, 32, 3, 128, 256, 2, 2, 2>(p, splitk, s);
-        }
-        v = 1;
-    }
-    if (v == 5) {      // 128x128 tile on the direct-to-LDS ring (4 stages): mid-size problems, one block per CU
-        if (aligned && p.K % 64 == 0 && p.M >= 128 && p.N >= 128) { g_gemm_last_variant = 5; return launch_large<TO, TA, TB, 64, 4, 128, 128, 2, 2, 1>(p, splitk, s); }
-        v = 1;
-    }
-    if (!big_ok) v = 1;
-    g_gemm_last_variant = v;
-    if (p.aux_blocked && !(v == 3 || (v >= 10 && v <= 13)))
-        return simseg_set_error("simseg_gemm: act 5 / 6 (tile-blocked saved derivative) needs the 256x256 ping-pong kernel; this call dispatches to variant %d", v);
-    if (v == 3 || (v >= 10 && v <= 13)) {
-        // more than one round of full tiles with an accumulator-layout epilogue: the persistent kernel (10 forces it wherever it
-        // applies, 3 forces the per-tile kernel - A/B runs)
-        // (variant 10 forces it wherever it applies, 11-13 are its schedule experiments; profiles/r3_gemm_persistent_ab.txt: +6 % over the
-        // per-tile kernel on the training shapes in isolation)
-        if constexpr (!TA) {
-            // The persistent kernel is the default for problems of >= 600 full tiles (SIMSEG_GEMM_PP2_MIN_TILES; variant 3 forces the per-tile
-            // kernel).  Measured in the default two-stream training step, same box, two rounds each: 90.9-91.4 ms per-tile -> 88.1-88.4 ms
-            // (thresholds 257..1100 within 0.3 ms of each other, 2000: 89.5); single stream 94.9 -> 93.8 ms.  The first half of round 3 had
-            // found the opposite (100.1 vs 93.8 ms) - with variant 10, which ALSO takes the split-K weight gradients off the ping-pong kernel
-            // (the `v >= 10 && !(big_ok && !TA)` rule below sends them to the 128x128 kernel): that, not the persistence, was the loss.
+        const bool pp_auto = tiles256 >= 96 && n_fits && (kper >= 12 || (kper >= 6 && tiles256 >= 1024));
+        if (big_ok && (sel == 0 ? pp_auto : ((sel == 3 || sel == 10) && p.K >= 128))) {
+            // More than one round of full tiles with an accumulator-layout epilogue: the persistent kernel, by default for problems of >= 600
+            // full tiles.  Measured in the default two-stream training step, same box, two rounds each: 90.9-91.4 ms per-tile -> 88.1-88.4 ms
+            // (thresholds 257..1100 within 0.3 ms of each other, 2000: 89.5); single stream 94.9 -> 93.8 ms.
             // SIMSEG_GEMM_PP2_RESERVE leaves CUs to the other stream's kernels (0, 8, 32 measured within 0.4 ms; 40+ slower): default 0.
-            static int reserve = -1, min_tiles = -1;
-            if (reserve < 0) {
-                const char* e = getenv("SIMSEG_GEMM_PP2_RESERVE"); reserve = e ? atoi(e) : 0;
-                e = getenv("SIMSEG_GEMM_PP2_MIN_TILES"); min_tiles = e ? atoi(e) : 600;
-            }
-            // (the times-saved-derivative epilogue stays on the per-tile kernel unless SIMSEG_GEMM_PP2_ACT4=1: beside the persistent kernel's tile-walking
-            //  state its 32 column-sum partials spill - 0.709 vs 0.709 ms on the fc2 dgrad, 2-6 % slower on the other shapes, tools/gemm_ab.py --act 4)
-            static int act4 = -1;
-            if (act4 < 0) { const char* e = getenv("SIMSEG_GEMM_PP2_ACT4"); act4 = e ? atoi(e) : 0; }
-            if ((g_gemm_variant == 18 || g_gemm_variant == 0) && tiles256 >= min_tiles && (p.act != 4 || p.aux_blocked || act4) && pp2_ok<TO>(p, splitk)) {
+            // The times-saved-derivative epilogue on a row-major tensor stays on the per-tile kernel: beside the persistent kernel's tile-walking
+            // state its 32 column-sum partials spill (0.709 vs 0.709 ms on the fc2 dgrad, 2-6 % slower on the other shapes).
+            static const int reserve = getenv("SIMSEG_GEMM_PP2_RESERVE") ? atoi(getenv("SIMSEG_GEMM_PP2_RESERVE")) : 0;
+            if ((sel == 10 || (sel == 0 && tiles256 >= 600)) && (p.act != 4 || p.aux_blocked) && pp2_ok<TO>(p, splitk)) {
                 g_gemm_last_variant = 10;
-                return launch_pp2_ek<TO, TA, TB>(p, s, reserve);
+                return with_pp_kind<TO, TB>(p, [&](auto ek) {      // (the persistent kernel's fp32-output instantiations are the EK = 0 ones)
+                    return launch_pp2<TO, TA, TB, decltype(ek)::value == 1 ? 0 : decltype(ek)::value>(p, s, sel == 0 ? reserve : 0);
+                });
             }
-            if (g_gemm_variant >= 10 && g_gemm_variant <= 13 && pp2_ok<TO>(p, splitk)) {
-                g_gemm_last_variant = 10;
-                if (g_gemm_variant != 10 && p.aux_blocked) return simseg_set_error("simseg_gemm: the schedule experiments (variants 11-13) do not carry the tile-blocked epilogues");
-                switch (g_gemm_variant) {           // 11..13: schedule experiments (see SCHED)
-                    case 11: return launch_pp2<TO, TA, TB, 1>(p, s);
-                    case 12: return launch_pp2<TO, TA, TB, 2>(p, s);
-                    case 13: return launch_pp2<TO, TA, TB, 3>(p, s);
-                    default: return launch_pp2_ek<TO, TA, TB>(p, s, 0);
-                }
-            }
+            g_gemm_last_variant = 3;
+            return with_pp_kind<TO, TB>(p, [&](auto ek) { return launch_pp<TO, TA, TB, decltype(ek)::value>(p, splitk, s); });
         }
-        g_gemm_last_variant = 3;
-        // 16-MFMA phases (round 3) unless variant 15 asks for the four-phase schedule (A/B runs)
-        if (!four_phase && p.K >= 128) {
-            if constexpr (sizeof(TO) == 2 && !TA) {
-                if constexpr (!TB) { if (p.act == 3 && p.aux_blocked == 1) return launch_pp<TO, TA, TB, 4, 1, 1, 2>(p, splitk, s); }
-                if constexpr (TB) { if (p.act == 4 && p.aux_blocked == 1) return launch_pp<TO, TA, TB, 4, 1, 1, 3>(p, splitk, s); }
-                if constexpr (!TB) { if (p.act == 3 && p.aux_blocked == 2) return launch_pp<TO, TA, TB, 4, 1, 1, 4>(p, splitk, s); }
-                if constexpr (TB) { if (p.act == 4 && p.aux_blocked == 2) return launch_pp<TO, TA, TB, 4, 1, 1, 5>(p, splitk, s); }
-            }
-            if (p.aux_blocked) return simseg_set_error("simseg_gemm: act 5 is a forward (x . W^T) epilogue, act 6 a dgrad (d . W) epilogue");
-            if (sizeof(TO) == 2 && p.act != 4) return launch_pp<TO, TA, TB, 4, 1, 1, 0>(p, splitk, s);
-            return launch_pp<TO, TA, TB, 4, 1, 1>(p, splitk, s);
-        }
-        if (p.aux_blocked) return simseg_set_error("simseg_gemm: the four-phase schedule (variant 15) does not carry the tile-blocked epilogues");
-        return launch_pp<TO, TA, TB>(p, splitk, s);
     }
-    if (v == 2) return launch_large<TO, TA, TB, 64, 2, 256, 256, 2, 4, 2>(p, splitk, s);
+    if (p.aux_blocked)
+        return simseg_set_error("simseg_gemm: act 5 - 8 (tile-blocked saved derivative) need the 256x256 ping-pong kernel; this call does not dispatch to it");
+    if constexpr (!TA && !TB) {
+        // one round of 128x128 tiles (more than the small-problem kernel takes, at most a block per CU): the ring's three slabs in
+        // flight beat the register-staged kernel's one (14.7 vs 16.8 us on 1025 x 2304 x 768)
+        const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128);
+        const bool ring_ok = aligned && p.K % 64 == 0 && p.M >= 128 && p.N >= 128 && splitk <= 1;
+        if (ring_ok && (sel == 5 || (sel == 0 && t128 >= 160 && t128 <= 256))) {
+            g_gemm_last_variant = 5;
+            return launch_large<TO, TA, TB, 64, 4, 128, 128, 2, 2, 1>(p, splitk, s);
+        }
+    }
+    g_gemm_last_variant = 1;
     return launch<bf16_t, TO, TA, TB>(p, splitk, s);
 }
 
 }  // namespace
 
-// which kernel the calling thread's last simseg_gemm launched: 1 = 128x128 register-staged, 2 = 256x256 direct-to-LDS ring,
-// 3 = 256x256 ping-pong, 4 = small-problem kernel (the measurement code labels its per-kernel timings with this instead of re-deriving the dispatch rule)
+// which kernel the calling thread's last simseg_gemm launched: 1 = 128x128 register-staged, 3 = 256x256 ping-pong (one tile per block),
+// 4 = small-problem kernel, 5 = 128x128 ring, 10 = persistent ping-pong (the measurement code labels its per-kernel timings with this
+// instead of re-deriving the dispatch rule)
 extern "C" int simseg_gemm_last_variant(void) {
     SS_HALF_FWD(simseg_gemm_last_variant); return g_gemm_last_variant; }
 
-// debugging: the ping-pong kernel writes 5 x u64 per block (start / K loop start / K loop end / end wall-clock stamps at 100 MHz, HW_ID)
-extern "C" int simseg_debug_gemm_stagger(int ticks) {
-#ifndef SS_GEMM_ABLATE
-    SS_CHECK(ticks < 1000, "debug_gemm_stagger: %d selects an epilogue ablation, which this build does not contain (-DSS_GEMM_ABLATE)", ticks);
-#endif
-    g_gemm_stagger = ticks;
-    return 0;
-}
-extern "C" int simseg_debug_gemm_wgrad_blocks(int blocks) {
-#ifndef SS_HALF
-    simseg_debug_gemm_wgrad_blocks_h16(blocks);
-#endif
-    g_gemm_wgrad_blocks = blocks;
-    return 0;
-}
+// debugging: the per-tile ping-pong kernel writes 5 x u64 per block (start / K loop start / K loop end / end wall-clock stamps at 100 MHz, HW_ID)
 extern "C" int simseg_debug_gemm_trace(void* buf) { g_gemm_debug_trace = static_cast<unsigned long long*>(buf); return 0; }
 
 extern "C" int simseg_set_gemm_variant(int v) {
+    SS_CHECK(v == 0 || v == 1 || v == 3 || v == 4 || v == 5 || v == 10,
+             "set_gemm_variant: %d is not a kernel selection (0 = auto, 1 = 128x128, 3 = ping-pong per tile, 4 = small-problem, 5 = 128x128 ring, 10 = persistent ping-pong)", v);
 #ifndef SS_HALF
     simseg_set_gemm_variant_h16(v);      // the fp16 flavour keeps its own (thread-local) selector
 #endif
-    g_gemm_debug_skip_epilogue = v >= 100;
-    g_gemm_variant = v % 100;
+    g_gemm_variant = v;
     return 0;
 }
-
-namespace {
-}  // namespace
 
 extern "C" int simseg_patch_text_sim(const void* x, const void* text, float* out, int64_t M, int64_t C, int64_t K, int dtype,
                                      float eps, int normalize, void* stream) {
@@ -2192,19 +2058,16 @@ extern "C" int simseg_gemm_wgrad_group(const int64_t* problems, int n, int64_t r
     g.n = n; g.rows = (int)rows;
     g.dbg_trace = g_gemm_debug_trace;
     // the adds from the accumulator layout (median block epilogue 9.1 against 23.9 us on the ViT-B block, 17.0 against 30.0 us on a 21 760-row
-    // text block: profiles/wgrad_group.txt); SIMSEG_GEMM_WGRAD_DIRECT=0: the staged epilogue (A/B runs; process-wide)
-    static const bool direct = !(getenv("SIMSEG_GEMM_WGRAD_DIRECT") && atoi(getenv("SIMSEG_GEMM_WGRAD_DIRECT")) == 0);
+    // text block: profiles/wgrad_group.txt)
     constexpr int SMEM = 9 * PP_HALF;
+    auto kern = gemm_pp_kernel<float, true, true, 1, true, true>;
     static bool configured = false;
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<float, true, true, 4, 1, 1, 1, true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pp_kernel<float, true, true, 4, 1, 1, 1, true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
         if (e != hipSuccess) return simseg_set_error("simseg_gemm_wgrad_group: cannot reserve %d bytes of LDS: %s", SMEM, hipGetErrorString(e));
         configured = true;
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (direct) hipLaunchKernelGGL((gemm_pp_kernel<float, true, true, 4, 1, 1, 1, true, true>), dim3((unsigned)blocks, 1, 1), dim3(512), SMEM, s, g);
-    else hipLaunchKernelGGL((gemm_pp_kernel<float, true, true, 4, 1, 1, 1, true, false>), dim3((unsigned)blocks, 1, 1), dim3(512), SMEM, s, g);
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, 1, 1), dim3(512), SMEM, (hipStream_t)stream, g);
     SS_LAUNCH_CHECK("simseg_gemm_wgrad_group");
     g_gemm_last_variant = 3;
     g_wgrad_group_last = n;
@@ -2252,21 +2115,21 @@ extern "C" int simseg_gemm(const void* A, const void* B, void* C, int64_t M, int
     p.A = A; p.B = B; p.C = C; p.M = (int)M; p.N = (int)N; p.K = (int)K;
     p.lda = lda; p.ldb = ldb; p.ldc = ldc; p.alpha = alpha; p.bias = bias; p.rowscale = rowscale;
     p.residual = residual; p.ldr = ldr; p.act = act; p.aux = aux; p.aux_out = aux_out;
-    p.row_group = row_group; p.res_mod = res_mod; p.accumulate = accumulate; p.dbg_skip_epilogue = g_gemm_debug_skip_epilogue; p.dbg_trace = g_gemm_debug_trace; p.stagger = g_gemm_stagger;
+    p.row_group = row_group; p.res_mod = res_mod; p.accumulate = accumulate; p.dbg_trace = g_gemm_debug_trace;
     p.drop_seed = drop_seed;
     p.colsum = colsum;
     p.drop_thresh = drop_p > 0.f ? (unsigned int)((double)drop_p * 4294967296.0) : 0u;
     p.drop_scale = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
     p.aux_blocked = blocked;
-    p.pf_next = g_gemm_variant != 16;                                // 16 = automatic choice without the next-tile fetch (A/B runs)
+    p.pf_next = 1;
     hipStream_t s = (hipStream_t)stream;
     g_gemm_last_variant = 1;
-    // 0 auto, 4 = the small-problem kernel wherever it applies (tests), any other value keeps it off
+    // selector 0: by the measured size rule; 4: the small-problem kernel wherever it applies (tests); any other value keeps it off
     const bool small_fit = !transA && !transB && aligned && splitk <= 1 && (K * (in_dtype == 0 ? 4 : 2)) % 128 == 0;
     // measured (profiles/r2_gemm_small_problem.txt): ahead of the 128x128 kernel up to ~160 of its tiles in bf16, ~200 in fp32
     const int64_t t128 = ((M + 127) / 128) * ((N + 127) / 128);
     const bool small_auto = small_fit && t128 < (in_dtype == 0 ? 200 : 160);
-    if (((g_gemm_variant == 0 || g_gemm_variant >= 15) && small_auto) || (g_gemm_variant == 4 && small_fit)) {
+    if ((g_gemm_variant == 0 && small_auto) || (g_gemm_variant == 4 && small_fit)) {
         g_gemm_last_variant = 4;
         if (in_dtype == 0) return dispatch_small<float, float>(p, s);
         return out_dtype ? dispatch_small<bf16_t, bf16_t>(p, s) : dispatch_small<bf16_t, float>(p, s);

@@ -144,19 +144,26 @@ def test_gemm_bf16_layouts(ops, ta, tb, M, N, K):
     _close(ops.gemm(a, b, trans_a=ta, trans_b=tb), ref, 1e-2, f"bf16 ta={ta} tb={tb} bf16 out")
 
 
-@pytest.mark.parametrize("variant", [1, 2, 3])
+@pytest.mark.parametrize("variant", [1, 5, 3])
 @pytest.mark.parametrize("ta,tb", [(False, False), (False, True), (True, True)])
 @pytest.mark.parametrize("M,N,K", [(512, 256, 128), (1000, 520, 192), (256, 136, 64), (2048, 768, 768), (16640, 768, 192)])
 def test_gemm_bf16_large_tile_kernel(ops, variant, ta, tb, M, N, K):
-    """The 256x256 direct-to-LDS kernels (swizzled LDS image, counted vmcnt ring) on interior and edge tiles."""
+    """The direct-to-LDS kernels (swizzled LDS image, counted vmcnt waits: the 128x128 ring as selector 5, the 256x256 ping-pong kernel as
+    3) and the 128x128 register-staged kernel (1) on interior and edge tiles.  The ring takes k-contiguous operands without split-K: for
+    that layout selector 5 must launch it; every other call under 5 ends on the 128x128 kernel and computes the same."""
+    from simseg_amd.lib import raw
     ops.set_gemm_variant(variant)
     try:
         a = _rand(*((K, M) if ta else (M, K)), seed=1, dtype=torch.bfloat16)
         b = _rand(*((K, N) if tb else (N, K)), seed=2, dtype=torch.bfloat16)
         ref = (a.float().T if ta else a.float()) @ (b.float() if tb else b.float().T)
         _close(ops.gemm(a, b, trans_a=ta, trans_b=tb, out_dtype=torch.float32), ref, 1e-5, f"large v{variant} ta={ta} tb={tb}")
+        # the kernel each selector must have run: the ring takes k-contiguous operands only, the forced ping-pong kernel k-contiguous A and K >= 128
+        ran = {1: 1, 5: 1 if ta or tb else 5, 3: 3 if K >= 128 and not ta else 1}[variant]
+        assert raw("simseg_gemm_last_variant") == ran
         bias, res = _rand(N, seed=3), _rand(M, N, seed=4)
         _close(ops.gemm(a, b, trans_a=ta, trans_b=tb, bias=bias, residual=res, out_dtype=torch.float32), ref + bias + res, 1e-5, "large + epilogue")
+        assert raw("simseg_gemm_last_variant") == ran
         acc = torch.zeros(M, N, device="cuda")
         ops.gemm(a, b, trans_a=ta, trans_b=tb, out=acc, accumulate=True, splitk=3)
         _close(acc, ref, 2e-5, "large split-K")
@@ -235,11 +242,6 @@ def test_gemm_persistent_pingpong_kernel(ops, tb, M, N, K):
             r = {}
             r["plain"] = ops.gemm(a, b, trans_b=tb)
             assert raw("simseg_gemm_last_variant") == variant, (variant, raw("simseg_gemm_last_variant"))
-            if variant == 10:
-                for sched in (11, 12, 13):          # the schedule experiments compute the same thing
-                    ops.set_gemm_variant(sched)
-                    assert torch.equal(ops.gemm(a, b, trans_b=tb), r["plain"]), sched
-                ops.set_gemm_variant(variant)
             r["bias_alpha"] = ops.gemm(a, b, trans_b=tb, bias=bias, alpha=0.5)
             pre = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
             r["gelu"] = ops.gemm(a, b, trans_b=tb, bias=bias, act=1, aux_out=pre)
@@ -272,6 +274,26 @@ def test_gemm_persistent_pingpong_kernel(ops, tb, M, N, K):
     # repeated launches are independent (no state carried in the ring / scratch between launches)
     again = ops.gemm(a, b, trans_b=tb, bias=bias, alpha=0.5)
     assert torch.equal(again, results[10]["bias_alpha"])
+
+
+def test_gemm_retired_selectors_are_rejected(ops):
+    """Selector values whose kernels were removed raise, and leave the selection made before them in force - in the library and in the
+    value ops pushes to other threads; the debug entry points that drove removed paths are gone from the library."""
+    from simseg_amd.lib import load, raw
+    a, b = _rand(256, 128, seed=1, dtype=torch.bfloat16), _rand(256, 128, seed=2, dtype=torch.bfloat16)
+    ref = a.float() @ b.float().T
+    ops.set_gemm_variant(3)                  # (auto would take the small-problem kernel, 4, for this shape)
+    try:
+        for v in (2, 6, 7, 8, 9, 11, 12, 13, 15, 16, 18, 102):
+            with pytest.raises(RuntimeError, match="set_gemm_variant"):
+                ops.set_gemm_variant(v)
+            assert ops._VARIANT["gemm"] == 3, v
+            _close(ops.gemm(a, b, out_dtype=torch.float32), ref, 1e-5, f"after rejected selector {v}")
+            assert raw("simseg_gemm_last_variant") == 3, v
+    finally:
+        ops.set_gemm_variant(0)
+    for name in ("simseg_debug_gemm_stagger", "simseg_debug_gemm_wgrad_blocks"):
+        assert not hasattr(load(), name) and not hasattr(load(), name + "_h16"), name
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Per-block timeline of the 256x256 ping-pong GEMM: where a tile's time goes (prologue / K loop / epilogue) and how the blocks of a
-launch line up in time.  argv: [M N K] [nt|nn]"""
+launch line up in time.  argv: [M N K] [nt|nn] [act]"""
 import os
 import sys
 
@@ -13,8 +13,7 @@ from simseg_amd.lib import call, ptr  # noqa: E402
 
 M, N, K = (int(x) for x in sys.argv[1:4]) if len(sys.argv) > 3 else (100864, 2304, 768)
 kind = sys.argv[4] if len(sys.argv) > 4 else "nt"
-stagger = int(sys.argv[5]) if len(sys.argv) > 5 else 0
-act = int(sys.argv[6]) if len(sys.argv) > 6 else 0
+act = int(sys.argv[5]) if len(sys.argv) > 5 else 0
 kw = {}
 if act == 3:
     kw = dict(act=3, bias=torch.zeros(N, device="cuda"), aux_out=torch.empty(M, N, device="cuda", dtype=torch.bfloat16))
@@ -26,7 +25,6 @@ elif act == 14:      # simseg_gemm act 6: times the tile-blocked saved derivativ
     kw = dict(act=6, aux=torch.randn(M, N, device="cuda").bfloat16(), colsum=torch.zeros(N, device="cuda"))
 elif act == 5:
     kw = dict(bias=torch.zeros(N, device="cuda"), residual=torch.randn(M, N, device="cuda"), out_dtype=torch.float32)
-call("simseg_debug_gemm_stagger", stagger)
 a = torch.randn(M, K, device="cuda").bfloat16()
 b = (torch.randn(K, N, device="cuda") if kind == "nn" else torch.randn(N, K, device="cuda")).bfloat16()
 tiles = ((M + 255) // 256) * ((N + 255) // 256)
@@ -54,7 +52,7 @@ for _ in range(10):
     ops.gemm(a, b, trans_b=(kind == "nn"), **kw)
 e1.record()
 torch.cuda.synchronize()
-print(f"stagger {stagger} ticks: {e0.elapsed_time(e1) / 10 * 1e3:.1f} us per launch (untraced)")
+print(f"{e0.elapsed_time(e1) / 10 * 1e3:.1f} us per launch (untraced)")
 print(f"{M}x{N}x{K} {kind}: {tiles} tiles, launch span {us[:, 3].max():.1f} us; per tile: prologue {pro.mean():.2f} (p90 {np.percentile(pro, 90):.2f}), "
       f"K loop {loop.mean():.2f} (p90 {np.percentile(loop, 90):.2f}), epilogue {epi.mean():.2f} (p90 {np.percentile(epi, 90):.2f}), total {(us[:, 3] - us[:, 0]).mean():.2f} us")
 # how synchronised are the blocks: fraction of blocks that are in their epilogue at each instant
@@ -65,7 +63,3 @@ active = np.array([((us[:, 0] <= g) & (us[:, 3] > g)).sum() for g in grid])
 print("time(us): active / in K loop / in epilogue  (every 4 us)")
 for i in range(0, len(grid), 4):
     print(f"  {grid[i]:7.0f}: {active[i]:4d} {in_loop[i]:4d} {in_epi[i]:4d}")
-if stagger:
-    for grp in range(4):
-        sel = [b for b in range(min(256, tiles)) if ((b >> 3) & 3) == grp]
-        print(f"first round, stagger group {grp}: start {us[sel, 0].mean():.1f} us, K loop {loop[sel].mean():.2f}, epilogue {epi[sel].mean():.2f} us")

@@ -3,8 +3,7 @@
 epilogue (the atomic adds) of every block and the K loop's time per 64-deep K-tile.
     argv: [M N K]                  one problem as launched per GEMM (output M x N, contraction K)
     argv: group ROWS [SLICES] [D]  a transformer block's four problems (fc2, fc1, proj, qkv at width D = 768) as ONE grouped launch
-                                   (ops.wgrad_group; SLICES defaults to the planner's choice).  SIMSEG_GEMM_WGRAD_DIRECT=0 in the environment
-                                   keeps the adds on the staged epilogue (default: from the accumulator layout)."""
+                                   (ops.wgrad_group; SLICES defaults to the planner's choice); its adds are issued from the accumulator layout."""
 import os
 import sys
 
@@ -57,8 +56,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "group":
     probs = [(torch.randn(rows, o, device="cuda").bfloat16(), torch.randn(rows, i, device="cuda").bfloat16(), torch.zeros(o, i, device="cuda")) for o, i in shapes]
     t, us_launch = trace(lambda: ops.wgrad_group(probs, slices=sk), sum(tiles) * z)
     assert ops.wgrad_group_last() == 4, "the group fell back to per-problem launches"
-    print(f"grouped dW {shapes}, rows={rows}: {sum(tiles)} tiles x {z} K-ranges of {ks} K-tiles = {sum(tiles) * z} blocks; "
-          f"epilogue: {'staged' if os.environ.get('SIMSEG_GEMM_WGRAD_DIRECT', '1') == '0' else 'accumulator layout'}")
+    print(f"grouped dW {shapes}, rows={rows}: {sum(tiles)} tiles x {z} K-ranges of {ks} K-tiles = {sum(tiles) * z} blocks")
     report(t, ks, us_launch)
 else:
     M, N, K = (int(x) for x in sys.argv[1:4]) if len(sys.argv) > 3 else (2304, 768, 100864)

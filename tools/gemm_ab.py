@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Within-process A/B of simseg_gemm kernel variants (cdna_hip_programming.md 5.4 rule 24: N variants x M rounds interleaved in ONE
 process, median and min reported).
-    python tools/gemm_ab.py --variants 3,10,11,12,13 [--shapes train] [--rounds 7] [--iters 5] [--only nt,nn] [--act 0]"""
+    python tools/gemm_ab.py --variants 0,3,10 [--shapes train] [--rounds 7] [--iters 5] [--only nt,nn] [--act 0]"""
 import argparse
 import os
 import statistics
@@ -35,7 +35,7 @@ def make(kind, M, N, K, act):
 
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("--variants", default="15,0")
+    ap.add_argument("--variants", default="0,3")
     ap.add_argument("--shapes", default="train")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=5)

@@ -94,7 +94,7 @@ if __name__ == "__main__":
     ap.add_argument("--shapes", default="train")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--only", default=None)
-    ap.add_argument("--variant", type=int, default=0)
+    ap.add_argument("--variant", type=int, default=0, choices=(0, 1, 3, 4, 5, 10), help="simseg_set_gemm_variant selector")
     ap.add_argument("--act", type=int, default=0, help="1: bias+GELU with pre-activation save; 2: times GELU'(aux)")
     ap.add_argument("--colsum", action="store_true", help="also accumulate column sums of the output (fused bias gradient)")
     ap.add_argument("--vendor", action="store_true", help="time torch.matmul (vendor BLAS) instead, as a yardstick")

@@ -39,7 +39,7 @@ if __name__ == "__main__":
         line = f"{name:5s} M={M} N={N} K={K} {'fp32 out + residual' if res else 'bf16 out':20s}"
         ops.set_gemm_variant(1)
         want = ops.gemm(a, w, **kw).float()
-        for v in (0, 1, 2, 3):
+        for v in (0, 1, 3, 5, 10):
             ops.set_gemm_variant(v)
             try:
                 got = ops.gemm(a, w, **kw).float()
