@@ -233,6 +233,40 @@ int simseg_scale_by_scalar(const float* x, const float* scalar, float* y, int64_
  * dLoss/dTemperature}. */
 int simseg_nce_pair(float* sims2, const float* temperature, float* row_scratch, float* out4, int64_t N1, int64_t N2, int64_t target0,
                     float smoothing, int write_grad, void* stream);
+/* MixUpNCE rows (mml_loss.py:146-197): simseg_nce_rows with TWO target columns per row, a = target0 + i and b = target0 + (N1 - 1 - i)
+ * (targets.flip(0)), and the weight alpha_i = alpha[i * alpha_stride] read on the device (alpha_stride 0: one scalar for every row,
+ * 1: a vector of N1; no host read either way):
+ *   loss_i = (1 - eps) * (alpha_i * nll_a + (1 - alpha_i) * nll_b) + eps * smooth_i,
+ *   dz_ij  = p_ij - eps / N2 - (1 - eps) * (alpha_i [j == a] + (1 - alpha_i) [j == b])     (a == b, the middle row of an odd N1: both
+ *            terms land on that column).
+ * Ignore weights, the mean over N1, dLoss/dT, z as the same rounded product in every pass, differences from the row maximum before the
+ * logarithm and the top-1 hit (against a, first-index rule) are simseg_nce_rows'.  out3 = {loss, top-1 acc, dLoss/dT}.  The same kernel
+ * instantiated with the mix terms: at alpha = 1 every output equals simseg_nce_rows' bit for bit (products with 1 and sums with 0 are
+ * exact).  alpha_stride outside {0, 1} and targets outside [0, N2) are refused before a launch. */
+int simseg_mix_nce_rows(float* sims, const float* temperature, const float* ignore_mask, const float* alpha, int alpha_stride,
+                        float* row_loss, float* row_correct, float* row_tdot, float* out3, int64_t N1, int64_t N2, int64_t target0,
+                        float smoothing, int write_grad, void* stream);
+/* Triplet rows: the max-violation hinge of VSE++ (mml_loss.py:280-347) over `blocks` (1 or 2) stacked sims[N1,N2] (fp32, from
+ * simseg_gemm), one block per row.  For row i of a matrix, with d_i = s[i, target0 + i]:
+ *   pre_ij  = fl32(fl32(margin + s_ij) - d_i)      two rounded fp32 operations in torch's order, never contracted;
+ *   cost_ij = max(pre_ij, 0), and 0 at masked columns;
+ *   mask_block = 1 (the reference's global_reduce branch): the whole own-rank block [target0, target0 + N1) is masked - the reference's
+ *     behaviour, quirk included: with ONE rank (N2 == N1) every column is masked, and the loss and all gradients are exactly 0;
+ *   mask_block = 0 (the local branch): only column target0 + i is masked;
+ *   reduce = 0 ("mean"): rowloss_i = sum_j cost_ij / (N1 - 1);   reduce = 1 ("max"): rowloss_i = max_j cost_ij, its arg the FIRST unmasked
+ *     column attaining the maximum;
+ *   top-1 hit over ALL columns against target0 + i with simseg_nce_rows' first-index rule (the same quantity it returns).
+ * write_grad: the row is overwritten IN PLACE by d rowloss_i / d s_ij.  Gradient flows through the clamp iff pre_ij > 0, which deviates
+ * from torch's subgradient (clamp(min=0) passes it where pre_ij >= 0) only at pre_ij == 0 exactly:
+ *   mean: fl32(1 / (N1 - 1)) at every unmasked j with pre_ij > 0 and fl32(-count_i / (N1 - 1)) at the target column (count_i = the number
+ *         of such j; each entry ONE rounded division, 0 when count_i = 0);
+ *   max:  +1 at the arg and -1 at the target column if the maximum is > 0, otherwise a zero row.
+ * A second launch gives out = {sum_i rowloss_i, top-1 acc} (blocks = 1) or {the sum over both matrices' rows, acc of matrix 0, acc of
+ * matrix 1} (blocks = 2, row i of matrix i / N1): the loss is a SUM over rows, not a mean, as in the reference.  row_loss / row_correct:
+ * blocks * N1 floats each.  Refused before any launch: N1 < 1, target0 + N1 > N2, reduce outside {0, 1}, blocks outside {1, 2}, and
+ * N1 < 2 with the mean (the reference's / (N1 - 1) would give NaN). */
+int simseg_triplet_rows(float* sims, float* row_loss, float* row_correct, float* out, int64_t N1, int64_t N2, int64_t target0, float margin,
+                        int reduce, int mask_block, int blocks, int write_grad, void* stream);
 /* n <= 6 fp32 transposes in ONE launch (out[k][c, r] = in[k][r, c], in[k] [rows[k], cols[k]] contiguous); jobs with scale[k] != 0 are
  * multiplied by alpha * scalar[0] - in the transposed copy and IN PLACE; y0[0] = scalar[0] * x0[0] when y0 is given.  The loss head's
  * backward (mml_loss.py:73 differentiated) needs dS, dS^T and the transposed embeddings as row . row GEMM operands, all times the upstream

@@ -1,17 +1,18 @@
 """InfoNCE of the SimSeg contrastive objective (mirror of simseg/models/criteria/losses/mml_loss.py:12-103) on the
 fused HIP loss path: fp32 MFMA similarity block -> in-place cross-entropy rows -> gradient GEMMs, with the embedding
-exchange as an RCCL all-gather forward / reduce-scatter backward."""
+exchange as an RCCL all-gather forward / reduce-scatter backward.  MixUpNCE (:105-197) and Triplet (:256-347) score the same
+similarity block with their own row kernels."""
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
 from simseg.utils import ENV, GatherLayer, logger
 from simseg.utils.dist import generate_local_groups
-from simseg_amd.heads import ClipLossFn, NCEFn, all_gather_rows
+from simseg_amd.heads import ClipLossFn, MixNCEFn, NCEFn, TripletFn, TripletLocalFn, all_gather_rows
 
 from .builder import LOSS
 
-__all__ = ["NCE", "LabelSmoothingCrossEntropy", "SoftTargetCrossEntropy"]
+__all__ = ["NCE", "MixUpNCE", "Triplet", "LabelSmoothingCrossEntropy", "SoftTargetCrossEntropy"]
 
 
 @LOSS.register_obj
@@ -67,6 +68,100 @@ class NCE(nn.Module):
         l1, a1 = NCEFn.apply(feat1, feat2, self.temperature, None, None, 0, self.smoothing)
         l2, a2 = NCEFn.apply(feat2, feat1, self.temperature, None, None, 0, self.smoothing)
         return 0.5 * (l1 + l2), a1, a2
+
+
+def _loss_group(cfg, who):
+    """(group, group rank) of a global_reduce loss: generate_local_groups(loss.group_size) under a process group, (None, 0) without one."""
+    if dist.is_available() and dist.is_initialized():
+        group_size = cfg.loss.group_size if cfg.loss.group_size >= 0 else ENV.size
+        group, rank = generate_local_groups(group_size)
+        logger.info(f"{who} Loss Group size, Group Rank, Env Rank:", group_size, rank, ENV.rank, root_only=False)
+        return group, rank
+    logger.info(f"{who}: no process group, global_reduce degenerates to the local batch")
+    return None, 0
+
+
+@LOSS.register_obj
+class MixUpNCE(nn.Module):
+    """InfoNCE against mixed targets (mml_loss.py:105-197 of the reference): one modality of the batch was mixed with its flipped self
+    (x_i <- alpha_i x_i + (1 - alpha_i) x_{B-1-i}), and row i is scored against its own column with weight alpha_i and against column
+    B - 1 - i (`targets.flip(0)`) with 1 - alpha_i, on the fused row path (simseg_amd.heads.MixNCEFn).  Constructed like NCE;
+    loss.global_reduce=False raises NotImplementedError, as in the reference.
+
+    forward(feat1, feat2, ignore_mask=None, image_alpha=... | text_alpha=...) needs exactly ONE of the two keywords: a float, a 0-dim
+    tensor or an [N1] tensor.  simseg_amd.mixup.Mixup.apply on the image batch yields exactly this weight as `lam`, and its partner order
+    B - 1 - i is this loss's flip.  The reference's formula applies the SAME alpha_i and flipped target in both directions (image -> text
+    and text -> image), whichever modality was mixed; so does this class.  Returns (loss, top-1 acc against the row's own column); there
+    is no `both` method."""
+
+    def __init__(self, cfg, rank):
+        super().__init__()
+        self.cfg = cfg
+        self.global_reduce = cfg.loss.global_reduce
+        if not self.global_reduce:
+            raise NotImplementedError("MixUpNCE: loss.global_reduce=False")
+        self.gather_backward = cfg.loss.nce_loss.gather_backward
+        self.group, self.rank = _loss_group(cfg, "MixUpNCE")
+        t = torch.ones([]) * cfg.loss.temperature.value
+        if cfg.loss.temperature.name == "parameter":
+            self.temperature = nn.Parameter(t)
+        elif cfg.loss.temperature.name == "constant":
+            self.register_buffer("temperature", t, persistent=False)
+        else:
+            raise NotImplementedError(cfg.loss.temperature.name)
+        self.smoothing = float(cfg.loss.smoothing)
+
+    _gather = NCE._gather
+
+    def forward(self, feat1, feat2, label=None, ignore_mask=None, **kwargs):
+        if ("image_alpha" in kwargs) == ("text_alpha" in kwargs):
+            raise NotImplementedError("MixUpNCE loss only supports mixing up one modal, please consider M3ixupNCE")
+        alpha = kwargs["image_alpha"] if "image_alpha" in kwargs else kwargs["text_alpha"]
+        N1 = feat1.shape[0]
+        alpha = torch.as_tensor(alpha, dtype=torch.float32).to(feat1.device).detach().reshape(-1).contiguous()
+        if alpha.numel() not in (1, N1):
+            raise ValueError(f"MixUpNCE: alpha holds {alpha.numel()} values for a batch of {N1}")
+        feat2_global = self._gather(feat2)
+        ignore_global = None if ignore_mask is None else all_gather_rows(ignore_mask.float(), self.group) if self.group else ignore_mask.float()
+        if feat2_global.shape[0] % N1 != 0:
+            raise AssertionError(f"global size: {feat2_global.shape[0]}, batch size: {N1}")
+        return MixNCEFn.apply(feat1, feat2_global, self.temperature, alpha, ignore_mask, ignore_global, self.rank, self.smoothing)
+
+
+@LOSS.register_obj
+class Triplet(nn.Module):
+    """The max-violation hinge of VSE++ (mml_loss.py:256-347 of the reference) on the fused row path: cost_ij = max(margin + s_ij - s_ii, 0)
+    over the negatives of row i, reduced per row by loss.triplet_loss.reduce_mode = "max" (the hardest negative) or "mean"
+    (sum / (N1 - 1)), and SUMMED over rows.  Gradient passes the clamp where margin + s_ij - s_ii > 0 (include/simseg_hip.h).
+
+    loss.global_reduce=True: feat1 against the gathered feat2; returns (loss, acc).  The reference masks the WHOLE own-rank block of
+    columns, not only the diagonal, and so does this class: with ONE rank every column is masked, and the loss and all gradients are
+    exactly 0.  loss.global_reduce=False: the symmetric local form over one matrix (rows: 1 -> 2, columns: 2 -> 1), only the diagonal
+    masked; returns (loss, i2t acc, t2i acc).
+
+    Gathering follows NCE._gather without gather_backward: with no process group the local tensor is used and gradient flows through
+    both roles; with a group the gather is detached, as the reference's all_gather / all_gather_group are.  The diagonal block is taken at
+    the GROUP rank: the reference overwrites it with the global rank (mml_loss.py:272), which is only correct where the two coincide.
+    ignore_mask is accepted and not applied, as in the reference.  There is no `both` method."""
+
+    def __init__(self, cfg, rank):
+        super().__init__()
+        self.cfg = cfg
+        self.margin = float(cfg.loss.triplet_loss.margin)
+        self.reduce = cfg.loss.triplet_loss.reduce_mode
+        if self.reduce not in ("mean", "max"):
+            raise NotImplementedError("Reduce method {} is not implemented yet".format(self.reduce))
+        self.global_reduce = cfg.loss.global_reduce
+        self.group, self.rank = _loss_group(cfg, "Triplet") if self.global_reduce else (None, 0)
+
+    def forward(self, feat1, feat2, label=None, ignore_mask=None):
+        reduce = 0 if self.reduce == "mean" else 1
+        if not self.global_reduce:
+            return TripletLocalFn.apply(feat1, feat2, self.margin, reduce)
+        feat2_global = feat2 if self.group is None else all_gather_rows(feat2, self.group)
+        if feat2_global.shape[0] % feat1.shape[0] != 0:
+            raise AssertionError(f"global size: {feat2_global.shape[0]}, batch size: {feat1.shape[0]}")
+        return TripletFn.apply(feat1, feat2_global, self.rank, self.margin, reduce)
 
 
 def _reduce(rows, reduction):

@@ -99,17 +99,19 @@ class CLIPModel(nn.Module):
         if embeddings is False and self.global_reduce and getattr(self.loss, "group", None) is not None:
             prefetch_gather(emb, self.loss.group)
 
-    def forward_loss(self, image_embeddings, text_embeddings, ignore_mask=None):
-        if (self.global_reduce and ignore_mask is None and hasattr(self.loss, "both") and image_embeddings.is_cuda
+    def forward_loss(self, image_embeddings, text_embeddings, ignore_mask=None, **loss_kwargs):
+        """loss_kwargs go to both loss calls as they are (MixUpNCE's image_alpha / text_alpha: the reference's formula applies the same
+        alpha_i and flipped target in both directions); a loss that takes keywords is not driven through `both`."""
+        if (self.global_reduce and ignore_mask is None and not loss_kwargs and hasattr(self.loss, "both") and image_embeddings.is_cuda
                 and os.environ.get("SIMSEG_AMD_FUSED_LOSS", "1") != "0"):
             # both directions as one node (same arithmetic and kernels as the two calls below: tests/test_gpu_model.py)
             loss, i2t_acc, t2i_acc = self.loss.both(image_embeddings, text_embeddings)
         elif self.global_reduce:
-            i2t_loss, i2t_acc = self.loss(image_embeddings, text_embeddings, ignore_mask=ignore_mask)
-            t2i_loss, t2i_acc = self.loss(text_embeddings, image_embeddings, ignore_mask=ignore_mask)
+            i2t_loss, i2t_acc = self.loss(image_embeddings, text_embeddings, ignore_mask=ignore_mask, **loss_kwargs)
+            t2i_loss, t2i_acc = self.loss(text_embeddings, image_embeddings, ignore_mask=ignore_mask, **loss_kwargs)
             loss = 0.5 * (i2t_loss + t2i_loss)
         else:
-            loss, i2t_acc, t2i_acc = self.loss(image_embeddings, text_embeddings, ignore_mask=ignore_mask)
+            loss, i2t_acc, t2i_acc = self.loss(image_embeddings, text_embeddings, ignore_mask=ignore_mask, **loss_kwargs)
         return {f"{self.cfg.loss.name}_loss".lower(): loss}, i2t_acc, t2i_acc
 
     def forward(self, batch, embeddings=False):
@@ -152,7 +154,12 @@ class CLIPModel(nn.Module):
                 txt = self.forward_text_project(self.forward_text_feature(ids, mask), mask)
         if embeddings == "all":
             return [img, txt]
-        return self.forward_loss(img, txt, ignore_mask=None)
+        # MixUpNCE alone reads the mixing weight of the batch (simseg_amd.mixup.Mixup.apply's `lam` for the mixed modality); under any
+        # other loss such a key is ignored
+        loss_kwargs = {}
+        if self.cfg.loss.name == "MixUpNCE":
+            loss_kwargs = {k: batch[k] for k in ("image_alpha", "text_alpha") if k in batch}
+        return self.forward_loss(img, txt, ignore_mask=None, **loss_kwargs)
 
 
 _SIDE = {}

@@ -1,4 +1,4 @@
-// Row kernels behind the similarity matrices: InfoNCE cross-entropy rows (K13), retrieval first-match ranks (K16),
+// Row kernels behind the similarity matrices: InfoNCE / MixUpNCE cross-entropy rows (K13), Triplet hinge rows, retrieval first-match ranks (K16),
 // and the fused AdamW step over the flat parameter buffer.
 #include "common.h"
 #include "tensor_table.h"
@@ -27,10 +27,16 @@ __device__ __forceinline__ float block_reduce_max(float v, float* sh) {
 // One block per local row i of sims[N1,N2] = feat1 . feat2_global^T  (mml_loss.py:73-77, 89-95, 350-376).
 //   z = s / clamp(T, 1e-3, 0.5);  loss_i = (1-eps) * nll_i + eps * mean_j(-logp_ij);  weight w_i = 1 - ignore_i
 //   total loss = (1/N1) sum_i w_i loss_i.   Writes (in place) dS_ij = dLoss/ds_ij, and per-row partials.
+// MIX (simseg_mix_nce_rows, mml_loss.py:146-197): row i has a second target b = target0 + (N1 - 1 - i) (targets.flip(0)) and a weight
+// al = alpha[i * alpha_stride] read on the device: nll_i becomes al * nll_a + (1 - al) * nll_b and the one-hot of the gradient
+// al [j == a] + (1 - al) [j == b].  A template flag, not a multiply by 1.0f: the instantiation without it is the kernel as it was, and at
+// al = 1 the MIX statements reproduce its bits (products with 1 and sums with 0 are exact).
+template <bool MIX>
 __global__ __launch_bounds__(256) void nce_rows_kernel(float* __restrict__ sims, const float* __restrict__ temperature,
                                                        const float* __restrict__ ignore, float* __restrict__ row_loss,
                                                        float* __restrict__ row_correct, float* __restrict__ row_tdot,
-                                                       int N1, int N2, int target0, float smoothing, int write_grad) {
+                                                       int N1, int N2, int target0, float smoothing, int write_grad,
+                                                       const float* __restrict__ alpha, int alpha_stride) {
     // (the pair form - simseg_nce_pair - launches 2 N1 blocks over two stacked [N1, N2] matrices: row i of matrix i / N1)
     // Every pass forms z = s * inv_t as the SAME rounded product: contracted into the subtractions below, one pass would see the exact
     // product and another the rounded one, and they would disagree about z - bmx by half an ulp of z.
@@ -71,9 +77,15 @@ __global__ __launch_bounds__(256) void nce_rows_kernel(float* __restrict__ sims,
     // sum, half an ulp of 20, is a tenth of nll and of 1 - p_target.  Differences from the maximum first, then the small logarithm.
     const float lg = __logf(se);
     const float zt = row[tgt] * inv_t;
-    const float nll = (bmx - zt) + lg;
+    float nll = (bmx - zt) + lg;
     const float smooth = (bmx - sz / N2) + lg;          // -mean_j logp_ij
     const float w = ignore ? 1.0f - ignore[il] : 1.0f;
+    const int tgt_b = MIX ? target0 + (N1 - 1 - il) : tgt;
+    const float al = MIX ? alpha[(long)il * alpha_stride] : 1.0f;
+    if (MIX) {
+        const float nll_b = (bmx - row[tgt_b] * inv_t) + lg;
+        nll = al * nll + (1.0f - al) * nll_b;
+    }
     const float loss = (1.0f - smoothing) * nll + smoothing * smooth;
     __syncthreads();
     float tdot = 0.f;
@@ -83,7 +95,12 @@ __global__ __launch_bounds__(256) void nce_rows_kernel(float* __restrict__ sims,
             const float s = row[j];
             const float pj = __expf((s * inv_t - bmx) - lg);
             float dz = pj - smoothing / N2;
-            if (j == tgt) dz -= (1.0f - smoothing);
+            if (MIX) {
+                if (j == tgt) dz -= (1.0f - smoothing) * al;
+                if (j == tgt_b) dz -= (1.0f - smoothing) * (1.0f - al);      // (a == b, the middle row of an odd N1: both land here)
+            } else {
+                if (j == tgt) dz -= (1.0f - smoothing);
+            }
             dz *= c;
             tdot += dz * s;
             row[j] = dz * inv_t;
@@ -140,6 +157,98 @@ __global__ __launch_bounds__(256) void nce_finalize_pair_kernel(const float* __r
         out[1] = c0 / N1;
         out[2] = c1 / N1;
         out[3] = (T >= 0.001f && T <= 0.5f) ? -0.5f * t / (temp * temp) : 0.f;
+    }
+}
+
+__device__ __forceinline__ int block_reduce_min_int(int v, int* shi) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) shi[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int b = 0x7fffffff;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) b = min(b, shi[w]);
+    return b;
+}
+
+// Max-violation hinge rows of VSE++ (mml_loss.py:280-347).  One block per row of `blocks` stacked [N1, N2] matrices (row i of matrix
+// i / N1), d = s[i, target0 + i]:
+//   pre_j = fl32(fl32(margin + s_j) - d)   (two rounded operations in torch's order; no contraction in this kernel)
+//   cost_j = max(pre_j, 0), 0 at masked columns: the own-rank block [target0, target0 + N1) with mask_block, else the target column alone
+//   reduce 0: row loss = sum_j cost_j / (N1 - 1);  reduce 1: max_j cost_j, its arg the FIRST unmasked column attaining it
+// and the top-1 hit over ALL columns (first index attaining the maximum, as nce_rows_kernel).  write_grad: the row becomes
+// d rowloss / d s_j, gradient passing the clamp iff pre_j > 0 - mean: 1 / (N1 - 1) at unmasked j with pre_j > 0 and -count / (N1 - 1) at
+// the target (each ONE rounded division); max: +1 at the arg and -1 at the target when the maximum is > 0, else a zero row.
+__global__ __launch_bounds__(256) void triplet_rows_kernel(float* __restrict__ sims, float* __restrict__ row_loss,
+                                                           float* __restrict__ row_correct, int N1, int N2, int target0, float margin,
+                                                           int reduce, int mask_block, int write_grad) {
+#pragma clang fp contract(off)
+    __shared__ float sh[8];
+    __shared__ int shi[8];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    float* row = sims + (long)i * N2;
+    const int il = i % N1;
+    const int tgt = target0 + il;
+    const int m0 = mask_block ? target0 : tgt, m1 = mask_block ? target0 + N1 : tgt + 1;      // masked columns [m0, m1)
+    const float d = row[tgt];
+    float mx = -INFINITY, cmx = 0.f, sum = 0.f, cnt = 0.f;
+    int arg = 0x7fffffff, carg = 0x7fffffff;
+    for (int j = tid; j < N2; j += 256) {
+        const float s = row[j];
+        if (s > mx) { mx = s; arg = j; }
+        const float pre = (margin + s) - d;
+        if ((j < m0 || j >= m1) && pre > 0.f) {
+            sum += pre;
+            cnt += 1.f;
+            if (pre > cmx) { cmx = pre; carg = j; }
+        }
+    }
+    const float bmx = block_reduce_max(mx, sh);
+    const int best = block_reduce_min_int(mx == bmx ? arg : 0x7fffffff, shi);
+    float loss;
+    int carg_b = 0x7fffffff;
+    if (reduce == 0) {
+        sum = block_reduce_sum(sum, sh);
+        cnt = block_reduce_sum(cnt, sh);          // (an integer below 2^24: exact)
+        loss = sum / (float)(N1 - 1);
+    } else {
+        loss = block_reduce_max(cmx, sh);         // >= 0: the masked columns cost 0
+        carg_b = block_reduce_min_int((loss > 0.f && cmx == loss) ? carg : 0x7fffffff, shi);
+    }
+    __syncthreads();       // (every thread holds d = row[tgt] and its pass-1 values before any thread rewrites the row)
+    if (write_grad) {
+        if (reduce == 0) {
+            const float den = (float)(N1 - 1);
+            const float g = 1.0f / den, gt = cnt > 0.f ? -cnt / den : 0.f;
+            for (int j = tid; j < N2; j += 256) {
+                const float pre = (margin + row[j]) - d;
+                row[j] = j == tgt ? gt : ((j < m0 || j >= m1) && pre > 0.f) ? g : 0.f;
+            }
+        } else {
+            for (int j = tid; j < N2; j += 256) row[j] = j == carg_b ? 1.f : (j == tgt && loss > 0.f) ? -1.f : 0.f;
+        }
+    }
+    if (tid == 0) {
+        row_loss[i] = loss;
+        row_correct[i] = (best == tgt) ? 1.f : 0.f;
+    }
+}
+
+// out = {sum of the row losses, top-1 acc} (blocks = 1) or {sum over both matrices' rows, acc of matrix 0, acc of matrix 1} (blocks = 2).
+// The loss is a SUM over rows, as in the reference (loss.sum()).
+__global__ __launch_bounds__(256) void triplet_finalize_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_correct,
+                                                               float* __restrict__ out, int N1, int blocks) {
+    __shared__ float sh[8];
+    float l = 0.f, c0 = 0.f, c1 = 0.f;
+    for (int i = threadIdx.x; i < blocks * N1; i += 256) {
+        l += row_loss[i];
+        if (i < N1) c0 += row_correct[i]; else c1 += row_correct[i];
+    }
+    l = block_reduce_sum(l, sh); c0 = block_reduce_sum(c0, sh); c1 = block_reduce_sum(c1, sh);
+    if (threadIdx.x == 0) {
+        out[0] = l;
+        out[1] = c0 / N1;
+        if (blocks == 2) out[2] = c1 / N1;
     }
 }
 
@@ -467,8 +576,8 @@ extern "C" int simseg_nce_rows(float* sims, const float* temperature, const floa
     SS_CHECK(sims && temperature && row_loss && row_correct && row_tdot && out3, "nce_rows: null pointer");
     SS_CHECK(N1 > 0 && N2 > 0 && target0 >= 0 && target0 + N1 <= N2, "nce_rows: targets [%lld, %lld) outside [0, %lld)",
              (long long)target0, (long long)(target0 + N1), (long long)N2);
-    hipLaunchKernelGGL(nce_rows_kernel, dim3((unsigned)N1), dim3(256), 0, STREAM, sims, temperature, ignore_mask, row_loss, row_correct,
-                       row_tdot, (int)N1, (int)N2, (int)target0, smoothing, write_grad);
+    hipLaunchKernelGGL(nce_rows_kernel<false>, dim3((unsigned)N1), dim3(256), 0, STREAM, sims, temperature, ignore_mask, row_loss, row_correct,
+                       row_tdot, (int)N1, (int)N2, (int)target0, smoothing, write_grad, (const float*)nullptr, 0);
     hipLaunchKernelGGL(nce_finalize_kernel, dim3(1), dim3(256), 0, STREAM, row_loss, row_correct, row_tdot, ignore_mask, temperature,
                        out3, (int)N1);
     SS_LAUNCH_CHECK("nce_rows");
@@ -481,10 +590,40 @@ extern "C" int simseg_nce_pair(float* sims2, const float* temperature, float* ro
     SS_CHECK(N1 > 0 && N2 > 0 && target0 >= 0 && target0 + N1 <= N2, "nce_pair: targets [%lld, %lld) outside [0, %lld)",
              (long long)target0, (long long)(target0 + N1), (long long)N2);
     float* rl = row_scratch; float* rc = rl + 2 * N1; float* rt = rc + 2 * N1;
-    hipLaunchKernelGGL(nce_rows_kernel, dim3((unsigned)(2 * N1)), dim3(256), 0, STREAM, sims2, temperature, (const float*)nullptr, rl, rc, rt, (int)N1,
-                       (int)N2, (int)target0, smoothing, write_grad);
+    hipLaunchKernelGGL(nce_rows_kernel<false>, dim3((unsigned)(2 * N1)), dim3(256), 0, STREAM, sims2, temperature, (const float*)nullptr, rl, rc, rt, (int)N1,
+                       (int)N2, (int)target0, smoothing, write_grad, (const float*)nullptr, 0);
     hipLaunchKernelGGL(nce_finalize_pair_kernel, dim3(1), dim3(256), 0, STREAM, rl, rc, rt, temperature, out4, (int)N1);
     SS_LAUNCH_CHECK("nce_pair");
+    return 0;
+}
+
+extern "C" int simseg_mix_nce_rows(float* sims, const float* temperature, const float* ignore_mask, const float* alpha, int alpha_stride,
+                                   float* row_loss, float* row_correct, float* row_tdot, float* out3, int64_t N1, int64_t N2,
+                                   int64_t target0, float smoothing, int write_grad, void* stream) {
+    SS_CHECK(sims && temperature && alpha && row_loss && row_correct && row_tdot && out3, "mix_nce_rows: null pointer");
+    SS_CHECK(alpha_stride == 0 || alpha_stride == 1, "mix_nce_rows: alpha_stride %d is neither 0 (scalar) nor 1 (per row)", alpha_stride);
+    SS_CHECK(N1 > 0 && N2 > 0 && target0 >= 0 && target0 + N1 <= N2, "mix_nce_rows: targets [%lld, %lld) outside [0, %lld)",
+             (long long)target0, (long long)(target0 + N1), (long long)N2);
+    hipLaunchKernelGGL(nce_rows_kernel<true>, dim3((unsigned)N1), dim3(256), 0, STREAM, sims, temperature, ignore_mask, row_loss, row_correct,
+                       row_tdot, (int)N1, (int)N2, (int)target0, smoothing, write_grad, alpha, alpha_stride);
+    hipLaunchKernelGGL(nce_finalize_kernel, dim3(1), dim3(256), 0, STREAM, row_loss, row_correct, row_tdot, ignore_mask, temperature,
+                       out3, (int)N1);
+    SS_LAUNCH_CHECK("mix_nce_rows");
+    return 0;
+}
+
+extern "C" int simseg_triplet_rows(float* sims, float* row_loss, float* row_correct, float* out, int64_t N1, int64_t N2, int64_t target0,
+                                   float margin, int reduce, int mask_block, int blocks, int write_grad, void* stream) {
+    SS_CHECK(sims && row_loss && row_correct && out, "triplet_rows: null pointer");
+    SS_CHECK(blocks == 1 || blocks == 2, "triplet_rows: blocks %d is neither 1 nor 2", blocks);
+    SS_CHECK(reduce == 0 || reduce == 1, "triplet_rows: reduce %d is neither 0 (mean) nor 1 (max)", reduce);
+    SS_CHECK(N1 >= 1 && N2 >= 1 && target0 >= 0 && target0 + N1 <= N2, "triplet_rows: targets [%lld, %lld) outside [0, %lld)",
+             (long long)target0, (long long)(target0 + N1), (long long)N2);
+    SS_CHECK(!(reduce == 0 && N1 < 2), "triplet_rows: the mean over N1 - 1 negatives needs N1 >= 2");
+    hipLaunchKernelGGL(triplet_rows_kernel, dim3((unsigned)(blocks * N1)), dim3(256), 0, STREAM, sims, row_loss, row_correct, (int)N1, (int)N2,
+                       (int)target0, margin, reduce, mask_block ? 1 : 0, write_grad);
+    hipLaunchKernelGGL(triplet_finalize_kernel, dim3(1), dim3(256), 0, STREAM, row_loss, row_correct, out, (int)N1, blocks);
+    SS_LAUNCH_CHECK("triplet_rows");
     return 0;
 }
 

@@ -174,6 +174,99 @@ class NCEFn(Function):
         return df1, df2, dt, None, None, None, None
 
 
+class MixNCEFn(Function):
+    """NCEFn against the two targets of MixUpNCE (mml_loss.py:146-197): row i is scored against column rank * Bl + i with weight alpha_i
+    and against column rank * Bl + (Bl - 1 - i) with 1 - alpha_i (ops.mix_nce_rows).  alpha: fp32 device tensor of one element or [Bl],
+    not differentiable.  Returns (loss, top-1 acc against the row's own column)."""
+
+    @staticmethod
+    def forward(ctx, feat1, feat2g, temperature, alpha, ignore, ignore_g, rank, smoothing):
+        f1 = feat1.contiguous().float()
+        f2 = feat2g.contiguous().float()
+        if ignore_g is not None:
+            f2 = ops.scale_rows(f2, ignore_g.contiguous().float(), one_minus=True)       # :172-173
+        sims = ops.gemm(f1, f2)
+        need = any(ctx.needs_input_grad[:3])
+        out3, _ = ops.mix_nce_rows(sims, temperature.detach().reshape(1).float(), rank * f1.shape[0], alpha,
+                                   None if ignore is None else ignore.contiguous().float(), smoothing, write_grad=need)
+        ctx.save_for_backward(sims if need else None, f1, f2, out3, ignore_g)
+        loss, acc = out3[0].clone(), out3[1].clone()
+        ctx.mark_non_differentiable(acc)
+        return loss, acc
+
+    @staticmethod
+    def backward(ctx, gloss, _gacc):
+        return NCEFn.backward(ctx, gloss, _gacc)[:3] + (None,) * 5
+
+
+class TripletFn(Function):
+    """The global direction of the Triplet loss (mml_loss.py:285-314): feat1 [N1,P] against feat2_global [N2,P], own columns
+    [rank * N1, (rank + 1) * N1) - all of them masked, as in the reference.  Built like NCEFn: one GEMM, ops.triplet_rows in place,
+    gradient GEMMs times the upstream gradient.  reduce: 0 mean, 1 max.  Returns (loss = SUM of the row losses, top-1 acc)."""
+
+    @staticmethod
+    def forward(ctx, feat1, feat2g, rank, margin, reduce):
+        f1 = feat1.contiguous().float()
+        f2 = feat2g.contiguous().float()
+        sims = ops.gemm(f1, f2)
+        need = any(ctx.needs_input_grad[:2])
+        out, _ = ops.triplet_rows(sims, rank * f1.shape[0], margin, reduce, True, write_grad=need)
+        ctx.save_for_backward(sims if need else None, f1, f2)
+        loss, acc = out[0].clone(), out[1].clone()
+        ctx.mark_non_differentiable(acc)
+        return loss, acc
+
+    @staticmethod
+    def backward(ctx, gloss, _gacc):
+        ds, f1, f2 = ctx.saved_tensors
+        g = gloss.contiguous().float().reshape(1)
+        df1 = df2 = None
+        if ctx.needs_input_grad[0]:
+            df1 = ops.scale_by_scalar(ops.gemm(ds, ops.transpose_f32(f2)), g)
+        if ctx.needs_input_grad[1]:
+            df2 = ops.scale_by_scalar(ops.gemm(ops.transpose_f32(ds), ops.transpose_f32(f1)), g)
+        return df1, df2, None, None, None
+
+
+class TripletLocalFn(Function):
+    """The local symmetric Triplet loss (mml_loss.py:316-347): ONE matrix S = feat1 . feat2^T reduced along its rows (1 -> 2) and along
+    its columns (2 -> 1), the diagonal masked.  S is computed once and S^T made as an exact copy, so both directions see the reference's
+    bits; the two blocks are stacked, scored by one rows launch, and the gradient is dS = dS_0 + dS_1^T - formed inside the gradient
+    GEMMs (the second of each pair accumulates into the first's result), after one launch that scales both blocks by the upstream
+    gradient and makes every transposed operand.  Returns (loss = sum of both directions' rows, i2t acc, t2i acc)."""
+
+    @staticmethod
+    def forward(ctx, feat1, feat2, margin, reduce):
+        f1 = feat1.contiguous().float()
+        f2 = feat2.contiguous().float()
+        N = f1.shape[0]
+        if f2.shape[0] != N:
+            raise ValueError(f"TripletLocalFn: {N} rows against {f2.shape[0]}: the local form pairs row i with row i")
+        sims = torch.empty(2, N, N, device=f1.device, dtype=F32)
+        ops.gemm(f1, f2, out=sims[0])
+        ops.transpose_f32(sims[0], out=sims[1])
+        need = any(ctx.needs_input_grad[:2])
+        out, _ = ops.triplet_rows(sims, 0, margin, reduce, False, write_grad=need)
+        ctx.save_for_backward(sims if need else None, f1, f2)
+        loss, a1, a2 = out[0].clone(), out[1].clone(), out[2].clone()
+        ctx.mark_non_differentiable(a1, a2)
+        return loss, a1, a2
+
+    @staticmethod
+    def backward(ctx, gloss, _g1, _g2):
+        ds, f1, f2 = ctx.saved_tensors
+        g = gloss.contiguous().float().reshape(1)
+        (ds0_t, ds1_t, f2_t, f1_t), _ = ops.transpose_multi([ds[0], ds[1], f2, f1], [1, 1, 0, 0], scalar=g)
+        df1 = df2 = None
+        if ctx.needs_input_grad[0]:
+            df1 = ops.gemm(ds[0], f2_t)                                  # dS_0 . feat2
+            ops.gemm(ds1_t, f2_t, out=df1, accumulate=True)              # + dS_1^T . feat2
+        if ctx.needs_input_grad[1]:
+            df2 = ops.gemm(ds0_t, f1_t)                                  # dS_0^T . feat1
+            ops.gemm(ds[1], f1_t, out=df2, accumulate=True)              # + dS_1 . feat1
+        return df1, df2, None, None
+
+
 class ClipLossFn(Function):
     """The whole loss head of CLIPModel.forward_loss (pipelines/clip.py:129-140) as ONE autograd node: 0.5 * (NCE(image, text) +
     NCE(text, image)) with the global-batch exchange inside (mml_loss.py:56-77: all-gather of the other modality's embeddings forward,

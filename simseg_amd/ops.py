@@ -469,11 +469,14 @@ def split_bf16x3(x2d, b_pattern=False, planes=False):
     return out
 
 
-def transpose_f32(x2d):
+def transpose_f32(x2d, out=None):
     require_gpu(x2d)
     R, C = x2d.shape
-    out = torch.empty(C, R, device=x2d.device, dtype=torch.float32)
-    call("simseg_transpose_f32", ptr(_c(x2d)), ptr(out), R, C, stream())
+    if out is None:
+        out = torch.empty(C, R, device=x2d.device, dtype=torch.float32)
+    elif tuple(out.shape) != (C, R) or out.dtype != torch.float32:
+        raise ValueError(f"transpose_f32: out must be fp32 [{C}, {R}], got {out.dtype} {tuple(out.shape)}")
+    call("simseg_transpose_f32", ptr(_c(x2d)), ptr(_c(out)), R, C, stream())
     return out
 
 
@@ -529,6 +532,52 @@ def nce_pair(sims2, temperature, target0, smoothing=0.0, write_grad=True):
     out4 = torch.empty(4, device=sims2.device, dtype=torch.float32)
     call("simseg_nce_pair", ptr(_c(sims2)), ptr(temperature), ptr(scratch), ptr(out4), N1, N2, int(target0), float(smoothing), int(write_grad), stream())
     return out4
+
+
+def _sim_block_check(who, sims, target0, blocks=False):
+    require_gpu(sims)
+    if sims.dim() != (3 if blocks else 2) or (blocks and sims.shape[0] not in (1, 2)):
+        raise ValueError(f"{who}: sims [N1, N2]" + (" or [blocks, N1, N2] with 1 or 2 blocks" if blocks else "") + f", got {tuple(sims.shape)}")
+    if sims.dtype != torch.float32:
+        raise TypeError(f"{who}: sims must be fp32, got {sims.dtype}")
+    _c(sims)
+    return sims.shape[-2], sims.shape[-1]
+
+
+def mix_nce_rows(sims, temperature, target0, alpha, ignore_mask=None, smoothing=0.0, write_grad=True):
+    """nce_rows against the two targets a = target0 + i and b = target0 + (N1 - 1 - i) weighted alpha_i / 1 - alpha_i (include/simseg_hip.h
+    simseg_mix_nce_rows).  In place: sims <- dLoss/dsims.  alpha: fp32 device tensor, one element (every row) or [N1].
+    -> (out3 = [loss, acc, dLoss/dT], row losses [N1] - each already times its ignore weight)."""
+    N1, N2 = _sim_block_check("mix_nce_rows", sims, target0)
+    require_gpu(temperature, alpha, ignore_mask)
+    if alpha.dtype != torch.float32:
+        raise TypeError(f"mix_nce_rows: alpha must be fp32, got {alpha.dtype}")
+    if alpha.numel() != 1 and tuple(alpha.shape) != (N1,):
+        raise ValueError(f"mix_nce_rows: alpha holds one element or [{N1}], got {tuple(alpha.shape)}")
+    if ignore_mask is not None and (ignore_mask.dtype != torch.float32 or tuple(ignore_mask.shape) != (N1,)):
+        raise ValueError(f"mix_nce_rows: ignore_mask must be fp32 [{N1}], got {ignore_mask.dtype} {tuple(ignore_mask.shape)}")
+    scratch = torch.empty(3, N1, device=sims.device, dtype=torch.float32)
+    out3 = torch.empty(3, device=sims.device, dtype=torch.float32)
+    call("simseg_mix_nce_rows", ptr(sims), ptr(temperature), ptr(_c(ignore_mask)), ptr(_c(alpha)), 0 if alpha.numel() == 1 else 1,
+         ptr(scratch[0]), ptr(scratch[1]), ptr(scratch[2]), ptr(out3), N1, N2, int(target0), float(smoothing), int(bool(write_grad)), stream())
+    return out3, scratch[0]
+
+
+def triplet_rows(sims, target0, margin, reduce, mask_block, write_grad=True):
+    """The max-violation hinge rows (include/simseg_hip.h simseg_triplet_rows) of sims [N1, N2], or of two stacked blocks [2, N1, N2] in
+    one launch.  reduce: 0 / "mean", 1 / "max".  In place: sims <- d rowloss / d sims.  -> (out = [sum of the row losses, acc] - with two
+    blocks [sum over both, acc0, acc1] -, row losses [N1] or [2, N1])."""
+    stacked = sims.dim() == 3
+    N1, N2 = _sim_block_check("triplet_rows", sims, target0, blocks=stacked)
+    blocks = sims.shape[0] if stacked else 1
+    reduce = {"mean": 0, "max": 1}.get(reduce, reduce)
+    if reduce == 0 and N1 < 2:
+        raise ValueError("triplet_rows: the mean over N1 - 1 negatives needs N1 >= 2 (the reference divides by zero here)")
+    scratch = torch.empty(2, blocks * max(N1, 1), device=sims.device, dtype=torch.float32)
+    out = torch.empty(1 + blocks, device=sims.device, dtype=torch.float32)
+    call("simseg_triplet_rows", ptr(sims), ptr(scratch[0]), ptr(scratch[1]), ptr(out), N1, N2, int(target0), float(margin), int(reduce),
+         int(bool(mask_block)), blocks, int(bool(write_grad)), stream())
+    return out, (scratch[0].view(blocks, N1) if stacked else scratch[0])
 
 
 def transpose_multi(mats, scale_flags, scalar=None, alpha=1.0, x0=None):
