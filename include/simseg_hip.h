@@ -302,7 +302,8 @@ int simseg_topk_search(const void* q, const void* g, int dtype, int64_t M, int64
 int simseg_topk_merge(const float* score_a, const int32_t* idx_a, const float* score_b, const int32_t* idx_b, float* score, int32_t* idx,
                       int64_t M, int K, void* stream);
 
-/* torch.optim.AdamW (configs/clip/simseg.vit-b.yaml:31-36) over a flat fp32 segment; refreshes the bf16 compute copy. */
+/* ---- optimizer steps and gradient checks (csrc/optim.hip; the 16-bit copies are written in the selected 16-bit type) ----------------
+ * torch.optim.AdamW (configs/clip/simseg.vit-b.yaml:31-36) over a flat fp32 segment; refreshes the bf16 compute copy. */
 int simseg_adamw_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2,
                       float eps, float weight_decay, int64_t step, float grad_scale, void* stream);
 
@@ -350,7 +351,7 @@ int simseg_adamw_multi_step_amp_clip(const void* table, const int64_t* sizes, co
                                      const float* loss_scale, const float* found_inf, const float* step_in, float* step_out,
                                      const float* grad_coef, void* stream);
 
-/* ---- linear-probe task (csrc/probe.hip; DESIGN.md "Linear probe") --------------------------------------------------------------
+/* ---- linear-probe task (loss rows: csrc/probe.hip, LARS: csrc/optim.hip; DESIGN.md "Linear probe") ------------------------------
  * Cross-entropy over integer class labels, top-k hits and the logit gradient in one pass over logits [B, C] (dt: 0 fp32, 1 the selected
  * 16-bit type; labels int64 on the device): nn.CrossEntropyLoss(reduction='mean') + accuracy(topk=(1, 5)) of the reference's
  * LinearProbModel.forward (simseg/models/pipelines/linear_prob.py:61-71, tasks/linear_prob/hooks/utils.py).  Per row i with label y, in fp32:

@@ -5,11 +5,14 @@
 #include <stdio.h>
 #include <string.h>
 
-// The 16-bit operand type.  gemm.hip, attn.hip, rowops.hip and loss.hip are compiled TWICE (simseg_amd/build.py): as they stand - bf16, the
+// The 16-bit operand type.  gemm.hip, attn.hip and rowops.hip are compiled TWICE (simseg_amd/build.py): as they stand - bf16, the
 // headline mode - and with -DSS_HALF, where the same sources are the IEEE fp16 flavour the reference's AMP mode uses (fp16 autocast + a
 // live GradScaler, clip_runner.py:226-230): `bf16_t` is then _Float16, the MFMA is v_mfma_f32_32x32x16_f16, and every C-ABI entry point
 // the file defines carries the suffix _h16 (half_names.h renames them by macro).  The bf16 build's entry points hand a call over to their
 // _h16 twin while the calling thread has selected fp16 (simseg_set_half_type(2)); dtype code 1 always means "the selected 16-bit type".
+// Only entry points whose kernels differ between the flavours belong in those three files.  Every other source is compiled ONCE: where
+// one of its kernels touches 16-bit data (optim.hip, probe.hip, mixup.hip) the type is a template argument picked per call from
+// g_ss_half, and fp32-only code (loss.hip, rowops_plain.hip) has no flavour at all.
 #ifdef SS_HALF
 typedef _Float16 bf16_t;
 #define SS_MFMA_32x32x16(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, x, y, z)
@@ -61,6 +64,25 @@ __device__ __forceinline__ float half_bits_to_float(short bits) {      // a 16-b
     return (float)u.h;
 }
 __device__ __forceinline__ bf16_t f2bf(float v) { return (bf16_t)v; }
+
+// 16 bytes (fp32) / 8 bytes (16-bit) of a row to and from four floats: the row kernels' unit of access (rowops.hip, rowops_plain.hip)
+template <typename TO> __device__ __forceinline__ void store4(TO* p, const float (&v)[4]);
+template <> __device__ __forceinline__ void store4<float>(float* p, const float (&v)[4]) {
+    *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
+}
+template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* p, const float (&v)[4]) {
+    bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
+    *reinterpret_cast<bf16x4*>(p) = o;
+}
+template <typename TI> __device__ __forceinline__ void load4(const TI* p, float (&v)[4]);
+template <> __device__ __forceinline__ void load4<float>(const float* p, float (&v)[4]) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+}
+template <> __device__ __forceinline__ void load4<bf16_t>(const bf16_t* p, float (&v)[4]) {
+    const bf16x4 t = *reinterpret_cast<const bf16x4*>(p);
+    v[0] = (float)t[0]; v[1] = (float)t[1]; v[2] = (float)t[2]; v[3] = (float)t[3];
+}
 
 // Normal CDF for the erf-GELU epilogues.  libm's erff costs ~30 VALU instructions per element, which made the GELU / GELU'
 // epilogues of the MLP GEMMs as long as their K loops (measured: +40 % / +60 % on [100864,768]x[3072,768]^T).  Abramowitz &
@@ -188,6 +210,23 @@ __device__ __forceinline__ float wave_min(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o, 64));
     return v;
+}
+// Sum over the block (any whole number of waves), through sh[blockDim.x / 64]; every thread gets the total.
+__device__ __forceinline__ float block_sum(float v, float* sh) {
+    v = wave_sum(v);
+    const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[w] = v;
+    __syncthreads();
+    float s = 0.f;
+    for (int i = 0; i < nw; ++i) s += sh[i];
+    return s;
+}
+
+// Blocks of `block` threads for n items, at least one and at most `cap` (the grid-stride kernels' launch size).
+inline int grid_for(long n, int block, int cap = 4096) {
+    long g = (n + block - 1) / block;
+    return (int)(g < 1 ? 1 : (g > cap ? cap : g));
 }
 
 // counter-based RNG for dropout: one 32-bit hash per element index, reproducible in backward.  32-bit arithmetic only (the

@@ -1,7 +1,6 @@
-// Row kernels behind the similarity matrices: InfoNCE / MixUpNCE cross-entropy rows (K13), Triplet hinge rows, retrieval first-match ranks (K16),
-// and the fused AdamW step over the flat parameter buffer.
+// Row kernels behind the similarity matrices: InfoNCE / MixUpNCE cross-entropy rows (K13), Triplet hinge rows, the loss head's transposes
+// and scales, retrieval first-match ranks (K16) and recall counts.  fp32 and integers only: compiled ONCE, no 16-bit flavour.
 #include "common.h"
-#include "tensor_table.h"
 
 namespace {
 
@@ -22,6 +21,16 @@ __device__ __forceinline__ float block_reduce_max(float v, float* sh) {
     float s = -INFINITY;
     for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s = fmaxf(s, sh[i]);
     return s;
+}
+__device__ __forceinline__ int block_reduce_min_int(int v, int* shi) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) shi[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int b = 0x7fffffff;
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) b = min(b, shi[w]);
+    return b;
 }
 
 // One block per local row i of sims[N1,N2] = feat1 . feat2_global^T  (mml_loss.py:73-77, 89-95, 350-376).
@@ -57,6 +66,7 @@ __global__ __launch_bounds__(256) void nce_rows_kernel(float* __restrict__ sims,
     }
     const float bmx = block_reduce_max(mx, sh);
     // first index attaining the maximum
+    // (block_reduce_min_int with the wave count fixed at 4: the helper's blockDim loop makes this kernel 101 instructions longer)
     int cand = (mx == bmx) ? arg : 0x7fffffff;
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
@@ -158,17 +168,6 @@ __global__ __launch_bounds__(256) void nce_finalize_pair_kernel(const float* __r
         out[2] = c1 / N1;
         out[3] = (T >= 0.001f && T <= 0.5f) ? -0.5f * t / (temp * temp) : 0.f;
     }
-}
-
-__device__ __forceinline__ int block_reduce_min_int(int v, int* shi) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) shi[threadIdx.x >> 6] = v;
-    __syncthreads();
-    int b = 0x7fffffff;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) b = min(b, shi[w]);
-    return b;
 }
 
 // Max-violation hinge rows of VSE++ (mml_loss.py:280-347).  One block per row of `blocks` stacked [N1, N2] matrices (row i of matrix
@@ -368,204 +367,6 @@ __global__ __launch_bounds__(256) void recall_count_kernel(const int* __restrict
     }
 }
 
-// torch.optim.AdamW step on a flat fp32 segment, optionally refreshing the bf16 compute copy of the weights.
-__global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                             bf16_t* __restrict__ p16, long n, float lr, float b1, float b2, float eps, float wd, float bc1,
-                             float bc2_sqrt, float grad_scale) {
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-        const float gi = g[i] * grad_scale;
-        float pi = p[i] * (1.0f - lr * wd);
-        const float mi = b1 * m[i] + (1.0f - b1) * gi;
-        const float vi = b2 * v[i] + (1.0f - b2) * gi * gi;
-        const float denom = sqrtf(vi) / bc2_sqrt + eps;
-        pi -= (lr / bc1) * (mi / denom);
-        p[i] = pi; m[i] = mi; v[i] = vi;
-        if (p16) p16[i] = (bf16_t)pi;
-    }
-}
-
-// Multi-tensor form: one launch for every parameter tensor over a tensor table (tensor_table.h).  table[t] = {p, g, m, v, p16, lr,
-// weight_decay}: five device pointers and the tensor's own learning rate / weight decay (the reference builds one param group per
-// parameter, tasks/clip/hooks/optimizer.py:18-36).  p16 (may be null) is the bf16 compute copy the next forward's GEMMs read: refreshed
-// here, so no per-step cast kernels.
-struct AdamTensors { float* p; const float* g; float* m; float* v; bf16_t* p16; float lr; float wd; };
-static_assert(sizeof(AdamTensors) == 48, "table rows are six 8-byte words");
-// AMP form (round 4): the loss scale, the overflow flag and the count of steps actually taken live on the DEVICE (amp.scale / amp.found_inf:
-// torch.amp.GradScaler's tensors, handed over through its `optimizer.grad_scale` / `optimizer.found_inf` contract; amp.step_in / step_out:
-// this optimizer's own two-slot counter).  The gradients are unscaled here (g / scale), and a step whose gradients held an inf / nan updates
-// nothing - the decision never travels to the host, so the reference's fp16 iteration (clip_runner.py:226-230, core/hooks/optimizer.py:73-82)
-// runs without the host read torch's scaler.step() makes for an optimizer that cannot skip by itself.  Bias corrections come from the device
-// counter (skipped steps do not count, as in torch's own fused Adam).
-struct AdamAmp { const float* scale; const float* found_inf; const float* step_in; float* step_out; };
-// CLIP (simseg_adamw_multi_step_clip / _amp_clip): every gradient element is also multiplied by coef[0], the global-norm clipping
-// coefficient simseg_grads_norm_finish left on the device - AFTER the unscale, the reference's order (core/hooks/optimizer.py:45-47:
-// scaler.unscale_ then clip_grad_norm_).  A template flag, not a multiply by 1.0f: the instantiation without it is the kernel as it was.
-template <bool CLIP>
-__global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamTensors* __restrict__ table, const long* __restrict__ sizes,
-                                                          const int* __restrict__ chunk_tid, const long* __restrict__ chunk_off,
-                                                          int chunk, float b1, float b2, float eps, float bc1, float bc2_sqrt,
-                                                          float grad_scale, AdamAmp amp, const float* __restrict__ coef) {
-    const int c = blockIdx.x;
-    if (amp.step_in) {
-        const bool skip = amp.found_inf && amp.found_inf[0] != 0.f;
-        const float st = amp.step_in[0] + (skip ? 0.f : 1.f);
-        if (c == 0 && threadIdx.x == 0) amp.step_out[0] = st;      // (the other slot: nobody reads it during this launch)
-        if (skip) return;
-        bc1 = 1.0f - powf(b1, st);
-        bc2_sqrt = sqrtf(1.0f - powf(b2, st));
-        if (amp.scale) grad_scale /= amp.scale[0];
-    }
-    const auto ch = table_chunk(table, sizes, chunk_tid, chunk_off, chunk);
-    const AdamTensors T = ch.T;      // (plain locals, not structured bindings: with them the compiler emits the loops below differently)
-    const long lo = ch.lo, hi = ch.hi;
-    const float decay = 1.0f - T.lr * T.wd;
-    const float step_size = T.lr / bc1;
-    const float clip = CLIP ? coef[0] : 1.0f;
-    auto one = [&](float g_, float& pi, float& mi, float& vi) {
-        float gi = g_ * grad_scale;
-        if (CLIP) gi *= clip;
-        pi *= decay;
-        mi = b1 * mi + (1.0f - b1) * gi;
-        vi = b2 * vi + (1.0f - b2) * gi * gi;
-        pi -= step_size * (mi / (sqrtf(vi) / bc2_sqrt + eps));
-    };
-    // 16 bytes per lane and streaming (non-temporal) accesses when the chunk allows it: every array is touched exactly once per step
-    // (30 bytes per parameter, 5.9 GB for ViT-B + BERT-base)
-    typedef float f4 __attribute__((ext_vector_type(4)));
-    const bool vec = (((uintptr_t)(T.g + lo) | (uintptr_t)(T.p + lo) | (uintptr_t)(T.m + lo) | (uintptr_t)(T.v + lo)) % 16 == 0) &&
-                     (!T.p16 || (uintptr_t)(T.p16 + lo) % 8 == 0);
-    long i0 = lo;
-    if (vec) {
-        const long n4 = (hi - lo) / 4;
-        for (long q = threadIdx.x; q < n4; q += 256) {
-            const long i = lo + 4 * q;
-            const f4 g4 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(T.g + i));
-            f4 p4 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(T.p + i));
-            f4 m4 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(T.m + i));
-            f4 v4 = __builtin_nontemporal_load(reinterpret_cast<const f4*>(T.v + i));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { float pe = p4[e], me = m4[e], ve = v4[e]; one(g4[e], pe, me, ve); p4[e] = pe; m4[e] = me; v4[e] = ve; }
-            __builtin_nontemporal_store(p4, reinterpret_cast<f4*>(T.p + i));
-            __builtin_nontemporal_store(m4, reinterpret_cast<f4*>(T.m + i));
-            __builtin_nontemporal_store(v4, reinterpret_cast<f4*>(T.v + i));
-            if (T.p16) {
-                bf16x4 o = {(bf16_t)p4[0], (bf16_t)p4[1], (bf16_t)p4[2], (bf16_t)p4[3]};
-                *reinterpret_cast<bf16x4*>(T.p16 + i) = o;             // (read by the next step's GEMMs: default policy)
-            }
-        }
-        i0 = lo + 4 * n4;
-    }
-    for (long i = i0 + threadIdx.x; i < hi; i += 256) {
-        float pi = T.p[i], mi = T.m[i], vi = T.v[i];
-        one(T.g[i], pi, mi, vi);
-        T.p[i] = pi; T.m[i] = mi; T.v[i] = vi;
-        if (T.p16) T.p16[i] = (bf16_t)pi;
-    }
-}
-
-// found[0] = 1 if any gradient element of the table's tensors is inf / nan (read-only pass, 16 bytes per lane, one store per block that
-// sees one): the overflow check of torch.amp.GradScaler (`_amp_foreach_non_finite_check_and_unscale_` with inverse scale 1: a read-modify-
-// write pass over every gradient tensor) as ONE launch over the optimizer's own tensor table; the unscaling itself rides on the AdamW kernel.
-__global__ __launch_bounds__(256) void grads_nonfinite_kernel(const AdamTensors* __restrict__ table, const long* __restrict__ sizes,
-                                                              const int* __restrict__ chunk_tid, const long* __restrict__ chunk_off,
-                                                              int chunk, float* __restrict__ found) {
-    const auto [t, T, lo, hi] = table_chunk(table, sizes, chunk_tid, chunk_off, chunk);
-    const float* g = T.g;
-    unsigned bad = 0;
-    long i0 = lo;
-    if ((uintptr_t)(g + lo) % 16 == 0) {
-        const long n4 = (hi - lo) / 4;
-        for (long q = threadIdx.x; q < n4; q += 256) {
-            const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(g + lo + 4 * q));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bad |= ((v[e] & 0x7f800000u) == 0x7f800000u) ? 1u : 0u;
-        }
-        i0 = lo + 4 * n4;
-    }
-    for (long i = i0 + threadIdx.x; i < hi; i += 256) bad |= ((__float_as_uint(g[i]) & 0x7f800000u) == 0x7f800000u) ? 1u : 0u;
-    if (__any(bad != 0) && (threadIdx.x & 63) == 0) found[0] = 1.0f;
-}
-
-// Global gradient norm, pass 1: partials[c] = sum of g^2 (norm_type 2) or max |g| (norm_type 0 = infinity) over chunk c of the table's
-// gradient tensors - the same read-only walk as grads_nonfinite_kernel (16 bytes per lane, streaming loads, scalar tail / unaligned
-// chunks).  fp32 sums: four independent accumulators per lane (<= 64 terms each for a 65536-element chunk), combined pairwise, a wave
-// butterfly, then LDS across the four waves in a fixed order; one plain store per block and no atomics, so a call is bit-reproducible.
-// inf and nan propagate through the sums by themselves.  The maximum is taken on the bit patterns of |g| as unsigned integers: for
-// non-negative floats that is the floating-point order, and every nan pattern lies above +inf, so a nan wins (fmaxf would drop it).
-__global__ __launch_bounds__(256) void grads_norm_partials_kernel(const AdamTensors* __restrict__ table, const long* __restrict__ sizes,
-                                                                  const int* __restrict__ chunk_tid, const long* __restrict__ chunk_off,
-                                                                  int chunk, int norm_type, float* __restrict__ partials) {
-    __shared__ float sh[4];
-    const int c = blockIdx.x;
-    const auto [t, T, lo, hi] = table_chunk(table, sizes, chunk_tid, chunk_off, chunk);
-    const float* g = T.g;
-    const bool vec = (uintptr_t)(g + lo) % 16 == 0;
-    const long n4 = vec ? (hi - lo) / 4 : 0;
-    const long i0 = lo + 4 * n4;
-    float r;
-    if (norm_type == 2) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        for (long q = threadIdx.x; q < n4; q += 256) {
-            const f32x4 v = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(g + lo + 4 * q));
-            a0 += v[0] * v[0]; a1 += v[1] * v[1]; a2 += v[2] * v[2]; a3 += v[3] * v[3];
-        }
-        for (long i = i0 + threadIdx.x; i < hi; i += 256) a0 += g[i] * g[i];
-        r = wave_sum((a0 + a1) + (a2 + a3));
-    } else {
-        unsigned m = 0;
-        for (long q = threadIdx.x; q < n4; q += 256) {
-            const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(g + lo + 4 * q));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) m = max(m, v[e] & 0x7fffffffu);
-        }
-        for (long i = i0 + threadIdx.x; i < hi; i += 256) m = max(m, __float_as_uint(g[i]) & 0x7fffffffu);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o, 64));
-        r = __uint_as_float(m);
-    }
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = r;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (norm_type == 2) r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-        else r = __uint_as_float(max(max(__float_as_uint(sh[0]), __float_as_uint(sh[1])), max(__float_as_uint(sh[2]), __float_as_uint(sh[3]))));
-        partials[c] = r;
-    }
-}
-
-// Pass 2, one block: the partials of every bucket reduced in double precision (fixed order: strided per lane, wave butterfly, LDS).
-// out2[0] = the total norm, divided by loss_scale[0] when given (the norm of the UNSCALED gradients, which is what the reference clips);
-// out2[1] = min(1, max_norm / (total_norm + 1e-6)), torch.nn.utils.clip_grad_norm_'s coefficient (a nan norm gives a nan coefficient, as
-// torch's clamp does).  Everything stays on the device.
-__global__ __launch_bounds__(256) void grads_norm_finish_kernel(const float* __restrict__ partials, long n, int norm_type, float max_norm,
-                                                                const float* __restrict__ loss_scale, float* __restrict__ out2) {
-    __shared__ double shd[4];
-    double acc = 0.0;
-    if (norm_type == 2) {
-        for (long i = threadIdx.x; i < n; i += 256) acc += (double)partials[i];
-    } else {
-        unsigned m = 0;
-        for (long i = threadIdx.x; i < n; i += 256) m = max(m, __float_as_uint(partials[i]));
-        acc = (double)m;          // (exact: the bit patterns are ordered like the values; turned back into a float below)
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double other = __shfl_xor(acc, o, 64);
-        acc = norm_type == 2 ? acc + other : fmax(acc, other);
-    }
-    if ((threadIdx.x & 63) == 0) shd[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double total;
-        if (norm_type == 2) total = sqrt((shd[0] + shd[1]) + (shd[2] + shd[3]));
-        else total = (double)__uint_as_float((unsigned)fmax(fmax(shd[0], shd[1]), fmax(shd[2], shd[3])));
-        if (loss_scale) total /= (double)loss_scale[0];
-        double coef = (double)max_norm / (total + 1e-6);
-        if (coef > 1.0) coef = 1.0;
-        out2[0] = (float)total;
-        out2[1] = (float)coef;
-    }
-}
-
 }  // namespace
 
 #define STREAM ((hipStream_t)stream)
@@ -704,113 +505,5 @@ extern "C" int simseg_recall_counts(const int32_t* has_match, const int32_t* ran
     if (blocks < 1) blocks = 1;
     hipLaunchKernelGGL(recall_count_kernel, dim3((unsigned)blocks), dim3(256), 0, STREAM, has_match, rank, (long)M, b0, b1, b2, counts4);
     SS_LAUNCH_CHECK("recall_counts");
-    return 0;
-}
-
-// The launch of the four simseg_adamw_multi_step* entry points: `step` is the host's count (bias corrections formed here), or the
-// device counter travels in `amp`; grad_coef selects CLIP.
-static int adamw_multi_launch(const char* who, const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
-                              int64_t n_chunks, int chunk, float beta1, float beta2, float eps, int64_t step, AdamAmp amp, float grad_scale,
-                              const float* grad_coef, void* stream) {
-    if (amp.step_in) SS_CHECK(chunk > 0, "%s: bad chunk", who);
-    else SS_CHECK(step >= 1 && chunk > 0, "%s: bad step/chunk", who);
-    if (n_chunks <= 0) return 0;
-    const float bc1 = amp.step_in ? 1.0f : 1.0f - powf(beta1, (float)step);
-    const float bc2_sqrt = amp.step_in ? 1.0f : sqrtf(1.0f - powf(beta2, (float)step));
-    const auto kernel = grad_coef ? adamw_multi_kernel<true> : adamw_multi_kernel<false>;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
-                       (const int*)chunk_tid, (const long*)chunk_off, chunk, beta1, beta2, eps, bc1, bc2_sqrt, grad_scale, amp, grad_coef);
-    SS_LAUNCH_CHECK(who);
-    return 0;
-}
-
-extern "C" int simseg_adamw_multi_step(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
-                                       int64_t n_chunks, int chunk, float beta1, float beta2, float eps, int64_t step,
-                                       float grad_scale, void* stream) {
-    SS_HALF_FWD(simseg_adamw_multi_step, table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, step, grad_scale, stream);
-    SS_CHECK(table && sizes && chunk_tid && chunk_off, "adamw_multi_step: null pointer");
-    return adamw_multi_launch("adamw_multi_step", table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, step, AdamAmp{},
-                              grad_scale, nullptr, stream);
-}
-
-extern "C" int simseg_adamw_multi_step_clip(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
-                                            int64_t n_chunks, int chunk, float beta1, float beta2, float eps, int64_t step,
-                                            float grad_scale, const float* grad_coef, void* stream) {
-    SS_HALF_FWD(simseg_adamw_multi_step_clip, table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, step, grad_scale,
-                grad_coef, stream);
-    SS_CHECK(table && sizes && chunk_tid && chunk_off && grad_coef, "adamw_multi_step_clip: null pointer");
-    return adamw_multi_launch("adamw_multi_step_clip", table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, step, AdamAmp{},
-                              grad_scale, grad_coef, stream);
-}
-
-extern "C" int simseg_adamw_multi_step_amp(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
-                                           int64_t n_chunks, int chunk, float beta1, float beta2, float eps, float grad_scale,
-                                           const float* loss_scale, const float* found_inf, const float* step_in, float* step_out, void* stream) {
-    SS_HALF_FWD(simseg_adamw_multi_step_amp, table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, grad_scale, loss_scale,
-                found_inf, step_in, step_out, stream);
-    SS_CHECK(table && sizes && chunk_tid && chunk_off && step_in && step_out && step_in != step_out, "adamw_multi_step_amp: null / aliased pointer");
-    return adamw_multi_launch("adamw_multi_step_amp", table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, 0,
-                              AdamAmp{loss_scale, found_inf, step_in, step_out}, grad_scale, nullptr, stream);
-}
-
-extern "C" int simseg_adamw_multi_step_amp_clip(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
-                                                int64_t n_chunks, int chunk, float beta1, float beta2, float eps, float grad_scale,
-                                                const float* loss_scale, const float* found_inf, const float* step_in, float* step_out,
-                                                const float* grad_coef, void* stream) {
-    SS_HALF_FWD(simseg_adamw_multi_step_amp_clip, table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, grad_scale,
-                loss_scale, found_inf, step_in, step_out, grad_coef, stream);
-    SS_CHECK(table && sizes && chunk_tid && chunk_off && step_in && step_out && step_in != step_out && grad_coef,
-             "adamw_multi_step_amp_clip: null / aliased pointer");
-    return adamw_multi_launch("adamw_multi_step_amp_clip", table, sizes, chunk_tid, chunk_off, n_chunks, chunk, beta1, beta2, eps, 0,
-                              AdamAmp{loss_scale, found_inf, step_in, step_out}, grad_scale, grad_coef, stream);
-}
-
-extern "C" int simseg_grads_nonfinite(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
-                                      int64_t n_chunks, int chunk, float* found_inf, void* stream) {
-    SS_HALF_FWD(simseg_grads_nonfinite, table, sizes, chunk_tid, chunk_off, n_chunks, chunk, found_inf, stream);
-    SS_CHECK(table && sizes && chunk_tid && chunk_off && found_inf, "grads_nonfinite: null pointer");
-    SS_CHECK(chunk > 0, "grads_nonfinite: bad chunk");
-    if (n_chunks <= 0) return 0;
-    hipLaunchKernelGGL(grads_nonfinite_kernel, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table, (const long*)sizes,
-                       (const int*)chunk_tid, (const long*)chunk_off, chunk, found_inf);
-    SS_LAUNCH_CHECK("grads_nonfinite");
-    return 0;
-}
-
-extern "C" int simseg_grads_norm_partials(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
-                                          int64_t n_chunks, int chunk, int norm_type, float* partials, void* stream) {
-    SS_CHECK(table && sizes && chunk_tid && chunk_off && partials, "grads_norm_partials: null pointer");
-    SS_CHECK(chunk > 0 && (norm_type == 2 || norm_type == 0), "grads_norm_partials: chunk > 0, norm_type 2 or 0 (infinity)");
-    if (n_chunks <= 0) return 0;
-    hipLaunchKernelGGL(grads_norm_partials_kernel, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const AdamTensors*)table,
-                       (const long*)sizes, (const int*)chunk_tid, (const long*)chunk_off, chunk, norm_type, partials);
-    SS_LAUNCH_CHECK("grads_norm_partials");
-    return 0;
-}
-
-extern "C" int simseg_grads_norm_finish(const float* partials, int64_t n_partials, int norm_type, float max_norm, const float* loss_scale,
-                                        float* out2, void* stream) {
-    SS_CHECK(out2 && (partials || n_partials <= 0), "grads_norm_finish: null pointer");
-    SS_CHECK(norm_type == 2 || norm_type == 0, "grads_norm_finish: norm_type 2 or 0 (infinity)");
-    SS_CHECK(max_norm >= 0.f, "grads_norm_finish: max_norm %g is negative (or nan)", (double)max_norm);
-    hipLaunchKernelGGL(grads_norm_finish_kernel, dim3(1), dim3(256), 0, STREAM, partials, (long)(n_partials > 0 ? n_partials : 0), norm_type,
-                       max_norm, loss_scale, out2);
-    SS_LAUNCH_CHECK("grads_norm_finish");
-    return 0;
-}
-
-extern "C" int simseg_adamw_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1,
-                                 float beta2, float eps, float weight_decay, int64_t step, float grad_scale, void* stream) {
-    SS_HALF_FWD(simseg_adamw_step, p, g, m, v, p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, grad_scale, stream);
-    SS_CHECK(p && g && m && v, "adamw_step: null pointer");
-    SS_CHECK(step >= 1, "adamw_step: step counts from 1");
-    if (n <= 0) return 0;
-    const float bc1 = 1.0f - powf(beta1, (float)step);
-    const float bc2 = 1.0f - powf(beta2, (float)step);
-    long blocks = (n + 255) / 256;
-    if (blocks > 16384) blocks = 16384;
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, STREAM, p, g, m, v, (bf16_t*)p_bf16, (long)n, lr, beta1, beta2, eps,
-                       weight_decay, bc1, sqrtf(bc2), grad_scale);
-    SS_LAUNCH_CHECK("adamw_step");
     return 0;
 }

@@ -1,12 +1,12 @@
-// Linear-probe task (simseg/tasks/linear_prob, simseg/models/pipelines/linear_prob.py, simseg/core/optimizer/lars.py of the reference):
-// cross-entropy rows over integer class labels with top-1 / top-5 hits and the logit gradient in one pass - also against the two-label
-// soft target of a Mixup / CutMix batch (the same kernels, SOFT) - and LARS as three launches over a tensor table.  Compiled ONCE: the 16-bit flavour (bf16 / fp16) is a template argument chosen from the calling thread's
-// simseg_set_half_type, so dtype code 1 means "the selected 16-bit type" as everywhere else in the ABI.
+// Linear-probe task (simseg/tasks/linear_prob, simseg/models/pipelines/linear_prob.py of the reference): cross-entropy rows over integer
+// class labels with top-1 / top-5 hits and the logit gradient in one pass - also against the two-label soft target of a Mixup / CutMix
+// batch (the same kernels, SOFT).  (The task's optimizer, LARS, is in optim.hip.)  Compiled ONCE: the 16-bit flavour (bf16 / fp16) is a
+// template argument chosen from the calling thread's simseg_set_half_type, so dtype code 1 means "the selected 16-bit type" as
+// everywhere else in the ABI.
 #include <float.h>
 #include <limits.h>
 
 #include "common.h"
-#include "tensor_table.h"
 
 namespace {
 
@@ -302,169 +302,6 @@ __global__ __launch_bounds__(256) void ce_finish_kernel(const float* __restrict_
     }
 }
 
-// ---- LARS over a tensor table (tensor_table.h) ---------------------------------------------------------------------------------------
-// table[t] = {p, g, buf, p16, (float lr, float weight_decay), flags}: fp32 master, fp32 gradient, fp32 momentum buffer (0 when momentum
-// == 0), the 16-bit compute copy to refresh (or 0), the tensor's learning rate and weight decay, and flags: bit 0 = lars_exclude (local
-// lr 1), bit 1 = first step of this tensor (no momentum buffer yet: buf = d).
-struct LarsTensors { float* p; const float* g; float* buf; void* p16; float lr; float wd; long flags; };
-static_assert(sizeof(LarsTensors) == 48, "table rows are six 8-byte words");
-
-// partials[2c] = sum of p^2, partials[2c + 1] = sum of g^2 over chunk c.  Read-only on p and g; double accumulators (the pass is bound by
-// its 8 bytes per element, not by the FMAs), wave butterfly, the four waves through LDS in a fixed order, one plain store per sum.
-__global__ __launch_bounds__(256) void lars_norm_partials_kernel(const LarsTensors* __restrict__ table, const long* __restrict__ sizes,
-                                                                 const int* __restrict__ chunk_tid, const long* __restrict__ chunk_off,
-                                                                 int chunk, double* __restrict__ partials) {
-    __shared__ double sh[8];
-    const int c = blockIdx.x;
-    const auto [t, T, lo, hi] = table_chunk(table, sizes, chunk_tid, chunk_off, chunk);
-    const float* p = T.p;
-    const float* g = T.g;
-    const bool vec = (((uintptr_t)(p + lo) | (uintptr_t)(g + lo)) % 16) == 0;
-    const long n4 = vec ? (hi - lo) / 4 : 0;
-    double pp = 0.0, gg = 0.0;
-    for (long q = threadIdx.x; q < n4; q += 256) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p + lo + 4 * q);
-        const f32x4 b = *reinterpret_cast<const f32x4*>(g + lo + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            pp = fma((double)a[e], (double)a[e], pp);
-            gg = fma((double)b[e], (double)b[e], gg);
-        }
-    }
-    for (long i = lo + 4 * n4 + threadIdx.x; i < hi; i += 256) {
-        pp = fma((double)p[i], (double)p[i], pp);
-        gg = fma((double)g[i], (double)g[i], gg);
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        pp += __shfl_xor(pp, o, 64);
-        gg += __shfl_xor(gg, o, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        sh[threadIdx.x >> 6] = pp;
-        sh[4 + (threadIdx.x >> 6)] = gg;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partials[2 * (long)c] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-        partials[2 * (long)c + 1] = (sh[4] + sh[5]) + (sh[6] + sh[7]);
-    }
-}
-
-// One block (one wave) per tensor: its chunks' partials, [tensor_first[t], tensor_first[t + 1]), are summed in CHUNK order in double
-// precision (the lanes fetch 64 at a time, the additions run in order), then
-//   local_lr[t] = eta * wn / (gn + weight_decay * wn + eps)   when wn != 0 and gn != 0, else 1;   1 for a lars_exclude tensor.
-// The reference reads both norms on the host (two .item() calls per tensor, lars.py:104-105); here nothing leaves the device.
-__global__ __launch_bounds__(64) void lars_finish_kernel(const LarsTensors* __restrict__ table, const int* __restrict__ tensor_first,
-                                                         const double* __restrict__ partials, float eta, float eps,
-                                                         float* __restrict__ local_lr) {
-    const int t = blockIdx.x, lane = threadIdx.x;
-    const int c0 = tensor_first[t], c1 = tensor_first[t + 1];
-    double sp = 0.0, sg = 0.0;
-    for (int base = c0; base < c1; base += 64) {
-        const int k = base + lane;
-        const double a = k < c1 ? partials[2 * (long)k] : 0.0;
-        const double b = k < c1 ? partials[2 * (long)k + 1] : 0.0;
-        const int n = min(64, c1 - base);
-        for (int j = 0; j < n; ++j) {
-            sp += __shfl(a, j, 64);
-            sg += __shfl(b, j, 64);
-        }
-    }
-    if (lane == 0) {
-        float out = 1.0f;
-        if (!(table[t].flags & 1)) {
-            const double wn = sqrt(sp), gn = sqrt(sg);
-            if (wn != 0.0 && gn != 0.0) out = (float)((double)eta * wn / (gn + (double)table[t].wd * wn + (double)eps));
-        }
-        local_lr[t] = out;
-    }
-}
-
-// The update, per element (lars.py:113-127 restated):
-//   d = (g + weight_decay * p) * (local_lr[t] * lr)
-//   momentum != 0:  buf = d on the tensor's first step, else momentum * buf + (1 - dampening) * d;   d = nesterov ? d + momentum * buf : buf
-//   p -= d;  p16 = p rounded to the 16-bit type
-// The arithmetic runs in double between the fp32 loads and stores (20 bytes of traffic per element: the kernel is bound by memory, and the
-// result is then the correctly rounded value of the law above rather than a chain of fp32 roundings); buf is rounded to fp32 BEFORE it
-// enters d, as the stored buffer is what the reference's update reads.
-template <typename H>
-__global__ __launch_bounds__(256) void lars_multi_kernel(const LarsTensors* __restrict__ table, const long* __restrict__ sizes,
-                                                         const int* __restrict__ chunk_tid, const long* __restrict__ chunk_off, int chunk,
-                                                         const float* __restrict__ local_lr, float momentum, float dampening,
-                                                         int nesterov) {
-    const auto ch = table_chunk(table, sizes, chunk_tid, chunk_off, chunk);
-    const LarsTensors T = ch.T;      // (plain locals, as in adamw_multi_kernel)
-    const int t = ch.t;
-    const long lo = ch.lo, hi = ch.hi;
-    H* p16 = reinterpret_cast<H*>(T.p16);
-    const double scale = (double)local_lr[t] * (double)T.lr;
-    const double wd = (double)T.wd, mom = (double)momentum, keep = 1.0 - (double)dampening;
-    const bool first = (T.flags & 2) != 0;
-    const bool use_buf = momentum != 0.f && T.buf != nullptr;
-    auto one = [&](float g_, float& pi, float& bi) {
-        double d = ((double)g_ + wd * (double)pi) * scale;
-        if (use_buf) {
-            bi = (float)(first ? d : mom * (double)bi + keep * d);
-            d = nesterov ? d + mom * (double)bi : (double)bi;
-        }
-        pi = (float)((double)pi - d);
-    };
-    const bool vec = (((uintptr_t)(T.g + lo) | (uintptr_t)(T.p + lo)) % 16 == 0) && (!use_buf || (uintptr_t)(T.buf + lo) % 16 == 0) &&
-                     (!p16 || (uintptr_t)(p16 + lo) % 8 == 0);
-    long i0 = lo;
-    if (vec) {
-        typedef H h4 __attribute__((ext_vector_type(4)));
-        const long n4 = (hi - lo) / 4;
-        for (long q = threadIdx.x; q < n4; q += 256) {
-            const long i = lo + 4 * q;
-            const f32x4 g4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(T.g + i));
-            f32x4 p4 = *reinterpret_cast<const f32x4*>(T.p + i);
-            f32x4 b4 = {0.f, 0.f, 0.f, 0.f};
-            if (use_buf && !first) b4 = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(T.buf + i));
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float pe = p4[e], be = b4[e];
-                one(g4[e], pe, be);
-                p4[e] = pe;
-                b4[e] = be;
-            }
-            *reinterpret_cast<f32x4*>(T.p + i) = p4;
-            if (use_buf) __builtin_nontemporal_store(b4, reinterpret_cast<f32x4*>(T.buf + i));
-            if (p16) {
-                const h4 o = {(H)p4[0], (H)p4[1], (H)p4[2], (H)p4[3]};
-                *reinterpret_cast<h4*>(p16 + i) = o;
-            }
-        }
-        i0 = lo + 4 * n4;
-    }
-    for (long i = i0 + threadIdx.x; i < hi; i += 256) {
-        float pi = T.p[i], bi = (use_buf && !first) ? T.buf[i] : 0.f;
-        one(T.g[i], pi, bi);
-        T.p[i] = pi;
-        if (use_buf) T.buf[i] = bi;
-        if (p16) p16[i] = (H)pi;
-    }
-}
-
-// The chunk tables as the HOST sees them, checked before anything is launched (the kernels index with them).
-int lars_check_tables(const char* who, const int64_t* sizes_host, const int32_t* chunk_tid_host, const int64_t* chunk_off_host,
-                      int64_t n_tensors, int64_t n_chunks, int chunk) {
-    SS_CHECK(sizes_host && chunk_tid_host && chunk_off_host, "%s: null host table", who);
-    SS_CHECK(n_tensors >= 1 && n_tensors < (1ll << 31) && n_chunks >= 0 && n_chunks < (1ll << 31) && chunk > 0,
-             "%s: bad table extents (%lld tensors, %lld chunks of %d)", who, (long long)n_tensors, (long long)n_chunks, chunk);
-    for (int64_t t = 0; t < n_tensors; ++t)
-        SS_CHECK(sizes_host[t] >= 0, "%s: tensor %lld has a negative size (%lld)", who, (long long)t, (long long)sizes_host[t]);
-    for (int64_t c = 0; c < n_chunks; ++c) {
-        const int64_t t = chunk_tid_host[c];
-        SS_CHECK(t >= 0 && t < n_tensors, "%s: chunk %lld names tensor id %lld, outside [0, %lld)", who, (long long)c, (long long)t,
-                 (long long)n_tensors);
-        SS_CHECK(chunk_off_host[c] >= 0 && chunk_off_host[c] < sizes_host[t], "%s: chunk offset %lld of chunk %lld is past the end of tensor %lld (%lld elements)",
-                 who, (long long)chunk_off_host[c], (long long)c, (long long)t, (long long)sizes_host[t]);
-    }
-    return 0;
-}
-
 }  // namespace
 
 #define STREAM ((hipStream_t)stream)
@@ -525,53 +362,5 @@ extern "C" int simseg_soft_ce_rows(const void* logits, int dt, const int64_t* la
     if (rc) return rc;
     hipLaunchKernelGGL(ce_finish_kernel, dim3(1), dim3(256), 0, STREAM, loss_rows, ranks, out3, (int)B);
     SS_LAUNCH_CHECK("soft_ce_rows");
-    return 0;
-}
-
-extern "C" int simseg_lars_norm_partials(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
-                                         const int64_t* sizes_host, const int32_t* chunk_tid_host, const int64_t* chunk_off_host,
-                                         int64_t n_tensors, int64_t n_chunks, int chunk, double* partials, void* stream) {
-    SS_CHECK(table && sizes && chunk_tid && chunk_off && partials, "lars_norm_partials: null pointer");
-    if (int rc = lars_check_tables("lars_norm_partials", sizes_host, chunk_tid_host, chunk_off_host, n_tensors, n_chunks, chunk)) return rc;
-    if (n_chunks == 0) return 0;
-    hipLaunchKernelGGL(lars_norm_partials_kernel, dim3((unsigned)n_chunks), dim3(256), 0, STREAM, (const LarsTensors*)table, (const long*)sizes,
-                       chunk_tid, (const long*)chunk_off, chunk, partials);
-    SS_LAUNCH_CHECK("lars_norm_partials");
-    return 0;
-}
-
-extern "C" int simseg_lars_finish(const void* table, const int32_t* tensor_first, const int32_t* tensor_first_host, const double* partials,
-                                  int64_t n_tensors, int64_t n_chunks, float eta, float eps, float* local_lr, void* stream) {
-    SS_CHECK(table && tensor_first && tensor_first_host && partials && local_lr, "lars_finish: null pointer");
-    SS_CHECK(n_tensors >= 1 && n_tensors < (1ll << 31) && n_chunks >= 0 && n_chunks < (1ll << 31), "lars_finish: bad table extents (%lld tensors, %lld chunks)",
-             (long long)n_tensors, (long long)n_chunks);
-    SS_CHECK(eta >= 0.f && eps >= 0.f, "lars_finish: eta %g / eps %g is negative (or nan)", (double)eta, (double)eps);
-    SS_CHECK(tensor_first_host[0] == 0 && tensor_first_host[n_tensors] == n_chunks, "lars_finish: the tensors' chunk ranges cover [%d, %d), not [0, %lld)",
-             tensor_first_host[0], tensor_first_host[n_tensors], (long long)n_chunks);
-    for (int64_t t = 0; t < n_tensors; ++t)
-        SS_CHECK(tensor_first_host[t] <= tensor_first_host[t + 1], "lars_finish: the chunk range of tensor %lld is reversed", (long long)t);
-    hipLaunchKernelGGL(lars_finish_kernel, dim3((unsigned)n_tensors), dim3(64), 0, STREAM, (const LarsTensors*)table, tensor_first, partials, eta, eps,
-                       local_lr);
-    SS_LAUNCH_CHECK("lars_finish");
-    return 0;
-}
-
-extern "C" int simseg_lars_multi_step(const void* table, const int64_t* sizes, const int32_t* chunk_tid, const int64_t* chunk_off,
-                                      const int64_t* sizes_host, const int32_t* chunk_tid_host, const int64_t* chunk_off_host, int64_t n_tensors,
-                                      int64_t n_chunks, int chunk, const float* local_lr, float momentum, float dampening, int nesterov,
-                                      void* stream) {
-    SS_CHECK(table && sizes && chunk_tid && chunk_off && local_lr, "lars_multi_step: null pointer");
-    SS_CHECK(momentum >= 0.f, "lars_multi_step: momentum %g is negative (or nan)", (double)momentum);
-    SS_CHECK(!nesterov || (momentum > 0.f && dampening == 0.f), "lars_multi_step: Nesterov momentum requires a momentum and zero dampening");
-    if (int rc = lars_check_tables("lars_multi_step", sizes_host, chunk_tid_host, chunk_off_host, n_tensors, n_chunks, chunk)) return rc;
-    if (n_chunks == 0) return 0;
-    const dim3 grid((unsigned)n_chunks);
-    if (g_ss_half == 2)
-        hipLaunchKernelGGL(lars_multi_kernel<_Float16>, grid, dim3(256), 0, STREAM, (const LarsTensors*)table, (const long*)sizes, chunk_tid,
-                           (const long*)chunk_off, chunk, local_lr, momentum, dampening, nesterov);
-    else
-        hipLaunchKernelGGL(lars_multi_kernel<__bf16>, grid, dim3(256), 0, STREAM, (const LarsTensors*)table, (const long*)sizes, chunk_tid,
-                           (const long*)chunk_off, chunk, local_lr, momentum, dampening, nesterov);
-    SS_LAUNCH_CHECK("lars_multi_step");
     return 0;
 }

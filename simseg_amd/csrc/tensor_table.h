@@ -1,4 +1,4 @@
-// The tensor-table contract of the table-driven passes (AdamW and its gradient checks in loss.hip, LARS in probe.hip; the host side is
+// The tensor-table contract of the table-driven passes (optim.hip: AdamW, its gradient checks and LARS; the host side is
 // simseg_amd.optim.TensorTable).  One launch serves every tensor of a bucket:
 //   table[t]      six 8-byte words per tensor.  Word 0 = the fp32 master, word 1 = its fp32 gradient; the other four belong to the pass
 //                 (AdamTensors, LarsTensors: each static_asserts its 48 bytes).

@@ -1023,7 +1023,7 @@ def train_transforms(src, plan, lut, want_u8=False):
     return out, u8
 
 
-# ---- linear-probe task (csrc/probe.hip) ------------------------------------------------------------------------------------------
+# ---- linear-probe task (csrc/probe.hip; LARS: csrc/optim.hip) --------------------------------------------------------------------
 CE_MAX_CLASSES = 65536         # simseg_ce_rows: 1 <= C <= 65536
 
 

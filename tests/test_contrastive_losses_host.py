@@ -198,8 +198,13 @@ def test_c_abi_declares_and_exports_the_new_entries():
                                                                 "row_correct", "row_tdot", "out3", "N1", "N2", "target0", "smoothing",
                                                                 "write_grad", "stream"]
     so = ctypes.CDLL(lib.LIB_PATH)          # (the built library: the suite runs after the build)
-    for name in ("simseg_triplet_rows", "simseg_mix_nce_rows", "simseg_triplet_rows_h16", "simseg_mix_nce_rows_h16"):
+    from simseg_amd import build
+    assert "loss.hip" not in build.TWICE     # fp32 rows: one entry point each, no second flavour
+    src = open(os.path.join(REPO, "simseg_amd/csrc/loss.hip")).read()
+    for name in ("simseg_triplet_rows", "simseg_mix_nce_rows"):
+        assert f'extern "C" int {name}(' in src, f"{name} is not defined in loss.hip"
         assert hasattr(so, name), f"{name} is not exported"
+        assert not hasattr(so, name + "_h16"), f"{name}_h16 is exported"
 
 
 @pytest.mark.parametrize("family", R.FAMILIES)

@@ -1114,19 +1114,32 @@ def test_retrieval_rank(ops, golden):
         assert torch.equal(rankc.long()[hasc.bool()], (s > bestc[None, :]).sum(0)[hasc.bool()])
 
 
-def test_adamw_step(ops):
+def _adamw_three_steps(ops, half, ref_opt=None, ref=None):
     n = 4096 * 3
     p, g = _rand(n, seed=1), _rand(n, seed=2)
-    ref = p.clone().requires_grad_(True)
-    opt = torch.optim.AdamW([ref], lr=1e-3, betas=(0.9, 0.98), eps=1e-6, weight_decay=1e-3)
     m, v = torch.zeros_like(p), torch.zeros_like(p)
-    p16 = torch.empty(n, device="cuda", dtype=torch.bfloat16)
+    p16 = torch.empty(n, device="cuda", dtype=half)
     for step in range(1, 4):
-        ref.grad = g * step
-        opt.step()
+        if ref_opt is not None:
+            ref.grad = g * step
+            ref_opt.step()
         ops.adamw_step(p, g * step, m, v, p16, 1e-3, (0.9, 0.98), 1e-6, 1e-3, step)
+    return p, m, v, p16
+
+
+@pytest.mark.parametrize("half", [torch.bfloat16, torch.float16], ids=["bf16", "fp16"])
+def test_adamw_step(ops, half):
+    """Both 16-bit types of the compute copy go through the one entry point (the copy's dtype selects the kernel instantiation): the copy
+    is the fp32 master rounded to that type, bit for bit, and the fp32 state does not depend on the type."""
+    ref = _rand(4096 * 3, seed=1).requires_grad_(True)
+    opt = torch.optim.AdamW([ref], lr=1e-3, betas=(0.9, 0.98), eps=1e-6, weight_decay=1e-3)
+    p, m, v, p16 = _adamw_three_steps(ops, half, opt, ref)
     _close(p, ref.detach(), 1e-6, "adamw")
-    assert torch.equal(p16, p.bfloat16())
+    assert p16.dtype == half and torch.equal(p16, p.to(half))
+    if half is torch.float16:
+        assert not torch.equal(p16.float(), p.bfloat16().float())       # (really fp16: values bf16 cannot hold)
+        pb, mb, vb, _ = _adamw_three_steps(ops, torch.bfloat16)
+        assert torch.equal(p, pb) and torch.equal(m, mb) and torch.equal(v, vb)
 
 
 def test_adamw_multi_tensor_optimizer():

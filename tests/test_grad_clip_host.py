@@ -1,4 +1,4 @@
-"""Host-side contract of the fused gradient clipping: the C ABI declares the new entry points (and their fp16-flavour twins), the
+"""Host-side contract of the fused gradient clipping: the C ABI declares the new entry points (one each for both 16-bit types), the
 optimizer has the two methods with the documented signatures, and an unsupported norm type is refused before any device work."""
 import inspect
 import math
@@ -12,7 +12,7 @@ from conftest import REPO
 NEW = ["simseg_grads_norm_partials", "simseg_grads_norm_finish", "simseg_adamw_multi_step_clip", "simseg_adamw_multi_step_amp_clip"]
 
 
-def test_header_declares_the_entry_points_and_the_second_flavour_names_them():
+def test_header_declares_the_entry_points_and_no_second_flavour_renames_them():
     from simseg_amd import lib
     decl = lib.parse_header()
     for name in NEW:
@@ -24,18 +24,22 @@ def test_header_declares_the_entry_points_and_the_second_flavour_names_them():
     assert [n for _, n in decl["simseg_grads_norm_partials"][1]] == ["table", "sizes", "chunk_tid", "chunk_off", "n_chunks", "chunk", "norm_type",
                                                                      "partials", "stream"]
     assert [n for _, n in decl["simseg_grads_norm_finish"][1]] == ["partials", "n_partials", "norm_type", "max_norm", "loss_scale", "out2", "stream"]
+    # one entry point serves both 16-bit types (the kernel takes the type as a template argument): no renamed second flavour
+    from simseg_amd import build
+    assert "optim.hip" not in build.TWICE
+    src = open(os.path.join(REPO, "simseg_amd", "csrc", "optim.hip")).read()
     names = open(os.path.join(REPO, "simseg_amd", "csrc", "half_names.h")).read()
     for name in NEW:
-        assert re.search(rf"^#define {name} {name}_h16$", names, flags=re.M), name
-        assert re.search(rf"^int {name}_h16\(", names, flags=re.M), name
+        assert re.search(rf'^extern "C" int {name}\(', src, flags=re.M), name
+        assert f"{name}_h16" not in names, name
 
 
-def test_library_exports_both_flavours():
+def test_library_exports_one_entry_for_both_flavours():
     import ctypes
     from simseg_amd import lib
     so = ctypes.CDLL(lib.LIB_PATH)
     for name in NEW:
-        assert hasattr(so, name) and hasattr(so, name + "_h16"), name
+        assert hasattr(so, name) and not hasattr(so, name + "_h16"), name
 
 
 def test_optimizer_methods_and_signatures():

@@ -106,6 +106,46 @@ def test_fp16_flavour_is_built_selectable_and_its_rename_header_is_current():
         assert l.simseg_set_half_type(1) == 0
 
 
+def test_no_unreachable_twin_in_the_twice_compiled_sources():
+    """Every C-ABI entry point DEFINED in a twice-compiled source hands over to its _h16 twin (an SS_HALF_FWD( call in its body) - or is
+    listed here with the reason why it does not.  An entry whose kernels do not depend on the 16-bit type belongs in a once-compiled source
+    (loss.hip, optim.hip, rowops_plain.hip, ...): there its twin would be a second copy nothing can call.  Source text only."""
+    import os
+    import re
+    from simseg_amd import build
+    allowed = {
+        "simseg_set_gemm_variant": "forwards by hand: sets both flavours' thread-local selectors after one argument check",
+        "simseg_set_attention_variant": "forwards by hand: sets both flavours' thread-local selectors after one argument check",
+        "simseg_debug_gemm_trace": "debug: arms the bf16 build's trace pointer only",
+        "simseg_debug_attn_trace": "debug: arms the bf16 build's trace pointer only",
+        "simseg_debug_attention_timeline": "debug: times the bf16 forward only",
+        "simseg_gemm_aux_blocked_ok": "host arithmetic on the shape, the same in both flavours; states the condition of gemm.hip's own dispatch",
+        "simseg_attention_bwd_workspace_bytes": "host arithmetic on the shape, the same in both flavours",
+        "simseg_layernorm_bwd_workspace_bytes": "host arithmetic, next to the kernels' grid constant (LN_BWD_MAX_GRID) it uses",
+        "simseg_topk_pool_workspace_bytes": "host arithmetic, next to the kernels' constants (POOL_SLICES, POOL_GROUPS) it uses",
+        "simseg_attention_fwd_x3": "exact mode: always the bf16 pieces of fp32 operands, next to the attention kernels' tile code it shares",
+    }
+    seen = set()
+    for f in build.TWICE:
+        src = open(os.path.join(build.CSRC, f)).read()
+        for m in re.finditer(r'extern "C"\s+(?:const char\*|int64_t|int)\s+(simseg_\w+)\s*\([^)]*\)\s*([{;])', src):
+            if m.group(2) == ";":            # a declaration of another file's entry point
+                continue
+            depth, i = 1, m.end()
+            while depth:
+                depth += {"{": 1, "}": -1}.get(src[i], 0)
+                i += 1
+            name, body = m.group(1), src[m.end():i]
+            assert name not in seen, f"{name} is defined twice"
+            seen.add(name)
+            if "SS_HALF_FWD(" in body:
+                assert name not in allowed, f"{name} forwards to its twin: take it off the allow-list"
+            else:
+                assert name in allowed, f"{f}: {name} never reaches its _h16 twin - move it to a once-compiled source (or say here why not)"
+    assert set(allowed) <= seen, sorted(set(allowed) - seen)
+    assert len(seen) >= 30 and len(allowed) <= 10
+
+
 def test_interpolate_pos_embed_and_miou_match_reference(golden):
     import types
     import numpy as np
