@@ -302,6 +302,25 @@ int simseg_topk_search(const void* q, const void* g, int dtype, int64_t M, int64
 int simseg_topk_merge(const float* score_a, const int32_t* idx_a, const float* score_b, const int32_t* idx_b, float* score, int32_t* idx,
                       int64_t M, int K, void* stream);
 
+/* Weighted k-nearest-neighbour vote (knn.hip) over the lists of simseg_topk_search / simseg_topk_merge: score [M, K] fp32 descending,
+ * idx [M, K] int32 with -1 (and -inf) in empty tail slots, 1 <= K <= 128.  gallery_label [N] int32 (>= 0) is gathered by the kernel:
+ * entry j of a row has the label gallery_label[idx[j]].  The row's valid entries are those before its first empty slot; an index outside
+ * [0, N) ends the list like an empty slot.  ks (HOST pointer): nk = 1..4 strictly ascending neighbourhood sizes, ks[nk - 1] <= K, all
+ * answered by one launch - the neighbours of size k are the first n = min(k, valid) entries, a prefix of the one sorted list.
+ * Per row and k, in fp32:
+ *   w_j = expf((s_j - s_0) / temperature)              (relative to the best neighbour: <= 1 at every temperature, no ranking changes),
+ *   vote(c) = sum of w_j over j < n with label c, ADDED IN ASCENDING j starting from 0 (the order is part of the contract: the result
+ *             does not depend on lanes or launch geometry),
+ *   classes with at least one neighbour, ranked by vote descending and equal votes by ascending class:
+ *   pred[ki, m, r] = the r-th class, vote[ki, m, r] = its vote, r < 5; -1 / 0 where the row has fewer than five classes.
+ * pred [nk, M, 5] int32, vote [nk, M, 5] fp32.  query_label [M] int32 or NULL; when given, counts [nk, 3] int64 +=
+ * {rows, rows with pred[.., 0] == label, rows with the label among pred[.., :5]} by integer atomics (exact, order-free): the caller
+ * zeroes counts and may accumulate over calls.  A row without a valid neighbour counts as a row and as two misses.  temperature > 0 and
+ * finite.  Refused before any device work: K, nk / ks, temperature, M < 0, N < 1 or N >= 2^31, null pointers. */
+int simseg_knn_vote_rows(const float* score, const int32_t* idx, const int32_t* gallery_label, const int32_t* query_label, int64_t M,
+                         int64_t N, int K, const int32_t* ks, int nk, float temperature, int32_t* pred, float* vote, int64_t* counts,
+                         void* stream);
+
 /* ---- optimizer steps and gradient checks (csrc/optim.hip; the 16-bit copies are written in the selected 16-bit type) ----------------
  * torch.optim.AdamW (configs/clip/simseg.vit-b.yaml:31-36) over a flat fp32 segment; refreshes the bf16 compute copy. */
 int simseg_adamw_step(float* p, const float* g, float* m, float* v, void* p_bf16, int64_t n, float lr, float beta1, float beta2,

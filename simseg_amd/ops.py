@@ -701,6 +701,70 @@ def topk_merge(score_a, idx_a, score_b, idx_b):
     return score, idx
 
 
+KNN_KS_MAX = 4                 # simseg_knn_vote_rows: up to four neighbourhood sizes per launch
+_INT_DTYPES = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def _labels_i32(who, t, device):
+    """Class labels of any integer dtype -> a contiguous int32 vector on `device`.  Values are checked (>= 0, < 2^31) where that reads no
+    device memory: always for a host tensor, by the dtype's range alone for a device one."""
+    if not torch.is_tensor(t) or t.dtype not in _INT_DTYPES:
+        raise TypeError(f"{who}: integer class labels, got {t.dtype if torch.is_tensor(t) else type(t).__name__}")
+    if t.dim() != 1:
+        raise ValueError(f"{who}: a vector of labels, got shape {tuple(t.shape)}")
+    if not t.is_cuda and t.numel():
+        lo, hi = int(t.min()), int(t.max())
+        if lo < 0 or hi > 0x7fffffff:
+            raise ValueError(f"{who}: labels must lie in [0, 2^31), got {lo} .. {hi}")
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def check_knn_ks(ks, K=None):
+    """ks as simseg_knn_vote_rows takes them: 1 to 4 strictly ascending integers >= 1, the last at most TOPK_MAX (and K when given)."""
+    ks = tuple(int(k) for k in ks)
+    if not 1 <= len(ks) <= KNN_KS_MAX:
+        raise ValueError(f"knn_vote: 1 to {KNN_KS_MAX} values of k, got {len(ks)}")
+    if ks[0] < 1 or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError(f"knn_vote: ks must be strictly ascending and >= 1, got {ks}")
+    if ks[-1] > TOPK_MAX:
+        raise ValueError(f"knn_vote: max(ks) = {ks[-1]} exceeds TOPK_MAX = {TOPK_MAX}, the longest list the search returns")
+    if K is not None and ks[-1] > K:
+        raise ValueError(f"knn_vote: max(ks) = {ks[-1]} exceeds the K = {K} neighbours given")
+    return ks
+
+
+def knn_vote(score, idx, gallery_label, ks, temperature=0.07, query_label=None, counts=None):
+    """Temperature-weighted k-NN vote over the (score, idx) [M, K] lists of topk_search / topk_merge / retrieval.search (idx int32 or
+    int64, -1 in empty slots), for every k of `ks` from one launch (include/simseg_hip.h: simseg_knn_vote_rows):
+    -> (pred [len(ks), M, 5] int32, vote [len(ks), M, 5] fp32, counts).  gallery_label [N] / query_label [M]: integer labels of any
+    dtype.  With query_label, counts [len(ks), 3] int64 += {rows, top-1 hits, top-5 hits}; pass the returned tensor back in to accumulate
+    over calls (None starts at zero).  Without query_label nothing is counted and counts is returned as given."""
+    require_gpu(score, idx)
+    if score.dim() != 2 or score.shape != idx.shape:
+        raise ValueError("knn_vote: score and idx are [M, K] tensors of one shape")
+    if score.dtype != torch.float32 or idx.dtype not in (torch.int32, torch.int64):
+        raise TypeError("knn_vote: fp32 scores and int32 / int64 indices")
+    M, K = score.shape
+    ks = check_knn_ks(ks, K)
+    dev = score.device
+    glabel = _labels_i32("knn_vote: gallery_label", gallery_label, dev)
+    qlabel = None
+    if query_label is not None:
+        qlabel = _labels_i32("knn_vote: query_label", query_label, dev)
+        if qlabel.numel() != M:
+            raise ValueError(f"knn_vote: {qlabel.numel()} query labels for {M} rows")
+        if counts is None:
+            counts = torch.zeros(len(ks), 3, device=dev, dtype=torch.int64)
+        elif counts.shape != (len(ks), 3) or counts.dtype != torch.int64 or not counts.is_cuda or not counts.is_contiguous():
+            raise ValueError(f"knn_vote: counts is a contiguous int64 [{len(ks)}, 3] tensor on the device")
+    idx32 = idx if idx.dtype == torch.int32 else idx.to(torch.int32)
+    pred = torch.empty(len(ks), M, 5, device=dev, dtype=torch.int32)
+    vote = torch.empty(len(ks), M, 5, device=dev, dtype=torch.float32)
+    call("simseg_knn_vote_rows", ptr(_c(score)), ptr(_c(idx32)), ptr(glabel), ptr(qlabel), M, glabel.numel(), K,
+         (ctypes.c_int32 * len(ks))(*ks), len(ks), float(temperature), ptr(pred), ptr(vote), ptr(counts) if qlabel is not None else None, stream())
+    return pred, vote, counts
+
+
 def adamw_step(p, g, m, v, p16, lr, betas, eps, weight_decay, step, grad_scale=1.0):
     call("simseg_adamw_step", ptr(p), ptr(g), ptr(m), ptr(v), ptr(p16), p.numel(), float(lr), float(betas[0]), float(betas[1]),
          float(eps), float(weight_decay), int(step), float(grad_scale), stream())
