@@ -118,6 +118,37 @@ int simseg_vit_im2col(const float* image, void* cols, int out_dtype, int64_t B, 
 int simseg_vit_cls_rows(const float* cls, const float* pos, float* x, int64_t B, int64_t T, int64_t D, void* stream);
 int simseg_vit_cls_grad(const float* dx, float* dcls, int64_t B, int64_t T, int64_t D, void* stream);
 
+/* Patch dropout of the image tower (csrc/patchdrop.hip; DESIGN.md "Patch dropout"): during training every image keeps a random subset of
+ * K of its N patch tokens (timm's PatchDropout, ordered, one prefix token) and the tower runs on [cls] + the kept ones.  All four entry
+ * points check their arguments on the host before any device work: null pointers, 1 <= K <= N <= 4096, B >= 1, B * N < 2^31, and where
+ * they apply H, W positive multiples of 16 with (H / 16) * (W / 16) <= 4096 and D a positive multiple of 4.
+ *
+ * The draw.  keep[B, K] and inv[B, N] (int32) are a pure function of (seed, b, N, K): key(b, n) = hash_u32(seed, b * N + n) (csrc/common.h;
+ * simseg_amd.pipeline.hash_u32_ref in numpy); image b keeps the K positions with the smallest keys, equal keys going to the lower n (for a
+ * fixed seed the hash is a bijection of 32-bit indices, so with B * N < 2^31 there are none); keep[b, 0] < ... < keep[b, K - 1];
+ * inv[b, n] = the j with keep[b, j] == n, or -1 for a dropped position.  Every K-subset is equally likely as far as the keys are
+ * independent uniform words.  One block per image: keys in LDS, the rank of a key by counting the smaller ones, the slot j by a
+ * block-wide prefix count of the kept positions below n - no sort, no host read. */
+int simseg_patch_keep_sample(int32_t* keep, int32_t* inv, int64_t B, int64_t N, int64_t K, uint64_t seed, void* stream);
+/* simseg_vit_im2col of the kept patches only: cols[b * K + j, :] = patch keep[b, j] of image b in (c, kh, kw) order, out_dtype 0 fp32 /
+ * 1 the selected 16-bit type (the same rounding as simseg_vit_im2col: the bits of that call's rows, selected).  A keep entry outside
+ * [0, (H / 16) * (W / 16)) gives a zero row and reads nothing. */
+int simseg_vit_im2col_keep(const float* image, const int32_t* keep, void* cols, int out_dtype, int64_t B, int64_t H, int64_t W, int64_t K,
+                           void* stream);
+/* The rest of the token embedding, in place on the fp32 stream x[B, 1 + K, D] whose patch rows hold fl(acc + bias) (simseg_gemm with bias
+ * and row_group = K, no residual): x[b, 0] = cls + pos[0];  x[b, 1 + j] += pos[1 + keep[b, j]] (pos [N + 1, D]) - the two fp32 additions
+ * of the full path's epilogue (+ bias, + residual) in the same order.  A keep entry outside [0, N) leaves its row as it is. */
+int simseg_vit_keep_rows(const float* cls, const float* pos, const int32_t* keep, float* x, int64_t B, int64_t N, int64_t K, int64_t D,
+                         void* stream);
+/* Gradient of the position table - and of [cls], its row 0 - from dx[B, 1 + K, D] (dx_dtype 0 fp32 / 1 the selected 16-bit type: the
+ * gradient or its 16-bit shadow).  Writes ALL N + 1 rows of fp32 dpos[N + 1, D] (nothing is accumulated, the buffer need not be zeroed):
+ *   dpos[0]     = sum_b dx[b, 0],
+ *   dpos[1 + n] = sum over the images b with inv[b, n] >= 0 of dx[b, 1 + inv[b, n]];   a position no image kept: exactly 0.
+ * Every sum is one fp32 accumulator per element that takes its terms in ascending b - the order is part of the contract, so the result is
+ * a function of the inputs alone (no atomics, nothing depends on how blocks are scheduled).  An inv entry >= K counts as dropped. */
+int simseg_vit_keep_pos_grad(const void* dx, int dx_dtype, const int32_t* inv, float* dpos, int64_t B, int64_t N, int64_t K, int64_t D,
+                             void* stream);
+
 /* HF BertEmbeddings: out[b,l,:] = word[ids[b,l]] + pos[l] + type[0] (LayerNorm is a separate call).
  * bwd: dword[ids] += dsum for unmasked tokens (masked tokens carry an exactly-zero gradient). */
 int simseg_bert_embed_fwd(const int64_t* ids, const float* word, const float* pos, const float* type0, float* out,

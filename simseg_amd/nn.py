@@ -7,7 +7,7 @@ from types import SimpleNamespace
 import torch
 import torch.nn as nn
 
-from . import towers
+from . import patchdrop, towers
 
 VIT_ARCH = {
     "vit_small_patch16_224_in21k": dict(dim=384, depth=12, heads=6),
@@ -105,8 +105,10 @@ class _Block(nn.Module):
 class ViT(nn.Module):
     """timm VisionTransformer(patch16, num_classes=0) feature extractor: all tokens after the final norm."""
 
-    def __init__(self, tag, img_size=224):
+    def __init__(self, tag, img_size=224, patch_drop_rate=0.0):
         super().__init__()
+        self.last_keep = self.last_inv = None
+        self.set_patch_drop(patch_drop_rate)
         if tag not in VIT_ARCH:
             raise KeyError(f"unknown ViT tag {tag!r}; known: {sorted(VIT_ARCH)}")
         a = VIT_ARCH[tag]
@@ -124,7 +126,22 @@ class ViT(nn.Module):
             if isinstance(m, nn.Linear):
                 _init_linear(m)
 
+    def set_patch_drop(self, rate):
+        """Patch dropout (simseg_amd/patchdrop.py): in train() mode with 0 < rate < 1 the tower runs on [cls] + a random
+        K = max(1, int(N * (1 - rate))) of every image's N patch tokens and returns [B, 1 + K, D]; evaluation never drops.  0 switches it
+        off (FLIP's closing "unmasked tuning" epochs).  An attribute, not a parameter or buffer: the state dict is unchanged."""
+        self.patch_drop_rate = patchdrop._check_rate(rate)
+
     def forward(self, x):
+        if self.training and self.patch_drop_rate > 0:
+            B, _, H, W = x.shape
+            N = (H // 16) * (W // 16)
+            K = patchdrop.num_keep(N, self.patch_drop_rate)
+            if K < N:
+                seed = next_dropout_seed()       # (drawn only here: with the feature off the text tower's seeds are the ones drawn without it)
+                keep, inv = patchdrop.sample_keep(B, N, K, seed, x.device)
+                self.last_keep, self.last_inv = keep, inv       # (plain int32 tensors, nothing to detach: for inspection)
+                return towers.vit_forward(self, x, compute_dtype(), keep, inv)
         return towers.vit_forward(self, x, compute_dtype())
 
 

@@ -253,6 +253,58 @@ def vit_cls_grad(dx, dcls):
     call("simseg_vit_cls_grad", ptr(_c(dx)), ptr(dcls), B, T, D, stream())
 
 
+def _keep_table(t, name, B, cols):
+    if t.dtype != torch.int32 or tuple(t.shape) != (B, cols):
+        raise ValueError(f"{name}: int32 [{B}, {cols}] expected, got {t.dtype} {tuple(t.shape)}")
+    require_gpu(t)
+    return _c(t)
+
+
+def patch_keep_sample(B, N, K, seed, device):
+    """Patch dropout's draw (include/simseg_hip.h): -> keep int32 [B, K] (ascending per image), inv int32 [B, N] (-1 = dropped).  No host read."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("simseg_amd ops run on MI355X only (device is %s); there is no CPU fallback" % device)
+    keep = torch.empty(int(B), int(K), device=device, dtype=torch.int32)
+    inv = torch.empty(int(B), int(N), device=device, dtype=torch.int32)
+    call("simseg_patch_keep_sample", ptr(keep), ptr(inv), int(B), int(N), int(K), int(seed) & 0xFFFFFFFFFFFFFFFF, stream())
+    return keep, inv
+
+
+def vit_im2col_keep(image, keep, out_dtype):
+    """vit_im2col of the kept patches only: cols [B * K, 768], row b * K + j = patch keep[b, j] of image b."""
+    require_gpu(image)
+    B, C, H, W = image.shape
+    if C != 3 or image.dtype != torch.float32:
+        raise ValueError("vit_im2col_keep expects fp32 [B,3,H,W]")
+    K = keep.shape[1]
+    cols = torch.empty(B * K, 768, device=image.device, dtype=out_dtype)
+    call("simseg_vit_im2col_keep", ptr(_c(image)), ptr(_keep_table(keep, "vit_im2col_keep: keep", B, K)), ptr(cols), dt(cols), B, H, W, K, stream())
+    return cols
+
+
+def vit_keep_rows(cls, pos, keep, x):
+    """In place on the fp32 stream x [B, 1 + K, D]: x[b, 0] = cls + pos[0]; x[b, 1 + j] += pos[1 + keep[b, j]]  (pos [N + 1, D])."""
+    require_gpu(x)
+    B, T, D = x.shape
+    if x.dtype != torch.float32 or cls.dtype != torch.float32 or pos.dtype != torch.float32 or cls.numel() != D or pos.dim() != 2 or pos.shape[1] != D:
+        raise ValueError("vit_keep_rows: fp32 x [B, 1 + K, D], cls [D] and pos [N + 1, D] expected")
+    call("simseg_vit_keep_rows", ptr(_c(cls)), ptr(_c(pos)), ptr(_keep_table(keep, "vit_keep_rows: keep", B, T - 1)), ptr(_c(x)), B, pos.shape[0] - 1, T - 1, D,
+         stream())
+    return x
+
+
+def vit_keep_pos_grad(dx, inv):
+    """dpos fp32 [N + 1, D] from dx [B, 1 + K, D] (fp32 or 16-bit) and inv [B, N]: row 0 = sum_b dx[b, 0] (the [cls] gradient as well), row
+    1 + n = the sum of the rows of the images that kept n, in ascending b; exactly 0 where no image did."""
+    require_gpu(dx)
+    B, T, D = dx.shape
+    N = inv.shape[1]
+    dpos = torch.empty(N + 1, D, device=dx.device, dtype=torch.float32)
+    call("simseg_vit_keep_pos_grad", ptr(_c(dx)), dt(dx), ptr(_keep_table(inv, "vit_keep_pos_grad: inv", B, N)), ptr(dpos), B, N, T - 1, D, stream())
+    return dpos
+
+
 def bert_embed_fwd(ids, word, pos, type_emb):
     require_gpu(ids, word)
     B, L = ids.shape

@@ -525,6 +525,60 @@ class ViTEmbedFn(_GradAwareFn):
         return None, dw, db, dcls, dpos, None
 
 
+class ViTEmbedKeepFn(_GradAwareFn):
+    """ViTEmbedFn under patch dropout (simseg_amd/patchdrop.py): only the patches keep[b, :] of image b are gathered and embedded, each with
+    the position row of its own position -> fp32 residual stream [B,1+K,D], the rows ViTEmbedFn's output has at [cls] and 1 + keep[b, :].
+    keep int32 [B,K] ascending, inv int32 [B,N] its inverse (-1 = dropped), both from patchdrop.sample_keep.  A shadow-aware producer like
+    ViTEmbedFn: the block chain behind it may run with lazy_ok."""
+
+    @staticmethod
+    def forward(ctx, image, pw, pb, cls, pos, keep, inv, adt):
+        B, _, H, W = image.shape
+        D = pw.shape[0]
+        N = (H // 16) * (W // 16)
+        if pos.shape[1] != N + 1:
+            raise ValueError(f"pos_embed has {pos.shape[1]} tokens but the {H}x{W} input makes {N + 1}")
+        if keep.dim() != 2 or keep.shape[0] != B or not 1 <= keep.shape[1] <= N or tuple(inv.shape) != (B, N):
+            raise ValueError(f"keep [B, K] with 1 <= K <= {N} and inv [{B}, {N}] expected, got {tuple(keep.shape)} and {tuple(inv.shape)}")
+        K = keep.shape[1]
+        keep, inv = keep.contiguous(), inv.contiguous()
+        cols = ops.vit_im2col_keep(image.contiguous().float(), keep, adt)
+        x = torch.empty(B, K + 1, D, device=image.device, dtype=F32)
+        # (bias only: the position row depends on the image, so it cannot be the epilogue's residual; vit_keep_rows adds it to fl(acc + bias),
+        #  the same two fp32 additions in the same order as ViTEmbedFn's epilogue)
+        _fwd_gemm(cols, pw, adt, _saving(ctx), bias=pb.detach(), row_group=K, out=x.view(-1, D))
+        ops.vit_keep_rows(cls.detach().reshape(-1), pos.detach().reshape(N + 1, D), keep, x)
+        ctx.adt, ctx.dims = adt, (B, N, K, D)
+        ctx.save_for_backward(cols, inv)
+        return x
+
+    @staticmethod
+    @_joins_wgrad
+    def backward(ctx, dx):
+        cols, inv = ctx.saved_tensors
+        B, N, K, D = ctx.dims
+        dx = dx.contiguous()
+        sh = _take_shadow(dx, ctx.adt) if ctx.adt != F32 else None
+        _need_shadow(dx, sh)
+        lazy = getattr(dx, "_simseg_lazy32", False)
+        if sh is not None:       # (as in ViTEmbedFn: the patch rows of the 16-bit copy the first block's backward left)
+            dx16 = sh[0].view(B, K + 1, D)
+            dp16 = dx16[:, 1:].contiguous().view(-1, D)
+        else:
+            dp16 = _act_grad(dx[:, 1:].contiguous().view(-1, D), ctx.adt)
+        dw = _wgrad(dp16, cols).view(D, 3, 16, 16) if ctx.needs_input_grad[1] else None
+        db = _bgrad(dp16) if ctx.needs_input_grad[2] else None
+        dcls = dpos = None
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            # one pass for both: row 0 of the position gradient is the [cls] gradient.  (lazy: the fp32 image of dx was never written)
+            g = ops.vit_keep_pos_grad(dx16 if lazy else dx, inv)
+            if ctx.needs_input_grad[3]:
+                dcls = g[0].clone().view(1, 1, D)
+            if ctx.needs_input_grad[4]:
+                dpos = g.view(1, N + 1, D)
+        return None, dw, db, dcls, dpos, None, None, None
+
+
 class ViTBlockFn(_GradAwareFn):
     """timm Block: x + proj(attn(norm1 x)); then + fc2(gelu(fc1(norm2 .)))   (pre-LN, eps 1e-6, erf GELU)."""
 
@@ -634,9 +688,15 @@ class ViTBlockFn(_GradAwareFn):
         return (dx, None, None, dn1w, dn1b, dqw, dqb, dpw, dpb, dn2w, dn2b, df1w, df1b, df2w, df2b, None)
 
 
-def vit_forward(m, image, adt):
-    """m: module tree with timm parameter names (see simseg_amd/nn.py ViT). Returns all tokens after the final LN."""
-    x = ViTEmbedFn.apply(image, m.patch_embed.proj.weight, m.patch_embed.proj.bias, m.cls_token, m.pos_embed, adt)
+def vit_forward(m, image, adt, keep=None, inv=None):
+    """m: module tree with timm parameter names (see simseg_amd/nn.py ViT). Returns all tokens after the final LN.
+    keep / inv (patch dropout, simseg_amd/patchdrop.py): the tower runs on [cls] + the patches keep[b, :] of every image -> [B, 1 + K, D]."""
+    if keep is not None:
+        if inv is None:
+            raise ValueError("vit_forward: keep comes with its inverse table inv (patchdrop.sample_keep returns both)")
+        x = ViTEmbedKeepFn.apply(image, m.patch_embed.proj.weight, m.patch_embed.proj.bias, m.cls_token, m.pos_embed, keep, inv, adt)
+    else:
+        x = ViTEmbedFn.apply(image, m.patch_embed.proj.weight, m.patch_embed.proj.bias, m.cls_token, m.pos_embed, adt)
     for blk in m.blocks:
         x = ViTBlockFn.apply(x, m.num_heads, adt, blk.norm1.weight, blk.norm1.bias, blk.attn.qkv.weight, blk.attn.qkv.bias,
                              blk.attn.proj.weight, blk.attn.proj.bias, blk.norm2.weight, blk.norm2.bias,

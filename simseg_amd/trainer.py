@@ -61,14 +61,35 @@ def param_groups(model, cfg):
     return groups
 
 
+def set_patch_drop(model, cfg, rate):
+    """Set patch dropout on the ViT of model.image_encoder (a model without one raises); ValueError when LoDA pooling would be left with
+    fewer kept tokens than the image_k it averages."""
+    from .nn import ViT
+    from .patchdrop import num_keep
+    vits = [m for m in model.image_encoder.modules() if isinstance(m, ViT)]
+    if len(vits) != 1:
+        raise ValueError(f"patch_drop_rate needs an image encoder with one simseg_amd.nn.ViT, found {len(vits)}")
+    vit = vits[0]
+    K = num_keep(vit.patch_embed.num_patches, rate)           # (validates the rate)
+    if cfg.model.pool.name == "loda" and K < cfg.model.pool.loda.image_k:
+        raise ValueError(f"patch_drop_rate {rate} keeps {K} of {vit.patch_embed.num_patches} patch tokens, fewer than the "
+                         f"model.pool.loda.image_k = {cfg.model.pool.loda.image_k} the LoDA pooling takes")
+    vit.set_patch_drop(rate)
+    return vit
+
+
 class Trainer:
-    def __init__(self, model, cfg, steps_per_epoch, net=None, amp_dtype=None):
+    def __init__(self, model, cfg, steps_per_epoch, net=None, amp_dtype=None, patch_drop_rate=None):
         """model: the bare CLIPModel; net: what is called (model or its DDP wrapper).
+        patch_drop_rate (None: nothing is touched): the image tower's ViT trains on [cls] + a random share 1 - rate of every image's patch
+        tokens (simseg_amd/patchdrop.py; ViT.set_patch_drop).  Under LoDA pooling the kept tokens must still number cfg.model.pool.loda.image_k.
         amp_dtype ("bf16" default / "fp16", or SIMSEG_AMD_AMP_DTYPE): the 16-bit type of the AMP mode cfg.dist.fp16 switches on.  "fp16" is
         the reference's own mode - torch.cuda.amp.autocast() + a live GradScaler (clip_runner.py:226-230, core/hooks/optimizer.py:73-82):
         scaled loss, unscale + overflow check + skipped steps, scale growth / back-off, the scaler's state in the checkpoint.  bf16 needs
         no loss scale (fp32's exponent range): the scaler then runs disabled, as an identity."""
         self.model, self.net, self.cfg = model, net or model, cfg
+        if patch_drop_rate is not None:
+            set_patch_drop(model, cfg, patch_drop_rate)
         amp = str(amp_dtype or os.environ.get("SIMSEG_AMD_AMP_DTYPE", "bf16")).lower().replace("torch.", "")
         if amp not in ("bf16", "bfloat16", "fp16", "float16", "half"):
             raise ValueError(f"amp_dtype {amp!r}: bf16 or fp16")
