@@ -47,6 +47,8 @@ def test_tr16_probe_layout(ops):
 def test_gemm_f32_nt(ops, M, N, K):
     a, b = _rand(M, K, seed=1), _rand(N, K, seed=2)
     _close(ops.gemm(a, b), a @ b.T, 1e-5, f"f32 NT {M}x{N}x{K}")
+    # the kernel each shape takes today: the small-problem kernel wherever a row is whole 128-byte slabs (every shape here is < 200 tiles of 128x128)
+    assert ops.gemm_last_variant() == (4 if K * 4 % 128 == 0 else 1)
 
 
 def test_gemm_f32_epilogues(ops):
@@ -55,6 +57,7 @@ def test_gemm_f32_epilogues(ops):
     bias, rs, res = _rand(N, seed=3), _rand(M, seed=4).abs() + 0.5, _rand(M, N, seed=5)
     ref = (a @ b.T) * 0.37 * rs[:, None] + bias
     _close(ops.gemm(a, b, alpha=0.37, bias=bias, rowscale=rs), ref, 1e-5, "alpha/rowscale/bias")
+    assert ops.gemm_last_variant() == 4          # (K * 4 % 128 == 0, 6 tiles of 128x128: the small-problem kernel, here and in every call below)
     pre = torch.empty(M, N, device="cuda")
     _close(ops.gemm(a, b, bias=bias, act=1, aux_out=pre, residual=res), F.gelu(a @ b.T + bias) + res, 1e-5, "gelu+res")
     _close(pre, a @ b.T + bias, 1e-5, "saved pre-activation")
@@ -82,6 +85,7 @@ def test_gemm_f32_epilogues(ops):
     cs = torch.zeros(N, device="cuda")
     y16 = ops.gemm(a.bfloat16(), b.bfloat16(), bias=bias, colsum=cs)
     _close(cs, (a.bfloat16().float() @ b.bfloat16().float().T + bias).sum(0), 1e-4, "epilogue column sums (bf16, pre-rounding values)")
+    assert ops.gemm_last_variant() == 4
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
@@ -469,6 +473,7 @@ def test_vit_patch_embed(ops):
     x = torch.empty(B, 1 + N, D, device="cuda")
     cols = ops.vit_im2col(img, torch.float32)
     ops.gemm(cols, w.view(D, 768), bias=bias, residual=pos.view(1 + N, D), row_group=N, res_mod=True, out=x.view(-1, D))
+    assert ops.gemm_last_variant() == 4          # (fp32, K * 4 % 128 == 0, one tile of 128x128: the small-problem kernel)
     ops.vit_cls_rows(cls.view(-1), pos.view(-1), x)
     _close(x, ref, 1e-5, "patch embed")
 
