@@ -10,6 +10,7 @@ Reference arithmetic: timm 0.6.13 VisionTransformer as driven by simseg/models/b
 HF BertModel as driven by huggingface_builder.py:16-17 (both third-party; see oracle/simseg_ref.py)."""
 import contextlib
 import os
+import threading
 import weakref
 
 import torch
@@ -20,47 +21,99 @@ from . import ops
 BF16, F32 = torch.bfloat16, torch.float32
 
 
-_W16 = {}      # id(parameter) -> (weakref(parameter), parameter._version, parameter.data_ptr(), bf16 copy)
+class DerivedCopies:
+    """Every copy derived from the fp32 master weights, in one place: (kind, source parameters) -> value, made under a tag.  The kinds:
+    "w16" (the 16-bit copy of a weight; tag = its dtype), "split" (the split-bf16x3 copy of exact-mode evaluation), "qscaled" (the folded
+    q-scaled qkv weight and bias; tag = the dtype) and "cat" (BERT's concatenated q / k / v weight; tag = the dtype).  The class makes no
+    copy and calls no kernel: the caller looks up, makes the copy on a miss and stores it.
+
+    An entry is a hit while every source is the same object (a weakref, not only its id) with the `_version`, `data_ptr()` and shape it had
+    when the entry was stored, and the tag is equal: torch-side writes bump `_version`, storage swaps change `data_ptr`.  Only copies whose
+    sources are all nn.Parameter are stored.  A reverse index (id of a source -> keys made from it) makes rewritten() cost O(entries derived
+    from that source); entries of dead parameters are swept, with their index keys, once SWEEP entries are held."""
+    SWEEP = 4096
+
+    def __init__(self):
+        self._ent = {}     # (kind, id of every source) -> ([(weakref, _version, data_ptr(), shape) of every source], tag, value)
+        self._of = {}      # id(source) -> the keys of the entries made from it
+
+    def get(self, kind, srcs, tag=None):
+        """The current value for (kind, sources, tag), or None.  Read-only."""
+        ent = self._ent.get((kind, *map(id, srcs)))
+        if ent is None or ent[1] != tag:
+            return None
+        for s, (ref, version, data, shape) in zip(srcs, ent[0]):
+            if ref() is not s or version != s._version or data != s.data_ptr() or shape != s.shape:
+                return None
+        return ent[2]
+
+    def put(self, kind, srcs, tag, value):
+        """Store `value` as the copy of `kind` made from `srcs` as they are now (nothing is stored unless all are parameters); returns it."""
+        state = []
+        for s in srcs:
+            if not isinstance(s, torch.nn.Parameter):
+                return value
+            state.append((weakref.ref(s), s._version, s.data_ptr(), s.shape))
+        if len(self._ent) > self.SWEEP:
+            for k in [k for k, e in self._ent.items() if any(src[0]() is None for src in e[0])]:
+                del self._ent[k]
+            for k in [k for k, keys in self._of.items() if not any(kk in self._ent for kk in keys)]:
+                del self._of[k]
+        key = (kind, *map(id, srcs))
+        self._ent[key] = (state, tag, value)
+        for s in srcs:
+            self._of.setdefault(id(s), set()).add(key)
+        return value
+
+    def rewritten(self, kind, param, tag, value):
+        """`param` was rewritten where torch cannot see it: forget (and release) every entry, of every kind, that has it among its sources,
+        then store `value` as its copy of `kind`.  One pass, because the optimizers call this for every parameter at every step - when, in
+        training, that copy is the only entry there is."""
+        i = id(param)
+        key = (kind, i)
+        keys = self._of.get(i)
+        if keys is None:
+            self._of[i] = {key}
+        elif len(keys) != 1 or key not in keys:
+            for k in keys:
+                self._ent.pop(k, None)
+            keys.clear()
+            keys.add(key)
+        self._ent[key] = ([(weakref.ref(param), param._version, param.data_ptr(), param.shape)], tag, value)
+
+    def clear(self):
+        self._ent.clear()
+        self._of.clear()
+
+    def count(self, kind):
+        return sum(1 for k in self._ent if k[0] == kind)
+
+
+COPIES = DerivedCopies()
 
 
 def weights_rewritten(param, w16):
     """An optimizer's kernel has just rewritten `param` and its 16-bit copy `w16` through raw pointers, so neither `param._version` nor
-    `param.data_ptr()` moved and no cache here can see the update by itself: `w16` becomes the current 16-bit copy (_wt), and the copies
-    derived from the OLD value are forgotten - the split-bf16 one of exact-mode evaluation (_wt_split) and the folded q-scaled qkv ones
-    made from it as weight or bias (_wt_qscaled; O(1): their keys are found through _WQS_OF, not by a scan).  The one call an optimizer
-    makes per parameter after its update; a derived cache added here joins this function."""
-    _W16[id(param)] = (weakref.ref(param), param._version, param.data_ptr(), w16)
-    _W3.pop(id(param), None)
-    for key in _WQS_OF.pop(id(param), ()):
-        _WQS.pop(key, None)
+    `param.data_ptr()` moved and no cached copy can see the update by itself: every copy derived from the OLD value, of every kind, is
+    forgotten, and `w16` becomes the current 16-bit copy (_wt).  The one call an optimizer makes per parameter after its update."""
+    COPIES.rewritten("w16", param, w16.dtype, w16)
 
 
 def invalidate_weight_cache():
-    """Drop every cached derived copy of the parameters: the 16-bit copies (_W16), the concatenated BERT q / k / v copies (_CAT), the
-    split-bf16 copies (_W3) and the folded q-scaled qkv copies (_WQS).  Needed only after writes torch cannot see (in-place ops on
-    `param.data`, which carry their own version counter); load_state_dict / copy_ / optimizers / .to() are detected without it."""
-    _W16.clear()
-    _CAT.clear()
-    _W3.clear()
-    _WQS.clear()
-    _WQS_OF.clear()
+    """Drop every cached derived copy of the parameters, of every kind (DerivedCopies).  Needed only after writes torch cannot see (in-place
+    ops on `param.data`, which carry their own version counter); load_state_dict / copy_ / optimizers / .to() are detected without it."""
+    COPIES.clear()
 
 
 def _wt(w, adt):
     """Weight in the activation dtype (bf16 compute copy of the fp32 master, like autocast's per-step cast).  The copy is
-    cached per parameter object and reused while the parameter is untouched: torch-side writes bump `_version`, storage
-    swaps change `data_ptr`, and simseg_amd.optim.AdamW refreshes the copy in its own kernel (weights_rewritten)."""
+    cached per parameter object and reused while the parameter is untouched (DerivedCopies); simseg_amd.optim.AdamW refreshes the copy in
+    its own kernel (weights_rewritten)."""
     if adt == F32:
         return w.detach()
-    ent = _W16.get(id(w))
-    if ent is not None and ent[0]() is w and ent[1] == w._version and ent[2] == w.data_ptr() and ent[3].shape == w.shape and ent[3].dtype == adt:
-        return ent[3]
-    w16 = ops.cast(w.detach().contiguous(), adt)
-    if isinstance(w, torch.nn.Parameter):
-        if len(_W16) > 4096:
-            for k in [k for k, e in _W16.items() if e[0]() is None]:
-                del _W16[k]
-        _W16[id(w)] = (weakref.ref(w), w._version, w.data_ptr(), w16)
+    w16 = COPIES.get("w16", (w,), adt)
+    if w16 is None:
+        w16 = COPIES.put("w16", (w,), adt, ops.cast(w.detach().contiguous(), adt))
     return w16
 
 
@@ -72,7 +125,6 @@ def _wt(w, adt):
 # passes that save nothing for a backward (the evaluation tools; training in exact mode keeps the fp32 kernels, whose operands the
 # backward re-reads) and only where the 256x256 bf16 kernel has at least a round of tiles to work on.
 _SPLIT_FP32 = os.environ.get("SIMSEG_AMD_SPLIT_FP32", "auto")      # 0 = never, 1 = wherever the shapes allow (tests), auto
-_W3 = {}       # id(parameter) -> (weakref(parameter), parameter._version, parameter.data_ptr(), split copy [out, 6 in])
 SPLIT_CALLS = [0]
 
 
@@ -84,47 +136,28 @@ def _split_ok(M, N, K):
 
 
 def _wt_split(w):
-    ent = _W3.get(id(w))
-    if ent is not None and ent[0]() is w and ent[1] == w._version and ent[2] == w.data_ptr() and ent[3].shape[0] == w.shape[0]:
-        return ent[3]
-    w3 = ops.split_bf16x3(w.detach().reshape(w.shape[0], -1).contiguous(), b_pattern=True)
-    if isinstance(w, torch.nn.Parameter):
-        if len(_W3) > 4096:
-            for k in [k for k, e in _W3.items() if e[0]() is None]:
-                del _W3[k]
-        _W3[id(w)] = (weakref.ref(w), w._version, w.data_ptr(), w3)
+    w3 = COPIES.get("split", (w,))
+    if w3 is None:
+        w3 = COPIES.put("split", (w,), None, ops.split_bf16x3(w.detach().reshape(w.shape[0], -1).contiguous(), b_pattern=True))
     return w3
 
 
-_WQS = {}     # (id(weight), id(bias)) -> (weakref(weight), weakref(bias), versions and data pointers, 16-bit weight, fp32 bias)
-_WQS_OF = {}  # id(weight) / id(bias) -> the _WQS keys made from it (weights_rewritten)
+_QSCALED = os.environ.get("SIMSEG_AMD_QSCALED", "1") != "0"      # (0: A/B runs and tests on the kernel that scales q itself)
 
 
 def _wt_qscaled(w, b, adt, D):
     """timm Attention.qkv for the long-sequence 16-bit forward (ops.attention_fwd_qscaled): the 16-bit copy of the weight [3D, D] and the
     fp32 bias [3D] with the q rows multiplied by softmax scale * log2(e) in fp32, BEFORE the rounding to 16 bits - the projection then
     delivers q * scale * log2(e) rounded once, and the attention kernel's exponent is its MFMA output.  Cached per parameter like _wt."""
-    key = (id(w), id(b))
-    ent = _WQS.get(key)
-    if (ent is not None and ent[0]() is w and ent[1]() is b and ent[2] == (w._version, b._version, w.data_ptr(), b.data_ptr())
-            and ent[3].dtype == adt):
-        return ent[3], ent[4]
+    hit = COPIES.get("qscaled", (w, b), adt)
+    if hit is not None:
+        return hit
     c = ops.attention_qscale(64 ** -0.5)
     ws = w.detach().float().clone()
     ws[:D] *= c
     bs = b.detach().float().clone()
     bs[:D] *= c
-    w16 = ops.cast(ws.contiguous(), adt)
-    if isinstance(w, torch.nn.Parameter):
-        if len(_WQS) > 1024:
-            for k in [k for k, e in _WQS.items() if e[0]() is None or e[1]() is None]:
-                del _WQS[k]
-            for k in [k for k, keys in _WQS_OF.items() if not any(kk in _WQS for kk in keys)]:
-                del _WQS_OF[k]
-        _WQS[key] = (weakref.ref(w), weakref.ref(b), (w._version, b._version, w.data_ptr(), b.data_ptr()), w16, bs)
-        _WQS_OF.setdefault(id(w), set()).add(key)
-        _WQS_OF.setdefault(id(b), set()).add(key)
-    return w16, bs
+    return COPIES.put("qscaled", (w, b), adt, (ops.cast(ws.contiguous(), adt), bs))
 
 
 def _fwd_gemm(x2d, w, adt, saving, **kw):
@@ -136,8 +169,6 @@ def _fwd_gemm(x2d, w, adt, saving, **kw):
         return ops.gemm(ops.split_bf16x3(x2d), _wt_split(w), **kw)
     return ops.gemm(x2d, _wt(w, adt) if w.dim() == 2 else _wt(w.reshape(w.shape[0], -1), adt), **kw)
 
-
-import threading
 
 _GRAD_MODE = threading.local()
 
@@ -157,8 +188,6 @@ def _saving(ctx):
     """Does this forward need to keep anything for a backward?  Under torch.no_grad() - every evaluation tool - the parameters still
     'need' gradients as far as ctx.needs_input_grad is concerned, and the blocks used to save statistics, log-sum-exps and GELU
     derivatives nobody would read."""
-    if os.environ.get("SIMSEG_AMD_EVAL_SAVES") == "1":      # A/B runs: the round-2 behaviour (evaluation forwards save as training ones do)
-        return any(ctx.needs_input_grad)
     return getattr(_GRAD_MODE, "on", True) and any(ctx.needs_input_grad)
 
 
@@ -174,28 +203,22 @@ def _as_one(*ts):
     return torch.as_strided(a, (sum(t.shape[0] for t in ts),) + tuple(a.shape[1:]), a.stride(), a.storage_offset())
 
 
-_CAT = {}      # id(first parameter) -> (the _W16 entries the concatenation was made from, concatenated bf16 weight)
-
-
 def _wt_stacked(ws, adt):
     """[sum out, in] weight of several nn.Linear modules that share their input (HF keeps BERT's query / key / value as three
     modules; one GEMM computes all three).  No copy when the operands are adjacent in memory: the fp32 masters are packed by the module
     (nn._BertSelf), the bf16 copies by the optimizer (optim.AdamW lays matrices out in parameter order).  Otherwise (bf16 without our
-    optimizer: evaluation) the concatenation is made once and reused until one of the bf16 copies is refreshed."""
+    optimizer: evaluation) the concatenation is made once and reused until one of the bf16 copies is refreshed: it is stored with the
+    copies it was made from."""
     parts = [_wt(w, adt) for w in ws]
     one = _as_one(*parts)
     if one is not None:
         return one
-    if adt != F32:
-        ents = [_W16.get(id(w)) for w in ws]
-        hit = _CAT.get(id(ws[0]))
-        if hit is not None and all(e is not None and e is h for e, h in zip(ents, hit[0])):
-            return hit[1]
-        cat = torch.cat(parts)
-        if all(e is not None for e in ents):
-            _CAT[id(ws[0])] = (ents, cat)
-        return cat
-    return torch.cat(parts)
+    if adt == F32:
+        return torch.cat(parts)
+    hit = COPIES.get("cat", ws, adt)
+    if hit is not None and all(p is h for p, h in zip(parts, hit[0])):
+        return hit[1]
+    return COPIES.put("cat", ws, adt, (parts, torch.cat(parts)))[1]
 
 
 def _splitk(m, n, k_rows):
@@ -263,59 +286,7 @@ def _zeros_or(device, targets, *shapes):
     return [t if u else next(rest) for t, u in zip(targets, use)]
 
 
-# Weight gradients on their own stream (opt-in experiment, SIMSEG_AMD_WGRAD_STREAM=1): a block's four weight-gradient GEMMs depend only on
-# tensors its backward already has and nothing reads their results before the optimizer, so they can run beside the data-gradient chain
-# (dgrad -> LayerNorm backward -> attention backward ...) instead of inside it.  One extra stream per stream the backward runs on (the two
-# towers have their own); joined before the block's backward returns.
-_WG_ON = os.environ.get("SIMSEG_AMD_WGRAD_STREAM", "0") == "1"
-_WG_STREAMS = {}
-_WG_PENDING = threading.local()
-
-
-def _wg_side(cur):
-    st = _WG_STREAMS.get(cur.cuda_stream)
-    if st is None:
-        st = _WG_STREAMS[cur.cuda_stream] = torch.cuda.Stream(device=cur.device)
-    return st
-
-
-def _wg_join():
-    pend = getattr(_WG_PENDING, "streams", None)
-    if pend:
-        cur = torch.cuda.current_stream()
-        for st in pend:
-            cur.wait_stream(st)
-        pend.clear()
-
-
-def _joins_wgrad(fn):
-    def wrapped(ctx, *grads):
-        try:
-            return fn(ctx, *grads)
-        finally:
-            _wg_join()
-    return wrapped
-
-
 def _wgrad(dy, x, out=None):
-    if _WG_ON and dy.is_cuda:
-        cur = torch.cuda.current_stream()
-        side = _wg_side(cur)
-        if out is None:
-            out = torch.zeros(dy.shape[1], x.shape[1], device=dy.device, dtype=F32)
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            _wgrad_now(dy, x, out)
-        pend = getattr(_WG_PENDING, "streams", None)
-        if pend is None:
-            pend = _WG_PENDING.streams = []
-        if side not in pend:
-            pend.append(side)
-        return out
-    return _wgrad_now(dy, x, out)
-
-
-def _wgrad_now(dy, x, out=None):
     """dW[out,in] = dy^T . x  (contraction over rows), fp32, split-K atomics into the zero-filled `out`.  bf16 operands go to the
     transposed-operand MFMA kernel; fp32 operands (exact mode) are transposed first - the fp32 kernel is row.row only."""
     out_f, in_f = dy.shape[1], x.shape[1]
@@ -330,14 +301,13 @@ def _wgrad_now(dy, x, out=None):
 
 # A block's four weight gradients as ONE grouped split-K launch (ops.wgrad_group) after the block's last LayerNorm backward, instead of four
 # launches between the data-gradient kernels: same contraction, same tile, one common slice count - no launch boundary inside the group and
-# fewer concurrent adders per output tile.  16-bit compute with all four gradients wanted and the side stream off; everything else keeps
-# _wgrad.  SIMSEG_AMD_WGRAD_GROUP=0: the per-GEMM launches (A/B runs).
+# fewer concurrent adders per output tile.  16-bit compute with all four gradients wanted; everything else keeps _wgrad.  SIMSEG_AMD_WGRAD_GROUP=0: the per-GEMM launches (A/B runs).
 _WG_GROUP = os.environ.get("SIMSEG_AMD_WGRAD_GROUP", "1") != "0"
 WGRAD_GROUPS = [0]    # grouped launches issued (tests assert that the fast path is the one that runs)
 
 
 def _wgrad_grouped(adt, needs):
-    return _WG_GROUP and not _WG_ON and adt != F32 and all(needs)
+    return _WG_GROUP and adt != F32 and all(needs)
 
 
 def _wgrad_flush(group):
@@ -351,9 +321,6 @@ def _dgrad(d, w_, **kw):
     if d.dtype == F32:
         return ops.gemm(d, ops.transpose_f32(w_), **kw)
     return ops.gemm(d, w_, trans_b=True, **kw)
-
-
-_FUSED_QKV_BIAS = os.environ.get("SIMSEG_AMD_FUSED_QKV_BIAS", "1") != "0"      # (A/B runs: 0 = a column-sum pass over dqkv instead)
 
 
 def _zeros_like_bias(out, n, device):
@@ -436,7 +403,6 @@ class LinearFn(_GradAwareFn):
         return y.view(*shp[:-1], w.shape[0])
 
     @staticmethod
-    @_joins_wgrad
     def backward(ctx, dy):
         xa, wa = ctx.saved_tensors
         d16 = _act_grad(dy.reshape(-1, dy.shape[-1]).contiguous(), ctx.adt)
@@ -495,7 +461,6 @@ class ViTEmbedFn(_GradAwareFn):
         return x
 
     @staticmethod
-    @_joins_wgrad
     def backward(ctx, dx):
         (cols,) = ctx.saved_tensors
         B, N, D = ctx.dims
@@ -553,7 +518,6 @@ class ViTEmbedKeepFn(_GradAwareFn):
         return x
 
     @staticmethod
-    @_joins_wgrad
     def backward(ctx, dx):
         cols, inv = ctx.saved_tensors
         B, N, K, D = ctx.dims
@@ -590,52 +554,43 @@ class ViTBlockFn(_GradAwareFn):
         x = x.contiguous()
         save = _saving(ctx)
         ln1, _, mean1, rstd1 = ops.layernorm_fwd(x, n1w.detach(), n1b.detach(), 1e-6, out_dtype=adt, save_stats=save)
-        if not save and adt != F32 and T >= ops.ATTN_QSCALED_MIN_T and os.environ.get("SIMSEG_AMD_QSCALED", "1") != "0":
+        lse = None
+        if not save and adt != F32 and T >= ops.ATTN_QSCALED_MIN_T and _QSCALED:
             # evaluation, 16-bit, long sequences (384^2 / 512^2 windows): the 64-queries-per-wave forward on a projection that already
-            # carries the softmax scale (SIMSEG_AMD_QSCALED=0: A/B runs on the kernel that scales q itself)
+            # carries the softmax scale
             qw_s, qb_s = _wt_qscaled(qw, qb, adt, D)
             qkv = ops.gemm(ln1.view(-1, D), qw_s, bias=qb_s)
             att, _ = ops.attention_fwd_qscaled(qkv.view(B, T, 3 * D), heads)
-            x1 = _fwd_gemm(att.view(-1, D), pw, adt, False, bias=pb.detach(), residual=x.view(-1, D), out_dtype=F32)
-            ln2, _, _, _ = ops.layernorm_fwd(x1, n2w.detach(), n2b.detach(), 1e-6, out_dtype=adt, save_stats=False)
-            act = _fwd_gemm(ln2, f1w, adt, False, bias=f1b.detach(), act=1)
-            return _fwd_gemm(act, f2w, adt, False, bias=f2b.detach(), residual=x1, out_dtype=F32).view(B, T, D)
-        if not save:        # evaluation: no operand is kept (exact mode: large problems go through the split-bf16 form of the fp32 products)
-            qkv = _fwd_gemm(ln1.view(-1, D), qw, adt, False, bias=qb.detach())
-            if adt == F32 and _SPLIT_FP32 != "0" and (_SPLIT_FP32 == "1" or (T >= 512 and B * heads >= 128)):
-                # exact mode, long sequences: the attention products through the bf16 pieces as well (the fp32 MFMA kernel is 20 % of an
-                # exact-mode ViT-B@512 evaluation once the GEMMs are split; measured 2.07 -> 1.58 ms per layer at 63 x 1025 tokens with the
-                # split pass, a tie at T = 325, slower at T = 197: tools/attn_x3_bench.py)
+        else:
+            qkv = _fwd_gemm(ln1.view(-1, D), qw, adt, save, bias=qb.detach())
+            if not save and adt == F32 and _SPLIT_FP32 != "0" and (_SPLIT_FP32 == "1" or (T >= 512 and B * heads >= 128)):
+                # exact-mode evaluation, long sequences: the attention products through the bf16 pieces as well (the fp32 MFMA kernel is 20 %
+                # of an exact-mode ViT-B@512 evaluation once the GEMMs are split; measured 2.07 -> 1.58 ms per layer at 63 x 1025 tokens with
+                # the split pass, a tie at T = 325, slower at T = 197: tools/attn_x3_bench.py)
                 SPLIT_CALLS[0] += 1
                 att = ops.attention_fwd_x3(qkv.view(B, T, 3 * D), heads, scale=64 ** -0.5)
             else:
-                att, _ = ops.attention_fwd(qkv.view(B, T, 3 * D), heads, None, scale=64 ** -0.5, save_lse=False)
-            x1 = _fwd_gemm(att.view(-1, D), pw, adt, False, bias=pb.detach(), residual=x.view(-1, D), out_dtype=F32)
-            ln2, _, _, _ = ops.layernorm_fwd(x1, n2w.detach(), n2b.detach(), 1e-6, out_dtype=adt, save_stats=False)
-            act = _fwd_gemm(ln2, f1w, adt, False, bias=f1b.detach(), act=1)
-            return _fwd_gemm(act, f2w, adt, False, bias=f2b.detach(), residual=x1, out_dtype=F32).view(B, T, D)
-        qw_, pw_, f1w_, f2w_ = _wt(qw, adt), _wt(pw, adt), _wt(f1w, adt), _wt(f2w, adt)
-        qkv = ops.gemm(ln1.view(-1, D), qw_, bias=qb.detach())
-        att, lse = ops.attention_fwd(qkv.view(B, T, 3 * D), heads, None, scale=64 ** -0.5, save_lse=save)
-        x1 = ops.gemm(att.view(-1, D), pw_, bias=pb.detach(), residual=x.view(-1, D), out_dtype=F32)
+                att, lse = ops.attention_fwd(qkv.view(B, T, 3 * D), heads, None, scale=64 ** -0.5, save_lse=save)
+        # one tail for evaluation and training (evaluation keeps no operand: in exact mode its large problems go through the split-bf16 form
+        # of the fp32 products, _fwd_gemm)
+        x1 = _fwd_gemm(att.view(-1, D), pw, adt, save, bias=pb.detach(), residual=x.view(-1, D), out_dtype=F32)
         ln2, _, mean2, rstd2 = ops.layernorm_fwd(x1, n2w.detach(), n2b.detach(), 1e-6, out_dtype=adt, save_stats=save)
         # (16-bit modes, full tiles: GELU' is saved as the tile-blocked accumulator image the dgrad through fc2 reads back - act 5 / 6, or
         #  7 / 8 = the same image with one byte per element, _GELU8)
         blk = save and adt != F32 and ops.gemm_aux_blocked_ok(B * T, 4 * D, D)
         g8 = blk and _GELU8
         pre = torch.empty(B * T, 4 * D, device=x.device, dtype=torch.uint8 if g8 else adt) if save else None
-        act = ops.gemm(ln2, f1w_, bias=f1b.detach(), act=((7 if g8 else 5) if blk else 3) if save else 1, aux_out=pre)     # pre holds GELU'(fc1 output)
-        y = ops.gemm(act, f2w_, bias=f2b.detach(), residual=x1, out_dtype=F32)
-        ctx.adt, ctx.heads, ctx.dims, ctx.blk = adt, heads, (B, T, D), (2 if g8 else 1) if blk else 0
-        ctx.lazy = bool(lazy_ok) and adt != F32 and _RES16
-        ctx.wparams = (f2w, f1w, pw, qw)                                  # (the parameter objects: _grad_target in the backward)
+        act = _fwd_gemm(ln2, f1w, adt, save, bias=f1b.detach(), act=((7 if g8 else 5) if blk else 3) if save else 1, aux_out=pre)     # pre holds GELU'(fc1 output)
+        y = _fwd_gemm(act, f2w, adt, save, bias=f2b.detach(), residual=x1, out_dtype=F32)
         if save:
-            ctx.save_for_backward(x, mean1, rstd1, ln1, qkv, att, lse, x1, mean2, rstd2, ln2, pre, act, qw_, pw_, f1w_, f2w_,
-                                  n1w.detach(), n2w.detach(), n1b.detach(), n2b.detach())
+            ctx.adt, ctx.heads, ctx.dims, ctx.blk = adt, heads, (B, T, D), (2 if g8 else 1) if blk else 0
+            ctx.lazy = bool(lazy_ok) and adt != F32 and _RES16
+            ctx.wparams = (f2w, f1w, pw, qw)                                  # (the parameter objects: _grad_target in the backward)
+            ctx.save_for_backward(x, mean1, rstd1, ln1, qkv, att, lse, x1, mean2, rstd2, ln2, pre, act, _wt(qw, adt), _wt(pw, adt), _wt(f1w, adt),
+                                  _wt(f2w, adt), n1w.detach(), n2w.detach(), n1b.detach(), n2b.detach())
         return y.view(B, T, D)
 
     @staticmethod
-    @_joins_wgrad
     def backward(ctx, dy):
         x, mean1, rstd1, ln1, qkv, att, lse, x1, mean2, rstd2, ln2, pre, act, qw_, pw_, f1w_, f2w_, n1w, n2w, n1b, n2b = ctx.saved_tensors
         B, T, D = ctx.dims
@@ -669,10 +624,7 @@ class ViTBlockFn(_GradAwareFn):
         datt = _dgrad(dx1_16, pw_)
         dpw = wg(dx1_16, att.view(-1, D), dpw_z) if need[7] else None
         dqb = _zeros_like_bias(dqb_z, 3 * D, qkv.device) if need[6] else None       # the qkv bias gradient rides on the attention backward
-        dqkv = ops.attention_bwd(qkv.view(B, T, 3 * D), att, datt.view(B, T, D), lse, ctx.heads, None, scale=64 ** -0.5,
-                                 colsum=dqb if _FUSED_QKV_BIAS else None).view(-1, 3 * D)
-        if dqb is not None and not _FUSED_QKV_BIAS:
-            ops.colsum_accum(dqkv, dqb)
+        dqkv = ops.attention_bwd(qkv.view(B, T, 3 * D), att, datt.view(B, T, D), lse, ctx.heads, None, scale=64 ** -0.5, colsum=dqb).view(-1, 3 * D)
         dln1 = _dgrad(dqkv, qw_)
         dqw = wg(dqkv, ln1.view(-1, D), dqw_z) if need[5] else None
         dx, dx16 = _ln_bwd(adt, x.view(-1, D), mean1, rstd1, n1w, dn1w, dn1b, dln1, dres=None if r16 else dx1_32, dres16=dx1_16 if r16 else None,
@@ -929,7 +881,6 @@ class BertLayerFn(_GradAwareFn):
         return y if packed else y.view(B, L, D)
 
     @staticmethod
-    @_joins_wgrad
     def backward(ctx, dy):
         (xa, mask, qkv, att, lse, s1, mean_a, rstd_a, aa, pre, act, s2, mean_o, rstd_o, wqkv, ow_, iw_, o2w_, law, low, attd, idx, inv, cu) = ctx.saved_tensors
         B, L, D = ctx.dims
@@ -960,7 +911,7 @@ class BertLayerFn(_GradAwareFn):
         dbqkv = _zeros_like_bias(dbqkv_z, 3 * D, qkv.device) if (need[7] or need[9] or need[11]) else None
         if ctx.rows:                                                 # attention backward straight on the packed rows
             dqkv = ops.attention_bwd_rows(qkv, att, datt.contiguous(), lse, ctx.heads, cu, L, scale=64 ** -0.5, drop_seed=seed, drop_p=p,
-                                          colsum=dbqkv if _FUSED_QKV_BIAS else None, n_real=ctx.nv)
+                                          colsum=dbqkv, n_real=ctx.nv)
         else:
             if packed:
                 datt = ops.gather_rows(datt, inv)                    # back to [B*L, D] (zero rows at the padded positions)
@@ -968,11 +919,9 @@ class BertLayerFn(_GradAwareFn):
             # the kernel works on equal the sums over the packed rows)
             dqkv = ops.attention_bwd(qkv.view(B, L, 3 * D), (attd if packed else att).view(B, L, D), datt.view(B, L, D), lse, ctx.heads, mask,
                                      scale=64 ** -0.5, drop_seed=seed, drop_p=p, skip_padded_rows=packed and _SKIP_PAD,
-                                     colsum=dbqkv if _FUSED_QKV_BIAS else None, zero_skipped=False).view(-1, 3 * D)
+                                     colsum=dbqkv, zero_skipped=False).view(-1, 3 * D)
             if packed:
                 dqkv = ops.gather_rows(dqkv, idx)                    # [Nv, 3D]
-        if dbqkv is not None and not _FUSED_QKV_BIAS:
-            ops.colsum_accum(dqkv, dbqkv)
         dx = _dgrad(dqkv, wqkv, residual=ds1_32, out_dtype=F32)
         dwqkv = wg(dqkv, xa, dwqkv_z) if (need[6] or need[8] or need[10]) else None
         if group:
@@ -1091,7 +1040,6 @@ class ProjectPoolFn(_GradAwareFn):
         return emb
 
     @staticmethod
-    @_joins_wgrad
     def backward(ctx, demb):
         fa, wa, emb, idx, norm = ctx.saved_tensors
         B, N, D = ctx.dims

@@ -267,11 +267,11 @@ def test_vitb_512_window_qscaled_attention_path(monkeypatch):
         want = ref(x)
         for mode, tol in (("bf16", 2e-2), ("fp16", 4e-3)):
             monkeypatch.setenv("SIMSEG_AMD_COMPUTE", mode)
-            monkeypatch.setenv("SIMSEG_AMD_QSCALED", "1")
-            n0 = len(towers._WQS)
+            monkeypatch.setattr(towers, "_QSCALED", True)
+            n0 = towers.COPIES.count("qscaled")
             got = m(x.cuda()).float().cpu()
-            assert len(towers._WQS) >= max(n0, 12)                       # one folded copy per block
-            monkeypatch.setenv("SIMSEG_AMD_QSCALED", "0")
+            assert towers.COPIES.count("qscaled") >= max(n0, 12)         # one folded copy per block
+            monkeypatch.setattr(towers, "_QSCALED", False)
             plain = m(x.cuda()).float().cpu()
             rel, rel0 = float((got - want).norm() / want.norm()), float((plain - want).norm() / want.norm())
             diff = float((got - plain).norm() / want.norm())
@@ -279,12 +279,12 @@ def test_vitb_512_window_qscaled_attention_path(monkeypatch):
             assert rel < tol and rel0 < tol and diff < tol and rel < 1.5 * rel0 + 1e-4
         # cache invalidation: perturb block 0's qkv weight in place
         monkeypatch.setenv("SIMSEG_AMD_COMPUTE", "bf16")
-        monkeypatch.setenv("SIMSEG_AMD_QSCALED", "1")
+        monkeypatch.setattr(towers, "_QSCALED", True)
         before = m(x.cuda()).float()
         w = dict(m.named_parameters())["blocks.0.attn.qkv.weight"]
         w.mul_(1.5)
         after = m(x.cuda()).float()
-        monkeypatch.setenv("SIMSEG_AMD_QSCALED", "0")
+        monkeypatch.setattr(towers, "_QSCALED", False)
         after_plain = m(x.cuda()).float()
         assert float((after - before).norm() / before.norm()) > 1e-2                     # the update is seen
         assert float((after - after_plain).norm() / after_plain.norm()) < 2e-2           # and it is the same update

@@ -521,8 +521,7 @@ def test_bf16_weight_copy_cache_coherence(golden, monkeypatch):
     opt.step()
     torch.cuda.synchronize()
     for p in (w, m.text_encoder.model.model.encoder.layer[0].attention.self.query.weight, m.image_projection.linear.weight):
-        ent = towers._W16[id(p)]
-        assert ent[3].data_ptr() == opt.state[p]["p16"].data_ptr()      # the optimizer's copy is the one the towers use
+        assert towers.COPIES.get("w16", (p,), torch.bfloat16).data_ptr() == opt.state[p]["p16"].data_ptr()     # the optimizer's copy is the one the towers use
         assert torch.equal(towers._wt(p, torch.bfloat16), p.detach().bfloat16())
     sd = {k: v.clone() for k, v in m.state_dict().items()}
     m.load_state_dict({k: v * 0 + 0.01 for k, v in sd.items()}, strict=False)

@@ -1,4 +1,5 @@
-"""The derived weight copies the 16-bit and split-fp32 towers cache per parameter (simseg_amd/towers.py: _W16, _CAT, _W3, _WQS) against a
+"""The derived weight copies the 16-bit and split-fp32 towers cache per parameter (simseg_amd/towers.py DerivedCopies: the kinds "w16",
+"cat", "split", "qscaled"; its staleness rules alone, without a GPU: tests/test_weight_copies_host.py) against a
 FRESH module: a new module of the same class and config, loaded with the model's state_dict, has no cache entry that could match, so after
 every way a weight can be written the model under test must evaluate bit for bit as that module does (same input, same compute mode, same
 switches).  Bit-identity is the bar: every copy is an exact function of the fp32 masters (the optimizer kernel rounds as torch does), the
@@ -63,7 +64,7 @@ class Route:
         self.adt = {"w16_bf16": BF16, "w16_fp16": F16, "cat": BF16, "w3": torch.float32, "wqs_bf16": BF16, "wqs_fp16": F16}[name]
         self.half = self.adt if self.adt != torch.float32 else F16          # the optimizer's copies: the route's type, else the reference's AMP type
         monkeypatch.setenv("SIMSEG_AMD_COMPUTE", {BF16: "bf16", F16: "fp16", torch.float32: "fp32"}[self.adt])
-        monkeypatch.setenv("SIMSEG_AMD_QSCALED", "1")
+        monkeypatch.setattr(towers, "_QSCALED", True)
         if name == "w3":
             monkeypatch.setattr(towers, "_SPLIT_FP32", "1")
         if name.startswith("wqs"):
@@ -135,21 +136,21 @@ class Route:
                 out = m(self.inp).float().reshape(-1)
         torch.cuda.synchronize()
         if self.name.startswith("w16"):
-            ent = towers._W16[id(w)]
-            assert ent[0]() is w and ent[1] == w._version and ent[3].dtype == self.adt
+            w16 = towers.COPIES.get("w16", (w,), self.adt)              # (a hit: made from this parameter at its current version, in the route's dtype)
+            assert w16 is not None and w16.dtype == self.adt
             if opt is not None and opt.half_dtype == self.adt:
-                assert ent[3] is opt.state[w]["p16"]                              # the towers read the optimizer's copy
+                assert w16 is opt.state[w]["p16"]                                 # the towers read the optimizer's copy
         elif self.name == "cat":
             lay = m.encoder.layer[0].attention.self
-            ents, _ = towers._CAT[id(lay.query.weight)]
-            assert all(e is towers._W16[id(p)] for e, p in zip(ents, (lay.query.weight, lay.key.weight, lay.value.weight)))
+            qkv = (lay.query.weight, lay.key.weight, lay.value.weight)
+            parts, _ = towers.COPIES.get("cat", qkv, self.adt)
+            assert all(p16 is not None and p16 is towers.COPIES.get("w16", (p,), self.adt) for p16, p in zip(parts, qkv))
         elif self.name == "w3":
             assert towers.SPLIT_CALLS[0] > n_split
-            assert towers._W3[id(w)][1] == w._version
+            assert towers.COPIES.get("split", (w,)) is not None                   # (made from this parameter at its current version)
         else:
             assert self.qs_calls[0] == n_qs + len(m.blocks)                        # one folded projection per block
-            ent = towers._WQS[(id(w), id(b))]
-            assert ent[0]() is w and ent[1]() is b
+            assert towers.COPIES.get("qscaled", (w, b), self.adt) is not None     # (made from this weight and this bias as they are now)
         return out
 
     def compare(self, m, opt=None):
@@ -157,10 +158,10 @@ class Route:
         from simseg_amd import towers
         out = self.run(m, opt)
         f = self.fresh(m)
-        n_wqs = len(towers._WQS)
+        n_wqs = towers.COPIES.count("qscaled")
         r1 = self.run(f)
         if self.name.startswith("wqs"):
-            assert len(towers._WQS) > n_wqs                                       # the fresh module made its own folded copies
+            assert towers.COPIES.count("qscaled") > n_wqs                                      # the fresh module made its own folded copies
         r2 = self.run(f)
         assert torch.equal(r1, r2), "the fresh module's route is not deterministic"
         assert torch.isfinite(out).all(), f"{self.name}: non-finite output"

@@ -85,6 +85,15 @@ def test_c_abi_exports_every_declared_symbol():
     assert b"null operand" in l.simseg_last_error()
 
 
+def test_qscaled_threshold_is_the_attention_kernels():
+    """ops.ATTN_QSCALED_MIN_T, from which the towers take the q-scaled forward, is a hand copy of W64_MINT in csrc/attn.hip."""
+    import re
+    from simseg_amd import ops
+    src = open(os.path.join(REPO, "simseg_amd", "csrc", "attn.hip")).read()
+    (mint,) = re.findall(r"constexpr int W64_MINT = (\d+)", src)
+    assert int(mint) == ops.ATTN_QSCALED_MIN_T
+
+
 def test_fp16_flavour_is_built_selectable_and_its_rename_header_is_current():
     """The 16-bit sources are compiled twice (bf16 as they stand, fp16 with -DSS_HALF); csrc/half_names.h - generated from the sources'
     entry points and the public header's prototypes - is the committed, current generation; every renamed twin is exported; the
