@@ -14,9 +14,14 @@
 #include "common.h"
 #include <type_traits>
 
-extern "C" int simseg_colsum_accum(const void* in, int in_dtype, float* out, int64_t rows, int64_t N, int64_t ld, void* stream);      // rowops.hip
-
 namespace {
+
+// the 16-bit type of THIS build of the file, for helpers outside it that take the element type outright (ss_colsum_accum)
+#ifdef SS_HALF
+constexpr int ELEM16 = SS_ELEM_FP16;
+#else
+constexpr int ELEM16 = SS_ELEM_BF16;
+#endif
 
 constexpr int KT = 64;            // keys per LDS tile
 constexpr float NEG = -1e30f;
@@ -2474,7 +2479,7 @@ int run_bwd_one(AttnParams& p, float* workspace, float* dqkv_colsum, const char*
     p.colsum_ws = dqkv_colsum ? workspace + (long)p.B * p.H * p.T : nullptr;
     if (int rc = p.drop_thresh ? launch_bwd_one<true>(p, (hipStream_t)stream) : launch_bwd_one<false>(p, (hipStream_t)stream)) return rc;
     SS_LAUNCH_CHECK(what);
-    if (dqkv_colsum) return simseg_colsum_accum(p.colsum_ws, 0, dqkv_colsum, p.B, 3 * p.H * 64, 3 * p.H * 64, stream);
+    if (dqkv_colsum) return ss_colsum_accum(p.colsum_ws, SS_ELEM_F32, dqkv_colsum, p.B, 3 * p.H * 64, 3 * p.H * 64, stream);
     return 0;
 }
 
@@ -2611,7 +2616,7 @@ extern "C" int simseg_attention_bwd(const void* qkv, const int64_t* key_mask, co
             hipLaunchKernelGGL((attn_bwd_f32_kernel<true, false>), grid, block, 0, s, p);
         }
         SS_LAUNCH_CHECK("attention_bwd (fp32)");
-        if (dqkv_colsum) return simseg_colsum_accum(dqkv, 0, dqkv_colsum, B * T, 3 * H * 64, 3 * H * 64, stream);
+        if (dqkv_colsum) return ss_colsum_accum(dqkv, SS_ELEM_F32, dqkv_colsum, B * T, 3 * H * 64, 3 * H * 64, stream);
         return 0;
     }
     if (T <= ONE_MAXT && g_attn_variant != 1) return run_bwd_one(p, workspace, dqkv_colsum, "attention_bwd", stream);
@@ -2626,7 +2631,7 @@ extern "C" int simseg_attention_bwd(const void* qkv, const int64_t* key_mask, co
         hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, block, 0, s, p);
     }
     SS_LAUNCH_CHECK("attention_bwd");
-    if (dqkv_colsum) return simseg_colsum_accum(dqkv, 1, dqkv_colsum, B * T, 3 * H * 64, 3 * H * 64, stream);
+    if (dqkv_colsum) return ss_colsum_accum(dqkv, ELEM16, dqkv_colsum, B * T, 3 * H * 64, 3 * H * 64, stream);
     return 0;
 }
 

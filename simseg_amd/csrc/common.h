@@ -5,14 +5,15 @@
 #include <stdio.h>
 #include <string.h>
 
-// The 16-bit operand type.  gemm.hip, attn.hip and rowops.hip are compiled TWICE (simseg_amd/build.py): as they stand - bf16, the
+// The 16-bit operand type.  gemm.hip and attn.hip are compiled TWICE (simseg_amd/build.py): as they stand - bf16, the
 // headline mode - and with -DSS_HALF, where the same sources are the IEEE fp16 flavour the reference's AMP mode uses (fp16 autocast + a
 // live GradScaler, clip_runner.py:226-230): `bf16_t` is then _Float16, the MFMA is v_mfma_f32_32x32x16_f16, and every C-ABI entry point
 // the file defines carries the suffix _h16 (half_names.h renames them by macro).  The bf16 build's entry points hand a call over to their
 // _h16 twin while the calling thread has selected fp16 (simseg_set_half_type(2)); dtype code 1 always means "the selected 16-bit type".
-// Only entry points whose kernels differ between the flavours belong in those three files.  Every other source is compiled ONCE: where
-// one of its kernels touches 16-bit data (optim.hip, probe.hip, mixup.hip) the type is a template argument picked per call from
-// g_ss_half, and fp32-only code (loss.hip, rowops_plain.hip) has no flavour at all.
+// Only entry points whose kernels differ between the flavours - the MFMA builtin and the loops around it - belong in those two files.
+// Every other source is compiled ONCE: where one of its kernels touches 16-bit data (rowops.hip, optim.hip, probe.hip, mixup.hip,
+// patchdrop.hip) the type is a template argument picked per call from g_ss_half (with_h16 below), and fp32-only code (loss.hip) has no
+// flavour at all.
 #ifdef SS_HALF
 typedef _Float16 bf16_t;
 #define SS_MFMA_32x32x16(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, x, y, z)
@@ -65,24 +66,43 @@ __device__ __forceinline__ float half_bits_to_float(short bits) {      // a 16-b
 }
 __device__ __forceinline__ bf16_t f2bf(float v) { return (bf16_t)v; }
 
-// 16 bytes (fp32) / 8 bytes (16-bit) of a row to and from four floats: the row kernels' unit of access (rowops.hip, rowops_plain.hip)
+// The once-compiled sources name the two 16-bit types themselves (never bf16_t, which is one of them per build of gemm.hip / attn.hip).
+// Element type of a buffer where a call states it outright instead of through dtype code 1: the values g_ss_half takes, and 0 for fp32.
+enum { SS_ELEM_F32 = 0, SS_ELEM_BF16 = 1, SS_ELEM_FP16 = 2 };
+template <typename H> struct h16_tag { typedef H type; };
+// f(h16_tag<H>()) for the 16-bit type `half` names (g_ss_half at an entry point): `[&](auto tag) { typedef typename decltype(tag)::type H; ... }`
+template <typename F> inline void with_h16(int half, F&& f) {
+    if (half == SS_ELEM_FP16) f(h16_tag<_Float16>());
+    else f(h16_tag<__bf16>());
+}
+template <typename H> using h16x4 = H __attribute__((ext_vector_type(4)));
+
+// 16 bytes (fp32) / 8 bytes (16-bit) of a row to and from four floats: the row kernels' unit of access (rowops.hip, patchdrop.hip)
 template <typename TO> __device__ __forceinline__ void store4(TO* p, const float (&v)[4]);
 template <> __device__ __forceinline__ void store4<float>(float* p, const float (&v)[4]) {
     *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]);
 }
-template <> __device__ __forceinline__ void store4<bf16_t>(bf16_t* p, const float (&v)[4]) {
-    bf16x4 o = {(bf16_t)v[0], (bf16_t)v[1], (bf16_t)v[2], (bf16_t)v[3]};
-    *reinterpret_cast<bf16x4*>(p) = o;
+template <typename H> __device__ __forceinline__ void store4_h16(H* p, const float (&v)[4]) {
+    h16x4<H> o = {(H)v[0], (H)v[1], (H)v[2], (H)v[3]};
+    *reinterpret_cast<h16x4<H>*>(p) = o;
 }
+template <> __device__ __forceinline__ void store4<__bf16>(__bf16* p, const float (&v)[4]) { store4_h16(p, v); }
+template <> __device__ __forceinline__ void store4<_Float16>(_Float16* p, const float (&v)[4]) { store4_h16(p, v); }
 template <typename TI> __device__ __forceinline__ void load4(const TI* p, float (&v)[4]);
 template <> __device__ __forceinline__ void load4<float>(const float* p, float (&v)[4]) {
     const float4 t = *reinterpret_cast<const float4*>(p);
     v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
 }
-template <> __device__ __forceinline__ void load4<bf16_t>(const bf16_t* p, float (&v)[4]) {
-    const bf16x4 t = *reinterpret_cast<const bf16x4*>(p);
+template <typename H> __device__ __forceinline__ void load4_h16(const H* p, float (&v)[4]) {
+    const h16x4<H> t = *reinterpret_cast<const h16x4<H>*>(p);
     v[0] = (float)t[0]; v[1] = (float)t[1]; v[2] = (float)t[2]; v[3] = (float)t[3];
 }
+template <> __device__ __forceinline__ void load4<__bf16>(const __bf16* p, float (&v)[4]) { load4_h16(p, v); }
+template <> __device__ __forceinline__ void load4<_Float16>(const _Float16* p, float (&v)[4]) { load4_h16(p, v); }
+
+// out[n] += sum_r in[r, n] over a [rows, N] block with row stride ld, `elem` one of SS_ELEM_*: the body of simseg_colsum_accum
+// (rowops.hip), for callers inside the library that know their operand's type - attn.hip folds the qkv bias gradient with it.
+int ss_colsum_accum(const void* in, int elem, float* out, int64_t rows, int64_t N, int64_t ld, void* stream);
 
 // Normal CDF for the erf-GELU epilogues.  libm's erff costs ~30 VALU instructions per element, which made the GELU / GELU'
 // epilogues of the MLP GEMMs as long as their K loops (measured: +40 % / +60 % on [100864,768]x[3072,768]^T).  Abramowitz &

@@ -1,9 +1,12 @@
-// HBM-bound row kernels of the encoder path that read or write the 16-bit type (compiled per flavour): LayerNorm fwd/bwd (K3), patch
-// gather (K1), LoDA top-k pooling + L2norm fwd/bwd (K11, K12), row norms, column sums, casts and the dropout mask.  Their fp32-only
-// neighbours are in rowops_plain.hip.  Every kernel moves 16 bytes per lane per access and reduces rows with wave shuffles.
+// HBM-bound row kernels of the encoder path: LayerNorm fwd/bwd (K3), patch gather (K1), LoDA top-k pooling + L2norm fwd/bwd (K11, K12), row
+// norms, column sums, casts and the dropout mask - which read or write 16-bit data and take its type as the template argument H, picked per
+// call from g_ss_half - then the ones without a 16-bit type: [cls]+pos rows (K2), BERT embedding gather/scatter (K9), the prompt-ensemble mean,
+// the fp32 transpose, the fp32 -> three-bf16-pieces split (always bf16) and the byte-wise row gather.  Compiled ONCE.  The 16-bit kernels
+// move 16 bytes (fp32) / 8 bytes per lane per access and reduce rows with wave shuffles.
 #include "common.h"
 #include <atomic>
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 
@@ -22,13 +25,13 @@ __device__ __forceinline__ void store4_nt(float* p, const float (&v)[4]) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// LayerNorm forward: one wave per row.  x fp32 (residual stream) -> y (TO) [+ optional bf16 copy y2]
+// LayerNorm forward: one wave per row.  x fp32 (residual stream) -> y (TO) [+ optional 16-bit copy y2]
 // timm Block.norm1/norm2/norm (eps 1e-6), HF BertSelfOutput/BertOutput/BertEmbeddings LayerNorm (eps 1e-12)
 // ---------------------------------------------------------------------------------------------
-template <typename TO>
+template <typename TO, typename H>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, TO* __restrict__ y,
-                                                     bf16_t* __restrict__ y2, float* __restrict__ mean_out,
+                                                     H* __restrict__ y2, float* __restrict__ mean_out,
                                                      float* __restrict__ rstd_out, int rows, int D, float eps) {
     const int lane = threadIdx.x & 63;
     const int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));     // wave-uniform: scalar row bases
@@ -70,7 +73,7 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd * g[j] + b[j];
             store4<TO>(y + (long)row * D + c * 4, o);
-            if (y2) store4<bf16_t>(y2 + (long)row * D + c * 4, o);
+            if (y2) store4<H>(y2 + (long)row * D + c * 4, o);
         }
     }
 }
@@ -90,10 +93,10 @@ __device__ __forceinline__ float half_wave_sum(float v, int half) {
     const float hi = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
     return half ? hi : lo;
 }
-template <typename TO>
+template <typename TO, typename H>
 __global__ __launch_bounds__(256) void ln_fwd2_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                       const float* __restrict__ beta, TO* __restrict__ y,
-                                                      bf16_t* __restrict__ y2, float* __restrict__ mean_out,
+                                                      H* __restrict__ y2, float* __restrict__ mean_out,
                                                       float* __restrict__ rstd_out, int rows, int D, float eps) {
     constexpr int MAXC2 = 4;                 // 16-byte chunks per lane: D <= 512
     const int lane = threadIdx.x & 63, half = lane >> 5, l32 = lane & 31;
@@ -140,7 +143,7 @@ __global__ __launch_bounds__(256) void ln_fwd2_kernel(const float* __restrict__ 
 #pragma unroll
             for (int j = 0; j < 4; ++j) o[j] = (v[i][j] - mean) * rstd * g[j] + b[j];
             store4<TO>(y + (long)row * D + c * 4, o);
-            if (y2) store4<bf16_t>(y2 + (long)row * D + c * 4, o);
+            if (y2) store4<H>(y2 + (long)row * D + c * 4, o);
         }
     }
 }
@@ -154,13 +157,13 @@ __global__ __launch_bounds__(256) void ln_fwd2_kernel(const float* __restrict__ 
 // next to the three column accumulators: 148 VGPRs at D = 768, 3 waves per SIMD, 768 of 1024 blocks resident), the row index is
 // wave-uniform (scalar row bases), and the host sizes the grid from hipOccupancyMaxActiveBlocksPerMultiprocessor: one resident round
 // whatever the register count.  The 16-bit ViT step's form (dy16 + y16 + dres16 -> dx16) runs ln_bwd16_kernel below.
-template <int MAXC>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ dy16, const float* __restrict__ dy32,
-                                                     const float* __restrict__ dres, const bf16_t* __restrict__ dres16,
-                                                     const float* __restrict__ x, const bf16_t* __restrict__ y16, const float* __restrict__ beta,
+template <int MAXC, typename H>
+__global__ __launch_bounds__(256) void ln_bwd_kernel(const H* __restrict__ dy16, const float* __restrict__ dy32,
+                                                     const float* __restrict__ dres, const H* __restrict__ dres16,
+                                                     const float* __restrict__ x, const H* __restrict__ y16, const float* __restrict__ beta,
                                                      const float* __restrict__ mean, const float* __restrict__ rstd,
                                                      const float* __restrict__ gamma, float* __restrict__ dx32,
-                                                     bf16_t* __restrict__ dx16, float* __restrict__ dgamma,
+                                                     H* __restrict__ dx16, float* __restrict__ dgamma,
                                                      float* __restrict__ dbeta, float* __restrict__ dxsum, float* __restrict__ partials,
                                                      int rows, int D,
                                                      unsigned long long drop_seed, unsigned int drop_thresh, float drop_scale) {
@@ -211,12 +214,12 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
                 const int o = c * 4;
                 float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4], xv[4], gm[4];
                 if (dy16) {
-                    const bf16x4 t = __builtin_nontemporal_load(reinterpret_cast<const bf16x4*>(dy16 + ro + o));
+                    const h16x4<H> t = __builtin_nontemporal_load(reinterpret_cast<const h16x4<H>*>(dy16 + ro + o));
                     a[0] = (float)t[0]; a[1] = (float)t[1]; a[2] = (float)t[2]; a[3] = (float)t[3];
                 }
                 if (dy32) { load4<float>(dy32 + ro + o, b); for (int j = 0; j < 4; ++j) a[j] += b[j]; }
                 if ((fromy >> i) & 1u) {
-                    const bf16x4 t = __builtin_nontemporal_load(reinterpret_cast<const bf16x4*>(y16 + ro + o));
+                    const h16x4<H> t = __builtin_nontemporal_load(reinterpret_cast<const h16x4<H>*>(y16 + ro + o));
                     float ig[4], bt[4];
                     load4<float>(par + D + c * 4, ig);
                     load4<float>(par + 2 * D + c * 4, bt);
@@ -229,7 +232,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
                 }
                 if (dres) load4_nt(dres + ro + o, rr[i]);       // requested with the rest of the row: one memory round trip per row
                 if (dres16) {                              // the residual gradient as the previous kernel's 16-bit copy (round 4: half the bytes)
-                    const bf16x4 t = __builtin_nontemporal_load(reinterpret_cast<const bf16x4*>(dres16 + ro + o));
+                    const h16x4<H> t = __builtin_nontemporal_load(reinterpret_cast<const h16x4<H>*>(dres16 + ro + o));
                     rr[i][0] += (float)t[0]; rr[i][1] += (float)t[1]; rr[i][2] += (float)t[2]; rr[i][3] += (float)t[3];
                 }
                 load4<float>(par + c * 4, gm);
@@ -259,7 +262,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
 #pragma unroll
                     for (int j = 0; j < 4; ++j) out[j] = dropout_keep(drop_seed, (unsigned long long)(ro + o) + j, drop_thresh) ? out[j] * drop_scale : 0.f;
                 }
-                if (dx16) store4<bf16_t>(dx16 + ro + o, out);
+                if (dx16) store4<H>(dx16 + ro + o, out);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) as[i][j] += out[j];
             }
@@ -310,11 +313,11 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
 //     b128 reads - 36 registers - or double-buffering the prefetch in registers).
 // Chunks whose gain fails the y16 test of the generic kernel (`okmask`; decided per launch, uniformly, `needx`) take xhat from the fp32
 // input x, requested at the top of the row - same arithmetic as the generic kernel chunk by chunk.
-template <int MAXC, bool FULL>
-__global__ __launch_bounds__(256) void ln_bwd16_kernel(const bf16_t* __restrict__ dy16, const bf16_t* __restrict__ dres16,
-                                                       const float* __restrict__ x, const bf16_t* __restrict__ y16, const float* __restrict__ beta,
+template <int MAXC, bool FULL, typename H>
+__global__ __launch_bounds__(256) void ln_bwd16_kernel(const H* __restrict__ dy16, const H* __restrict__ dres16,
+                                                       const float* __restrict__ x, const H* __restrict__ y16, const float* __restrict__ beta,
                                                        const float* __restrict__ mean, const float* __restrict__ rstd,
-                                                       const float* __restrict__ gamma, bf16_t* __restrict__ dx16, float* __restrict__ dgamma,
+                                                       const float* __restrict__ gamma, H* __restrict__ dx16, float* __restrict__ dgamma,
                                                        float* __restrict__ dbeta, float* __restrict__ dxsum, float* __restrict__ partials,
                                                        int rows, int D,
                                                        unsigned long long drop_seed, unsigned int drop_thresh, float drop_scale) {
@@ -348,13 +351,13 @@ __global__ __launch_bounds__(256) void ln_bwd16_kernel(const bf16_t* __restrict_
     __syncthreads();
     const int stride = gridDim.x * 4;
     int row = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
-    bf16x4 rdy[MAXC], ry[MAXC];
+    h16x4<H> rdy[MAXC], ry[MAXC];
 #define LN16_ISSUE(R)                                                                                             \
     do {                                                                                                          \
         const long ro_ = (long)(R) * D;                                                                           \
         _Pragma("unroll") for (int i = 0; i < MAXC; ++i) {                                                        \
-            rdy[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x4*>(dy16 + ro_ + off[i]));            \
-            ry[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x4*>(y16 + ro_ + off[i]));              \
+            rdy[i] = __builtin_nontemporal_load(reinterpret_cast<const h16x4<H>*>(dy16 + ro_ + off[i]));            \
+            ry[i] = __builtin_nontemporal_load(reinterpret_cast<const h16x4<H>*>(y16 + ro_ + off[i]));              \
         }                                                                                                         \
     } while (0)
     if (row < rows) LN16_ISSUE(row);
@@ -362,11 +365,11 @@ __global__ __launch_bounds__(256) void ln_bwd16_kernel(const bf16_t* __restrict_
         const float rs = rstd[row];
         const long ro = (long)row * D;
         float g[MAXC][4], xh[MAXC][4];
-        bf16x4 rcur[MAXC];
+        h16x4<H> rcur[MAXC];
         float s1 = 0.f, s2 = 0.f;
         asm volatile("" ::: "memory");       // the LDS parameter reads below are loop-invariant: keep them in the loop
 #pragma unroll
-        for (int i = 0; i < MAXC; ++i) rcur[i] = __builtin_nontemporal_load(reinterpret_cast<const bf16x4*>(dres16 + ro + off[i]));
+        for (int i = 0; i < MAXC; ++i) rcur[i] = __builtin_nontemporal_load(reinterpret_cast<const h16x4<H>*>(dres16 + ro + off[i]));
         if (needx) {                         // (xh[] is not live yet: the fp32 rows land in its registers)
             const float mu = mean[row];
 #pragma unroll
@@ -417,7 +420,7 @@ __global__ __launch_bounds__(256) void ln_bwd16_kernel(const bf16_t* __restrict_
                 for (int j = 0; j < 4; ++j) out[j] = dropout_keep(drop_seed, (unsigned long long)(ro + off[i]) + j, drop_thresh) ? out[j] * drop_scale : 0.f;
             }
             if (valid) {
-                store4<bf16_t>(dx16 + ro + off[i], out);
+                store4<H>(dx16 + ro + off[i], out);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) as[i][j] += out[j];
             }
@@ -726,17 +729,19 @@ __global__ __launch_bounds__(256) void row_rnorm_kernel(const TI* __restrict__ x
     if (lane == 0) rn[row] = 1.0f / fmaxf(sqrtf(s), eps);
 }
 
-__global__ void cast_f32_bf16_kernel(const float* __restrict__ in, bf16_t* __restrict__ out, long n4) {
+template <typename H>
+__global__ void cast_f32_bf16_kernel(const float* __restrict__ in, H* __restrict__ out, long n4) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         float v[4];
         load4<float>(in + i * 4, v);
-        store4<bf16_t>(out + i * 4, v);
+        store4<H>(out + i * 4, v);
     }
 }
-__global__ void cast_bf16_f32_kernel(const bf16_t* __restrict__ in, float* __restrict__ out, long n4) {
+template <typename H>
+__global__ void cast_bf16_f32_kernel(const H* __restrict__ in, float* __restrict__ out, long n4) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         float v[4];
-        load4<bf16_t>(in + i * 4, v);
+        load4<H>(in + i * 4, v);
         store4<float>(out + i * 4, v);
     }
 }
@@ -746,6 +751,149 @@ template <typename T>
 __global__ void dropout_apply_kernel(T* __restrict__ g, long n, unsigned long long seed, unsigned int thresh, float scale) {
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
         g[i] = (T)(dropout_keep(seed, (unsigned long long)i, thresh) ? (float)g[i] * scale : 0.f);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Kernels that do not depend on the selected 16-bit type
+// ---------------------------------------------------------------------------------------------
+// x[b, 0, :] = cls + pos[0]   (vit_builder.py:15-17; the patch rows are written by the patch GEMM epilogue)
+__global__ void vit_cls_rows_kernel(const float* __restrict__ cls, const float* __restrict__ pos, float* __restrict__ x,
+                                    int B, int T, int D) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * D) return;
+    const int b = i / D, d = i % D;
+    x[(long)b * T * D + d] = cls[d] + pos[d];
+}
+// backward: dcls += sum_b dx[b,0,:],  dpos[0] handled by the position column-sum over all rows
+// (blockIdx.y: slices of 16 images - three blocks walking all 512 rows serially, each load a DRAM latency, took 195 us; one atomic per
+//  column and slice)
+__global__ void vit_cls_grad_kernel(const float* __restrict__ dx, float* __restrict__ dcls, int B, int T, int D) {
+    const int d = blockIdx.x * blockDim.x + threadIdx.x;
+    if (d >= D) return;
+    const int b0 = blockIdx.y * 16, b1 = min(B, b0 + 16);
+    float s = 0.f;
+#pragma unroll 8
+    for (int b = b0; b < b1; ++b) s += dx[(long)b * T * D + d];
+    atomicAdd(dcls + d, s);
+}
+
+// ---------------------------------------------------------------------------------------------
+// BERT embeddings (HF BertEmbeddings): sum[b,l,:] = word[id] + pos[l] + type[0]     (LayerNorm runs next)
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void bert_embed_kernel(const long* __restrict__ ids, const float* __restrict__ word,
+                                                         const float* __restrict__ pos, const float* __restrict__ type0,
+                                                         float* __restrict__ out, int rows, int L, int D, int vocab) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    long id = ids[row];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    const int l = row % L;
+    for (int c = lane; c < (D >> 2); c += 64) {
+        float a[4], b[4], t[4], o[4];
+        load4<float>(word + id * D + c * 4, a);
+        load4<float>(pos + (long)l * D + c * 4, b);
+        load4<float>(type0 + c * 4, t);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = a[j] + t[j] + b[j];
+        store4<float>(out + (long)row * D + c * 4, o);
+    }
+}
+// backward: dword[id] += dsum[row] for valid (unmasked) tokens.  Masked tokens carry an exactly-zero gradient
+// (they are masked as keys and overwritten before pooling), so they are skipped.
+__global__ __launch_bounds__(256) void bert_embed_bwd_kernel(const long* __restrict__ ids, const long* __restrict__ mask,
+                                                             const float* __restrict__ dsum, float* __restrict__ dword,
+                                                             int rows, int D, int vocab) {
+    const int lane = threadIdx.x & 63;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= rows) return;
+    if (mask && mask[row] == 0) return;
+    long id = ids[row];
+    id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
+    for (int c = lane; c < D; c += 64) atomicAdd(dword + id * D + c, dsum[(long)row * D + c]);
+}
+
+// Prompt-ensemble reduction of the zero-shot classifier (tools/seg_evaluation.py:71-73): out[s,:] = normalize(mean_p x[s,p,:])
+__global__ void segment_mean_l2norm_kernel(const float* __restrict__ x, float* __restrict__ out, int Pn, int D) {
+    __shared__ float sh[16];
+    const int sgm = blockIdx.x, c = threadIdx.x;
+    const float* base = x + (long)sgm * Pn * D + c;
+    float acc = 0.f;
+    for (int i = 0; i < Pn; ++i) acc += base[(long)i * D];
+    acc /= Pn;
+    const float nrm = sqrtf(block_sum(acc * acc, sh));
+    out[(long)sgm * D + c] = acc / nrm;
+}
+
+// out[c, r] = in[r, c]  (fp32, 32x32 LDS tiles)
+__global__ void transpose_f32_kernel(const float* __restrict__ in, float* __restrict__ out, int R, int C) {
+    __shared__ float t[32][33];
+    const int c0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;   // 32 x 8
+    for (int j = ty; j < 32; j += 8)
+        if (r0 + j < R && c0 + tx < C) t[j][tx] = in[(long)(r0 + j) * C + c0 + tx];
+    __syncthreads();
+    for (int j = ty; j < 32; j += 8)
+        if (c0 + j < C && r0 + tx < R) out[(long)(c0 + j) * R + r0 + tx] = t[tx][j];
+}
+
+// ---- fp32 operand -> three bf16 pieces, laid out for ONE bf16 GEMM that reproduces the fp32 product -----------------------------
+// x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid): three round-to-nearest pieces of 8 significant
+// bits each carry x's 24 (bf16 has fp32's exponent range, so the residuals are exact and in range).  A product a.b is then the sum
+// of nine piece products; the three smallest (mid.lo, lo.mid, lo.lo <= 2^-24 |a||b|) are dropped, like the rounding of the fp32 FMA
+// chain they replace.  The six kept ones are laid out along K - the A operand as [hi | hi | hi | mid | mid | lo], the B operand as
+// [hi | mid | lo | hi | mid | hi], K' = 6 K - so that one launch of the bf16 MFMA kernel (v_mfma_f32_32x32x16_bf16, fp32 accumulate)
+// forms all of them in its accumulators: six times the MFMA work at sixteen times the matrix rate of v_mfma_f32_32x32x2_f32.
+// One thread per 8 consecutive k of a row: 32 B in, six 16-byte stores out.  The pieces are bf16 whatever 16-bit type the caller has
+// selected (fp16's five exponent bits could not hold the residuals).
+__global__ __launch_bounds__(256) void split_bf16x3_kernel(const float* __restrict__ in, __bf16* __restrict__ out, long rows, int K, long ld_in, int bpat) {
+    const int kc = K >> 3;
+    const long total = rows * kc;
+    for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
+        const long r = t / kc;
+        const int k0 = (int)(t - r * kc) << 3;
+        const float4 a = *reinterpret_cast<const float4*>(in + r * ld_in + k0), b = *reinterpret_cast<const float4*>(in + r * ld_in + k0 + 4);
+        const float x[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+        union { __bf16 h[8]; u32x4 v; } hi, mid, lo;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            hi.h[e] = (__bf16)x[e];
+            const float r1 = x[e] - (float)hi.h[e];
+            mid.h[e] = (__bf16)r1;
+            lo.h[e] = (__bf16)(r1 - (float)mid.h[e]);
+        }
+        if (bpat == 2) {                                 // three planes [piece][row][K] (the attention kernel's operand form)
+            __bf16* o = out + r * (long)K + k0;
+            *reinterpret_cast<u32x4*>(o) = hi.v;
+            *reinterpret_cast<u32x4*>(o + rows * (long)K) = mid.v;
+            *reinterpret_cast<u32x4*>(o + 2 * rows * (long)K) = lo.v;
+            continue;
+        }
+        __bf16* o = out + r * (6L * K) + k0;
+        // A pattern: hi hi hi mid mid lo;  B pattern: hi mid lo hi mid hi
+        *reinterpret_cast<u32x4*>(o) = hi.v;
+        *reinterpret_cast<u32x4*>(o + K) = bpat ? mid.v : hi.v;
+        *reinterpret_cast<u32x4*>(o + 2L * K) = bpat ? lo.v : hi.v;
+        *reinterpret_cast<u32x4*>(o + 3L * K) = bpat ? hi.v : mid.v;
+        *reinterpret_cast<u32x4*>(o + 4L * K) = mid.v;
+        *reinterpret_cast<u32x4*>(o + 5L * K) = bpat ? hi.v : lo.v;
+    }
+}
+
+// Row gather: dst[i,:] = src[idx[i],:] for i < n (idx < 0: a zero row).  Rows are `chunks` 16-byte pieces wide; dtype-agnostic.
+// The text tower uses it to drop the padded token rows of a ragged caption batch before its GEMMs / LayerNorms and to put rows back
+// (idx = inverse map, -1 at padded positions -> zeros) around the attention kernels, which keep the dense [B, L] layout.
+__global__ __launch_bounds__(256) void gather_rows_kernel(const u32x4* __restrict__ src, const int* __restrict__ idx, u32x4* __restrict__ dst,
+                                                          long n, int chunks) {
+    const long total = n * chunks;
+    for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < total; t += (long)gridDim.x * 256) {
+        const long i = t / chunks;
+        const int c = (int)(t - i * chunks);
+        const int r = idx[i];
+        u32x4 v = {0u, 0u, 0u, 0u};
+        if (r >= 0) v = src[(long)r * chunks + c];
+        dst[t] = v;
+    }
 }
 
 // One resident round of the LayerNorm backward: blocks per CU from the runtime's occupancy calculator for the instantiation's registers
@@ -758,7 +906,8 @@ inline int ln_bwd_grid(const void* fn, int slot, size_t lds, long rows) {
     // never pairs one call's occupancy with another call's LDS size.  A lost race costs a repeated query, never a wrong grid.
     constexpr int MAXDEV = 16;
     static std::atomic<int> ncu[MAXDEV];                       // CUs of the device, asked once (hipGetDeviceProperties is a millisecond-class call)
-    static std::atomic<unsigned long long> cached[MAXDEV][32]; // per (device, instantiation slot)
+    constexpr int SLOTS = 64;                                  // slot = (MAXC * 3 + form) + 32 * (H is fp16): the two types' instantiations differ in registers
+    static std::atomic<unsigned long long> cached[MAXDEV][SLOTS]; // per (device, instantiation slot)
     static std::atomic<int> forced{-1};                        // SIMSEG_LN_BWD_BLOCKS_PER_CU (tools/ln_bench.py sweeps), read once
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) dev = 0;
@@ -776,7 +925,7 @@ inline int ln_bwd_grid(const void* fn, int slot, size_t lds, long rows) {
         f = v > 0 ? v : 0;
         forced.store(f, std::memory_order_relaxed);
     }
-    const bool ok = slot >= 0 && slot < 32;
+    const bool ok = slot >= 0 && slot < SLOTS;
     const unsigned long long ent = ok ? cached[dev][slot].load(std::memory_order_relaxed) : 0ull;
     int per_cu = (ent != 0 && (ent >> 8) == (unsigned long long)lds) ? (int)(ent & 0xff) : 0;
     if (per_cu <= 0) {
@@ -796,24 +945,25 @@ inline int ln_bwd_grid(const void* fn, int slot, size_t lds, long rows) {
 
 extern "C" int simseg_layernorm_fwd(const float* x, const float* gamma, const float* beta, void* y, int out_dtype,
                                     void* y_bf16, float* mean, float* rstd, int64_t rows, int64_t D, float eps, void* stream) {
-    SS_HALF_FWD(simseg_layernorm_fwd, x, gamma, beta, y, out_dtype, y_bf16, mean, rstd, rows, D, eps, stream);
     SS_CHECK(x && gamma && beta && y, "layernorm_fwd: null pointer");
     SS_CHECK(D % 4 == 0 && D <= LN_MAXC * 256 && D > 0, "layernorm_fwd: D=%lld must be a multiple of 4 and <= %d", (long long)D, LN_MAXC * 256);
     if (rows <= 0) return 0;
-    if (D <= 512) {                           // two rows per wave
-        dim3 grid2((unsigned)((rows + 7) / 8));
+    with_h16(g_ss_half, [&](auto tag) {
+        typedef typename decltype(tag)::type H;
+        if (D <= 512) {                           // two rows per wave
+            dim3 grid2((unsigned)((rows + 7) / 8));
+            if (out_dtype == 0)
+                hipLaunchKernelGGL((ln_fwd2_kernel<float, H>), grid2, dim3(256), 0, STREAM, x, gamma, beta, (float*)y, (H*)y_bf16, mean, rstd, (int)rows, (int)D, eps);
+            else
+                hipLaunchKernelGGL((ln_fwd2_kernel<H, H>), grid2, dim3(256), 0, STREAM, x, gamma, beta, (H*)y, (H*)y_bf16, mean, rstd, (int)rows, (int)D, eps);
+            return;
+        }
+        dim3 grid((unsigned)((rows + 3) / 4));
         if (out_dtype == 0)
-            hipLaunchKernelGGL(ln_fwd2_kernel<float>, grid2, dim3(256), 0, STREAM, x, gamma, beta, (float*)y, (bf16_t*)y_bf16, mean, rstd, (int)rows, (int)D, eps);
+            hipLaunchKernelGGL((ln_fwd_kernel<float, H>), grid, dim3(256), 0, STREAM, x, gamma, beta, (float*)y, (H*)y_bf16, mean, rstd, (int)rows, (int)D, eps);
         else
-            hipLaunchKernelGGL(ln_fwd2_kernel<bf16_t>, grid2, dim3(256), 0, STREAM, x, gamma, beta, (bf16_t*)y, (bf16_t*)y_bf16, mean, rstd, (int)rows, (int)D, eps);
-        SS_LAUNCH_CHECK("layernorm_fwd");
-        return 0;
-    }
-    dim3 grid((unsigned)((rows + 3) / 4));
-    if (out_dtype == 0)
-        hipLaunchKernelGGL(ln_fwd_kernel<float>, grid, dim3(256), 0, STREAM, x, gamma, beta, (float*)y, (bf16_t*)y_bf16, mean, rstd, (int)rows, (int)D, eps);
-    else
-        hipLaunchKernelGGL(ln_fwd_kernel<bf16_t>, grid, dim3(256), 0, STREAM, x, gamma, beta, (bf16_t*)y, (bf16_t*)y_bf16, mean, rstd, (int)rows, (int)D, eps);
+            hipLaunchKernelGGL((ln_fwd_kernel<H, H>), grid, dim3(256), 0, STREAM, x, gamma, beta, (H*)y, (H*)y_bf16, mean, rstd, (int)rows, (int)D, eps);
+    });
     SS_LAUNCH_CHECK("layernorm_fwd");
     return 0;
 }
@@ -823,7 +973,6 @@ extern "C" int simseg_layernorm_bwd(const void* dy_bf16, const float* dy_f32, co
                                     const float* mean, const float* rstd, const float* gamma, float* dx_f32, void* dx_bf16,
                                     float* dgamma, float* dbeta, float* dxsum, float* partials, int64_t rows, int64_t D,
                                     uint64_t drop_seed, float drop_p, void* stream) {
-    SS_HALF_FWD(simseg_layernorm_bwd, dy_bf16, dy_f32, dres, dres_bf16, x, y_bf16, beta, mean, rstd, gamma, dx_f32, dx_bf16, dgamma, dbeta, dxsum, partials, rows, D, drop_seed, drop_p, stream);
     SS_CHECK((dy_bf16 || dy_f32) && x && mean && rstd && gamma && dgamma && dbeta && (dx_f32 || dx_bf16) && (!y_bf16 || beta), "layernorm_bwd: null pointer");
     SS_CHECK(D % 4 == 0 && D <= LN_MAXC * 256 && D > 0, "layernorm_bwd: bad D=%lld", (long long)D);
     SS_CHECK(drop_p >= 0.f && drop_p < 1.f, "layernorm_bwd: dropout p out of range");
@@ -835,24 +984,29 @@ extern "C" int simseg_layernorm_bwd(const void* dy_bf16, const float* dy_f32, co
     const bool fast = dy_bf16 && y_bf16 && dres_bf16 && dx_bf16 && !dy_f32 && !dres && !dx_f32;
     const size_t lds = (size_t)(y_bf16 ? 3 : 1) * D * sizeof(float);
     int grid = 0;
+    // (H and its occupancy-cache slot offset `fl` come from the lambda below: each type's instantiation has a slot of its own)
 #define LN_BWD_LAUNCH(C)                                                                                                              \
     do {                                                                                                                              \
-        grid = ln_bwd_grid((const void*)ln_bwd_kernel<C>, C * 3, lds, rows);                                                          \
-        hipLaunchKernelGGL(ln_bwd_kernel<C>, dim3(grid), dim3(256), lds, STREAM, (const bf16_t*)dy_bf16, dy_f32, dres, (const bf16_t*)dres_bf16, x, (const bf16_t*)y_bf16, beta, mean, rstd, gamma, \
-                           dx_f32, (bf16_t*)dx_bf16, dgamma, dbeta, dxsum, partials, (int)rows, (int)D, (unsigned long long)drop_seed, thresh, scale); \
+        grid = ln_bwd_grid((const void*)ln_bwd_kernel<C, H>, fl + C * 3, lds, rows);                                                  \
+        hipLaunchKernelGGL((ln_bwd_kernel<C, H>), dim3(grid), dim3(256), lds, STREAM, (const H*)dy_bf16, dy_f32, dres, (const H*)dres_bf16, x, (const H*)y_bf16, beta, mean, rstd, gamma, \
+                           dx_f32, (H*)dx_bf16, dgamma, dbeta, dxsum, partials, (int)rows, (int)D, (unsigned long long)drop_seed, thresh, scale); \
     } while (0)
 #define LN_BWD16_LAUNCH(C, F)                                                                                                         \
     do {                                                                                                                              \
-        grid = ln_bwd_grid((const void*)ln_bwd16_kernel<C, F>, C * 3 + (F ? 1 : 2), lds, rows);                                       \
-        hipLaunchKernelGGL((ln_bwd16_kernel<C, F>), dim3(grid), dim3(256), lds, STREAM, (const bf16_t*)dy_bf16, (const bf16_t*)dres_bf16, x, (const bf16_t*)y_bf16, beta, mean, rstd, gamma, \
-                           (bf16_t*)dx_bf16, dgamma, dbeta, dxsum, partials, (int)rows, (int)D, (unsigned long long)drop_seed, thresh, scale); \
+        grid = ln_bwd_grid((const void*)ln_bwd16_kernel<C, F, H>, fl + C * 3 + (F ? 1 : 2), lds, rows);                               \
+        hipLaunchKernelGGL((ln_bwd16_kernel<C, F, H>), dim3(grid), dim3(256), lds, STREAM, (const H*)dy_bf16, (const H*)dres_bf16, x, (const H*)y_bf16, beta, mean, rstd, gamma, \
+                           (H*)dx_bf16, dgamma, dbeta, dxsum, partials, (int)rows, (int)D, (unsigned long long)drop_seed, thresh, scale); \
     } while (0)
 #define LN_BWD_PICK(C) do { if (!fast) LN_BWD_LAUNCH(C); else if (D == (C) * 256) LN_BWD16_LAUNCH(C, true); else LN_BWD16_LAUNCH(C, false); } while (0)
-    if (nc <= 1) LN_BWD_PICK(1);
-    else if (nc == 2) LN_BWD_PICK(2);
-    else if (nc == 3) LN_BWD_PICK(3);
-    else if (nc == 4) LN_BWD_PICK(4);
-    else LN_BWD_PICK(8);
+    with_h16(g_ss_half, [&](auto tag) {
+        typedef typename decltype(tag)::type H;
+        constexpr int fl = std::is_same<H, _Float16>::value ? 32 : 0;
+        if (nc <= 1) LN_BWD_PICK(1);
+        else if (nc == 2) LN_BWD_PICK(2);
+        else if (nc == 3) LN_BWD_PICK(3);
+        else if (nc == 4) LN_BWD_PICK(4);
+        else LN_BWD_PICK(8);
+    });
 #undef LN_BWD_PICK
 #undef LN_BWD16_LAUNCH
 #undef LN_BWD_LAUNCH
@@ -866,8 +1020,7 @@ extern "C" int simseg_layernorm_bwd(const void* dy_bf16, const float* dy_f32, co
 /* floats the caller must provide as `partials` for a launch over `rows` rows of width D (the grid never exceeds LN_BWD_MAX_GRID blocks) */
 extern "C" int64_t simseg_layernorm_bwd_workspace_bytes(int64_t rows, int64_t D) { return (int64_t)grid_for(rows, 4, LN_BWD_MAX_GRID) * 3 * D * (int64_t)sizeof(float); }
 
-extern "C" int simseg_colsum_accum(const void* in, int in_dtype, float* out, int64_t rows, int64_t N, int64_t ld, void* stream) {
-    SS_HALF_FWD(simseg_colsum_accum, in, in_dtype, out, rows, N, ld, stream);
+int ss_colsum_accum(const void* in, int elem, float* out, int64_t rows, int64_t N, int64_t ld, void* stream) {
     SS_CHECK(in && out, "colsum: null pointer");
     SS_CHECK(N % 8 == 0 && ld % 8 == 0, "colsum: N and ld must be multiples of 8");
     if (rows <= 0) return 0;
@@ -880,16 +1033,22 @@ extern "C" int simseg_colsum_accum(const void* in, int in_dtype, float* out, int
     }
     const int rpb = (int)((rows + chunks - 1) / chunks);
     dim3 grid((unsigned)nbx, (unsigned)((rows + rpb - 1) / rpb));
-    if (in_dtype == 0)
+    if (elem == SS_ELEM_F32)
         hipLaunchKernelGGL(colsum_kernel<float>, grid, dim3(256), 0, STREAM, (const float*)in, out, (long)rows, (int)N, (long)ld, rpb);
     else
-        hipLaunchKernelGGL(colsum_kernel<bf16_t>, grid, dim3(256), 0, STREAM, (const bf16_t*)in, out, (long)rows, (int)N, (long)ld, rpb);
+        with_h16(elem, [&](auto tag) {
+            typedef typename decltype(tag)::type H;
+            hipLaunchKernelGGL(colsum_kernel<H>, grid, dim3(256), 0, STREAM, (const H*)in, out, (long)rows, (int)N, (long)ld, rpb);
+        });
     SS_LAUNCH_CHECK("colsum");
     return 0;
 }
 
+extern "C" int simseg_colsum_accum(const void* in, int in_dtype, float* out, int64_t rows, int64_t N, int64_t ld, void* stream) {
+    return ss_colsum_accum(in, in_dtype == 0 ? SS_ELEM_F32 : g_ss_half, out, rows, N, ld, stream);
+}
+
 extern "C" int simseg_vit_im2col(const float* image, void* cols, int out_dtype, int64_t B, int64_t H, int64_t W, void* stream) {
-    SS_HALF_FWD(simseg_vit_im2col, image, cols, out_dtype, B, H, W, stream);
     SS_CHECK(image && cols, "im2col: null pointer");
     SS_CHECK(H % 16 == 0 && W % 16 == 0 && H > 0 && W > 0, "im2col: H, W must be multiples of the 16x16 patch");
     const long total = B * (H / 16) * (W / 16) * 192;
@@ -898,7 +1057,10 @@ extern "C" int simseg_vit_im2col(const float* image, void* cols, int out_dtype, 
     if (out_dtype == 0)
         hipLaunchKernelGGL(im2col_kernel<float>, dim3(grid), dim3(256), 0, STREAM, image, (float*)cols, (int)B, (int)H, (int)W);
     else
-        hipLaunchKernelGGL(im2col_kernel<bf16_t>, dim3(grid), dim3(256), 0, STREAM, image, (bf16_t*)cols, (int)B, (int)H, (int)W);
+        with_h16(g_ss_half, [&](auto tag) {
+            typedef typename decltype(tag)::type T16;      // (H is the image height here)
+            hipLaunchKernelGGL(im2col_kernel<T16>, dim3(grid), dim3(256), 0, STREAM, image, (T16*)cols, (int)B, (int)H, (int)W);
+        });
     SS_LAUNCH_CHECK("im2col");
     return 0;
 }
@@ -908,7 +1070,6 @@ extern "C" int64_t simseg_topk_pool_workspace_bytes(int64_t B, int64_t P, int k)
 extern "C" int simseg_topk_pool_l2norm_fwd(const void* tok, int dtype, const int64_t* mask, float* emb, int32_t* idx, float* norm,
                                            float* scratch, int64_t B, int64_t N, int64_t P, int k, float eps, int normalize,
                                            void* stream) {
-    SS_HALF_FWD(simseg_topk_pool_l2norm_fwd, tok, dtype, mask, emb, idx, norm, scratch, B, N, P, k, eps, normalize, stream);
     SS_CHECK(tok && emb && idx && norm, "topk_pool_fwd: null pointer");
     SS_CHECK(P % 64 == 0 && P <= 1024, "topk_pool_fwd: P=%lld must be a multiple of 64 and <= 1024", (long long)P);
     SS_CHECK(k >= 1 && k <= POOL_MAXK && k <= N, "topk_pool_fwd: k=%d out of range (1..%d, <= N)", k, POOL_MAXK);
@@ -922,7 +1083,10 @@ extern "C" int simseg_topk_pool_l2norm_fwd(const void* tok, int dtype, const int
         if (dtype == 0)
             hipLaunchKernelGGL(topk_pool_slice_kernel<float>, g, dim3((unsigned)P), 0, STREAM, (const float*)tok, (const long*)mask, cv, ci, (int)N, (int)P, k);
         else
-            hipLaunchKernelGGL(topk_pool_slice_kernel<bf16_t>, g, dim3((unsigned)P), 0, STREAM, (const bf16_t*)tok, (const long*)mask, cv, ci, (int)N, (int)P, k);
+            with_h16(g_ss_half, [&](auto tag) {
+                typedef typename decltype(tag)::type H;
+                hipLaunchKernelGGL(topk_pool_slice_kernel<H>, g, dim3((unsigned)P), 0, STREAM, (const H*)tok, (const long*)mask, cv, ci, (int)N, (int)P, k);
+            });
         hipLaunchKernelGGL(topk_pool_merge_kernel<false>, dim3((unsigned)B, POOL_GROUPS), dim3((unsigned)P), 0, STREAM, cv, ci, gv, gi, emb, idx, norm,
                            POOL_SLICES, POOL_SLICES / POOL_GROUPS, (int)P, k, eps, normalize);
         hipLaunchKernelGGL(topk_pool_merge_kernel<true>, dim3((unsigned)B, 1), dim3((unsigned)P), 0, STREAM, gv, gi, gv, gi, emb, idx, norm,
@@ -933,27 +1097,31 @@ extern "C" int simseg_topk_pool_l2norm_fwd(const void* tok, int dtype, const int
     if (dtype == 0)
         hipLaunchKernelGGL(topk_pool_fwd_kernel<float>, dim3((unsigned)B), dim3((unsigned)P), 0, STREAM, (const float*)tok, (const long*)mask, emb, idx, norm, (int)N, (int)P, k, eps, normalize);
     else
-        hipLaunchKernelGGL(topk_pool_fwd_kernel<bf16_t>, dim3((unsigned)B), dim3((unsigned)P), 0, STREAM, (const bf16_t*)tok, (const long*)mask, emb, idx, norm, (int)N, (int)P, k, eps, normalize);
+        with_h16(g_ss_half, [&](auto tag) {
+            typedef typename decltype(tag)::type H;
+            hipLaunchKernelGGL(topk_pool_fwd_kernel<H>, dim3((unsigned)B), dim3((unsigned)P), 0, STREAM, (const H*)tok, (const long*)mask, emb, idx, norm, (int)N, (int)P, k, eps, normalize);
+        });
     SS_LAUNCH_CHECK("topk_pool_fwd");
     return 0;
 }
 
 extern "C" int simseg_topk_pool_l2norm_bwd(const float* demb, const float* emb, const float* norm, const int32_t* idx, void* dtok,
                                            int dtype, int64_t B, int64_t N, int64_t P, int k, float eps, int normalize, void* stream) {
-    SS_HALF_FWD(simseg_topk_pool_l2norm_bwd, demb, emb, norm, idx, dtok, dtype, B, N, P, k, eps, normalize, stream);
     SS_CHECK(demb && emb && norm && idx && dtok, "topk_pool_bwd: null pointer");
     SS_CHECK(P % 64 == 0 && P <= 1024 && k >= 1 && k <= POOL_MAXK, "topk_pool_bwd: bad P/k");
     if (B <= 0) return 0;
     if (dtype == 0)
         hipLaunchKernelGGL(topk_pool_bwd_kernel<float>, dim3((unsigned)B), dim3((unsigned)P), 0, STREAM, demb, emb, norm, idx, (float*)dtok, (int)N, (int)P, k, eps, normalize);
     else
-        hipLaunchKernelGGL(topk_pool_bwd_kernel<bf16_t>, dim3((unsigned)B), dim3((unsigned)P), 0, STREAM, demb, emb, norm, idx, (bf16_t*)dtok, (int)N, (int)P, k, eps, normalize);
+        with_h16(g_ss_half, [&](auto tag) {
+            typedef typename decltype(tag)::type H;
+            hipLaunchKernelGGL(topk_pool_bwd_kernel<H>, dim3((unsigned)B), dim3((unsigned)P), 0, STREAM, demb, emb, norm, idx, (H*)dtok, (int)N, (int)P, k, eps, normalize);
+        });
     SS_LAUNCH_CHECK("topk_pool_bwd");
     return 0;
 }
 
 extern "C" int simseg_row_rnorm(const void* x, int dtype, float* rnorm, int64_t rows, int64_t D, float eps, void* stream) {
-    SS_HALF_FWD(simseg_row_rnorm, x, dtype, rnorm, rows, D, eps, stream);
     SS_CHECK(x && rnorm, "row_rnorm: null pointer");
     SS_CHECK(D % 4 == 0, "row_rnorm: D must be a multiple of 4");
     if (rows <= 0) return 0;
@@ -961,27 +1129,31 @@ extern "C" int simseg_row_rnorm(const void* x, int dtype, float* rnorm, int64_t 
     if (dtype == 0)
         hipLaunchKernelGGL(row_rnorm_kernel<float>, grid, dim3(256), 0, STREAM, (const float*)x, rnorm, (long)rows, (int)D, eps);
     else
-        hipLaunchKernelGGL(row_rnorm_kernel<bf16_t>, grid, dim3(256), 0, STREAM, (const bf16_t*)x, rnorm, (long)rows, (int)D, eps);
+        with_h16(g_ss_half, [&](auto tag) {
+            typedef typename decltype(tag)::type H;
+            hipLaunchKernelGGL(row_rnorm_kernel<H>, grid, dim3(256), 0, STREAM, (const H*)x, rnorm, (long)rows, (int)D, eps);
+        });
     SS_LAUNCH_CHECK("row_rnorm");
     return 0;
 }
 
 extern "C" int simseg_cast(const void* in, void* out, int64_t n, int to_bf16, void* stream) {
-    SS_HALF_FWD(simseg_cast, in, out, n, to_bf16, stream);
     SS_CHECK(in && out, "cast: null pointer");
     SS_CHECK(n % 4 == 0, "cast: element count must be a multiple of 4");
     if (n <= 0) return 0;
     const int grid = grid_for(n / 4, 256, 8192);
-    if (to_bf16)
-        hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(grid), dim3(256), 0, STREAM, (const float*)in, (bf16_t*)out, (long)(n / 4));
-    else
-        hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(grid), dim3(256), 0, STREAM, (const bf16_t*)in, (float*)out, (long)(n / 4));
+    with_h16(g_ss_half, [&](auto tag) {
+        typedef typename decltype(tag)::type H;
+        if (to_bf16)
+            hipLaunchKernelGGL(cast_f32_bf16_kernel<H>, dim3(grid), dim3(256), 0, STREAM, (const float*)in, (H*)out, (long)(n / 4));
+        else
+            hipLaunchKernelGGL(cast_bf16_f32_kernel<H>, dim3(grid), dim3(256), 0, STREAM, (const H*)in, (float*)out, (long)(n / 4));
+    });
     SS_LAUNCH_CHECK("cast");
     return 0;
 }
 
 extern "C" int simseg_dropout_apply(void* g, int dtype, int64_t n, uint64_t seed, float p, void* stream) {
-    SS_HALF_FWD(simseg_dropout_apply, g, dtype, n, seed, p, stream);
     SS_CHECK(g, "dropout_apply: null pointer");
     SS_CHECK(p >= 0.f && p < 1.f, "dropout_apply: p out of range");
     if (n <= 0 || p == 0.f) return 0;
@@ -991,7 +1163,90 @@ extern "C" int simseg_dropout_apply(void* g, int dtype, int64_t n, uint64_t seed
     if (dtype == 0)
         hipLaunchKernelGGL(dropout_apply_kernel<float>, dim3(grid), dim3(256), 0, STREAM, (float*)g, (long)n, (unsigned long long)seed, thresh, scale);
     else
-        hipLaunchKernelGGL(dropout_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, STREAM, (bf16_t*)g, (long)n, (unsigned long long)seed, thresh, scale);
+        with_h16(g_ss_half, [&](auto tag) {
+            typedef typename decltype(tag)::type H;
+            hipLaunchKernelGGL(dropout_apply_kernel<H>, dim3(grid), dim3(256), 0, STREAM, (H*)g, (long)n, (unsigned long long)seed, thresh, scale);
+        });
     SS_LAUNCH_CHECK("dropout_apply");
+    return 0;
+}
+
+extern "C" int simseg_vit_cls_rows(const float* cls, const float* pos, float* x, int64_t B, int64_t T, int64_t D, void* stream) {
+    SS_CHECK(cls && pos && x, "vit_cls_rows: null pointer");
+    if (B <= 0) return 0;
+    hipLaunchKernelGGL(vit_cls_rows_kernel, dim3((unsigned)((B * D + 255) / 256)), dim3(256), 0, STREAM, cls, pos, x, (int)B, (int)T, (int)D);
+    SS_LAUNCH_CHECK("vit_cls_rows");
+    return 0;
+}
+
+extern "C" int simseg_vit_cls_grad(const float* dx, float* dcls, int64_t B, int64_t T, int64_t D, void* stream) {
+    SS_CHECK(dx && dcls, "vit_cls_grad: null pointer");
+    if (B <= 0 || D <= 0) return 0;
+    hipLaunchKernelGGL(vit_cls_grad_kernel, dim3((unsigned)((D + 255) / 256), (unsigned)((B + 15) / 16)), dim3(256), 0, STREAM, dx, dcls, (int)B, (int)T, (int)D);
+    SS_LAUNCH_CHECK("vit_cls_grad");
+    return 0;
+}
+
+extern "C" int simseg_bert_embed_fwd(const int64_t* ids, const float* word, const float* pos, const float* type0, float* out,
+                                     int64_t B, int64_t L, int64_t D, int64_t vocab, void* stream) {
+    SS_CHECK(ids && word && pos && type0 && out, "bert_embed_fwd: null pointer");
+    SS_CHECK(D % 4 == 0, "bert_embed_fwd: D must be a multiple of 4");
+    const long rows = B * L;
+    if (rows <= 0) return 0;
+    hipLaunchKernelGGL(bert_embed_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, STREAM, (const long*)ids, word, pos, type0, out,
+                       (int)rows, (int)L, (int)D, (int)vocab);
+    SS_LAUNCH_CHECK("bert_embed_fwd");
+    return 0;
+}
+
+extern "C" int simseg_bert_embed_bwd(const int64_t* ids, const int64_t* mask, const float* dsum, float* dword, int64_t B,
+                                     int64_t L, int64_t D, int64_t vocab, void* stream) {
+    SS_CHECK(ids && dsum && dword, "bert_embed_bwd: null pointer");
+    const long rows = B * L;
+    if (rows <= 0) return 0;
+    hipLaunchKernelGGL(bert_embed_bwd_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, STREAM, (const long*)ids, (const long*)mask, dsum,
+                       dword, (int)rows, (int)D, (int)vocab);
+    SS_LAUNCH_CHECK("bert_embed_bwd");
+    return 0;
+}
+
+extern "C" int simseg_segment_mean_l2norm(const float* x, float* out, int64_t S, int64_t P, int64_t D, void* stream) {
+    SS_CHECK(x && out, "segment_mean_l2norm: null pointer");
+    SS_CHECK(D % 64 == 0 && D <= 1024 && P >= 1, "segment_mean_l2norm: D must be a multiple of 64 and <= 1024");
+    if (S <= 0) return 0;
+    hipLaunchKernelGGL(segment_mean_l2norm_kernel, dim3((unsigned)S), dim3((unsigned)D), 0, STREAM, x, out, (int)P, (int)D);
+    SS_LAUNCH_CHECK("segment_mean_l2norm");
+    return 0;
+}
+
+extern "C" int simseg_split_bf16x3(const float* in, void* out, int64_t rows, int64_t K, int64_t ld_in, int b_pattern, void* stream) {
+    SS_CHECK(in && out, "split_bf16x3: null pointer");
+    SS_CHECK(K > 0 && K % 8 == 0 && ld_in >= K && ld_in % 4 == 0, "split_bf16x3: K must be a multiple of 8 (got %lld)", (long long)K);
+    SS_CHECK(((uintptr_t)in % 16) == 0 && ((uintptr_t)out % 16) == 0, "split_bf16x3: operands must be 16-byte aligned");
+    if (rows <= 0) return 0;
+    const int grid = grid_for(rows * (K / 8), 256, 16384);
+    hipLaunchKernelGGL(split_bf16x3_kernel, dim3(grid), dim3(256), 0, STREAM, in, (__bf16*)out, (long)rows, (int)K, (long)ld_in, b_pattern);
+    SS_LAUNCH_CHECK("split_bf16x3");
+    return 0;
+}
+
+extern "C" int simseg_transpose_f32(const float* in, float* out, int64_t R, int64_t C, void* stream) {
+    SS_CHECK(in && out, "transpose: null pointer");
+    if (R <= 0 || C <= 0) return 0;
+    dim3 grid((unsigned)((C + 31) / 32), (unsigned)((R + 31) / 32));
+    hipLaunchKernelGGL(transpose_f32_kernel, grid, dim3(256), 0, STREAM, in, out, (int)R, (int)C);
+    SS_LAUNCH_CHECK("transpose");
+    return 0;
+}
+
+extern "C" int simseg_gather_rows(const void* src, const int32_t* idx, void* dst, int64_t n, int64_t row_bytes, void* stream) {
+    SS_CHECK(src && idx && dst, "gather_rows: null pointer");
+    SS_CHECK(row_bytes > 0 && row_bytes % 16 == 0 && ((uintptr_t)src % 16) == 0 && ((uintptr_t)dst % 16) == 0,
+             "gather_rows: rows must be multiples of 16 bytes and 16-byte aligned");
+    if (n <= 0) return 0;
+    const long total = n * (row_bytes / 16);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)grid_for(total, 256, 16384)), dim3(256), 0, STREAM, (const u32x4*)src, idx, (u32x4*)dst,
+                       (long)n, (int)(row_bytes / 16));
+    SS_LAUNCH_CHECK("gather_rows");
     return 0;
 }

@@ -205,6 +205,15 @@ def test_c_abi_declares_and_exports_the_new_entries():
         assert f'extern "C" int {name}(' in src, f"{name} is not defined in loss.hip"
         assert hasattr(so, name), f"{name} is not exported"
         assert not hasattr(so, name + "_h16"), f"{name}_h16 is exported"
+    # the same for the row kernels these losses sit next to in a step: one object, the 16-bit type chosen per call
+    assert "rowops.hip" not in build.TWICE
+    src = open(os.path.join(REPO, "simseg_amd/csrc/rowops.hip")).read()
+    for name in ("simseg_layernorm_fwd", "simseg_layernorm_bwd", "simseg_layernorm_bwd_workspace_bytes", "simseg_colsum_accum",
+                 "simseg_vit_im2col", "simseg_topk_pool_workspace_bytes", "simseg_topk_pool_l2norm_fwd", "simseg_topk_pool_l2norm_bwd",
+                 "simseg_row_rnorm", "simseg_cast", "simseg_dropout_apply"):
+        assert src.count(f" {name}(") == 1, f"{name} is not defined exactly once in rowops.hip"
+        assert hasattr(so, name), f"{name} is not exported"
+        assert not hasattr(so, name + "_h16"), f"{name}_h16 is exported"
 
 
 @pytest.mark.parametrize("family", R.FAMILIES)

@@ -119,6 +119,142 @@ def test_layernorm_and_rowops_fp16():
     assert float((s - dy.to(F16).float().sum(0)).abs().max()) < 1e-2
 
 
+def _halves(r, shape, lo=-4, hi=4):
+    """Multiples of 1/2 in [lo, hi]: exact in bf16 and in fp16, and so is every fp32 sum of a few thousand of them, in any order."""
+    return torch.from_numpy(r.integers(2 * lo, 2 * hi + 1, shape) * 0.5).float().cuda()
+
+
+def _ln_bwd_operands(r, rows, D, zero_rows=()):
+    """LayerNorm-backward operands on which the kernel's fp32 arithmetic is EXACT, so that neither the order of the column atomics nor a
+    contraction to FMA can move a bit: gains +-1 / +-2, xhat and dy multiples of 1/2, rstd a power of two, and the two row sums the kernel
+    divides by D settled at sum(dy gamma) = D / 4 (through dy[:, :16], where gamma = 1 and xhat = 0) and sum(dy gamma xhat) = D / 2
+    (through xhat[:, 16:48], where dy gamma = 1/2).  x and the saved output y are consistent with xhat: the kernel may take it from
+    either.  One 4-channel chunk has |beta| > 4 |gamma|: the 16-bit step form then reads xhat from x there (its `needx` path).
+    zero_rows: rows without a gradient (dy = dres = 0 -> dx = 0)."""
+    gamma = r.choice([-2.0, -1.0, 1.0, 2.0], D)
+    gamma[:48] = 1.0
+    beta = r.integers(-2, 3, D).astype(np.float64)
+    gamma[64:68], beta[64:68] = 1.0, 8.0
+    xh = r.integers(-4, 5, (rows, D)) * 0.5
+    dy = r.integers(-4, 5, (rows, D)) * 0.5
+    xh[:, :16], dy[:, 16:48] = 0.0, 0.5
+    n = np.rint((D / 4 - (dy * gamma).sum(1)) / 0.5).astype(np.int64)[:, None]
+    dy[:, :16] += 0.5 * (n // 16 + (np.arange(16) < n % 16))
+    m = np.rint((D / 2 - (dy * gamma * xh).sum(1)) / 0.25).astype(np.int64)[:, None]
+    xh[:, 16:48] += 0.5 * (m // 32 + (np.arange(32) < m % 32))
+    dres = r.integers(-4, 5, (rows, D)) * 0.5
+    rs = r.choice([0.25, 0.5, 1.0], rows)[:, None]
+    mu = r.integers(-3, 4, rows).astype(np.float64)[:, None]
+    s1, s2 = 0.25, 0.5
+    for z in zero_rows:
+        dy[z], dres[z] = 0.0, 0.0
+    live = np.ones((rows, 1))
+    live[list(zero_rows)] = 0.0
+    assert np.array_equal((dy * gamma).sum(1, keepdims=True), live * D / 4) and np.array_equal((dy * gamma * xh).sum(1, keepdims=True), live * D / 2)
+    dx = rs * (dy * gamma - live * s1 - xh * live * s2) + dres
+    assert max(np.abs(dy).max(), np.abs(xh * gamma + beta).max(), np.abs(dres).max()) <= 64         # <= 8 significant bits: exact in bf16
+    f = lambda a: torch.from_numpy(np.ascontiguousarray(a)).float().cuda()      # noqa: E731
+    return dict(gamma=f(gamma), beta=f(beta), x=f(xh / rs + mu), y=f(xh * gamma + beta), dy=f(dy), dres=f(dres), mean=f(mu[:, 0]), rstd=f(rs[:, 0]),
+                dx=f(dx), dgamma=f((dy * xh).sum(0)), dbeta=f(dy.sum(0)), dxsum=f(dx.sum(0)))
+
+
+_ROWOPS_RUNS = {}
+
+
+def _rowops_run(hd):
+    """Every entry point of csrc/rowops.hip that picks the 16-bit type per call, on one fixed set of exactly representable values with
+    its 16-bit tensors of type `hd` - or, hd = float32, through dtype code 0.  -> (f32, h16, twin): the fp32 / integer outputs by name, the
+    16-bit outputs by name, and for some of those the fp32 tensor the same launch (or the same entry's fp32 launch) wrote."""
+    if hd in _ROWOPS_RUNS:
+        return _ROWOPS_RUNS[hd]
+    from simseg_amd import ops
+    r = np.random.default_rng(5)
+    is16 = hd != torch.float32
+    f32, h16, twin = {}, {}, {}
+    put = (lambda k, t: h16.__setitem__(k, t)) if is16 else (lambda k, t: f32.__setitem__(k, t))      # an output of the type under test
+    for D, rows in ((384, 13), (768, 5)):                    # two rows per wave with a ragged tail; one row per wave
+        x, w, b = _halves(r, (rows, D)), _halves(r, (D,)), _halves(r, (D,))
+        y, _, f32[f"ln_fwd{D}.mean"], f32[f"ln_fwd{D}.rstd"] = ops.layernorm_fwd(x, w, b, 1e-6, out_dtype=hd, save_stats=True)
+        put(f"ln_fwd{D}.y", y)
+        o = _ln_bwd_operands(r, rows, D)
+        if is16:
+            k = f"ln_fwd{D}.copy"                            # fp32 output and its 16-bit copy from one launch
+            twin[k], h16[k], f32[k + ".mean"], f32[k + ".rstd"] = ops.layernorm_fwd(x, w, b, 1e-6, want_bf16_copy=hd, save_stats=True)
+            k = f"ln_bwd{D}"                                 # the generic backward: dx in both types from one launch
+            f32[k + ".dgamma"], f32[k + ".dbeta"], f32[k + ".dxsum"] = (torch.zeros(D, device="cuda") for _ in range(3))
+            twin[k], h16[k] = ops.layernorm_bwd(o["x"], o["mean"], o["rstd"], o["gamma"], f32[k + ".dgamma"], f32[k + ".dbeta"], dy16=o["dy"].to(hd),
+                                                dres=o["dres"], dxsum=f32[k + ".dxsum"])
+            f32[k + ".dx32"] = twin[k]
+            for name in ("dgamma", "dbeta", "dxsum"):
+                assert torch.equal(f32[f"{k}.{name}"], o[name]), (k, name)
+            assert torch.equal(twin[k], o["dx"]), k
+    for D, rows, p in ((768, 13, 0.0), (768, 13, 0.1), (320, 13, 0.0), (320, 13, 0.1)):       # FULL and not; 13 rows: four blocks
+        # (with dropout the kept values carry the factor 1 / 0.9 and their column sums are no longer exact: rows 4 .. 11 - the second and third
+        #  block - then have no gradient, which leaves two non-zero partial sums per column, and a + b does not depend on the order)
+        o = _ln_bwd_operands(r, rows, D, zero_rows=range(4, 12) if p else ())
+        if not is16:
+            continue
+        k = f"ln_bwd16.{D}.{p}"
+        f32[k + ".dgamma"], f32[k + ".dbeta"], f32[k + ".dxsum"] = (torch.zeros(D, device="cuda") for _ in range(3))
+        a16 = dict(dy16=o["dy"].to(hd), dres16=o["dres"].to(hd), y16=o["y"].to(hd), beta=o["beta"])
+        _, h16[k] = ops.layernorm_bwd(o["x"], o["mean"], o["rstd"], o["gamma"], f32[k + ".dgamma"], f32[k + ".dbeta"], want_f32=False, want_bf16=hd,
+                                      dxsum=f32[k + ".dxsum"], drop_seed=9, drop_p=p, **a16)
+        # its fp32-output run: the same entry asked for dx in fp32 too (written before the mask), times the mask the dropout entry writes in fp32
+        dg, db = torch.zeros(D, device="cuda"), torch.zeros(D, device="cuda")
+        dx32, _ = ops.layernorm_bwd(o["x"], o["mean"], o["rstd"], o["gamma"], dg, db, want_f32=True, want_bf16=hd, **a16)
+        keep = torch.ones(rows * D, device="cuda")
+        ops.dropout_apply_(keep, 9, p)
+        twin[k] = torch.where(keep.view(rows, D) != 0, dx32 * keep.view(rows, D), torch.zeros_like(dx32))
+        assert torch.equal(dx32, o["dx"]) and torch.equal(f32[k + ".dgamma"], o["dgamma"]) and torch.equal(f32[k + ".dbeta"], o["dbeta"]), k
+        if not p:
+            assert torch.equal(f32[k + ".dxsum"], o["dxsum"]), k
+    x = _halves(r, (300, 64))                                # few rows: the grid of 8-row blocks
+    f32["colsum"] = ops.colsum_accum(x.to(hd), torch.zeros(64, device="cuda"))
+    assert torch.equal(f32["colsum"], x.sum(0))
+    put("im2col", ops.vit_im2col(_halves(r, (2, 3, 32, 48)), hd))
+    for k, (B, N) in (("pool", (3, 37)), ("pool_sliced", (2, 256))):
+        tok, demb = _halves(r, (B, N, 64)), _halves(r, (B, 64))
+        mask = torch.from_numpy(r.integers(0, 4, (B, N)) > 0).long().cuda() if k == "pool" else None
+        f32[k + ".emb"], f32[k + ".idx"], f32[k + ".norm"] = ops.topk_pool_l2norm_fwd(tok.to(hd), 5, mask)
+        put(k + ".dtok", ops.topk_pool_l2norm_bwd(demb, f32[k + ".emb"], f32[k + ".norm"], f32[k + ".idx"], N, hd))
+    f32["rnorm"] = ops.row_rnorm(_halves(r, (5, 64)).to(hd))
+    g = _halves(r, (1000,)).to(hd)
+    ops.dropout_apply_(g, 11, 0.5)
+    put("dropout", g)
+    x = torch.from_numpy(r.standard_normal(1028)).float().cuda()
+    if is16:
+        twin["cast"], h16["cast"] = x, ops.cast(x, hd)       # (values that DO round: the cast is the one entry whose job that is)
+        f32["cast.back"] = ops.cast(_halves(r, (1028,)).to(hd), torch.float32)
+    torch.cuda.synchronize()
+    _ROWOPS_RUNS[hd] = (f32, h16, twin)
+    return _ROWOPS_RUNS[hd]
+
+
+def _bits(t):
+    return t.view({2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+@pytest.mark.parametrize("hd", [BF16, F16], ids=["bf16", "fp16"])
+def test_rowops_pick_the_16bit_type_per_call(hd):
+    """csrc/rowops.hip is compiled once and chooses __bf16 or _Float16 at eleven launch sites.  Both types run every site on the same
+    values, all exactly representable in both (see _halves, _ln_bwd_operands):
+      1. what a launch writes in fp32 or int32 - mean, rstd, dx32, dgamma, dbeta, dxsum, column sums, emb, norm, idx, rnorm, the cast back -
+         is bit-equal between the bf16 run and the fp16 run (a launch that reads one type as the other is off by orders of magnitude);
+      2. each 16-bit output equals the same entry's fp32 output on the same values - dtype code 0, or the fp32 tensor the launch writes next
+         to it - rounded once to that type, bit for bit.
+    No tolerance anywhere: profiles/rowops_once.txt."""
+    f32, h16, twin = _rowops_run(hd)
+    of32, oh16, _ = _rowops_run(F16 if hd == BF16 else BF16)
+    plain, _, _ = _rowops_run(torch.float32)
+    assert set(f32) == set(of32) and set(h16) == set(oh16) and len(h16) == 15
+    for k, v in f32.items():
+        assert v.dtype in (torch.float32, torch.int32) and torch.equal(_bits(v), _bits(of32[k])), k
+    for k, v in h16.items():
+        ref = twin[k] if k in twin else plain[k]
+        assert v.dtype == hd and ref.dtype == torch.float32 and torch.equal(_bits(v), _bits(ref.to(hd))), k
+    assert not torch.equal(_bits(h16["cast"]), _bits(oh16["cast"]))          # (the two runs did differ in type)
+
+
 def test_model_fp16_gradients_vs_exact_fp32(golden, monkeypatch):
     """The drop-in CLIPModel under torch.autocast(dtype=float16): loss and every parameter gradient against the exact-fp32 run of the
     same step (the reference's own gradients are pinned against that mode), next to the bf16 autocast run of the same step.  Bars: loss

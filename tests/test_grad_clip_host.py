@@ -10,6 +10,10 @@ import pytest
 from conftest import REPO
 
 NEW = ["simseg_grads_norm_partials", "simseg_grads_norm_finish", "simseg_adamw_multi_step_clip", "simseg_adamw_multi_step_amp_clip"]
+# the row kernels' entry points (csrc/rowops.hip), which had an fp16 twin each while that source was compiled twice
+ROWOPS = ["simseg_layernorm_fwd", "simseg_layernorm_bwd", "simseg_layernorm_bwd_workspace_bytes", "simseg_colsum_accum", "simseg_vit_im2col",
+          "simseg_topk_pool_workspace_bytes", "simseg_topk_pool_l2norm_fwd", "simseg_topk_pool_l2norm_bwd", "simseg_row_rnorm", "simseg_cast",
+          "simseg_dropout_apply"]
 
 
 def test_header_declares_the_entry_points_and_no_second_flavour_renames_them():
@@ -26,19 +30,20 @@ def test_header_declares_the_entry_points_and_no_second_flavour_renames_them():
     assert [n for _, n in decl["simseg_grads_norm_finish"][1]] == ["partials", "n_partials", "norm_type", "max_norm", "loss_scale", "out2", "stream"]
     # one entry point serves both 16-bit types (the kernel takes the type as a template argument): no renamed second flavour
     from simseg_amd import build
-    assert "optim.hip" not in build.TWICE
-    src = open(os.path.join(REPO, "simseg_amd", "csrc", "optim.hip")).read()
+    assert "optim.hip" not in build.TWICE and "rowops.hip" not in build.TWICE
     names = open(os.path.join(REPO, "simseg_amd", "csrc", "half_names.h")).read()
-    for name in NEW:
-        assert re.search(rf'^extern "C" int {name}\(', src, flags=re.M), name
-        assert f"{name}_h16" not in names, name
+    for f, entries in (("optim.hip", NEW), ("rowops.hip", ROWOPS)):
+        src = open(os.path.join(REPO, "simseg_amd", "csrc", f)).read()
+        for name in entries:
+            assert len(re.findall(rf'^extern "C" (?:int|int64_t) {name}\(', src, flags=re.M)) == 1, name
+            assert f"{name}_h16" not in names, name
 
 
 def test_library_exports_one_entry_for_both_flavours():
     import ctypes
     from simseg_amd import lib
     so = ctypes.CDLL(lib.LIB_PATH)
-    for name in NEW:
+    for name in NEW + ROWOPS:
         assert hasattr(so, name) and not hasattr(so, name + "_h16"), name
 
 

@@ -104,7 +104,11 @@ def test_fp16_flavour_is_built_selectable_and_its_rename_header_is_current():
     assert open(os.path.join(build.CSRC, "half_names.h")).read() == text, "csrc/half_names.h is stale: python -m simseg_amd.build"
     so = ctypes.CDLL(lib.LIB_PATH)
     twins = [ln.split()[2] for ln in text.splitlines() if ln.startswith("#define ")]
-    assert len(twins) >= 30 and all(t.endswith("_h16") and hasattr(so, t) for t in twins)
+    import re
+    defined = [m.group(1) + "_h16" for f in build.TWICE
+               for m in re.finditer(r'^extern "C"\s+(?:const char\*|int64_t|int)\s+(simseg_\w+)\s*\([^)]*\)\s*\{', open(os.path.join(build.CSRC, f)).read(), flags=re.M)]
+    assert defined and len(defined) == len(set(defined))
+    assert sorted(twins) == sorted(defined) and all(hasattr(so, t) for t in twins)      # exactly the entry points the TWICE sources define
     l = lib.load()
     assert l.simseg_set_half_type(3) != 0 and b"simseg_set_half_type" in l.simseg_last_error()
     assert l.simseg_set_half_type(2) == 0
@@ -118,7 +122,7 @@ def test_fp16_flavour_is_built_selectable_and_its_rename_header_is_current():
 def test_no_unreachable_twin_in_the_twice_compiled_sources():
     """Every C-ABI entry point DEFINED in a twice-compiled source hands over to its _h16 twin (an SS_HALF_FWD( call in its body) - or is
     listed here with the reason why it does not.  An entry whose kernels do not depend on the 16-bit type belongs in a once-compiled source
-    (loss.hip, optim.hip, rowops_plain.hip, ...): there its twin would be a second copy nothing can call.  Source text only."""
+    (loss.hip, optim.hip, rowops.hip, ...): there its twin would be a second copy nothing can call.  Source text only."""
     import os
     import re
     from simseg_amd import build
@@ -130,8 +134,6 @@ def test_no_unreachable_twin_in_the_twice_compiled_sources():
         "simseg_debug_attention_timeline": "debug: times the bf16 forward only",
         "simseg_gemm_aux_blocked_ok": "host arithmetic on the shape, the same in both flavours; states the condition of gemm.hip's own dispatch",
         "simseg_attention_bwd_workspace_bytes": "host arithmetic on the shape, the same in both flavours",
-        "simseg_layernorm_bwd_workspace_bytes": "host arithmetic, next to the kernels' grid constant (LN_BWD_MAX_GRID) it uses",
-        "simseg_topk_pool_workspace_bytes": "host arithmetic, next to the kernels' constants (POOL_SLICES, POOL_GROUPS) it uses",
         "simseg_attention_fwd_x3": "exact mode: always the bf16 pieces of fp32 operands, next to the attention kernels' tile code it shares",
     }
     seen = set()
@@ -152,7 +154,7 @@ def test_no_unreachable_twin_in_the_twice_compiled_sources():
             else:
                 assert name in allowed, f"{f}: {name} never reaches its _h16 twin - move it to a once-compiled source (or say here why not)"
     assert set(allowed) <= seen, sorted(set(allowed) - seen)
-    assert len(seen) >= 30 and len(allowed) <= 10
+    assert len(seen) == 20 and len(allowed) <= 8
 
 
 def test_interpolate_pos_embed_and_miou_match_reference(golden):
@@ -502,20 +504,23 @@ def test_layernorm_backward_kernels_fit_four_waves_per_simd():
     if not os.path.exists(os.path.join(kr.LLVM, "llvm-readelf")):
         pytest.skip("no llvm-readelf in this image")
     seen = set()
-    for obj in ("rowops.o", "rowops_h16.o"):
-        path = os.path.join(REPO, "simseg_amd", "build", obj)
-        if not os.path.exists(path):
-            pytest.skip("simseg_amd/build/*.o not present (the library was built elsewhere)")
-        for name, vgpr, spill, scratch, lds in kr.kernel_resources(path):
-            m = re.search(r"ln_bwd(16)?_kernelILi(\d)E(?:Lb(\d)E)?", name)
-            if not m:
-                continue
-            fast, maxc, full = m.group(1) is not None, int(m.group(2)), m.group(3)
-            if maxc > 3 or (fast and maxc == 3 and full == "0"):       # (D = 768 is always the FULL instantiation; wider rows are not on the step's path)
-                continue
-            seen.add((obj, fast, maxc))
-            assert vgpr <= 128 and spill == 0 and scratch == 0, (obj, name, vgpr, spill, scratch)
-    assert {(o, f, c) for o in ("rowops.o", "rowops_h16.o") for f in (False, True) for c in (2, 3)} <= seen, seen
+    path = os.path.join(REPO, "simseg_amd", "build", "rowops.o")          # one object: the 16-bit type is the kernels' last template argument
+    if not os.path.exists(path):
+        pytest.skip("simseg_amd/build/*.o not present (the library was built elsewhere)")
+    types = {"DF16b": "bf16", "__bf16": "bf16", "DF16_": "fp16", "_Float16": "fp16"}
+    for name, vgpr, spill, scratch, lds in kr.kernel_resources(path):
+        # (a demangler that does not know the two types' encodings leaves the name mangled: read either spelling)
+        m = (re.search(r"ln_bwd(16)?_kernelILi(\d)E(?:Lb(\d)E)?(DF16b|DF16_)E", name)
+             or re.search(r"ln_bwd(16)?_kernel<(\d), (?:(true|false), )?(__bf16|_Float16)>", name))
+        if not m:
+            assert "ln_bwd_kernel" not in name and "ln_bwd16_kernel" not in name, name
+            continue
+        fast, maxc, full, h = m.group(1) is not None, int(m.group(2)), m.group(3) in ("1", "true"), types[m.group(4)]
+        if maxc > 3 or (fast and maxc == 3 and not full):       # (D = 768 is always the FULL instantiation; wider rows are not on the step's path)
+            continue
+        seen.add((h, fast, maxc))
+        assert vgpr <= 128 and spill == 0 and scratch == 0, (name, vgpr, spill, scratch)
+    assert {(h, f, c) for h in ("bf16", "fp16") for f in (False, True) for c in (2, 3)} <= seen, seen
 
 
 def test_long_sequence_attention_forward_register_budget():
