@@ -298,6 +298,27 @@ int simseg_mix_nce_rows(float* sims, const float* temperature, const float* igno
  * N1 < 2 with the mean (the reference's / (N1 - 1) would give NaN). */
 int simseg_triplet_rows(float* sims, float* row_loss, float* row_correct, float* out, int64_t N1, int64_t N2, int64_t target0, float margin,
                         int reduce, int mask_block, int blocks, int write_grad, void* stream);
+/* SigLIP rows: the pairwise sigmoid loss of Zhai et al. (ICCV'23; open_clip's SigLipLoss) over sims[N1,N2] (fp32, from simseg_gemm), one
+ * block per row, fp32 only.  Every (row, column) pair is a binary problem - no row-wise softmax.  For row i, with tgt = target0 + i,
+ * temp = clamp(T, 1e-3f, 0.5f) (temperature[0] = T; the fp32 constants of simseg_nce_rows), inv_t = fl32(1 / temp), b = bias[0]:
+ *   z_ij = fl32(fl32(s_ij * inv_t) + b)            a rounded product and a rounded sum, never contracted;
+ *   y_ij = +1 at j == tgt, otherwise -1;   x_ij = -y_ij * z_ij;   e_ij = exp(-|x_ij|)
+ *   l_ij = softplus(x_ij) = -log sigmoid(y_ij z_ij) = max(x_ij, 0) + log1p(e_ij)      (log1p: the small e_ij of the negatives keep
+ *          their low bits; e <= 1 and underflows to 0, so nothing overflows at |z| ~ 1000)
+ *   rowloss_i = sum_j l_ij;   loss = (1 / N1) * sum_i rowloss_i                      (SigLIP's normalisation by the LOCAL batch)
+ *   dz_ij = -y_ij * sigmoid(x_ij) / N1,  sigmoid(x) = x >= 0 ? 1 / (1 + e) : e / (1 + e)  from the same e
+ *   write_grad: the row is overwritten IN PLACE by dLoss/ds_ij = dz_ij * inv_t; write_grad = 0 leaves sims bit for bit and gives the
+ *   same out4[0:2] and row losses
+ *   row_tdot_i = sum_j dz_ij * s_ij;   row_bdot_i = sum_j dz_ij
+ *   top-1 hit: the FIRST index attaining the row maximum of s itself (z is increasing in s) against tgt - simseg_triplet_rows' rule.
+ * A second, one-block launch sums the rows in a fixed order (no atomics: the same input gives the same bits):
+ *   out4 = {loss, top-1 acc = hits / N1, dLoss/dT, dLoss/db},
+ *   dLoss/dT = -sum_i row_tdot_i / temp^2 when 1e-3f <= T <= 0.5f and exactly 0 outside the clamp (as simseg_nce_rows),
+ *   dLoss/db = sum_i row_bdot_i, always.
+ * row_loss / row_correct / row_tdot / row_bdot: N1 floats each.  Refused before any launch: N1 < 1, N2 < 1, target0 < 0,
+ * target0 + N1 > N2 and N2 >= 2^31 (the kernel's column and row indices are 32-bit). */
+int simseg_siglip_rows(float* sims, const float* temperature, const float* bias, float* row_loss, float* row_correct, float* row_tdot,
+                       float* row_bdot, float* out4, int64_t N1, int64_t N2, int64_t target0, int write_grad, void* stream);
 /* n <= 6 fp32 transposes in ONE launch (out[k][c, r] = in[k][r, c], in[k] [rows[k], cols[k]] contiguous); jobs with scale[k] != 0 are
  * multiplied by alpha * scalar[0] - in the transposed copy and IN PLACE; y0[0] = scalar[0] * x0[0] when y0 is given.  The loss head's
  * backward (mml_loss.py:73 differentiated) needs dS, dS^T and the transposed embeddings as row . row GEMM operands, all times the upstream

@@ -1,18 +1,18 @@
 """InfoNCE of the SimSeg contrastive objective (mirror of simseg/models/criteria/losses/mml_loss.py:12-103) on the
 fused HIP loss path: fp32 MFMA similarity block -> in-place cross-entropy rows -> gradient GEMMs, with the embedding
 exchange as an RCCL all-gather forward / reduce-scatter backward.  MixUpNCE (:105-197) and Triplet (:256-347) score the same
-similarity block with their own row kernels."""
+similarity block with their own row kernels, and so does SigLip - the pairwise sigmoid loss of SigLIP, which the reference does not have."""
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
 from simseg.utils import ENV, GatherLayer, logger
 from simseg.utils.dist import generate_local_groups
-from simseg_amd.heads import ClipLossFn, MixNCEFn, NCEFn, TripletFn, TripletLocalFn, all_gather_rows
+from simseg_amd.heads import ClipLossFn, MixNCEFn, NCEFn, SigLipFn, TripletFn, TripletLocalFn, all_gather_rows
 
 from .builder import LOSS
 
-__all__ = ["NCE", "MixUpNCE", "Triplet", "LabelSmoothingCrossEntropy", "SoftTargetCrossEntropy"]
+__all__ = ["NCE", "MixUpNCE", "Triplet", "SigLip", "LabelSmoothingCrossEntropy", "SoftTargetCrossEntropy"]
 
 
 @LOSS.register_obj
@@ -162,6 +162,68 @@ class Triplet(nn.Module):
         if feat2_global.shape[0] % feat1.shape[0] != 0:
             raise AssertionError(f"global size: {feat2_global.shape[0]}, batch size: {feat1.shape[0]}")
         return TripletFn.apply(feat1, feat2_global, self.rank, self.margin, reduce)
+
+
+@LOSS.register_obj
+class SigLip(nn.Module):
+    """The pairwise sigmoid loss of SigLIP (Zhai et al., "Sigmoid Loss for Language Image Pre-Training", ICCV'23; open_clip's SigLipLoss)
+    on the fused row path (simseg_amd.heads.SigLipFn; formulas in include/simseg_hip.h, simseg_siglip_rows): every (row, column) pair of
+    the [N1, N2] similarity block is a binary problem, loss = (1 / N1) sum_ij -log sigmoid(y_ij (s_ij / T + b)) with y = +1 on the row's
+    own column and -1 elsewhere.  No row-wise softmax, and a learnable bias b beside the temperature.  Not in the reference: selected by
+    loss.name=SigLip and driven by keys that exist - loss.temperature.{name, value}, loss.global_reduce, loss.nce_loss.gather_backward,
+    loss.group_size, loss.smoothing (which must be 0).
+
+    T is the quantity the other losses here call the temperature, clamped to [1e-3, 0.5] like NCE's - the logit scale is t = 1 / T, and
+    what is learned is T itself, not log t as in the paper.  The bias has no config key: INIT_BIAS = -10.0, or the constructor's
+    init_bias.  With loss.temperature.value=0.1 that is the paper's initialisation, t = 10 and b = -10.  Under
+    loss.temperature.name=parameter both temperature and bias are nn.Parameters (trained, and in the state dict); under `constant` the
+    temperature is a non-persistent buffer as in NCE and the bias a PERSISTENT one: it is not derivable from the config, so a checkpoint
+    carries it.  As parameters both fall under the optimizer's base weight_decay like any other (trainer.param_groups): decay pulls the
+    bias from -10 towards 0 and shrinks T.  open_clip exempts its logit scale and bias; to do the same add an optim.param_group_rules
+    entry such as {regex: "^loss\\.(bias|temperature)$", param: {weight_decay: 0.0}}.
+
+    The group and the exchange are NCE's (_loss_group, NCE._gather).  With a process group and gather_backward=False the gathered
+    embeddings are detached: each rank's loss then differentiates only through its own rows' role as feat1, and the gradient a rank's
+    embeddings receive as OTHER ranks' negatives - for this loss every off-diagonal pair is a term of its own, so that is most of the
+    negatives' signal - is dropped; gather_backward=True (or no process group) keeps it.  The loss is normalised by the local batch N1
+    on every rank, as in the paper.
+
+    forward(feat1, feat2, label=None, ignore_mask=None) -> (loss, top-1 acc).  There is no `both` method: CLIPModel.forward_loss calls
+    the module once per direction and returns {"siglip_loss": 0.5 * (i2t + t2i)}.  loss.global_reduce=False, a non-zero loss.smoothing and
+    an ignore mask are refused."""
+
+    INIT_BIAS = -10.0
+
+    def __init__(self, cfg, rank, init_bias=None):
+        super().__init__()
+        self.cfg = cfg
+        self.global_reduce = cfg.loss.global_reduce
+        if not self.global_reduce:
+            raise NotImplementedError("SigLip: loss.global_reduce=False (the local form) is not built; the loss scores feat1 against the gathered feat2")
+        if float(cfg.loss.smoothing) != 0.0:
+            raise ValueError(f"SigLip: loss.smoothing={cfg.loss.smoothing} - the pairwise sigmoid loss has no label smoothing, set it to 0")
+        self.gather_backward = cfg.loss.nce_loss.gather_backward
+        self.group, self.rank = _loss_group(cfg, "SigLip")
+        t = torch.ones([]) * cfg.loss.temperature.value
+        b = torch.ones([]) * float(self.INIT_BIAS if init_bias is None else init_bias)
+        if cfg.loss.temperature.name == "parameter":
+            self.temperature = nn.Parameter(t)
+            self.bias = nn.Parameter(b)
+        elif cfg.loss.temperature.name == "constant":
+            self.register_buffer("temperature", t, persistent=False)
+            self.register_buffer("bias", b, persistent=True)
+        else:
+            raise NotImplementedError(cfg.loss.temperature.name)
+
+    _gather = NCE._gather
+
+    def forward(self, feat1, feat2, label=None, ignore_mask=None):
+        if ignore_mask is not None:
+            raise NotImplementedError("SigLip: an ignore_mask is not supported (every pair is a term of the loss; no row weights are built)")
+        feat2_global = self._gather(feat2)
+        if feat2_global.shape[0] % feat1.shape[0] != 0:
+            raise AssertionError(f"global size: {feat2_global.shape[0]}, batch size: {feat1.shape[0]}")
+        return SigLipFn.apply(feat1, feat2_global, self.temperature, self.bias, self.rank)
 
 
 def _reduce(rows, reduction):

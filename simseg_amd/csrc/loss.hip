@@ -1,4 +1,4 @@
-// Row kernels behind the similarity matrices: InfoNCE / MixUpNCE cross-entropy rows (K13), Triplet hinge rows, the loss head's transposes
+// Row kernels behind the similarity matrices: InfoNCE / MixUpNCE cross-entropy rows (K13), Triplet hinge rows, SigLIP pairwise-sigmoid rows, the loss head's transposes
 // and scales, retrieval first-match ranks (K16) and recall counts.  fp32 and integers only: compiled ONCE, no 16-bit flavour.
 #include "common.h"
 
@@ -251,6 +251,85 @@ __global__ __launch_bounds__(256) void triplet_finalize_kernel(const float* __re
     }
 }
 
+// Pairwise sigmoid rows of SigLIP (Zhai et al., ICCV'23).  One block per local row i of sims[N1,N2], tgt = target0 + i,
+// temp = clamp(T, 1e-3f, 0.5f) as nce_rows_kernel, inv_t = 1 / temp, b = bias[0]:
+//   z_j = fl32(fl32(s_j * inv_t) + b);  y_j = +1 at j == tgt, else -1;  x_j = -y_j z_j;  e_j = exp(-|x_j|)
+//   l_j = softplus(x_j) = max(x_j, 0) + log1p(e_j);  row loss = sum_j l_j;  loss = (1 / N1) sum_i row loss_i
+//   dz_j = -y_j sigmoid(x_j) / N1, sigmoid(x) = x >= 0 ? 1 / (1 + e) : e / (1 + e) from the same e;  write_grad: row_j <- dz_j * inv_t
+//   row_tdot = sum_j dz_j s_j, row_bdot = sum_j dz_j;  top-1 hit on s itself (z is increasing in s), first index attaining the maximum.
+// No term depends on a row-wide quantity - there is no softmax normalisation -, so ONE pass reads s_j, scores it and overwrites it: z is
+// formed once per element, as a rounded product and a rounded sum (no contraction: an fma here would make z another number than the
+// one the header states).  log1p, not log(1 + e): at the default init (t = 10, b = -10) the negatives' e_j are 1e-5 .. 1e-3 and
+// hundreds of them make up the row's sum beside the target's term; 1 + e_j would drop their low bits.  exp(-|x|) <= 1 and underflows to 0
+// at |z| ~ 1000, where l = max(x, 0) and sigmoid = 0 or 1 exactly: nothing overflows.  The sums are computed whether or not the gradient is
+// written: write_grad = 0 gives the same loss and accuracy bits and leaves the row alone.
+__global__ __launch_bounds__(256) void siglip_rows_kernel(float* __restrict__ sims, const float* __restrict__ temperature,
+                                                          const float* __restrict__ bias, float* __restrict__ row_loss,
+                                                          float* __restrict__ row_correct, float* __restrict__ row_tdot,
+                                                          float* __restrict__ row_bdot, int N1, int N2, int target0, int write_grad) {
+#pragma clang fp contract(off)
+    __shared__ float sh[8];
+    __shared__ int shi[8];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    float* row = sims + (long)i * N2;
+    const float temp = fminf(fmaxf(temperature[0], 0.001f), 0.5f);
+    const float inv_t = 1.0f / temp;
+    const float b = bias[0];
+    const float n1 = (float)N1;
+    const int tgt = target0 + i;
+    float mx = -INFINITY, loss = 0.f, tdot = 0.f, bdot = 0.f;
+    int arg = 0x7fffffff;
+    for (int j = tid; j < N2; j += 256) {
+        const float s = row[j];
+        if (s > mx) { mx = s; arg = j; }
+        const float z = s * inv_t + b;
+        const float x = (j == tgt) ? -z : z;
+        const float e = expf(-fabsf(x));
+        loss += fmaxf(x, 0.f) + log1pf(e);
+        const float sig = (x >= 0.f) ? 1.0f / (1.0f + e) : e / (1.0f + e);
+        // (one rounded division per element: sig * fl32(1 / N1) would lean every term of tdot and bdot the same way)
+        const float dz = ((j == tgt) ? -sig : sig) / n1;
+        tdot += dz * s;
+        bdot += dz;
+        if (write_grad) row[j] = dz * inv_t;
+    }
+    const float bmx = block_reduce_max(mx, sh);
+    const int best = block_reduce_min_int(mx == bmx ? arg : 0x7fffffff, shi);
+    loss = block_reduce_sum(loss, sh);
+    tdot = block_reduce_sum(tdot, sh);
+    bdot = block_reduce_sum(bdot, sh);
+    if (tid == 0) {
+        row_loss[i] = loss;
+        row_correct[i] = (best == tgt) ? 1.f : 0.f;
+        row_tdot[i] = tdot;
+        row_bdot[i] = bdot;
+    }
+}
+
+// out = {loss = sum_i row_loss / N1, top-1 acc = hits / N1, dLoss/dT, dLoss/db}; one block, a fixed order of additions.
+// z = s / temp + b  ->  dLoss/dtemp = -sum_ij dz_ij s_ij / temp^2 (0 outside the clamp, as nce_finalize_kernel);  dLoss/db = sum_ij dz_ij.
+__global__ __launch_bounds__(256) void siglip_finalize_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_correct,
+                                                              const float* __restrict__ row_tdot, const float* __restrict__ row_bdot,
+                                                              const float* __restrict__ temperature, float* __restrict__ out, int N1) {
+    __shared__ float sh[8];
+    float l = 0.f, c = 0.f, t = 0.f, d = 0.f;
+    for (int i = threadIdx.x; i < N1; i += 256) {
+        l += row_loss[i];
+        c += row_correct[i];
+        t += row_tdot[i];
+        d += row_bdot[i];
+    }
+    l = block_reduce_sum(l, sh); c = block_reduce_sum(c, sh); t = block_reduce_sum(t, sh); d = block_reduce_sum(d, sh);
+    if (threadIdx.x == 0) {
+        const float T = temperature[0];
+        const float temp = fminf(fmaxf(T, 0.001f), 0.5f);
+        out[0] = l / N1;
+        out[1] = c / N1;
+        out[2] = (T >= 0.001f && T <= 0.5f) ? -t / (temp * temp) : 0.f;
+        out[3] = d;
+    }
+}
+
 // The loss head's backward preparation in ONE launch: up to six fp32 matrices are transposed (32 x 32 LDS tiles), the ones flagged `scale`
 // are multiplied by alpha * scalar[0] on the way - in the transposed copy AND in place - and y0[0] = scalar[0] * x0[0].  (The fp32
 // GEMM kernel contracts row . row: its transposed operands are made here, together with the upstream-gradient scale the round-3 loss head
@@ -425,6 +504,21 @@ extern "C" int simseg_triplet_rows(float* sims, float* row_loss, float* row_corr
                        (int)target0, margin, reduce, mask_block ? 1 : 0, write_grad);
     hipLaunchKernelGGL(triplet_finalize_kernel, dim3(1), dim3(256), 0, STREAM, row_loss, row_correct, out, (int)N1, blocks);
     SS_LAUNCH_CHECK("triplet_rows");
+    return 0;
+}
+
+extern "C" int simseg_siglip_rows(float* sims, const float* temperature, const float* bias, float* row_loss, float* row_correct,
+                                  float* row_tdot, float* row_bdot, float* out4, int64_t N1, int64_t N2, int64_t target0, int write_grad,
+                                  void* stream) {
+    SS_CHECK(sims && temperature && bias && row_loss && row_correct && row_tdot && row_bdot && out4, "siglip_rows: null pointer");
+    SS_CHECK(N1 >= 1 && N2 >= 1 && target0 >= 0 && target0 + N1 <= N2, "siglip_rows: targets [%lld, %lld) outside [0, %lld)",
+             (long long)target0, (long long)(target0 + N1), (long long)N2);
+    SS_CHECK(N2 <= 0x7fffffffLL, "siglip_rows: N2 = %lld columns do not fit the kernel's 32-bit indices", (long long)N2);      // (N1, target0 <= N2)
+    hipLaunchKernelGGL(siglip_rows_kernel, dim3((unsigned)N1), dim3(256), 0, STREAM, sims, temperature, bias, row_loss, row_correct, row_tdot,
+                       row_bdot, (int)N1, (int)N2, (int)target0, write_grad);
+    hipLaunchKernelGGL(siglip_finalize_kernel, dim3(1), dim3(256), 0, STREAM, row_loss, row_correct, row_tdot, row_bdot, temperature, out4,
+                       (int)N1);
+    SS_LAUNCH_CHECK("siglip_rows");
     return 0;
 }
 

@@ -199,6 +199,41 @@ class MixNCEFn(Function):
         return NCEFn.backward(ctx, gloss, _gacc)[:3] + (None,) * 5
 
 
+class SigLipFn(Function):
+    """One direction of the pairwise sigmoid loss of SigLIP (Zhai et al., ICCV'23): feat1 [N1,P] against feat2_global [N2,P], the positive
+    of row i at column rank * N1 + i, every other column a negative; z = s / clamp(T, 1e-3, 0.5) + b (ops.siglip_rows).  Built like NCEFn:
+    one GEMM, the rows in place, gradient GEMMs times the upstream gradient; temperature and bias are 0-dim fp32 tensors, both
+    differentiable.  Returns (loss = sum of the pair losses / N1, top-1 acc)."""
+
+    @staticmethod
+    def forward(ctx, feat1, feat2g, temperature, bias, rank):
+        f1 = feat1.contiguous().float()
+        f2 = feat2g.contiguous().float()
+        sims = ops.gemm(f1, f2)
+        need = any(ctx.needs_input_grad[:4])
+        out4, _ = ops.siglip_rows(sims, temperature.detach().reshape(1).float(), bias.detach().reshape(1).float(), rank * f1.shape[0],
+                                  write_grad=need)
+        ctx.save_for_backward(sims if need else None, f1, f2, out4)
+        loss, acc = out4[0].clone(), out4[1].clone()
+        ctx.mark_non_differentiable(acc)
+        return loss, acc
+
+    @staticmethod
+    def backward(ctx, gloss, _gacc):
+        ds, f1, f2, out4 = ctx.saved_tensors
+        g = gloss.contiguous().float().reshape(1)
+        df1 = df2 = dt = db = None
+        if ctx.needs_input_grad[0]:
+            df1 = ops.scale_by_scalar(ops.gemm(ds, ops.transpose_f32(f2)), g)
+        if ctx.needs_input_grad[1]:
+            df2 = ops.scale_by_scalar(ops.gemm(ops.transpose_f32(ds), ops.transpose_f32(f1)), g)
+        if ctx.needs_input_grad[2]:
+            dt = ops.scale_by_scalar(out4[2:3], g).reshape(())
+        if ctx.needs_input_grad[3]:
+            db = ops.scale_by_scalar(out4[3:4], g).reshape(())
+        return df1, df2, dt, db, None
+
+
 class TripletFn(Function):
     """The global direction of the Triplet loss (mml_loss.py:285-314): feat1 [N1,P] against feat2_global [N2,P], own columns
     [rank * N1, (rank + 1) * N1) - all of them masked, as in the reference.  Built like NCEFn: one GEMM, ops.triplet_rows in place,

@@ -632,6 +632,24 @@ def triplet_rows(sims, target0, margin, reduce, mask_block, write_grad=True):
     return out, (scratch[0].view(blocks, N1) if stacked else scratch[0])
 
 
+def siglip_rows(sims, temperature, bias, target0, write_grad=True):
+    """The pairwise sigmoid rows of SigLIP (include/simseg_hip.h simseg_siglip_rows) of sims [N1, N2]: z = s / clamp(T, 1e-3, 0.5) + b,
+    row i's positive is column target0 + i, every other column a negative.  In place: sims <- dLoss/dsims (write_grad=False leaves it).
+    temperature, bias: fp32 device tensors of one element.  -> (out4 = [loss, acc, dLoss/dT, dLoss/db], row losses [N1])."""
+    N1, N2 = _sim_block_check("siglip_rows", sims, target0)
+    require_gpu(temperature, bias)
+    for name, t in (("temperature", temperature), ("bias", bias)):
+        if t.dtype != torch.float32:
+            raise TypeError(f"siglip_rows: {name} must be fp32, got {t.dtype}")
+        if t.numel() != 1:
+            raise ValueError(f"siglip_rows: {name} holds one element, got {tuple(t.shape)}")
+    scratch = torch.empty(4, max(N1, 1), device=sims.device, dtype=torch.float32)
+    out4 = torch.empty(4, device=sims.device, dtype=torch.float32)
+    call("simseg_siglip_rows", ptr(sims), ptr(temperature), ptr(bias), ptr(scratch[0]), ptr(scratch[1]), ptr(scratch[2]), ptr(scratch[3]),
+         ptr(out4), N1, N2, int(target0), int(bool(write_grad)), stream())
+    return out4, scratch[0]
+
+
 def transpose_multi(mats, scale_flags, scalar=None, alpha=1.0, x0=None):
     """Transposes of up to six contiguous fp32 matrices in ONE launch; matrices whose flag is set are multiplied by alpha * scalar[0] in
     the copy and in place.  Returns (list of transposed tensors, scalar[0] * x0[0] as a 1-element tensor or None)."""

@@ -3,12 +3,15 @@
 features: NCE (heads.NCEFn), MixUpNCE (heads.MixNCEFn, per-row alpha), Triplet-max and Triplet-mean (heads.TripletFn - the global
 direction with the own-rank block masked), at P = 512 on similarity blocks of [512, 512] and [512, 4096] (rank 1 of 8 for the wide
 one; [512, 512] is the one-rank case, where the Triplet's block mask covers every column and loss and gradients are 0 on both routes).
-The local symmetric Triplet (heads.TripletLocalFn) is timed at [512, 512] as well.
+The local symmetric Triplet (heads.TripletLocalFn) is timed at [512, 512] as well.  SigLip (heads.SigLipFn, the pairwise sigmoid loss
+at T = 0.1, b = -10, gradients w.r.t. the temperature and the bias too) has no statement in the reference: its torch route is
+-F.logsigmoid(y * (s / T + b)).sum() / N1.
 
 All in one process on one GPU, routes interleaved round by round; every window is `--iters` back-to-back iterations between two device
 events.  Median [min .. max] over `--rounds` windows, and the loss both routes computed.
 
-    python tools/contrastive_loss_bench.py [--quick] [--out profiles/contrastive_losses.txt]"""
+    python tools/contrastive_loss_bench.py [--quick] [--legs NCE,SigLip] [--out profiles/contrastive_losses.txt]
+(profiles/siglip_loss.txt is `--legs NCE,SigLip`.)"""
 import argparse
 import os
 import statistics
@@ -66,6 +69,14 @@ def torch_nce(f1, f2g, temperature, rank, alpha=None):
             + (1 - alpha) * F.cross_entropy(logits, targets.flip(0), reduction="none")).mean()
 
 
+def torch_siglip(f1, f2g, temperature, bias, rank):
+    N1, N2 = f1.shape[0], f2g.shape[0]
+    s = f1 @ f2g.T
+    y = torch.full_like(s, -1.0)
+    y[torch.arange(N1, device=s.device), N1 * rank + torch.arange(N1, device=s.device)] = 1.0
+    return -F.logsigmoid(y * (s / torch.clamp(temperature, 0.001, 0.5) + bias)).sum() / N1
+
+
 def torch_triplet(f1, f2g, rank, margin, reduce):
     N1 = f1.shape[0]
     scores = f1.mm(f2g.t())
@@ -100,11 +111,13 @@ def section(a, N1, N2, P):
     f2g.requires_grad_(True)
     temperature = torch.tensor(0.05, device="cuda", requires_grad=True)
     alpha = torch.rand(N1, device="cuda", generator=g)
+    sig_t = torch.tensor(0.1, device="cuda", requires_grad=True)          # the SigLIP paper's init: t = 1 / T = 10, b = -10
+    sig_b = torch.tensor(-10.0, device="cuda", requires_grad=True)
     margin, got = 0.2, {}
 
     def run(name, loss_fn):
         def fn():
-            f1.grad = f2g.grad = temperature.grad = None
+            f1.grad = f2g.grad = temperature.grad = sig_t.grad = sig_b.grad = None
             loss = loss_fn()
             loss.backward()
             got[name] = loss.detach()
@@ -116,12 +129,15 @@ def section(a, N1, N2, P):
          lambda: torch_nce(f1, f2g, temperature, rank, alpha)),
         ("Triplet-max", lambda: heads.TripletFn.apply(f1, f2g, rank, margin, 1)[0], lambda: torch_triplet(f1, f2g, rank, margin, "max")),
         ("Triplet-mean", lambda: heads.TripletFn.apply(f1, f2g, rank, margin, 0)[0], lambda: torch_triplet(f1, f2g, rank, margin, "mean")),
+        ("SigLip", lambda: heads.SigLipFn.apply(f1, f2g, sig_t, sig_b, rank)[0], lambda: torch_siglip(f1, f2g, sig_t, sig_b, rank)),
     ]
     if N2 == N1:
         legs += [
             ("Triplet-max local", lambda: heads.TripletLocalFn.apply(f1, f2g, margin, 1)[0], lambda: torch_triplet_local(f1, f2g, margin, "max")),
             ("Triplet-mean local", lambda: heads.TripletLocalFn.apply(f1, f2g, margin, 0)[0], lambda: torch_triplet_local(f1, f2g, margin, "mean")),
         ]
+    if a.legs:
+        legs = [leg for leg in legs if leg[0].split()[0] in a.legs.split(",")]
     routes = []
     for name, hip, ref in legs:
         routes += [(name + "/hip", run(name + "/hip", hip)), (name + "/torch", run(name + "/torch", ref))]
@@ -139,6 +155,7 @@ def main():
     ap.add_argument("--quick", action="store_true", help="small blocks, one round (a rehearsal of the script, not a measurement)")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--legs", default=None, help="comma-separated subset of NCE,MixUpNCE,Triplet-max,Triplet-mean,SigLip (default: all)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -147,12 +164,12 @@ def main():
     if a.quick:
         a.rounds, a.iters = 1, 2
     pr = torch.cuda.get_device_properties(0)
-    say(f"# tools/contrastive_loss_bench.py{' --quick' if a.quick else ''}   device: {pr.name}, torch {torch.__version__}")
-    say(f"# loss head forward + backward from the embeddings (gradients w.r.t. both embedding matrices, and the temperature for the NCE "
-        f"legs), fp32; ms per iteration: median [min .. max] over {a.rounds} windows of {a.iters} back-to-back iterations between two "
+    say(f"# tools/contrastive_loss_bench.py{' --quick' if a.quick else ''}{' --legs ' + a.legs if a.legs else ''}   device: {pr.name}, torch {torch.__version__}")
+    say(f"# loss head forward + backward from the embeddings (gradients w.r.t. both embedding matrices, the temperature for the NCE "
+        f"legs, temperature and bias for SigLip), fp32; ms per iteration: median [min .. max] over {a.rounds} windows of {a.iters} back-to-back iterations between two "
         "device events, routes interleaved round by round")
-    say("# HIP = simseg_amd.heads (NCEFn / MixNCEFn / TripletFn / TripletLocalFn); torch = the reference's statements (mml_loss.py) in "
-        "torch ops with autograd")
+    say("# HIP = simseg_amd.heads (NCEFn / MixNCEFn / TripletFn / TripletLocalFn / SigLipFn); torch = the reference's statements "
+        "(mml_loss.py) in torch ops with autograd; SigLip, which the reference lacks: -F.logsigmoid(y * (s / T + b)).sum() / N1")
     say()
     for N1, N2 in shapes:
         section(a, N1, N2, P)
