@@ -17,41 +17,9 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-TWICE = ("gemm.hip", "attn.hip")     # compiled as bf16 (as they stand) and, with -DSS_HALF, as the fp16 flavour
-# Only entry points with two real flavours - another MFMA builtin, other loops around it - live there (tests/test_host_logic.py holds the
-# short list of exceptions).  rowops.hip, optim.hip, probe.hip, mixup.hip and patchdrop.hip serve both 16-bit types from ONE object: their
-# kernels take the type as a template argument, picked per call from g_ss_half; loss.hip is fp32 / integer code without a flavour.
-
-
-def gen_half_names(write=True):
-    """csrc/half_names.h: the C-ABI entry points that the twice-compiled sources define, renamed name -> name_h16 for the -DSS_HALF
-    build (macros) and declared under that name for the bf16 build that forwards to them.  Derived from the sources' definitions and the
-    public header's prototypes; committed, and checked against a fresh generation by the CPU tests."""
-    import re
-    names = []
-    for f in TWICE:
-        src = open(os.path.join(CSRC, f)).read()
-        for m in re.finditer(r'extern "C"\s+(?:const char\*|int64_t|int)\s+(simseg_\w+)\s*\(', src):
-            if m.group(1) not in names:
-                names.append(m.group(1))
-    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(HERE, "..", "include", "simseg_hip.h")).read(), flags=re.S)
-    protos = {}
-    for m in re.finditer(r"(const char\*|int64_t|int)\s+(simseg_\w+)\s*\(([^)]*)\)\s*;", hdr):
-        protos[m.group(2)] = (m.group(1), " ".join(m.group(3).split()))
-    out = ["// GENERATED by simseg_amd/build.py (gen_half_names) from the extern \"C\" definitions of " + ", ".join(TWICE) + " and the",
-           "// prototypes of include/simseg_hip.h - do not edit.  See common.h (SS_HALF).", "#pragma once", "#ifdef SS_HALF"]
-    out += [f"#define {n} {n}_h16" for n in names]
-    out += ["#else", 'extern "C" {']
-    for n in names:
-        if n not in protos:
-            raise RuntimeError(f"{n} is defined in csrc but not declared in include/simseg_hip.h")
-        out.append(f"{protos[n][0]} {n}_h16({protos[n][1]});")
-    out += ["}", "#endif", ""]
-    text = "\n".join(out)
-    path = os.path.join(CSRC, "half_names.h")
-    if write and (not os.path.exists(path) or open(path).read() != text):
-        open(path, "w").write(text)
-    return text
+TWICE = ()     # sources compiled once per 16-bit type: none any more
+# Every source is ONE object.  Where a kernel touches 16-bit data it takes the type (bf16 or fp16) as a template argument, picked per call
+# from g_ss_half (csrc/common.h: with_h16); fp32 / integer code has no 16-bit type at all.
 
 
 def build(force=False, verbose=True, always=(), report=None):
@@ -63,24 +31,21 @@ def build(force=False, verbose=True, always=(), report=None):
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     objs, procs = [], []
-    gen_half_names()
-    hdrs = sorted(set(hdrs + [os.path.join(CSRC, "half_names.h")]))
-    jobs = [(s, os.path.join(objdir, os.path.basename(s)[:-4] + ".o"), []) for s in srcs]
-    jobs += [(s, os.path.join(objdir, os.path.basename(s)[:-4] + "_h16.o"), ["-DSS_HALF=1"]) for s in srcs if os.path.basename(s) in TWICE]
-    for s, o, extra in jobs:
+    for s in srcs:
+        o = os.path.join(objdir, os.path.basename(s)[:-4] + ".o")
         objs.append(o)
         fresh = force or _stale(o, [s] + hdrs) or os.path.basename(s) in always
         if report is not None:
             report.append((os.path.basename(s), os.path.basename(o), "compiled" if fresh else "reused"))
         if fresh:
-            cmd = [hipcc] + FLAGS + extra + ["-c", s, "-o", o]
+            cmd = [hipcc] + FLAGS + ["-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)
             procs.append((s, subprocess.Popen(cmd)))
     for s, p in procs:
         if p.wait() != 0:
             raise RuntimeError(f"hipcc failed on {s}")
-    for o in set(glob.glob(os.path.join(objdir, "*.o"))) - set(objs):      # objects of sources that are gone or no longer compiled twice
+    for o in set(glob.glob(os.path.join(objdir, "*.o"))) - set(objs):      # objects of sources that are gone
         os.remove(o)
     if force or procs or _stale(LIB, objs):
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs

@@ -16,13 +16,6 @@
 
 namespace {
 
-// the 16-bit type of THIS build of the file, for helpers outside it that take the element type outright (ss_colsum_accum)
-#ifdef SS_HALF
-constexpr int ELEM16 = SS_ELEM_FP16;
-#else
-constexpr int ELEM16 = SS_ELEM_BF16;
-#endif
-
 constexpr int KT = 64;            // keys per LDS tile
 constexpr float NEG = -1e30f;
 
@@ -438,16 +431,18 @@ __global__ __launch_bounds__(256) void attn_bwd_f32_kernel(AttnParams p) {
 constexpr int KP16 = 144, VP16 = 192;
 typedef s16x4 __attribute__((address_space(3))) * lds_s16x4_ptr;
 
-__device__ __forceinline__ bf16x8 tr_frag(const char* p0, int row_step_bytes) {
+template <typename H>
+__device__ __forceinline__ h16x8<H> tr_frag(const char* p0, int row_step_bytes) {
     s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p0));
     s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(p0 + row_step_bytes));
-    union { struct { s16x4 lo, hi; } s; bf16x8 v; } u;
+    union { struct { s16x4 lo, hi; } s; h16x8<H> v; } u;
     u.s.lo = lo; u.s.hi = hi;
     return u.v;
 }
 
-__device__ __forceinline__ bf16x8 ld_bf16x8(const void* p) {
-    union { u32x4 v; bf16x8 h; } u;
+template <typename H>
+__device__ __forceinline__ h16x8<H> ld_h16x8(const void* p) {
+    union { u32x4 v; h16x8<H> h; } u;
     u.v = *reinterpret_cast<const u32x4*>(p);
     return u.h;
 }
@@ -457,7 +452,8 @@ __device__ __forceinline__ bf16x8 ld_bf16x8(const void* p) {
 // 16-byte pieces per thread always cover the 512 pieces of a K or V tile).
 struct KVRegs { u32x4 k[3], v[3]; };
 
-__device__ __forceinline__ void kv_fetch(KVRegs& r, const bf16_t* base, long RS, int HD, int kv0, int T, int tid, int nthr) {
+template <typename H>
+__device__ __forceinline__ void kv_fetch(KVRegs& r, const H* base, long RS, int HD, int kv0, int T, int tid, int nthr) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         const int idx = tid + i * nthr;
@@ -465,7 +461,7 @@ __device__ __forceinline__ void kv_fetch(KVRegs& r, const bf16_t* base, long RS,
         if (idx < KT * 8) {
             const int key = idx >> 3, c = idx & 7;
             if (kv0 + key < T) {
-                const bf16_t* rp = base + (long)(kv0 + key) * RS + c * 8;
+                const H* rp = base + (long)(kv0 + key) * RS + c * 8;
                 kv = *reinterpret_cast<const u32x4*>(rp + HD);
                 vv = *reinterpret_cast<const u32x4*>(rp + 2 * HD);
             }
@@ -486,13 +482,14 @@ __device__ __forceinline__ void kv_commit(const KVRegs& r, char* ldsK, char* lds
     }
 }
 
-__device__ __forceinline__ void kv_direct(const bf16_t* base, long RS, int HD, int kv0, int T, char* ldsK, char* ldsV, int vpitch,
+template <typename H>
+__device__ __forceinline__ void kv_direct(const H* base, long RS, int HD, int kv0, int T, char* ldsK, char* ldsV, int vpitch,
                                           int tid, int nthr) {
     for (int idx = tid; idx < KT * 8; idx += nthr) {
         const int key = idx >> 3, c = idx & 7;
         u32x4 kv = {0u, 0u, 0u, 0u}, vv = kv;
         if (kv0 + key < T) {
-            const bf16_t* rp = base + (long)(kv0 + key) * RS + c * 8;
+            const H* rp = base + (long)(kv0 + key) * RS + c * 8;
             kv = *reinterpret_cast<const u32x4*>(rp + HD);
             vv = *reinterpret_cast<const u32x4*>(rp + 2 * HD);
         }
@@ -542,7 +539,8 @@ __device__ __forceinline__ void glds16_asm(const void* src, char* lds_dst) {
 
 // this wave's share of one tile: pieces 0..7 = K rows, 8..15 = V rows; every wave issues exactly `per` instructions so
 // the vmcnt bookkeeping is uniform (surplus ones repeat piece 15: same bytes to the same place)
-__device__ __forceinline__ void kv_glds(const bf16_t* base, long RS, int HD, int kv0, int T, char* stage, int wave, int nw, int per,
+template <typename H>
+__device__ __forceinline__ void kv_glds(const H* base, long RS, int HD, int kv0, int T, char* stage, int wave, int nw, int per,
                                         int lane) {
     for (int i = 0; i < per; ++i) {
         int piece = wave + i * nw;
@@ -552,7 +550,7 @@ __device__ __forceinline__ void kv_glds(const bf16_t* base, long RS, int HD, int
         const int c = (lane & 7) ^ (isv ? v_swz(r) : k_swz(r));
         int key = kv0 + r;
         key = key < T ? key : T - 1;
-        const bf16_t* src = base + (long)key * RS + (isv + 1) * HD + c * 8;
+        const H* src = base + (long)key * RS + (isv + 1) * HD + c * 8;
         glds16_asm(src, stage + piece * 1024);
     }
 }
@@ -569,7 +567,7 @@ __device__ __forceinline__ void wait_vm_dyn(int n) {
     }
 }
 
-template <bool DROP, bool MASK, bool DBG>
+template <typename H, bool DROP, bool MASK, bool DBG>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_fwd_bf16_kernel(AttnParams p) {
     __shared__ __attribute__((aligned(1024))) char lds[GNS * GSTAGE + (MASK ? MAXT_BIAS * 4 : 16)];
     float* kb_all = reinterpret_cast<float*>(lds + GNS * GSTAGE);
@@ -579,7 +577,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const int b = bh_ / p.H, h = bh_ % p.H;
     const int T = p.T;
     const long RS = 3L * p.H * 64;
-    const bf16_t* base = static_cast<const bf16_t*>(p.qkv) + (long)b * T * RS + h * 64;
+    const H* base = static_cast<const H*>(p.qkv) + (long)b * T * RS + h * 64;
     const int nthr = blockDim.x, nw = nthr >> 6;
     const int per = (16 + nw - 1) / nw;
     const int q = qb_ * (nthr >> 1) + (tid >> 6) * 32 + ql;
@@ -589,10 +587,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     unsigned long long dbg[6] = {0, 0, 0, 0, 0, 0};
     unsigned long long dt0 = __builtin_readcyclecounter();
     const unsigned long long dbg_start = dt0;
-    bf16x8 qr[4];
+    h16x8<H> qr[4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-        union { u32x4 v; bf16x8 hh; } u;
+        union { u32x4 v; h16x8<H> hh; } u;
         u.v = (u32x4){0u, 0u, 0u, 0u};
         if (q < T) u.v = *reinterpret_cast<const u32x4*>(base + (long)q * RS + (2 * kk + h2) * 8);
         qr[kk] = u.hh;
@@ -646,9 +644,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         // all eight K fragments are requested before the first MFMA (one LDS round trip per tile instead of one per
         // MFMA), and the two key blocks' accumulation chains are interleaved so no MFMA waits on its predecessor
         const bool two = !EDGE || kv0 + 32 < T;     // else the second 32-key block is all padding (its P is exactly 0)
-        bf16x8 kf[8];
+        h16x8<H> kf[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) kf[i] = ld_bf16x8(sk + (i >> 2) * 32 * 128 + krow + (((2 * (i & 3) + h2) ^ ksw) << 4));
+        for (int i = 0; i < 8; ++i) kf[i] = ld_h16x8<H>(sk + (i >> 2) * 32 * 128 + krow + (((2 * (i & 3) + h2) ^ ksw) << 4));
         __builtin_amdgcn_sched_barrier(0);
         f32x16 s[2];
 #pragma unroll
@@ -658,12 +656,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         if (two) {
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                s[0] = SS_MFMA_32x32x16(kf[kk], qr[kk], s[0], 0, 0, 0);
-                s[1] = SS_MFMA_32x32x16(kf[4 + kk], qr[kk], s[1], 0, 0, 0);
+                s[0] = mfma_32x32x16(kf[kk], qr[kk], s[0]);
+                s[1] = mfma_32x32x16(kf[4 + kk], qr[kk], s[1]);
             }
         } else {
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) s[0] = SS_MFMA_32x32x16(kf[kk], qr[kk], s[0], 0, 0, 0);
+            for (int kk = 0; kk < 4; ++kk) s[0] = mfma_32x32x16(kf[kk], qr[kk], s[0]);
         }
         if (DBG) { asm volatile("" ::"v"(s[0][0]), "v"(s[1][15])); unsigned long long t1 = __builtin_readcyclecounter(); dbg[1] += t1 - dt0; dt0 = t1; }
         if (MASK) softmax_tile_lean<true, false>(s, kb_all + kv0, h2, p.scale_log2e, m, lsum, o, KT);
@@ -680,12 +678,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 }
         }
         {   // same for V: all transposed fragments first, then eight MFMAs alternating between the two d-blocks
-            bf16x8 vf[8];
+            h16x8<H> vf[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {     // i = kb*4 + s2*2 + db
                 const int roff = ((i >> 2) * 32 + 16 * ((i >> 1) & 1)) * 128 + vrow;
                 const int coff = ((((i & 1) * 4 + vch) ^ vsw) << 4) + vsub;
-                vf[i] = tr_frag(sv + roff + coff, 8 * 128);
+                vf[i] = tr_frag<H>(sv + roff + coff, 8 * 128);
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -693,12 +691,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 if (kb == 1 && !two) break;
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
-                    bf16x8 pf;
+                    h16x8<H> pf;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) pf[e] = (bf16_t)s[kb][8 * s2 + e];
+                    for (int e = 0; e < 8; ++e) pf[e] = (H)s[kb][8 * s2 + e];
 #pragma unroll
                     for (int db = 0; db < 2; ++db)
-                        o[db] = SS_MFMA_32x32x16(vf[kb * 4 + s2 * 2 + db], pf, o[db], 0, 0, 0);
+                        o[db] = mfma_32x32x16(vf[kb * 4 + s2 * 2 + db], pf, o[db]);
                 }
             }
         }
@@ -710,14 +708,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     const float ltot = lsum + __shfl_xor(lsum, 32, 64);
     const float inv = 1.0f / ltot;
     if (q < T) {
-        bf16_t* orow = static_cast<bf16_t*>(p.out) + ((long)b * T + q) * p.H * 64 + h * 64;
+        H* orow = static_cast<H*>(p.out) + ((long)b * T + q) * p.H * 64 + h * 64;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
                 const int d = db * 32 + 8 * r4 + 4 * h2;
-                bf16x4 v = {(bf16_t)(o[db][4 * r4] * inv), (bf16_t)(o[db][4 * r4 + 1] * inv), (bf16_t)(o[db][4 * r4 + 2] * inv), (bf16_t)(o[db][4 * r4 + 3] * inv)};
-                *reinterpret_cast<bf16x4*>(orow + d) = v;
+                h16x4<H> v = {(H)(o[db][4 * r4] * inv), (H)(o[db][4 * r4 + 1] * inv), (H)(o[db][4 * r4 + 2] * inv), (H)(o[db][4 * r4 + 3] * inv)};
+                *reinterpret_cast<h16x4<H>*>(orow + d) = v;
             }
         if (p.lse && h2 == 0) p.lse[((long)b * p.H + h) * T + q] = m + log2f(ltot);
     }
@@ -758,11 +756,7 @@ constexpr int W64_MINT = 512;          // (shorter sequences - 325 tokens at 288
 // of their formats at any magnitude, so the bound only has to keep P representable: 2^14 for fp16 (largest finite 65504), 2^30 for bf16.
 // (At 2^8 peaked rows - a few keys far above the class token's score, the first offset - sent a wave through the re-centring path every
 // few tiles: unscaled N(0,1) operands, scores of +-30 in the exponent, ran 20 % slower than scaled ones.)
-#ifdef SS_HALF
-constexpr float W64_BIG = 16384.0f;
-#else
-constexpr float W64_BIG = 1073741824.0f;
-#endif
+template <typename H> constexpr float W64_BIG = std::is_same<H, _Float16>::value ? 16384.0f : 1073741824.0f;
 
 // The w64 kernel's K / V copies: buffer loads straight into LDS.  One descriptor per (batch, head) whose range ends with the batch's last
 // row - rows past T read as zeros, no per-row clamp - a lane's share of the address is two 32-bit offsets fixed for the whole kernel (its row
@@ -787,8 +781,8 @@ __device__ __forceinline__ void w64_dma(__amdgpu_buffer_rsrc_t rsrc, int offK, i
 // their total.  pk[qb][s2]: P as the PV products' B operands, the eight keys of 16-key step s2.
 // QS = false (the generic entry point: q as the projection delivers it): d is the RAW score minus the offset, in raw units, and the scale
 // c = scale * log2(e) goes into one multiply per score in front of the v_exp - no second rounding of q.
-template <int NQB, bool QS>
-__device__ __forceinline__ void softmax_w64_step(int i, const f32x16 (&d)[NQB], bf16x8 (&pk)[NQB][2], float (&acc)[NQB][4], float c) {
+template <typename H, int NQB, bool QS>
+__device__ __forceinline__ void softmax_w64_step(int i, const f32x16 (&d)[NQB], h16x8<H> (&pk)[NQB][2], float (&acc)[NQB][4], float c) {
     constexpr int RS = 4 / NQB;                  // scores per query block and step
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) {
@@ -797,14 +791,14 @@ __device__ __forceinline__ void softmax_w64_step(int i, const f32x16 (&d)[NQB], 
             const int r = i * RS + j;
             const float pr = __builtin_amdgcn_exp2f(QS ? d[qb][r] : d[qb][r] * c);
             acc[qb][r & 3] += pr;
-            pk[qb][r >> 3][r & 7] = (bf16_t)pr;
+            pk[qb][r >> 3][r & 7] = (H)pr;
         }
     }
     // (the sums and the packed pairs are pinned to THIS step: left alone the compiler pairs the adds of both query blocks into v_pk_add_f32
     //  and sinks all of them, and the converts, behind the phase's last MFMA - ~50 instructions that nothing covers)
 #pragma unroll
     for (int qb = 0; qb < NQB; ++qb) {
-        union { bf16x8 v; unsigned w[4]; } u;
+        union { h16x8<H> v; unsigned w[4]; } u;
         const int r0 = i * RS;
         u.v = pk[qb][r0 >> 3];
         if (RS == 2) asm volatile("" : "+v"(acc[qb][r0 & 3]), "+v"(acc[qb][(r0 + 1) & 3]), "+v"(u.w[(r0 & 7) >> 1]));
@@ -813,12 +807,13 @@ __device__ __forceinline__ void softmax_w64_step(int i, const f32x16 (&d)[NQB], 
     }
 }
 
-// The rare path for one query block: some half-row's sum over a key block left [0, W64_BIG] (or is not finite) - never while m is the row's
+// The rare path for one query block: some half-row's sum over a key block left [0, W64_BIG<H>] (or is not finite) - never while m is the row's
 // true maximum, since the sum of 16 probabilities is then at most 16.  d: the block's exponents, formed AGAIN by the caller (the fast path
 // lets them die).  Raises m by max(0, largest exponent) per row (rows in range keep theirs), rescales O and l, rewrites the offset tuple
 // and P; returns the new half-row sum and, in `inc`, what the caller still has to subtract from exponents formed with the old offset.
 // (m, d, inc in the exponent's own units - raw score units with c = scale * log2(e) when q is not pre-scaled, else c = 1)
-__device__ __forceinline__ float w64_recenter(const f32x16& d, bf16x8 (&pk)[2], float& m, f32x16& negm, float& lsum, f32x16 (&o)[2], float& inc,
+template <typename H>
+__device__ __forceinline__ float w64_recenter(const f32x16& d, h16x8<H> (&pk)[2], float& m, f32x16& negm, float& lsum, f32x16 (&o)[2], float& inc,
                                               float c) {
     float mx[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -839,7 +834,7 @@ __device__ __forceinline__ float w64_recenter(const f32x16& d, bf16x8 (&pk)[2], 
     for (int r = 0; r < 16; ++r) {
         const float pr = __builtin_amdgcn_exp2f((d[r] - inc) * c);
         acc[r & 3] += pr;
-        pk[r >> 3][r & 7] = (bf16_t)pr;
+        pk[r >> 3][r & 7] = (H)pr;
     }
     return (acc[0] + acc[1]) + (acc[2] + acc[3]);
 }
@@ -856,7 +851,7 @@ __device__ __forceinline__ float w64_recenter(const f32x16& d, bf16x8 (&pk)[2], 
 // part of the main launch the underfilled fifth block of every (batch, head) - one wave with one valid row holding a two-per-CU block slot
 // for a full pass over the keys - took 21 % of the kernel's block-slot time at T = 1025.
 // One block's work: (batch, head) bh_, block qblk of the rows from qbase on.  gx: blocks per (batch, head) of the launch (DBG records only).
-template <int NQB, bool SPLIT, bool HAS_EDGE, bool QS, bool DBG>
+template <typename H, int NQB, bool SPLIT, bool HAS_EDGE, bool QS, bool DBG>
 __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh_, int qblk, int qbase, int gx) {
     constexpr int RW = 32 * NQB, RB = (SPLIT ? 2 : 4) * RW;       // query rows per wave / per block
     constexpr int NS = 4 * NQB;                     // MFMAs per phase
@@ -865,7 +860,7 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
     const int b = bh_ / p.H, h = bh_ % p.H;
     const long RS = 3L * p.H * 64;
     const int HD = p.H * 64;
-    const bf16_t* base = static_cast<const bf16_t*>(p.qkv) + (long)b * T * RS + h * 64;
+    const H* base = static_cast<const H*>(p.qkv) + (long)b * T * RS + h * 64;
     const int grp = SPLIT ? (wave & 1) : wave, part = SPLIT ? (wave >> 1) : 0;
     const int q0 = qbase + qblk * RB + grp * RW;
     const bool active = q0 < T;                     // wave-uniform
@@ -888,31 +883,31 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
     // Q, k_0, v_0 requested first, the copies of tiles 0 and 1 right behind them: the requests complete in order, so the prologue's arithmetic
     // (offset tuple, O = v_0) waits for its own operands only and runs while the tiles land
     const int rs_bytes = (int)RS * 2;
-    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base), 0, T * rs_bytes - h * 128, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<H*>(base), 0, T * rs_bytes - h * 128, 0x00020000);
     const int drow = lane >> 3;                     // row within an 8-row piece; k_swz / v_swz of the row depend on the lane only
     const int offK = drow * rs_bytes + HD * 2 + (((lane & 7) ^ ((lane >> 4) & 3) ^ ((wave & 1) << 2)) << 4);
     const int offV = drow * rs_bytes + HD * 4 + (((lane & 7) ^ (((lane >> 4) & 1) << 2)) << 4);
-    bf16x8 qr[NQB][4];                              // QS: the projection's q columns carry scale * log2(e) (simseg_attention_fwd_qscaled)
+    h16x8<H> qr[NQB][4];                              // QS: the projection's q columns carry scale * log2(e) (simseg_attention_fwd_qscaled)
     const float cexp = QS ? 1.0f : p.scale_log2e;   // what an exponent is multiplied by in front of the v_exp
     f32x16 o[NQB][2];                               // [query block][d block], unnormalised
     f32x16 negm[NQB];
     float m[NQB], lsum[NQB];
     {
-        bf16x8 k0[4];
+        h16x8<H> k0[4];
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) k0[kk] = ld_bf16x8(base + HD + (2 * kk + h2) * 8);
+        for (int kk = 0; kk < 4; ++kk) k0[kk] = ld_h16x8<H>(base + HD + (2 * kk + h2) * 8);
 #pragma unroll
         for (int qb = 0; qb < NQB; ++qb) {
             int q = q0 + qb * 32 + ql;
             q = q < T ? q : T - 1;
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) qr[qb][kk] = ld_bf16x8(base + (long)q * RS + (2 * kk + h2) * 8);
+            for (int kk = 0; kk < 4; ++kk) qr[qb][kk] = ld_h16x8<H>(base + (long)q * RS + (2 * kk + h2) * 8);
         }
-        bf16x4 v0[2][4];
+        h16x4<H> v0[2][4];
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
-            for (int r4 = 0; r4 < 4; ++r4) v0[db][r4] = *reinterpret_cast<const bf16x4*>(base + 2 * HD + db * 32 + 8 * r4 + 4 * h2);
+            for (int r4 = 0; r4 < 4; ++r4) v0[db][r4] = *reinterpret_cast<const h16x4<H>*>(base + 2 * HD + db * 32 + 8 * r4 + 4 * h2);
         if (nt > 0) w64_dma(rsrc, offK, offV, 1, rs_bytes, lds, wave);
         if (nt > 1) w64_dma(rsrc, offK, offV, 1 + KT, rs_bytes, lds + GSTAGE, wave);
         // key 0 opens the softmax: m = s_0, p_0 = 1, l = 1, O = v_0.  The offset tuple -s_0 comes out of the matrix pipe: an A fragment whose 32
@@ -920,7 +915,7 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
         // per wave and 2 k cycles of every block's prologue)
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            union { bf16x8 v; unsigned w[4]; } u;
+            union { h16x8<H> v; unsigned w[4]; } u;
             u.v = k0[kk];
 #pragma unroll
             for (int j = 0; j < 4; ++j) u.w[j] ^= 0x80008000u;
@@ -931,7 +926,7 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
 #pragma unroll
             for (int r = 0; r < 16; ++r) negm[qb][r] = 0.f;
 #pragma unroll
-            for (int kk = 0; kk < 4; ++kk) negm[qb] = SS_MFMA_32x32x16(k0[kk], qr[qb][kk], negm[qb], 0, 0, 0);
+            for (int kk = 0; kk < 4; ++kk) negm[qb] = mfma_32x32x16(k0[kk], qr[qb][kk], negm[qb]);
             m[qb] = -negm[qb][0];
             lsum[qb] = (h2 == 0 && part == 0) ? 1.f : 0.f;   // (a key-split's later parts: the same offset and nothing summed yet); the two
                                                              // half-waves' sums are added at the end
@@ -976,56 +971,56 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
             //   1  S(kb 0) = K0.Q'^T - m                        2  S(kb 1)  ||  P(kb 0) = exp2(S(kb 0))
             //   3  O += V0^T.P(kb 0)  ||  P(kb 1)                4  O += V1^T.P(kb 1)
             // Every K / V fragment is read from LDS once and feeds all of the wave's query blocks.
-            auto kfrag = [&](int kb, int kk) { return ld_bf16x8(sk + kb * 32 * 128 + krow + (((2 * kk + h2) ^ ksw) << 4)); };
+            auto kfrag = [&](int kb, int kk) { return ld_h16x8<H>(sk + kb * 32 * 128 + krow + (((2 * kk + h2) ^ ksw) << 4)); };
             auto vfrag = [&](int kb, int s2, int db) {
                 const int roff = (kb * 32 + 16 * s2) * 128 + vrow;
                 const int coff = (((db * 4 + vch) ^ vsw) << 4) + vsub;
-                return tr_frag(sv + roff + coff, 8 * 128);
+                return tr_frag<H>(sv + roff + coff, 8 * 128);
             };
             // MFMA i of a phase: scores - chain step kk = i / NQB of query block i % NQB; PV - (s2, db, qb) = (i / 2 NQB, i / NQB % 2, i % NQB)
-            auto qk_step = [&](int i, int kb, const bf16x8 (&kf)[4], f32x16 (&s)[NQB]) {
+            auto qk_step = [&](int i, int kb, const h16x8<H> (&kf)[4], f32x16 (&s)[NQB]) {
                 const int kk = i / NQB, qb = i % NQB;
-                if (kk == 0) s[qb] = SS_MFMA_32x32x16(kf[0], qr[qb][0], chain0(qb, kb), 0, 0, 0);
-                else s[qb] = SS_MFMA_32x32x16(kf[kk], qr[qb][kk], s[qb], 0, 0, 0);
+                if (kk == 0) s[qb] = mfma_32x32x16(kf[0], qr[qb][0], chain0(qb, kb));
+                else s[qb] = mfma_32x32x16(kf[kk], qr[qb][kk], s[qb]);
             };
-            auto pv_step = [&](int i, const bf16x8 (&vf)[4], const bf16x8 (&pk)[NQB][2]) {
+            auto pv_step = [&](int i, const h16x8<H> (&vf)[4], const h16x8<H> (&pk)[NQB][2]) {
                 const int s2 = i / (2 * NQB), db = (i / NQB) & 1, qb = i % NQB;
-                o[qb][db] = SS_MFMA_32x32x16(vf[s2 * 2 + db], pk[qb][s2], o[qb][db], 0, 0, 0);
+                o[qb][db] = mfma_32x32x16(vf[s2 * 2 + db], pk[qb][s2], o[qb][db]);
             };
-            auto kload = [&](int kb, bf16x8 (&kf)[4]) {
+            auto kload = [&](int kb, h16x8<H> (&kf)[4]) {
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) kf[kk] = kfrag(kb, kk);
             };
-            auto vload = [&](int kb, bf16x8 (&vf)[4]) {
+            auto vload = [&](int kb, h16x8<H> (&vf)[4]) {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) vf[i] = vfrag(kb, i >> 1, i & 1);
             };
             // the re-centring path of key block kb (wave-uniform, rare): exponents formed again; `other` = the other key block's exponents
             // when they were formed with the old offset and are still to be used
-            auto recentre = [&](int kb, bf16x8 (&pk)[NQB][2], float (&ps)[NQB], f32x16 (*other)[NQB]) {
+            auto recentre = [&](int kb, h16x8<H> (&pk)[NQB][2], float (&ps)[NQB], f32x16 (*other)[NQB]) {
                 f32x16 s[NQB];
-                bf16x8 kf[4];
+                h16x8<H> kf[4];
                 kload(kb, kf);
 #pragma unroll
                 for (int i = 0; i < NS; ++i) qk_step(i, kb, kf, s);
 #pragma unroll
                 for (int qb = 0; qb < NQB; ++qb) {
                     float inc;
-                    ps[qb] = w64_recenter(s[qb], pk[qb], m[qb], negm[qb], lsum[qb], o[qb], inc, cexp);
+                    ps[qb] = w64_recenter<H>(s[qb], pk[qb], m[qb], negm[qb], lsum[qb], o[qb], inc, cexp);
                     if (other)
 #pragma unroll
                         for (int r = 0; r < 16; ++r) (*other)[qb][r] -= inc;
                 }
             };
             auto in_range = [&](const float (&ps)[NQB]) {
-                bool ok = ps[0] <= W64_BIG;
+                bool ok = ps[0] <= W64_BIG<H>;
 #pragma unroll
-                for (int qb = 1; qb < NQB; ++qb) ok = ok && ps[qb] <= W64_BIG;
+                for (int qb = 1; qb < NQB; ++qb) ok = ok && ps[qb] <= W64_BIG<H>;
                 return __all(ok);
             };
             f32x16 s0[NQB], s1[NQB];
-            bf16x8 pk0[NQB][2], pk1[NQB][2];
-            bf16x8 kf[4], vf[4];
+            h16x8<H> pk0[NQB][2], pk1[NQB][2];
+            h16x8<H> kf[4], vf[4];
             float acc[NQB][4], ps[NQB];
             kload(0, kf);
 #pragma unroll
@@ -1039,7 +1034,7 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
 #pragma unroll
             for (int i = 0; i < NS; ++i) {                                       // phase 2
                 qk_step(i, 1, kf, s1);
-                softmax_w64_step<NQB, QS>(i, s0, pk0, acc, cexp);
+                softmax_w64_step<H, NQB, QS>(i, s0, pk0, acc, cexp);
                 __builtin_amdgcn_sched_barrier(0);
             }
             vload(0, vf);
@@ -1056,7 +1051,7 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
 #pragma unroll
             for (int i = 0; i < NS; ++i) {                                       // phase 3
                 pv_step(i, vf, pk0);
-                softmax_w64_step<NQB, QS>(i, s1, pk1, acc, cexp);
+                softmax_w64_step<H, NQB, QS>(i, s1, pk1, acc, cexp);
                 __builtin_amdgcn_sched_barrier(0);
             }
             vload(1, vf);
@@ -1090,9 +1085,9 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
             const char* sk = lds + cur * GSTAGE + kb * 32 * 128;
             const char* sv = lds + cur * GSTAGE + KT * 128 + kb * 32 * 128;
             auto scores = [&](f32x16 (&s)[NQB]) {
-                bf16x8 kf[4];
+                h16x8<H> kf[4];
 #pragma unroll
-                for (int kk = 0; kk < 4; ++kk) kf[kk] = ld_bf16x8(sk + krow + (((2 * kk + h2) ^ ksw) << 4));
+                for (int kk = 0; kk < 4; ++kk) kf[kk] = ld_h16x8<H>(sk + krow + (((2 * kk + h2) ^ ksw) << 4));
 #pragma unroll
                 for (int qb = 0; qb < NQB; ++qb) {
                     f32x16 c = negm[qb];
@@ -1100,15 +1095,15 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
 #pragma unroll
                         for (int r = 0; r < 16; ++r) c[r] = (kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h2) < rem ? negm[qb][r] : NEG;
                     }
-                    s[qb] = SS_MFMA_32x32x16(kf[0], qr[qb][0], c, 0, 0, 0);
+                    s[qb] = mfma_32x32x16(kf[0], qr[qb][0], c);
                 }
 #pragma unroll
                 for (int kk = 1; kk < 4; ++kk)
 #pragma unroll
-                    for (int qb = 0; qb < NQB; ++qb) s[qb] = SS_MFMA_32x32x16(kf[kk], qr[qb][kk], s[qb], 0, 0, 0);
+                    for (int qb = 0; qb < NQB; ++qb) s[qb] = mfma_32x32x16(kf[kk], qr[qb][kk], s[qb]);
             };
             f32x16 s[NQB];
-            bf16x8 pk[NQB][2], vf[4];
+            h16x8<H> pk[NQB][2], vf[4];
             float acc[NQB][4], ps[NQB];
             scores(s);
 #pragma unroll
@@ -1116,26 +1111,26 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
 #pragma unroll
                 for (int j = 0; j < 4; ++j) acc[qb][j] = 0.f;
 #pragma unroll
-            for (int i = 0; i < NS; ++i) softmax_w64_step<NQB, QS>(i, s, pk, acc, cexp);
+            for (int i = 0; i < NS; ++i) softmax_w64_step<H, NQB, QS>(i, s, pk, acc, cexp);
             bool ok = true;
 #pragma unroll
             for (int qb = 0; qb < NQB; ++qb) {
                 ps[qb] = (acc[qb][0] + acc[qb][1]) + (acc[qb][2] + acc[qb][3]);
-                ok = ok && ps[qb] <= W64_BIG;
+                ok = ok && ps[qb] <= W64_BIG<H>;
             }
             if (!__all(ok)) {
                 scores(s);
 #pragma unroll
                 for (int qb = 0; qb < NQB; ++qb) {
                     float inc;
-                    ps[qb] = w64_recenter(s[qb], pk[qb], m[qb], negm[qb], lsum[qb], o[qb], inc, cexp);
+                    ps[qb] = w64_recenter<H>(s[qb], pk[qb], m[qb], negm[qb], lsum[qb], o[qb], inc, cexp);
                 }
             }
 #pragma unroll
             for (int i = 0; i < 4; ++i) {            // i = s2*2 + db   (behind the branch: 16 registers less across it)
                 const int roff = (16 * (i >> 1)) * 128 + vrow;
                 const int coff = ((((i & 1) * 4 + vch) ^ vsw) << 4) + vsub;
-                vf[i] = tr_frag(sv + roff + coff, 8 * 128);
+                vf[i] = tr_frag<H>(sv + roff + coff, 8 * 128);
             }
 #pragma unroll
             for (int qb = 0; qb < NQB; ++qb) lsum[qb] += ps[qb];
@@ -1144,7 +1139,7 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
 #pragma unroll
                 for (int db = 0; db < 2; ++db)
 #pragma unroll
-                    for (int qb = 0; qb < NQB; ++qb) o[qb][db] = SS_MFMA_32x32x16(vf[s2 * 2 + db], pk[qb][s2], o[qb][db], 0, 0, 0);
+                    for (int qb = 0; qb < NQB; ++qb) o[qb][db] = mfma_32x32x16(vf[s2 * 2 + db], pk[qb][s2], o[qb][db]);
         }
         cur = cur + 1 == GNS ? 0 : cur + 1;
     };
@@ -1195,15 +1190,15 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
         const float ltot = lsum[qb] + __shfl_xor(lsum[qb], 32, 64);
         const float inv = 1.0f / ltot;
         if (q < T) {
-            bf16_t* orow = static_cast<bf16_t*>(p.out) + ((long)b * T + q) * HD + h * 64;
+            H* orow = static_cast<H*>(p.out) + ((long)b * T + q) * HD + h * 64;
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) {
                     const int d = db * 32 + 8 * r4 + 4 * h2;
-                    bf16x4 v = {(bf16_t)(o[qb][db][4 * r4] * inv), (bf16_t)(o[qb][db][4 * r4 + 1] * inv), (bf16_t)(o[qb][db][4 * r4 + 2] * inv),
-                                (bf16_t)(o[qb][db][4 * r4 + 3] * inv)};
-                    *reinterpret_cast<bf16x4*>(orow + d) = v;
+                    h16x4<H> v = {(H)(o[qb][db][4 * r4] * inv), (H)(o[qb][db][4 * r4 + 1] * inv), (H)(o[qb][db][4 * r4 + 2] * inv),
+                                (H)(o[qb][db][4 * r4 + 3] * inv)};
+                    *reinterpret_cast<h16x4<H>*>(orow + d) = v;
                 }
             if (p.lse && h2 == 0) p.lse[((long)b * p.H + h) * T + q] = m[qb] * cexp + log2f(ltot);
         }
@@ -1228,34 +1223,34 @@ __device__ __forceinline__ void w64_block(const AttnParams& p, char* lds, int bh
 
 // the key-split form as a CALL: its registers are allocated apart from the main path's (inlined next to it, the second tile loop cost the
 // main loop ~100 spilled registers)
-template <bool HAS_EDGE, bool QS>
+template <typename H, bool HAS_EDGE, bool QS>
 __device__ __forceinline__ void w64_split_block(const AttnParams& p, char* lds, int bh_, int qblk, int qbase) {
-    w64_block<1, true, HAS_EDGE, QS, false>(p, lds, bh_, qblk, qbase, 0);
+    w64_block<H, 1, true, HAS_EDGE, QS, false>(p, lds, bh_, qblk, qbase, 0);
 }
 
 // p.gxw blocks per (batch, head), all on one XCD (attn_block_map's scheme): the first p.gxm of them full-size main blocks, the others
 // key-split blocks of 64 rows for the rows behind (they run beside their head's main blocks and find its K / V in the XCD's L2; as a
 // launch of their own they re-read all of K and V from HBM: 805 MB, 270 us, at 256 x 12 heads of 1025 tokens).  NQB = 1: tools only.
-template <int NQB, bool HAS_EDGE, bool QS, bool DBG = false>
+template <typename H, int NQB, bool HAS_EDGE, bool QS, bool DBG = false>
 __global__ __launch_bounds__(256, NQB == 2 ? 2 : 3) void attn_fwd_w64_kernel(AttnParams p) {
     __shared__ __attribute__((aligned(1024))) char lds[GNS * GSTAGE];
     const int gx = p.gxw;
     const int L = blockIdx.x, slot = L >> 3;
     const int bh_ = (slot / gx) * 8 + (L & 7), qblk = slot % gx;
     if (bh_ >= p.B * p.H) return;
-    if (NQB == 2 && qblk >= p.gxm) w64_split_block<HAS_EDGE, QS>(p, lds, bh_, qblk - p.gxm, p.gxm * 256);
-    else w64_block<NQB, false, HAS_EDGE, QS, DBG>(p, lds, bh_, qblk, 0, gx);
+    if (NQB == 2 && qblk >= p.gxm) w64_split_block<H, HAS_EDGE, QS>(p, lds, bh_, qblk - p.gxm, p.gxm * 256);
+    else w64_block<H, NQB, false, HAS_EDGE, QS, DBG>(p, lds, bh_, qblk, 0, gx);
 }
 
 // host side.  Full blocks of 4 x 64 query rows (plus a partial one when more than half a block is left over); the rows behind them go to
 // key-split blocks of the same launch.  variant 6 (tools): one query block per wave throughout.
-template <int NQB, bool QS, bool DBG>
+template <typename H, int NQB, bool QS, bool DBG>
 static void launch_w64_grid(const AttnParams& p, hipStream_t stream, unsigned blocks) {
-    if ((p.T - 1) % 64) hipLaunchKernelGGL((attn_fwd_w64_kernel<NQB, true, QS, DBG>), dim3(blocks), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL((attn_fwd_w64_kernel<NQB, false, QS, DBG>), dim3(blocks), dim3(256), 0, stream, p);
+    if ((p.T - 1) % 64) hipLaunchKernelGGL((attn_fwd_w64_kernel<H, NQB, true, QS, DBG>), dim3(blocks), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((attn_fwd_w64_kernel<H, NQB, false, QS, DBG>), dim3(blocks), dim3(256), 0, stream, p);
 }
 
-template <bool DBG>
+template <typename H, bool DBG>
 static void launch_w64(const AttnParams& p0, hipStream_t stream, int nqb) {
     AttnParams p = p0;
     const long bh8 = ((long)(p.B * p.H + 7) / 8) * 8;
@@ -1270,8 +1265,8 @@ static void launch_w64(const AttnParams& p0, hipStream_t stream, int nqb) {
     }
     if (nqb != 2) {
         p.gxm = p.gxw = (p.T + 127) / 128;
-        if (p.qscaled) launch_w64_grid<1, true, DBG>(p, stream, (unsigned)(p.gxw * bh8));
-        else launch_w64_grid<1, false, false>(p, stream, (unsigned)(p.gxw * bh8));
+        if (p.qscaled) launch_w64_grid<H, 1, true, DBG>(p, stream, (unsigned)(p.gxw * bh8));
+        else launch_w64_grid<H, 1, false, false>(p, stream, (unsigned)(p.gxw * bh8));
         return;
     }
     int full = p.T / 256;
@@ -1279,8 +1274,8 @@ static void launch_w64(const AttnParams& p0, hipStream_t stream, int nqb) {
     if (left > 64) ++full;              // (two key-split blocks - 65 rows at T = 577 - measured slower than one half-empty main block)
     p.gxm = full;
     p.gxw = full + ((left > 0 && left <= 64) ? 1 : 0);
-    if (p.qscaled) launch_w64_grid<2, true, DBG>(p, stream, (unsigned)(p.gxw * bh8));
-    else launch_w64_grid<2, false, false>(p, stream, (unsigned)(p.gxw * bh8));
+    if (p.qscaled) launch_w64_grid<H, 2, true, DBG>(p, stream, (unsigned)(p.gxw * bh8));
+    else launch_w64_grid<H, 2, false, false>(p, stream, (unsigned)(p.gxw * bh8));
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1296,9 +1291,9 @@ static void launch_w64(const AttnParams& p0, hipStream_t stream, int nqb) {
 constexpr int X3_STAGE = 6 * KT * 128;
 constexpr int X3_NS = 3;
 
-struct AttnX3Params { const bf16_t* qkv3; long plane; float* out; int B, T, H; float scale_log2e; };
+struct AttnX3Params { const __bf16* qkv3; long plane; float* out; int B, T, H; float scale_log2e; };
 
-__device__ __forceinline__ void kv_glds_x3(const bf16_t* base, long plane, long RS, int HD, int kv0, int T, char* stage, int wave, int nw, int per,
+__device__ __forceinline__ void kv_glds_x3(const __bf16* base, long plane, long RS, int HD, int kv0, int T, char* stage, int wave, int nw, int per,
                                            int lane) {
     for (int i = 0; i < per; ++i) {                    // 48 pieces of 1 KiB per tile; every wave issues `per` (surplus ones repeat piece 47)
         int piece = wave + i * nw;
@@ -1309,7 +1304,7 @@ __device__ __forceinline__ void kv_glds_x3(const bf16_t* base, long plane, long 
         const int c = (lane & 7) ^ (isv ? v_swz(r) : k_swz(r));
         int key = kv0 + r;
         key = key < T ? key : T - 1;
-        const bf16_t* src = base + pc * plane + (long)key * RS + (isv + 1) * HD + c * 8;
+        const __bf16* src = base + pc * plane + (long)key * RS + (isv + 1) * HD + c * 8;
         glds16_asm(src, stage + piece * 1024);
     }
 }
@@ -1326,17 +1321,17 @@ __global__ __launch_bounds__(512) void attn_fwd_x3_kernel(AttnX3Params p) {
     const int b = bh_ / p.H, h = bh_ % p.H;
     const int T = p.T;
     const long RS = 3L * p.H * 64;
-    const bf16_t* base = p.qkv3 + (long)b * T * RS + h * 64;
+    const __bf16* base = p.qkv3 + (long)b * T * RS + h * 64;
     const int q = (qb_ * nw + wave) * 32 + ql;
     const bool active = (qb_ * nw + wave) * 32 < T;         // (wave-uniform; a padding wave still copies and meets the barriers)
     const int HD = p.H * 64;
     const int nt = (T + KT - 1) / KT;
-    bf16x8 qr[3][4];
+    h16x8<__bf16> qr[3][4];
 #pragma unroll
     for (int pc = 0; pc < 3; ++pc)
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            union { u32x4 v; bf16x8 hh; } u;
+            union { u32x4 v; h16x8<__bf16> hh; } u;
             u.v = *reinterpret_cast<const u32x4*>(base + pc * p.plane + (long)min(q, T - 1) * RS + (2 * kk + h2) * 8);     // (queries >= T: row T-1, never stored)
             qr[pc][kk] = u.hh;
         }
@@ -1361,16 +1356,16 @@ __global__ __launch_bounds__(512) void attn_fwd_x3_kernel(AttnX3Params p) {
             for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
 #pragma unroll
         for (int pc = 2; pc >= 0; --pc) {
-            bf16x8 kf[8];
+            h16x8<__bf16> kf[8];
 #pragma unroll
-            for (int i = 0; i < 8; ++i) kf[i] = ld_bf16x8(sk + pc * (KT * 128) + (i >> 2) * 32 * 128 + krow + (((2 * (i & 3) + h2) ^ ksw) << 4));
+            for (int i = 0; i < 8; ++i) kf[i] = ld_h16x8<__bf16>(sk + pc * (KT * 128) + (i >> 2) * 32 * 128 + krow + (((2 * (i & 3) + h2) ^ ksw) << 4));
 #pragma unroll
             for (int qp = 2; qp >= 0; --qp) {
                 if (qp + pc > 2) continue;
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
-                    s[0] = SS_MFMA_32x32x16(kf[kk], qr[qp][kk], s[0], 0, 0, 0);
-                    s[1] = SS_MFMA_32x32x16(kf[4 + kk], qr[qp][kk], s[1], 0, 0, 0);
+                    s[0] = mfma_32x32x16(kf[kk], qr[qp][kk], s[0]);
+                    s[1] = mfma_32x32x16(kf[4 + kk], qr[qp][kk], s[1]);
                 }
             }
         }
@@ -1408,7 +1403,7 @@ __global__ __launch_bounds__(512) void attn_fwd_x3_kernel(AttnX3Params p) {
         __builtin_amdgcn_sched_barrier(0);
         softmax_tile_lean<false, EDGE>(s, nullptr, h2, p.scale_log2e, m, lsum, o, T - kv0);
         // the fp32 probabilities as three exact bf16 pieces (index [piece][kb * 2 + s2])
-        bf16x8 pp[3][4];
+        h16x8<__bf16> pp[3][4];
 #pragma unroll
         for (int kb = 0; kb < 2; ++kb)
 #pragma unroll
@@ -1416,21 +1411,21 @@ __global__ __launch_bounds__(512) void attn_fwd_x3_kernel(AttnX3Params p) {
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float x = s[kb][8 * s2 + e];
-                    const bf16_t hi = (bf16_t)x;
+                    const __bf16 hi = (__bf16)x;
                     const float r1 = x - (float)hi;
-                    const bf16_t mid = (bf16_t)r1;
+                    const __bf16 mid = (__bf16)r1;
                     pp[0][kb * 2 + s2][e] = hi;
                     pp[1][kb * 2 + s2][e] = mid;
-                    pp[2][kb * 2 + s2][e] = (bf16_t)(r1 - (float)mid);
+                    pp[2][kb * 2 + s2][e] = (__bf16)(r1 - (float)mid);
                 }
 #pragma unroll
         for (int vc = 2; vc >= 0; --vc) {
-            bf16x8 vf[8];
+            h16x8<__bf16> vf[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {     // i = kb*4 + s2*2 + db
                 const int roff = ((i >> 2) * 32 + 16 * ((i >> 1) & 1)) * 128 + vrow;
                 const int coff = ((((i & 1) * 4 + vch) ^ vsw) << 4) + vsub;
-                vf[i] = tr_frag(sv + vc * (KT * 128) + roff + coff, 8 * 128);
+                vf[i] = tr_frag<__bf16>(sv + vc * (KT * 128) + roff + coff, 8 * 128);
             }
 #pragma unroll
             for (int pq = 2; pq >= 0; --pq) {
@@ -1441,7 +1436,7 @@ __global__ __launch_bounds__(512) void attn_fwd_x3_kernel(AttnX3Params p) {
                     for (int s2 = 0; s2 < 2; ++s2)
 #pragma unroll
                         for (int db = 0; db < 2; ++db)
-                            o[db] = SS_MFMA_32x32x16(vf[kb * 4 + s2 * 2 + db], pp[pq][kb * 2 + s2], o[db], 0, 0, 0);
+                            o[db] = mfma_32x32x16(vf[kb * 4 + s2 * 2 + db], pp[pq][kb * 2 + s2], o[db]);
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -1505,7 +1500,7 @@ __device__ __forceinline__ int attn_teff(const AttnParams& p, int b) {
     return last < 0 ? p.T : last + 1;
 }
 
-template <bool DROP, bool MASK>
+template <typename H, bool DROP, bool MASK>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void attn_fwd_bf16_res_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h2 = lane >> 5, ql = lane & 31;
@@ -1515,7 +1510,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     if (T <= 0) return;                                        // (an empty sequence of a ragged batch; uniform per block)
     const long row0 = p.row_start ? (long)p.row_start[b] : (long)b * Tf;      // first row of this sequence in qkv / out
     const long RS = p.rs;
-    const bf16_t* base = static_cast<const bf16_t*>(p.qkv) + row0 * RS + h * p.ps;
+    const H* base = static_cast<const H*>(p.qkv) + row0 * RS + h * p.ps;
     const int nthr = blockDim.x, nw = nthr >> 6;
     const long HD = p.H * p.ps;                                        // from a head's q plane to its k plane
     const int nt = (T + KT - 1) / KT, q32 = (T + 31) / 32;
@@ -1531,19 +1526,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         const int r = pp * 8 + (lane >> 3);
         const int c = (lane & 7) ^ (isv ? v_swz(r) : k_swz(r));
         const int key = r < T ? r : T - 1;
-        const bf16_t* src = base + (long)key * RS + (isv + 1) * HD + c * 8;
+        const H* src = base + (long)key * RS + (isv + 1) * HD + c * 8;
         // (a non-temporal policy here: 0.213 -> 0.209 ms at T = 197 but 0.056 -> 0.070 ms at T = 77; left at the default)
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                          (__attribute__((address_space(3))) void*)((isv ? ldsV : ldsK) + pp * 1024), 16, 0, 0);
     }
     // this wave's query tiles: wave, wave + nw (T <= 256 and nw = min(4, q32): at most two).  The first tile's Q rows are fetched
     // with the K / V copies; the second tile's replace them as soon as the first pass has formed its last scores.
-    bf16x8 qr[4];
+    h16x8<H> qr[4];
     auto load_q = [&](int qt) {
         const int q = qt * 32 + ql;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            union { u32x4 v; bf16x8 hh; } u;      // (queries >= T: row T-1, never stored - an unconditional request needs no wait of its own)
+            union { u32x4 v; h16x8<H> hh; } u;      // (queries >= T: row T-1, never stored - an unconditional request needs no wait of its own)
             // (uniform base + a 32-bit lane offset: as a 64-bit per-lane pointer the second pass's address lived in a spilled register pair)
             const unsigned voff = ((unsigned)min(q, T - 1) * (unsigned)RS + (unsigned)((2 * kk + h2) * 8)) * 2u;
             u.v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(base) + voff);
@@ -1585,39 +1580,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
                 for (int r = 0; r < 16; ++r) s[kb][r] = 0.f;
             {
-                bf16x8 kf[8];
+                h16x8<H> kf[8];
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     if (!EDGE) {
-                        kf[i] = ld_bf16x8(sk + (i >> 2) * 32 * 128 + krow + (((2 * (i & 3) + h2) ^ ksw) << 4));
+                        kf[i] = ld_h16x8<H>(sk + (i >> 2) * 32 * 128 + krow + (((2 * (i & 3) + h2) ^ ksw) << 4));
                     } else {
                         int r = kv0 + (i >> 2) * 32 + ql;
                         r = r < rows8 ? r : rows8 - 1;
-                        kf[i] = ld_bf16x8(ldsK + r * 128 + (((2 * (i & 3) + h2) ^ k_swz(r)) << 4));
+                        kf[i] = ld_h16x8<H>(ldsK + r * 128 + (((2 * (i & 3) + h2) ^ k_swz(r)) << 4));
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);      // all fragments requested before the first MFMA (one LDS round trip, not eight)
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) {
-                    s[0] = SS_MFMA_32x32x16(kf[kk], qr[kk], s[0], 0, 0, 0);
-                    if (two) s[1] = SS_MFMA_32x32x16(kf[4 + kk], qr[kk], s[1], 0, 0, 0);
+                    s[0] = mfma_32x32x16(kf[kk], qr[kk], s[0]);
+                    if (two) s[1] = mfma_32x32x16(kf[4 + kk], qr[kk], s[1]);
                 }
             }
             if (EDGE && qt + nw < q32) load_q(qt + nw);      // Q of the next pass: lands under this tile's softmax, PV and stores
             // the transposed V fragments are requested before the softmax arithmetic: their LDS round trip runs under it
-            bf16x8 vf[8];
+            h16x8<H> vf[8];
 #pragma unroll
             for (int i = 0; i < 8; ++i) {     // i = kb*4 + s2*2 + db
                 if (!EDGE) {
                     const int roff = ((i >> 2) * 32 + 16 * ((i >> 1) & 1)) * 128 + vrow;
                     const int coff = ((((i & 1) * 4 + vch) ^ vsw) << 4) + vsub;
-                    vf[i] = tr_frag(sv + roff + coff, 8 * 128);
+                    vf[i] = tr_frag<H>(sv + roff + coff, 8 * 128);
                 } else {
                     const int r0 = kv0 + (i >> 2) * 32 + 16 * ((i >> 1) & 1) + 4 * h2 + (a16 >> 2);
                     const int ra = r0 < rows8 ? r0 : rows8 - 1, rb = r0 + 8 < rows8 ? r0 + 8 : rows8 - 1;
                     const char* pa = ldsV + ra * 128 + ((((i & 1) * 4 + vch) ^ v_swz(ra)) << 4) + vsub;
                     const char* pb = ldsV + rb * 128 + ((((i & 1) * 4 + vch) ^ v_swz(rb)) << 4) + vsub;
-                    union { struct { s16x4 lo, hi; } h; bf16x8 v; } u;
+                    union { struct { s16x4 lo, hi; } h; h16x8<H> v; } u;
                     u.h.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(pa));
                     u.h.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(pb));
                     vf[i] = u.v;
@@ -1641,12 +1636,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
                 if (kb == 1 && !two) break;
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
-                    bf16x8 pf;
+                    h16x8<H> pf;
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) pf[e] = (bf16_t)s[kb][8 * s2 + e];
+                    for (int e = 0; e < 8; ++e) pf[e] = (H)s[kb][8 * s2 + e];
 #pragma unroll
                     for (int db = 0; db < 2; ++db)
-                        o[db] = SS_MFMA_32x32x16(vf[kb * 4 + s2 * 2 + db], pf, o[db], 0, 0, 0);
+                        o[db] = mfma_32x32x16(vf[kb * 4 + s2 * 2 + db], pf, o[db]);
                 }
             }
         };
@@ -1661,14 +1656,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         const float ltot = lsum + __shfl_xor(lsum, 32, 64);
         const float inv = 1.0f / ltot;
         if (q < T) {
-            bf16_t* orow = static_cast<bf16_t*>(p.out) + (row0 + q) * p.H * 64 + h * 64;
+            H* orow = static_cast<H*>(p.out) + (row0 + q) * p.H * 64 + h * 64;
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) {
                     const int d = db * 32 + 8 * r4 + 4 * h2;
-                    bf16x4 v = {(bf16_t)(o[db][4 * r4] * inv), (bf16_t)(o[db][4 * r4 + 1] * inv), (bf16_t)(o[db][4 * r4 + 2] * inv), (bf16_t)(o[db][4 * r4 + 3] * inv)};
-                    *reinterpret_cast<bf16x4*>(orow + d) = v;
+                    h16x4<H> v = {(H)(o[db][4 * r4] * inv), (H)(o[db][4 * r4 + 1] * inv), (H)(o[db][4 * r4 + 2] * inv), (H)(o[db][4 * r4 + 3] * inv)};
+                    *reinterpret_cast<h16x4<H>*>(orow + d) = v;
                 }
             if (p.lse && h2 == 0) p.lse[((long)b * p.H + h) * Tf + q] = m + log2f(ltot);
         }
@@ -1677,11 +1672,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 
 __host__ int res_smem(int T, bool mask) { return 2 * ((T + 7) & ~7) * 128 + (mask ? ((T + KT - 1) / KT) * KT * 4 : 0); }
 
-template <bool DROP, bool MASK>
+template <typename H, bool DROP, bool MASK>
 int launch_fwd_res(const AttnParams& p, hipStream_t stream) {
     const int q32 = (p.T + 31) / 32;
     static bool configured = false;
-    auto kern = attn_fwd_bf16_res_kernel<DROP, MASK>;
+    auto kern = attn_fwd_bf16_res_kernel<H, DROP, MASK>;
     if (!configured) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, res_smem(RES_MAXT, true));
         if (e != hipSuccess) return simseg_set_error("attention_fwd: cannot reserve LDS: %s", hipGetErrorString(e));
@@ -1696,24 +1691,25 @@ int launch_fwd_res(const AttnParams& p, hipStream_t stream) {
 //   kernel A (per 128-key tile): dK = dS^T.Q, dV = P_d^T.dO      (queries streamed through LDS, 32 at a time)
 //   kernel B (per 128-query tile): dQ = dS.K                     (keys streamed through LDS, 64 at a time)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void attn_delta_kernel(const bf16_t* __restrict__ o, const bf16_t* __restrict__ dout,
-                                                         float* __restrict__ delta, int B, int T, int H) {
+template <typename H>
+__global__ __launch_bounds__(256) void attn_delta_kernel(const H* __restrict__ o, const H* __restrict__ dout,
+                                                         float* __restrict__ delta, int B, int T, int NH) {
     // one 8-lane group per (b, t, h): 64 d = 8 lanes x 8 elements
     const long gid = ((long)blockIdx.x * blockDim.x + threadIdx.x) >> 3;
     const int sub = threadIdx.x & 7;
-    if (gid >= (long)B * T * H) return;
+    if (gid >= (long)B * T * NH) return;
     const long off = gid * 64 + sub * 8;
-    const bf16x8 a = ld_bf16x8(o + off), g = ld_bf16x8(dout + off);
+    const h16x8<H> a = ld_h16x8<H>(o + off), g = ld_h16x8<H>(dout + off);
     float s = 0.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) s += (float)a[e] * (float)g[e];
     s += __shfl_xor(s, 1, 64); s += __shfl_xor(s, 2, 64); s += __shfl_xor(s, 4, 64);
     if (sub == 0) {
-        const int h = (int)(gid % H);
-        const long bt = gid / H;
+        const int h = (int)(gid % NH);
+        const long bt = gid / NH;
         const int t = (int)(bt % T);
         const int b = (int)(bt / T);
-        delta[((long)b * H + h) * T + t] = s;
+        delta[((long)b * NH + h) * T + t] = s;
     }
 }
 
@@ -1721,9 +1717,10 @@ constexpr int QT = 32;   // queries per LDS tile in the dK/dV kernel
 constexpr int QP = 144;  // pitch of the Q / dO tiles (read both k-contiguous and transposed)
 constexpr int QBUF = 2 * QT * QP + 2 * QT * 4;   // one stage: Q tile, dO tile, lse[32], delta[32]
 
-__device__ __forceinline__ void store_bf16x4(bf16_t* dst, float a, float b, float c, float d) {
-    const bf16x4 v = {(bf16_t)a, (bf16_t)b, (bf16_t)c, (bf16_t)d};
-    *reinterpret_cast<bf16x4*>(dst) = v;
+template <typename H>
+__device__ __forceinline__ void store_h16x4(H* dst, float a, float b, float c, float d) {
+    const h16x4<H> v = {(H)a, (H)b, (H)c, (H)d};
+    *reinterpret_cast<h16x4<H>*>(dst) = v;
 }
 
 // Schedule notes (both backward kernels, same as the forward): every LDS fragment a group of MFMAs needs is requested
@@ -1731,7 +1728,7 @@ __device__ __forceinline__ void store_bf16x4(bf16_t* dst, float a, float b, floa
 // alternate so no MFMA waits on its predecessor; the gradient products are formed TRANSPOSED (A = transposed LDS
 // fragment, B = the probabilities), which leaves each lane with four consecutive d of its own key / query row: 8-byte
 // stores instead of 2-byte ones.  The Q/dO stage is double buffered: one barrier per 32-query tile.
-template <bool DROP>
+template <typename H, bool DROP>
 __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(AttnParams p) {
     __shared__ __attribute__((aligned(16))) char lds[2 * QBUF];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h2 = lane >> 5, kl = lane & 31;
@@ -1740,8 +1737,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(AttnParams p) {
     const int b = bh_ / p.H, h = bh_ % p.H;
     const int T = p.T;
     const long RS = 3L * p.H * 64, OS = (long)p.H * 64;
-    const bf16_t* base = static_cast<const bf16_t*>(p.qkv) + (long)b * T * RS + h * 64;
-    const bf16_t* gbase = static_cast<const bf16_t*>(p.dout) + (long)b * T * OS + h * 64;
+    const H* base = static_cast<const H*>(p.qkv) + (long)b * T * RS + h * 64;
+    const H* gbase = static_cast<const H*>(p.dout) + (long)b * T * OS + h * 64;
     const float* lse_g = p.lse + ((long)b * p.H + h) * T;
     const float* del_g = p.delta + ((long)b * p.H + h) * T;
     const int nthr = blockDim.x;
@@ -1749,10 +1746,10 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(AttnParams p) {
     const bool kvalid = key < T;
     const float kb_ = (kvalid && (!p.mask || p.mask[(long)b * T + key] != 0)) ? 0.f : NEG;
 
-    bf16x8 kr[4], vr[4];     // this lane's K and V row chunks: B operands of S = Q.K^T and dP = dO.V^T
+    h16x8<H> kr[4], vr[4];     // this lane's K and V row chunks: B operands of S = Q.K^T and dP = dO.V^T
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-        union { u32x4 v; bf16x8 hh; } uk, uv;
+        union { u32x4 v; h16x8<H> hh; } uk, uv;
         uk.v = (u32x4){0u, 0u, 0u, 0u}; uv.v = uk.v;
         if (kvalid) {
             uk.v = *reinterpret_cast<const u32x4*>(base + (long)key * RS + p.H * 64 + (2 * kk + h2) * 8);
@@ -1834,11 +1831,11 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(AttnParams p) {
         const char* cg = cq + QT * QP;
         const float* cl = reinterpret_cast<const float*>(cq + 2 * QT * QP);
         // S[q][key], dP[q][key]: MFMA rows = queries (A from LDS), columns = keys (B = this lane's K / V row)
-        bf16x8 aq[4], ag[4];
+        h16x8<H> aq[4], ag[4];
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            aq[kk] = ld_bf16x8(cq + kl * QP + (2 * kk + h2) * 16);
-            ag[kk] = ld_bf16x8(cg + kl * QP + (2 * kk + h2) * 16);
+            aq[kk] = ld_h16x8<H>(cq + kl * QP + (2 * kk + h2) * 16);
+            ag[kk] = ld_h16x8<H>(cg + kl * QP + (2 * kk + h2) * 16);
         }
         __builtin_amdgcn_sched_barrier(0);
         f32x16 s, dp;
@@ -1846,8 +1843,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(AttnParams p) {
         for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            s = SS_MFMA_32x32x16(aq[kk], kr[kk], s, 0, 0, 0);
-            dp = SS_MFMA_32x32x16(ag[kk], vr[kk], dp, 0, 0, 0);
+            s = mfma_32x32x16(aq[kk], kr[kk], s);
+            dp = mfma_32x32x16(ag[kk], vr[kk], dp);
         }
         // requested while the MFMAs run: lse / delta of this lane's 16 query rows, and the transposed dO / Q fragments
         float4 l4[4], d4[4];
@@ -1856,13 +1853,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(AttnParams p) {
             l4[j] = *reinterpret_cast<const float4*>(cl + 8 * j + 4 * h2);
             d4[j] = *reinterpret_cast<const float4*>(cl + QT + 8 * j + 4 * h2);
         }
-        bf16x8 gf[4], qf[4];                              // index s2 * 2 + db
+        h16x8<H> gf[4], qf[4];                              // index s2 * 2 + db
         auto load_tr = [&]() {
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int off = (16 * (i >> 1) + 4 * h2 + (a16 >> 2)) * QP + ((i & 1) * 32 + 16 * g16 + 4 * (a16 & 3)) * 2;
-                gf[i] = tr_frag(cg + off, 8 * QP);        // dO^T fragment: [d][q-slots]
-                qf[i] = tr_frag(cq + off, 8 * QP);        // Q^T fragment
+                gf[i] = tr_frag<H>(cg + off, 8 * QP);        // dO^T fragment: [d][q-slots]
+                qf[i] = tr_frag<H>(cq + off, 8 * QP);        // Q^T fragment
             }
         };
         if (!DROP) load_tr();                             // (the dropout variant has no registers to spare for this overlap)
@@ -1891,13 +1888,13 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(AttnParams p) {
         }
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-            bf16x8 pf, df;
+            h16x8<H> pf, df;
 #pragma unroll
-            for (int e = 0; e < 8; ++e) { pf[e] = (bf16_t)pd[8 * s2 + e]; df[e] = (bf16_t)ds[8 * s2 + e]; }
+            for (int e = 0; e < 8; ++e) { pf[e] = (H)pd[8 * s2 + e]; df[e] = (H)ds[8 * s2 + e]; }
 #pragma unroll
             for (int db = 0; db < 2; ++db) {
-                dv[db] = SS_MFMA_32x32x16(gf[s2 * 2 + db], pf, dv[db], 0, 0, 0);
-                dk[db] = SS_MFMA_32x32x16(qf[s2 * 2 + db], df, dk[db], 0, 0, 0);
+                dv[db] = mfma_32x32x16(gf[s2 * 2 + db], pf, dv[db]);
+                dk[db] = mfma_32x32x16(qf[s2 * 2 + db], df, dk[db]);
             }
         }
         if (more) {
@@ -1908,19 +1905,19 @@ __global__ __launch_bounds__(512) void attn_bwd_dkv_kernel(AttnParams p) {
     }
     // dk/dv accumulators (transposed): column = this lane's key, rows d = db*32 + (r%4) + 8*(r/4) + 4*h2
     if (kvalid) {
-        bf16_t* drow = static_cast<bf16_t*>(p.dqkv) + (long)b * T * RS + h * 64 + (long)key * RS;
+        H* drow = static_cast<H*>(p.dqkv) + (long)b * T * RS + h * 64 + (long)key * RS;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4) {
                 const int d = db * 32 + 8 * r4 + 4 * h2;
-                store_bf16x4(drow + p.H * 64 + d, dk[db][4 * r4], dk[db][4 * r4 + 1], dk[db][4 * r4 + 2], dk[db][4 * r4 + 3]);
-                store_bf16x4(drow + 2 * p.H * 64 + d, dv[db][4 * r4], dv[db][4 * r4 + 1], dv[db][4 * r4 + 2], dv[db][4 * r4 + 3]);
+                store_h16x4(drow + p.H * 64 + d, dk[db][4 * r4], dk[db][4 * r4 + 1], dk[db][4 * r4 + 2], dk[db][4 * r4 + 3]);
+                store_h16x4(drow + 2 * p.H * 64 + d, dv[db][4 * r4], dv[db][4 * r4 + 1], dv[db][4 * r4 + 2], dv[db][4 * r4 + 3]);
             }
     }
 }
 
-template <bool DROP>
+template <typename H, bool DROP>
 __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(AttnParams p) {
     __shared__ __attribute__((aligned(16))) char lds[KT * KP16 + KT * KP16 + KT * 4];
     char* ldsK = lds;
@@ -1932,16 +1929,16 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(AttnParams p) {
     const int b = bh_ / p.H, h = bh_ % p.H;
     const int T = p.T;
     const long RS = 3L * p.H * 64, OS = (long)p.H * 64;
-    const bf16_t* base = static_cast<const bf16_t*>(p.qkv) + (long)b * T * RS + h * 64;
-    const bf16_t* gbase = static_cast<const bf16_t*>(p.dout) + (long)b * T * OS + h * 64;
+    const H* base = static_cast<const H*>(p.qkv) + (long)b * T * RS + h * 64;
+    const H* gbase = static_cast<const H*>(p.dout) + (long)b * T * OS + h * 64;
     const int nthr = blockDim.x;
     const int q = qb_ * (nthr >> 1) + wave * 32 + ql;
     const bool qvalid = q < T;
 
-    bf16x8 qr[4], gr[4];
+    h16x8<H> qr[4], gr[4];
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-        union { u32x4 v; bf16x8 hh; } uq, ug;
+        union { u32x4 v; h16x8<H> hh; } uq, ug;
         uq.v = (u32x4){0u, 0u, 0u, 0u}; ug.v = uq.v;
         if (qvalid) {
             uq.v = *reinterpret_cast<const u32x4*>(base + (long)q * RS + (2 * kk + h2) * 8);
@@ -1972,11 +1969,11 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(AttnParams p) {
         for (int kb = 0; kb < 2; ++kb) {
             if (kb == 1 && kv0 + 32 >= T) break;          // the second 32-key block is all padding
             // S^T[key][q], dP^T[key][q]: rows = keys (A from LDS), columns = queries (B = this lane's Q / dO row)
-            bf16x8 ak[4], av[4];
+            h16x8<H> ak[4], av[4];
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                ak[kk] = ld_bf16x8(ldsK + (kb * 32 + ql) * KP16 + (2 * kk + h2) * 16);
-                av[kk] = ld_bf16x8(ldsV + (kb * 32 + ql) * KP16 + (2 * kk + h2) * 16);
+                ak[kk] = ld_h16x8<H>(ldsK + (kb * 32 + ql) * KP16 + (2 * kk + h2) * 16);
+                av[kk] = ld_h16x8<H>(ldsV + (kb * 32 + ql) * KP16 + (2 * kk + h2) * 16);
             }
             __builtin_amdgcn_sched_barrier(0);
             f32x16 s, dp;
@@ -1984,16 +1981,16 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(AttnParams p) {
             for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                s = SS_MFMA_32x32x16(ak[kk], qr[kk], s, 0, 0, 0);
-                dp = SS_MFMA_32x32x16(av[kk], gr[kk], dp, 0, 0, 0);
+                s = mfma_32x32x16(ak[kk], qr[kk], s);
+                dp = mfma_32x32x16(av[kk], gr[kk], dp);
             }
             float4 b4[4];                                 // key bias of this lane's 16 key rows
 #pragma unroll
             for (int j = 0; j < 4; ++j) b4[j] = *reinterpret_cast<const float4*>(kbias + kb * 32 + 8 * j + 4 * h2);
-            bf16x8 kf[4];                                 // K^T fragments [d][key-slots], index s2 * 2 + db
+            h16x8<H> kf[4];                                 // K^T fragments [d][key-slots], index s2 * 2 + db
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-                kf[i] = tr_frag(ldsK + (kb * 32 + 16 * (i >> 1) + 4 * h2 + (a16 >> 2)) * KP16 + ((i & 1) * 32 + 16 * g16 + 4 * (a16 & 3)) * 2,
+                kf[i] = tr_frag<H>(ldsK + (kb * 32 + 16 * (i >> 1) + 4 * h2 + (a16 >> 2)) * KP16 + ((i & 1) * 32 + 16 * g16 + 4 * (a16 & 3)) * 2,
                                 8 * KP16);
             __builtin_amdgcn_sched_barrier(0);
             float ds[16];
@@ -2012,11 +2009,11 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(AttnParams p) {
             // dQ^T[d][q] += K^T[d][keys] . dS^T[keys][q]
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                bf16x8 df;
+                h16x8<H> df;
 #pragma unroll
-                for (int e = 0; e < 8; ++e) df[e] = (bf16_t)ds[8 * s2 + e];
+                for (int e = 0; e < 8; ++e) df[e] = (H)ds[8 * s2 + e];
 #pragma unroll
-                for (int db = 0; db < 2; ++db) dq[db] = SS_MFMA_32x32x16(kf[s2 * 2 + db], df, dq[db], 0, 0, 0);
+                for (int db = 0; db < 2; ++db) dq[db] = mfma_32x32x16(kf[s2 * 2 + db], df, dq[db]);
             }
         }
         if (more) {
@@ -2028,12 +2025,12 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(AttnParams p) {
     }
     // dq accumulators (transposed): column = this lane's query, rows d = db*32 + (r%4) + 8*(r/4) + 4*h2
     if (qvalid) {
-        bf16_t* drow = static_cast<bf16_t*>(p.dqkv) + (long)b * T * RS + h * 64 + (long)q * RS;
+        H* drow = static_cast<H*>(p.dqkv) + (long)b * T * RS + h * 64 + (long)q * RS;
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll
             for (int r4 = 0; r4 < 4; ++r4)
-                store_bf16x4(drow + db * 32 + 8 * r4 + 4 * h2, dq[db][4 * r4], dq[db][4 * r4 + 1], dq[db][4 * r4 + 2], dq[db][4 * r4 + 3]);
+                store_h16x4(drow + db * 32 + 8 * r4 + 4 * h2, dq[db][4 * r4], dq[db][4 * r4 + 1], dq[db][4 * r4 + 2], dq[db][4 * r4 + 3]);
     }
 }
 
@@ -2052,7 +2049,8 @@ __global__ __launch_bounds__(512) void attn_bwd_dq_kernel(AttnParams p) {
 __device__ __forceinline__ int qd_swz(int r) { return (3 * (r >> 1)) & 7; }
 
 // copy `rows32` rows of 128 B (row stride `stride` elements, rows >= T repeat row T-1) into the swizzled LDS image at dst
-__device__ __forceinline__ void res_copy_rows(const bf16_t* src, long stride, int T, int rows32, char* dst, int wave, int nw, int lane) {
+template <typename H>
+__device__ __forceinline__ void res_copy_rows(const H* src, long stride, int T, int rows32, char* dst, int wave, int nw, int lane) {
     for (int piece = wave; piece < (rows32 >> 3); piece += nw) {
         const int r = piece * 8 + (lane >> 3);
         const int c = (lane & 7) ^ qd_swz(r);
@@ -2062,8 +2060,9 @@ __device__ __forceinline__ void res_copy_rows(const bf16_t* src, long stride, in
     }
 }
 
-__device__ __forceinline__ bf16x8 tr_frag2(const char* pa, const char* pb) {
-    union { struct { s16x4 lo, hi; } h; bf16x8 v; } u;
+template <typename H>
+__device__ __forceinline__ h16x8<H> tr_frag2(const char* pa, const char* pb) {
+    union { struct { s16x4 lo, hi; } h; h16x8<H> v; } u;
     u.h.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(pa));
     u.h.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(pb));
     return u.v;
@@ -2092,7 +2091,7 @@ __host__ __device__ inline int one_smem(int T) {
     return 3 * rows32 * 128 + 2 * q32 * ONE_ST + 2 * rows32 * 4 + 8 * 256;      // (+ the landing pad of the next head's touches, 256 B per wave)
 }
 
-template <bool DROP>
+template <typename H, bool DROP>
 __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(1024))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), h2 = lane >> 5, kl = lane & 31;
@@ -2117,9 +2116,9 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
     if (p.trace && tid == 0) p.trace[(long)bh_ * 4] = wall_clock64();
     const long RS = p.rs, OS = (long)p.H * 64, HP = p.H * p.ps;               // HP: from a head's q plane to its k plane, k to v
     const long row0 = p.row_start ? (long)p.row_start[b] : (long)b * Tf;      // first row of this sequence in qkv / out / dout / dqkv
-    const bf16_t* base = static_cast<const bf16_t*>(p.qkv) + row0 * RS + h * p.ps;
-    const bf16_t* gbase = static_cast<const bf16_t*>(p.dout) + row0 * OS + h * 64;
-    const bf16_t* obase = static_cast<const bf16_t*>(p.out) + row0 * OS + h * 64;
+    const H* base = static_cast<const H*>(p.qkv) + row0 * RS + h * p.ps;
+    const H* gbase = static_cast<const H*>(p.dout) + row0 * OS + h * 64;
+    const H* obase = static_cast<const H*>(p.out) + row0 * OS + h * 64;
     const int q32 = (T + 31) / 32, rows32 = q32 * 32;
     char* ldsQ = lds;
     char* ldsG = lds + rows32 * 128;
@@ -2138,11 +2137,11 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
     const float lse_ld = p.lse[((long)b * p.H + h) * Tf + min(tid, T - 1)];
     // delta = rowsum(dO o O): eight lanes per query row, one 16-byte chunk each; O is requested here, dO is read from its LDS image
     const int per = nthr >> 3;                        // rows per pass; rows32 <= 4 * per (one wave per 32 rows)
-    bf16x8 o8[4];
+    h16x8<H> o8[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int q = (tid >> 3) + i * per;
-        union { u32x4 v; bf16x8 hh; } uo;
+        union { u32x4 v; h16x8<H> hh; } uo;
         uo.v = *reinterpret_cast<const u32x4*>(obase + (long)min(q, T - 1) * OS + (tid & 7) * 8);
         o8[i] = uo.hh;
     }
@@ -2154,10 +2153,10 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
 
     const int key = wave * 32 + kl;                   // this lane's key (dK / dV) and, for dQ, its query
     const bool kvalid = active && key < T;
-    bf16x8 kr[4], vr[4];         // this lane's K and V row chunks: B operands of S = Q.K^T and dP = dO.V^T (K from its image, below)
+    h16x8<H> kr[4], vr[4];         // this lane's K and V row chunks: B operands of S = Q.K^T and dP = dO.V^T (K from its image, below)
 #pragma unroll
     for (int kk = 0; kk < 4; ++kk) {
-        union { u32x4 v; bf16x8 hh; } uv;          // (keys >= T: row T-1, finite; their probabilities are exactly 0)
+        union { u32x4 v; h16x8<H> hh; } uv;          // (keys >= T: row T-1, finite; their probabilities are exactly 0)
         uv.v = *reinterpret_cast<const u32x4*>(base + (long)min(key, T - 1) * RS + 2 * HP + (2 * kk + h2) * 8);
         vr[kk] = uv.hh;
     }
@@ -2184,7 +2183,7 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
         const int q = (tid >> 3) + i * per;
         float d = 0.f;
         if (q < T) {
-            const bf16x8 g8 = ld_bf16x8(ldsG + q * 128 + (((tid & 7) ^ qd_swz(q)) << 4));
+            const h16x8<H> g8 = ld_h16x8<H>(ldsG + q * 128 + (((tid & 7) ^ qd_swz(q)) << 4));
 #pragma unroll
             for (int e = 0; e < 8; ++e) d += (float)o8[i][e] * (float)g8[e];
         }
@@ -2192,7 +2191,7 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
         if ((tid & 7) == 0 && q < rows32) del_l[q] = -d;             // MINUS delta (rows >= T: 0)
     }
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) kr[kk] = ld_bf16x8(ldsK + (active ? wave * 32 * 128 : 0) + arow + (((2 * kk + h2) ^ asw) << 4));
+    for (int kk = 0; kk < 4; ++kk) kr[kk] = ld_h16x8<H>(ldsK + (active ? wave * 32 * 128 : 0) + arow + (((2 * kk + h2) ^ asw) << 4));
     // (the dropout instantiation re-reads these four fragments from the K image in every step instead of holding them: its hash
     // arithmetic needs the 16 registers - spilled, a V fragment's scratch round trip sits in the prologue and in every step)
     __syncthreads();
@@ -2232,13 +2231,13 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
             const int q0 = qt * 32;
             const char* cq = ldsQ + q0 * 128;
             const char* cg = ldsG + q0 * 128;
-            bf16x8 aq[4], ag[4];
+            h16x8<H> aq[4], ag[4];
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
                 const int off = arow + (((2 * kk + h2) ^ asw) << 4);
-                aq[kk] = ld_bf16x8(cq + off);
-                ag[kk] = ld_bf16x8(cg + off);
-                if (DROP) kr[kk] = ld_bf16x8(ldsK + wave * 32 * 128 + off);
+                aq[kk] = ld_h16x8<H>(cq + off);
+                ag[kk] = ld_h16x8<H>(cg + off);
+                if (DROP) kr[kk] = ld_h16x8<H>(ldsK + wave * 32 * 128 + off);
             }
             __builtin_amdgcn_sched_barrier(0);
             // The accumulators start from the per-lane key bias (S) and from minus delta of their query rows (dP, straight from LDS), so the
@@ -2260,8 +2259,8 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
             }
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                s = SS_MFMA_32x32x16(aq[kk], kr[kk], s, 0, 0, 0);
-                dp = SS_MFMA_32x32x16(ag[kk], vr[kk], dp, 0, 0, 0);
+                s = mfma_32x32x16(aq[kk], kr[kk], s);
+                dp = mfma_32x32x16(ag[kk], vr[kk], dp);
             }
             // the rest in two halves of 16 query rows (MFMA step s2): lse / delta of the rows, the transposed dO / Q fragments, the
             // exponentials, then dV^T[d][key] += dO^T[d][q] . P[q][key] and dK^T[d][key] += Q^T[d][q] . dS[q][key].  (All 32 rows at
@@ -2275,17 +2274,17 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
                     l4[i] = *reinterpret_cast<const float4*>(lse_l + q0 + 8 * (2 * s2 + i) + 4 * h2);
                     if (DROP) d4[i] = *reinterpret_cast<const float4*>(del_l + q0 + 8 * (2 * s2 + i) + 4 * h2);
                 }
-                bf16x8 gf[2], qf[2];                          // index db
+                h16x8<H> gf[2], qf[2];                          // index db
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
                     const int ro = (16 * s2) * 128 + trow;
                     const int ca = (((db * 4 + tch) ^ tsw) << 4) + tsub, cb = (((db * 4 + tch) ^ tsw ^ 4) << 4) + tsub;
-                    gf[db] = tr_frag2(cg + ro + ca, cg + ro + 8 * 128 + cb);      // dO^T fragment: [d][q-slots]
-                    qf[db] = tr_frag2(cq + ro + ca, cq + ro + 8 * 128 + cb);      // Q^T fragment
+                    gf[db] = tr_frag2<H>(cg + ro + ca, cg + ro + 8 * 128 + cb);      // dO^T fragment: [d][q-slots]
+                    qf[db] = tr_frag2<H>(cq + ro + ca, cq + ro + 8 * 128 + cb);      // Q^T fragment
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 // lane: key column kl, rows q = (r%4) + 8*(r/4) + 4*h2
-                bf16x8 pf, df;
+                h16x8<H> pf, df;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const int r = 8 * s2 + e;
@@ -2297,21 +2296,21 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
                         const unsigned idx = ((unsigned)bh_ * Tf + (q0 + qq)) * Tf + key;
                         keep = dropout_keep32(seed_fold(p.drop_seed), idx, p.drop_thresh) ? p.drop_scale : 0.f;
                     }
-                    pf[e] = (bf16_t)(pr * keep);                                   // dropped probabilities feed dV
-                    if (DROP) df[e] = (bf16_t)(pr * (dp[r] * keep + reinterpret_cast<const float*>(&d4[e >> 2])[e & 3]));
-                    else df[e] = (bf16_t)(pr * dp[r]);                             // dS / scale feeds dK and dQ
+                    pf[e] = (H)(pr * keep);                                   // dropped probabilities feed dV
+                    if (DROP) df[e] = (H)(pr * (dp[r] * keep + reinterpret_cast<const float*>(&d4[e >> 2])[e & 3]));
+                    else df[e] = (H)(pr * dp[r]);                             // dS / scale feeds dK and dQ
                 }
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {                        // the same bf16 dS, staged [key][query] for the wave that owns query tile qt
-                    union { bf16_t hh[4]; uint2 u; } w;
+                    union { H hh[4]; uint2 u; } w;
 #pragma unroll
                     for (int e = 0; e < 4; ++e) w.hh[e] = df[4 * g + e];
                     *reinterpret_cast<uint2*>(mine + (8 * (2 * s2 + g)) * 2) = w.u;
                 }
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    dv[db] = SS_MFMA_32x32x16(gf[db], pf, dv[db], 0, 0, 0);
-                    dk[db] = SS_MFMA_32x32x16(qf[db], df, dk[db], 0, 0, 0);
+                    dv[db] = mfma_32x32x16(gf[db], pf, dv[db]);
+                    dk[db] = mfma_32x32x16(qf[db], df, dk[db]);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -2323,20 +2322,20 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
             if (kt < 0) kt += q32;
             const char* ck = ldsK + kt * 32 * 128;
             const char* src = stj + kt * ONE_ST + st_r;
-            bf16x8 kf[4];                                     // index s2 * 2 + db
+            h16x8<H> kf[4];                                     // index s2 * 2 + db
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int ro = (16 * (i >> 1)) * 128 + trow;
                 const int ca = ((((i & 1) * 4 + tch) ^ tsw) << 4) + tsub, cb = ((((i & 1) * 4 + tch) ^ tsw ^ 4) << 4) + tsub;
-                kf[i] = tr_frag2(ck + ro + ca, ck + ro + 8 * 128 + cb);
+                kf[i] = tr_frag2<H>(ck + ro + ca, ck + ro + 8 * 128 + cb);
             }
 #pragma unroll
             for (int s2 = 0; s2 < 2; ++s2) {
-                union { struct { s16x4 lo, hi; } hq; bf16x8 v; } u;
+                union { struct { s16x4 lo, hi; } hq; h16x8<H> v; } u;
                 u.hq.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(src + s2 * 16 * ONE_TP));
                 u.hq.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(src + s2 * 16 * ONE_TP + 8 * ONE_TP));
 #pragma unroll
-                for (int db = 0; db < 2; ++db) dq[db] = SS_MFMA_32x32x16(kf[s2 * 2 + db], u.v, dq[db], 0, 0, 0);
+                for (int db = 0; db < 2; ++db) dq[db] = mfma_32x32x16(kf[s2 * 2 + db], u.v, dq[db]);
             }
         }
     }
@@ -2349,16 +2348,16 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
     if (active) {
         constexpr int OP = 144;                       // bytes per staged row (128 + 16: 16-byte aligned rows)
         char* ob = stage + wave * (2 * ONE_ST);       // 32 x 144 = 4 608 B
-        bf16_t* dbase = static_cast<bf16_t*>(p.dqkv) + row0 * RS + h * p.ps + (long)(wave * 32) * RS;
+        H* dbase = static_cast<H*>(p.dqkv) + row0 * RS + h * p.ps + (long)(wave * 32) * RS;
         float* cpart = reinterpret_cast<float*>(ldsQ);                 // [wave][3][64] column sums (the operand images are free by now)
         auto put = [&](const f32x16 (&acc)[2], int sel, float mul) {
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
                 for (int r4 = 0; r4 < 4; ++r4) {
-                    union { bf16_t hh[4]; uint2 u; } w;
+                    union { H hh[4]; uint2 u; } w;
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) w.hh[e] = (bf16_t)(acc[db][4 * r4 + e] * mul);
+                    for (int e = 0; e < 4; ++e) w.hh[e] = (H)(acc[db][4 * r4 + e] * mul);
                     *reinterpret_cast<uint2*>(ob + kl * OP + (db * 32 + 8 * r4 + 4 * h2) * 2) = w.u;
                 }
             __builtin_amdgcn_wave_barrier();
@@ -2375,7 +2374,7 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
 #pragma unroll
                 for (int i = 0; i < 8; ++i) {
                     const int row = rg + 4 * i;
-                    union { uint2 u; bf16_t hh[4]; } v;
+                    union { uint2 u; H hh[4]; } v;
                     v.u = *reinterpret_cast<const uint2*>(ob + row * OP + cg * 8);        // (unconditional: a branch per row serialises the eight reads)
                     const float keepf = row < nrow ? 1.f : 0.f;
 #pragma unroll
@@ -2405,11 +2404,11 @@ __global__ __launch_bounds__(512) void attn_bwd_one_kernel(AttnParams p) {
     if (p.trace && tid == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); p.trace[(long)bh_ * 4 + 3] = wall_clock64(); }
 }
 
-template <bool DROP>
+template <typename H, bool DROP>
 int launch_bwd_one(const AttnParams& p, hipStream_t stream) {
     static bool configured = false;
     if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_one_kernel<DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, one_smem(ONE_MAXT));
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attn_bwd_one_kernel<H, DROP>), hipFuncAttributeMaxDynamicSharedMemorySize, one_smem(ONE_MAXT));
         if (e != hipSuccess) return simseg_set_error("attention_bwd: cannot reserve LDS: %s", hipGetErrorString(e));
         configured = true;
     }
@@ -2423,7 +2422,7 @@ int launch_bwd_one(const AttnParams& p, hipStream_t stream) {
     // one block per CU is resident (LDS) for T > 128; shorter sequences fit two
     const int per_cu = one_smem(p.T) > 80 * 1024 ? 1 : 2;
     q.pf_stride = (cus > 0 && per_cu == 1 && (long)p.B * p.H > (long)cus) ? cus : 0;      // (two blocks per CU - T = 77 - measured 9 % slower with them)
-    hipLaunchKernelGGL(attn_bwd_one_kernel<DROP>, dim3((unsigned)(p.B * p.H)), dim3(q32 * 64), one_smem(p.T), stream, q);
+    hipLaunchKernelGGL((attn_bwd_one_kernel<H, DROP>), dim3((unsigned)(p.B * p.H)), dim3(q32 * 64), one_smem(p.T), stream, q);
     return 0;
 }
 
@@ -2449,9 +2448,12 @@ int w64_forced_nqb() { return g_attn_variant == 6 ? 1 : (g_attn_variant == 7 ? 2
 
 // the resident forward's instantiation for p: dropout implies the key-bias form, as does a key mask
 int launch_fwd_res_for(const AttnParams& p, hipStream_t stream) {
-    if (p.drop_thresh) return launch_fwd_res<true, true>(p, stream);
-    if (p.mask) return launch_fwd_res<false, true>(p, stream);
-    return launch_fwd_res<false, false>(p, stream);
+    return with_h16(g_ss_half, [&](auto tag) {
+        typedef typename decltype(tag)::type H;
+        if (p.drop_thresh) return launch_fwd_res<H, true, true>(p, stream);
+        if (p.mask) return launch_fwd_res<H, false, true>(p, stream);
+        return launch_fwd_res<H, false, false>(p, stream);
+    });
 }
 
 int fill_params(AttnParams& p, const void* qkv, const int64_t* mask, int64_t B, int64_t T, int64_t H, float scale,
@@ -2477,7 +2479,11 @@ int fill_params(AttnParams& p, const void* qkv, const int64_t* mask, int64_t B, 
 // 4.7 MB at the training shape instead of a pass over the 465 MB of dqkv)
 int run_bwd_one(AttnParams& p, float* workspace, float* dqkv_colsum, const char* what, void* stream) {
     p.colsum_ws = dqkv_colsum ? workspace + (long)p.B * p.H * p.T : nullptr;
-    if (int rc = p.drop_thresh ? launch_bwd_one<true>(p, (hipStream_t)stream) : launch_bwd_one<false>(p, (hipStream_t)stream)) return rc;
+    if (int rc = with_h16(g_ss_half, [&](auto tag) {
+            typedef typename decltype(tag)::type H;
+            return p.drop_thresh ? launch_bwd_one<H, true>(p, (hipStream_t)stream) : launch_bwd_one<H, false>(p, (hipStream_t)stream);
+        }))
+        return rc;
     SS_LAUNCH_CHECK(what);
     if (dqkv_colsum) return ss_colsum_accum(p.colsum_ws, SS_ELEM_F32, dqkv_colsum, p.B, 3 * p.H * 64, 3 * p.H * 64, stream);
     return 0;
@@ -2489,10 +2495,7 @@ int run_bwd_one(AttnParams& p, float* workspace, float* dqkv_colsum, const char*
 extern "C" int simseg_debug_attn_trace(void* buf) { g_attn_trace = static_cast<unsigned long long*>(buf); return 0; }
 
 extern "C" int simseg_set_attention_variant(int v) {
-#ifndef SS_HALF
     SS_CHECK(v == 0 || v == 1 || v == 6 || v == 7, "set_attention_variant: %d is not a kernel selection (0 = auto, 1 = ring kernels, 6 / 7 = w64 forward with one / two query blocks per wave)", v);
-    simseg_set_attention_variant_h16(v);      // the fp16 flavour keeps its own (thread-local) selector; v is checked here, once, for both
-#endif
     g_attn_variant = v;
     return 0;
 }
@@ -2501,7 +2504,6 @@ extern "C" int simseg_set_attention_variant(int v) {
 extern "C" int simseg_attention_fwd(const void* qkv, const int64_t* key_mask, void* out, float* lse, int dtype, int64_t B,
                                     int64_t T, int64_t H, float scale, uint64_t drop_seed, float drop_p, int skip_padded_rows,
                                     void* stream) {
-    SS_HALF_FWD(simseg_attention_fwd, qkv, key_mask, out, lse, dtype, B, T, H, scale, drop_seed, drop_p, skip_padded_rows, stream);
     AttnParams p;
     if (int rc = fill_params(p, qkv, key_mask, B, T, H, scale, drop_seed, drop_p)) return rc;
     p.pack = skip_padded_rows && key_mask && dtype == 1 && T <= RES_MAXT;
@@ -2518,11 +2520,14 @@ extern "C" int simseg_attention_fwd(const void* qkv, const int64_t* key_mask, vo
         hipLaunchKernelGGL(attn_fwd_f32_kernel, grid, block, 0, (hipStream_t)stream, p);
     else if (T <= RES_MAXT && !ring && !(nqb && w64)) {          // (a forced 6 / 7 pre-empts the resident kernel where the w64 forward applies)
         if (int rc = launch_fwd_res_for(p, (hipStream_t)stream)) return rc;
-    } else if (w64)
-        launch_w64<false>(p, (hipStream_t)stream, nqb);
-    else if (p.drop_thresh) hipLaunchKernelGGL((attn_fwd_bf16_kernel<true, true, false>), grid, block, 0, (hipStream_t)stream, p);
-    else if (p.mask) hipLaunchKernelGGL((attn_fwd_bf16_kernel<false, true, false>), grid, block, 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((attn_fwd_bf16_kernel<false, false, false>), grid, block, 0, (hipStream_t)stream, p);
+    } else
+        with_h16(g_ss_half, [&](auto tag) {
+            typedef typename decltype(tag)::type H16;      // (H is the head count here)
+            if (w64) launch_w64<H16, false>(p, (hipStream_t)stream, nqb);
+            else if (p.drop_thresh) hipLaunchKernelGGL((attn_fwd_bf16_kernel<H16, true, true, false>), grid, block, 0, (hipStream_t)stream, p);
+            else if (p.mask) hipLaunchKernelGGL((attn_fwd_bf16_kernel<H16, false, true, false>), grid, block, 0, (hipStream_t)stream, p);
+            else hipLaunchKernelGGL((attn_fwd_bf16_kernel<H16, false, false, false>), grid, block, 0, (hipStream_t)stream, p);
+        });
     SS_LAUNCH_CHECK("attention_fwd");
     return 0;
 }
@@ -2531,13 +2536,12 @@ extern "C" int simseg_attention_fwd(const void* qkv, const int64_t* key_mask, vo
 // of the projection weight and bias before rounding them to 16 bits: the product is rounded once, as q itself would have been, where the
 // kernel's own scaling of a 16-bit q rounds a second time).  T >= 512, no mask, no dropout; lse (optional) in the log2 domain as above.
 extern "C" int simseg_attention_fwd_qscaled(const void* qkv, void* out, float* lse, int64_t B, int64_t T, int64_t H, void* stream) {
-    SS_HALF_FWD(simseg_attention_fwd_qscaled, qkv, out, lse, B, T, H, stream);
     AttnParams p;
     if (int rc = fill_params(p, qkv, nullptr, B, T, H, 1.0f, 0, 0.f)) return rc;
     SS_CHECK(out, "attention_fwd_qscaled: null out");
     SS_CHECK(T >= W64_MINT, "attention_fwd_qscaled: sequences of at least %d tokens", W64_MINT);
     p.out = out; p.lse = lse; p.qscaled = 1;
-    launch_w64<false>(p, (hipStream_t)stream, w64_forced_nqb());
+    with_h16(g_ss_half, [&](auto tag) { launch_w64<typename decltype(tag)::type, false>(p, (hipStream_t)stream, w64_forced_nqb()); });
     SS_LAUNCH_CHECK("attention_fwd_qscaled");
     return 0;
 }
@@ -2555,7 +2559,7 @@ extern "C" int simseg_attention_fwd_x3(const void* qkv3, int64_t plane_elems, fl
         configured = true;
     }
     AttnX3Params p;
-    p.qkv3 = static_cast<const bf16_t*>(qkv3); p.plane = (long)plane_elems; p.out = out; p.B = (int)B; p.T = (int)T; p.H = (int)H;
+    p.qkv3 = static_cast<const __bf16*>(qkv3); p.plane = (long)plane_elems; p.out = out; p.B = (int)B; p.T = (int)T; p.H = (int)H;
     p.scale_log2e = scale * 1.4426950408889634f;
     // waves (32-query tiles) per block: 4..8, the count that leaves the fewest padding waves in a head's last block (33 tiles at
     // T = 1025: five blocks of 7; 11 at T = 325: two of 6); ties go to the larger block
@@ -2579,9 +2583,9 @@ extern "C" int simseg_debug_attention_timeline(const void* qkv, void* out, float
     if (int rc = fill_params(p, qkv, nullptr, B, T, H, 0.125f, 0, 0.f)) return rc;
     p.out = out; p.lse = lse; p.delta = reinterpret_cast<const float*>(dbg);
     if (T >= W64_MINT && (T - 1) % 64 == 0 && g_attn_variant != 1)      // the w64 kernel's record layout: see the end of attn_fwd_w64_kernel
-        { p.qscaled = 1; launch_w64<true>(p, (hipStream_t)stream, w64_forced_nqb()); }      // (timing only: q taken as pre-scaled)
+        { p.qscaled = 1; launch_w64<__bf16, true>(p, (hipStream_t)stream, w64_forced_nqb()); }      // (timing only: q taken as pre-scaled)
     else
-        hipLaunchKernelGGL((attn_fwd_bf16_kernel<false, false, true>), dim3(attn_ring_grid(B, T, H)), dim3(attn_waves_per_block((int)((T + 31) / 32)) * 64), 0,
+        hipLaunchKernelGGL((attn_fwd_bf16_kernel<__bf16, false, false, true>), dim3(attn_ring_grid(B, T, H)), dim3(attn_waves_per_block((int)((T + 31) / 32)) * 64), 0,
                            (hipStream_t)stream, p);
     SS_LAUNCH_CHECK("attention_timeline");
     return 0;
@@ -2596,7 +2600,6 @@ extern "C" int64_t simseg_attention_bwd_workspace_bytes(int64_t B, int64_t T, in
 extern "C" int simseg_attention_bwd(const void* qkv, const int64_t* key_mask, const void* out, const void* dout, const float* lse,
                                     float* workspace, void* dqkv, float* dqkv_colsum, int dtype, int64_t B, int64_t T, int64_t H, float scale,
                                     uint64_t drop_seed, float drop_p, int skip_padded_rows, void* stream) {
-    SS_HALF_FWD(simseg_attention_bwd, qkv, key_mask, out, dout, lse, workspace, dqkv, dqkv_colsum, dtype, B, T, H, scale, drop_seed, drop_p, skip_padded_rows, stream);
     float* delta = workspace;
     AttnParams p;
     if (int rc = fill_params(p, qkv, key_mask, B, T, H, scale, drop_seed, drop_p)) return rc;
@@ -2621,17 +2624,20 @@ extern "C" int simseg_attention_bwd(const void* qkv, const int64_t* key_mask, co
     }
     if (T <= ONE_MAXT && g_attn_variant != 1) return run_bwd_one(p, workspace, dqkv_colsum, "attention_bwd", stream);
     const long groups = B * T * H;
-    hipLaunchKernelGGL(attn_delta_kernel, dim3((unsigned)((groups * 8 + 255) / 256)), dim3(256), 0, s, (const bf16_t*)out,
-                       (const bf16_t*)dout, delta, (int)B, (int)T, (int)H);
-    if (p.drop_thresh) {
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<true>, grid, block, 0, s, p);
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<true>, grid, block, 0, s, p);
-    } else {
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<false>, grid, block, 0, s, p);
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<false>, grid, block, 0, s, p);
-    }
+    with_h16(g_ss_half, [&](auto tag) {
+        typedef typename decltype(tag)::type H16;      // (H is the head count here)
+        hipLaunchKernelGGL(attn_delta_kernel<H16>, dim3((unsigned)((groups * 8 + 255) / 256)), dim3(256), 0, s, (const H16*)out,
+                           (const H16*)dout, delta, (int)B, (int)T, (int)H);
+        if (p.drop_thresh) {
+            hipLaunchKernelGGL((attn_bwd_dkv_kernel<H16, true>), grid, block, 0, s, p);
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<H16, true>), grid, block, 0, s, p);
+        } else {
+            hipLaunchKernelGGL((attn_bwd_dkv_kernel<H16, false>), grid, block, 0, s, p);
+            hipLaunchKernelGGL((attn_bwd_dq_kernel<H16, false>), grid, block, 0, s, p);
+        }
+    });
     SS_LAUNCH_CHECK("attention_bwd");
-    if (dqkv_colsum) return ss_colsum_accum(dqkv, ELEM16, dqkv_colsum, B * T, 3 * H * 64, 3 * H * 64, stream);
+    if (dqkv_colsum) return ss_colsum_accum(dqkv, g_ss_half, dqkv_colsum, B * T, 3 * H * 64, 3 * H * 64, stream);
     return 0;
 }
 
@@ -2643,7 +2649,6 @@ extern "C" int simseg_attention_bwd(const void* qkv, const int64_t* key_mask, co
 // dense entry points: for prefix masks the same probabilities are dropped.  bf16 only.
 extern "C" int simseg_attention_fwd_rows(const void* qkv, const int32_t* row_start, void* out, float* lse, int64_t B, int64_t T, int64_t H,
                                          float scale, uint64_t drop_seed, float drop_p, void* stream) {
-    SS_HALF_FWD(simseg_attention_fwd_rows, qkv, row_start, out, lse, B, T, H, scale, drop_seed, drop_p, stream);
     AttnParams p;
     if (int rc = fill_params(p, qkv, nullptr, B, T, H, scale, drop_seed, drop_p)) return rc;
     SS_CHECK(out && row_start, "attention_fwd_rows: null pointer");
@@ -2657,7 +2662,6 @@ extern "C" int simseg_attention_fwd_rows(const void* qkv, const int32_t* row_sta
 extern "C" int simseg_attention_bwd_rows(const void* qkv, const int32_t* row_start, const void* out, const void* dout, const float* lse,
                                          float* workspace, void* dqkv, float* dqkv_colsum, int64_t B, int64_t T, int64_t H, float scale,
                                          uint64_t drop_seed, float drop_p, void* stream) {
-    SS_HALF_FWD(simseg_attention_bwd_rows, qkv, row_start, out, dout, lse, workspace, dqkv, dqkv_colsum, B, T, H, scale, drop_seed, drop_p, stream);
     AttnParams p;
     if (int rc = fill_params(p, qkv, nullptr, B, T, H, scale, drop_seed, drop_p)) return rc;
     SS_CHECK(out && dout && lse && workspace && dqkv && row_start, "attention_bwd_rows: null pointer");
@@ -2673,7 +2677,6 @@ extern "C" int simseg_attention_bwd_rows(const void* qkv, const int32_t* row_sta
 // row_start is null (dense batch, no key mask), else rows [row_start[b], row_start[b + 1]) as in the *_rows entry points.  T <= 256, 16-bit only.
 extern "C" int simseg_attention_fwd_planes(const void* qkv, int64_t plane_rows, const int32_t* row_start, void* out, float* lse, int64_t B, int64_t T,
                                            int64_t H, float scale, uint64_t drop_seed, float drop_p, void* stream) {
-    SS_HALF_FWD(simseg_attention_fwd_planes, qkv, plane_rows, row_start, out, lse, B, T, H, scale, drop_seed, drop_p, stream);
     AttnParams p;
     if (int rc = fill_params(p, qkv, nullptr, B, T, H, scale, drop_seed, drop_p)) return rc;
     SS_CHECK(out, "attention_fwd_planes: null pointer");
@@ -2688,7 +2691,6 @@ extern "C" int simseg_attention_fwd_planes(const void* qkv, int64_t plane_rows, 
 extern "C" int simseg_attention_bwd_planes(const void* qkv, int64_t plane_rows, const int32_t* row_start, const void* out, const void* dout,
                                            const float* lse, float* workspace, void* dqkv, float* dqkv_colsum, int64_t B, int64_t T, int64_t H,
                                            float scale, uint64_t drop_seed, float drop_p, void* stream) {
-    SS_HALF_FWD(simseg_attention_bwd_planes, qkv, plane_rows, row_start, out, dout, lse, workspace, dqkv, dqkv_colsum, B, T, H, scale, drop_seed, drop_p, stream);
     AttnParams p;
     if (int rc = fill_params(p, qkv, nullptr, B, T, H, scale, drop_seed, drop_p)) return rc;
     SS_CHECK(out && dout && lse && workspace && dqkv, "attention_bwd_planes: null pointer");

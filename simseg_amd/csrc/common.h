@@ -5,34 +5,12 @@
 #include <stdio.h>
 #include <string.h>
 
-// The 16-bit operand type.  gemm.hip and attn.hip are compiled TWICE (simseg_amd/build.py): as they stand - bf16, the
-// headline mode - and with -DSS_HALF, where the same sources are the IEEE fp16 flavour the reference's AMP mode uses (fp16 autocast + a
-// live GradScaler, clip_runner.py:226-230): `bf16_t` is then _Float16, the MFMA is v_mfma_f32_32x32x16_f16, and every C-ABI entry point
-// the file defines carries the suffix _h16 (half_names.h renames them by macro).  The bf16 build's entry points hand a call over to their
-// _h16 twin while the calling thread has selected fp16 (simseg_set_half_type(2)); dtype code 1 always means "the selected 16-bit type".
-// Only entry points whose kernels differ between the flavours - the MFMA builtin and the loops around it - belong in those two files.
-// Every other source is compiled ONCE: where one of its kernels touches 16-bit data (rowops.hip, optim.hip, probe.hip, mixup.hip,
-// patchdrop.hip) the type is a template argument picked per call from g_ss_half (with_h16 below), and fp32-only code (loss.hip) has no
-// flavour at all.
-#ifdef SS_HALF
-typedef _Float16 bf16_t;
-#define SS_MFMA_32x32x16(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, x, y, z)
-#else
-typedef __bf16 bf16_t;
-#define SS_MFMA_32x32x16(a, b, c, x, y, z) __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, x, y, z)
-#endif
-typedef __attribute__((ext_vector_type(8))) bf16_t bf16x8;
-typedef __attribute__((ext_vector_type(4))) bf16_t bf16x4;
-#include "half_names.h"
-#ifndef SS_HALF
+// The 16-bit operand type is __bf16 (the headline mode) or _Float16 (the IEEE fp16 the reference's AMP mode uses: fp16 autocast + a live
+// GradScaler, clip_runner.py:226-230).  Every source is compiled ONCE.  A kernel or device helper that touches 16-bit data takes the type
+// as its leading template argument `H`; an entry point picks it per call from g_ss_half - what the calling thread selected with
+// simseg_set_half_type - through with_h16 below, and dtype code 1 always means "the selected 16-bit type".  Host state (selectors, trace
+// pointers, last-variant values) exists once per thread; fp32 kernels have one instantiation whatever the thread selected.
 extern thread_local int g_ss_half;          // 1 = bf16 (default), 2 = fp16: simseg_set_half_type
-#define SS_HALF_FWD(name, ...)                                  \
-    do {                                                        \
-        if (g_ss_half == 2) return name##_h16(__VA_ARGS__);     \
-    } while (0)
-#else
-#define SS_HALF_FWD(name, ...)
-#endif
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(8))) short s16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
@@ -58,24 +36,25 @@ int simseg_set_error(const char* fmt, ...);
     } while (0)
 
 // ---- numeric helpers --------------------------------------------------------------------------
-__device__ __forceinline__ float bf2f(bf16_t v) { return (float)v; }
-__device__ __forceinline__ float half_bits_to_float(short bits) {      // a 16-bit operand that travelled as raw bits (transposing LDS reads)
-    union { short s; bf16_t h; } u;
-    u.s = bits;
-    return (float)u.h;
-}
-__device__ __forceinline__ bf16_t f2bf(float v) { return (bf16_t)v; }
-
-// The once-compiled sources name the two 16-bit types themselves (never bf16_t, which is one of them per build of gemm.hip / attn.hip).
 // Element type of a buffer where a call states it outright instead of through dtype code 1: the values g_ss_half takes, and 0 for fp32.
 enum { SS_ELEM_F32 = 0, SS_ELEM_BF16 = 1, SS_ELEM_FP16 = 2 };
 template <typename H> struct h16_tag { typedef H type; };
-// f(h16_tag<H>()) for the 16-bit type `half` names (g_ss_half at an entry point): `[&](auto tag) { typedef typename decltype(tag)::type H; ... }`
-template <typename F> inline void with_h16(int half, F&& f) {
-    if (half == SS_ELEM_FP16) f(h16_tag<_Float16>());
-    else f(h16_tag<__bf16>());
+// f(h16_tag<H>()) for the 16-bit type `half` names (g_ss_half at an entry point): `[&](auto tag) { typedef typename decltype(tag)::type H; ... }`;
+// returns what f returns (an entry point's int status, or nothing)
+template <typename F> inline auto with_h16(int half, F&& f) {
+    if (half == SS_ELEM_FP16) return f(h16_tag<_Float16>());
+    return f(h16_tag<__bf16>());
 }
 template <typename H> using h16x4 = H __attribute__((ext_vector_type(4)));
+template <typename H> using h16x8 = H __attribute__((ext_vector_type(8)));
+
+// acc + a . b on the 32x32x16 MFMA of the operands' type: v_mfma_f32_32x32x16_bf16 / v_mfma_f32_32x32x16_f16
+__device__ __forceinline__ f32x16 mfma_32x32x16(h16x8<__bf16> a, h16x8<__bf16> b, f32x16 acc) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0);
+}
+__device__ __forceinline__ f32x16 mfma_32x32x16(h16x8<_Float16> a, h16x8<_Float16> b, f32x16 acc) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0);
+}
 
 // 16 bytes (fp32) / 8 bytes (16-bit) of a row to and from four floats: the row kernels' unit of access (rowops.hip, patchdrop.hip)
 template <typename TO> __device__ __forceinline__ void store4(TO* p, const float (&v)[4]);

@@ -4,7 +4,7 @@
 //     C[M,N] = epilogue( alpha * opA(A)[M,K] . opB(B)[K,N] )
 //
 // Five kernels, numbered as simseg_set_gemm_variant / simseg_gemm_last_variant number them; every instantiation in this file is one the
-// automatic dispatch (selector 0; dispatch_bf16 and the tail of simseg_gemm) reaches for some valid call:
+// automatic dispatch (selector 0; dispatch_h16 and the tail of simseg_gemm) reaches for some valid call:
 //    4  gemm_small_kernel   32x64 / 64x64 tiles, the K slab split between wave groups: k-contiguous fp32 or 16-bit problems that leave
 //                           the 128x128 tiling with fewer than 160 (fp32: 200) blocks - the batch-1 evaluation shapes
 //    3  gemm_pp_kernel      256x256 ping-pong kernel, one tile per block: 16-bit forward / dgrad problems of >= 96 tiles with a long
@@ -79,7 +79,8 @@ struct GemmParams {
 
 template <typename T> struct TT;
 template <> struct TT<float> { static constexpr int EPC = 4, BK = 32; };
-template <> struct TT<bf16_t> { static constexpr int EPC = 8, BK = 64; };
+template <> struct TT<__bf16> { static constexpr int EPC = 8, BK = 64; };
+template <> struct TT<_Float16> { static constexpr int EPC = 8, BK = 64; };
 
 // ---- global -> register staging ----------------------------------------------------------------
 template <typename T, bool TRANS, bool AL, int KB>
@@ -151,9 +152,9 @@ __device__ __forceinline__ u32x4 read_frag(const char* lds, int row32, int kk, i
 template <typename T>
 __device__ __forceinline__ void mma(f32x16& acc, const u32x4& a, const u32x4& b) {
     if constexpr (sizeof(T) == 2) {
-        union { u32x4 v; bf16x8 h; } ua, ub;
+        union { u32x4 v; h16x8<T> h; } ua, ub;
         ua.v = a; ub.v = b;
-        acc = SS_MFMA_32x32x16(ua.h, ub.h, acc, 0, 0, 0);
+        acc = mfma_32x32x16(ua.h, ub.h, acc);
     } else {
         union { u32x4 v; float f[4]; } ua, ub;
         ua.v = a; ub.v = b;
@@ -186,20 +187,22 @@ template <> struct Vec8<float> {
         *reinterpret_cast<float4*>(p + 4) = make_float4(v[4], v[5], v[6], v[7]);
     }
 };
-template <> struct Vec8<bf16_t> {
-    static __device__ __forceinline__ void load(const bf16_t* p, float (&v)[8]) {
-        union { u32x4 q; bf16x8 h; } u;
+template <typename H> struct Vec8h16 {
+    static __device__ __forceinline__ void load(const H* p, float (&v)[8]) {
+        union { u32x4 q; h16x8<H> h; } u;
         u.q = *reinterpret_cast<const u32x4*>(p);
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = (float)u.h[e];
     }
-    static __device__ __forceinline__ void store(bf16_t* p, const float (&v)[8]) {
-        union { u32x4 q; bf16x8 h; } u;
+    static __device__ __forceinline__ void store(H* p, const float (&v)[8]) {
+        union { u32x4 q; h16x8<H> h; } u;
 #pragma unroll
-        for (int e = 0; e < 8; ++e) u.h[e] = (bf16_t)v[e];
+        for (int e = 0; e < 8; ++e) u.h[e] = (H)v[e];
         *reinterpret_cast<u32x4*>(p) = u.q;
     }
 };
+template <> struct Vec8<__bf16> : Vec8h16<__bf16> {};
+template <> struct Vec8<_Float16> : Vec8h16<_Float16> {};
 
 // Emits rows [row0, row0+32) x cols [col0, col0+64) from two 32x32 accumulators (left/right 32 columns).
 // col1 = first output column of the RIGHT 32 staged columns (col0 + 32 for the contiguous tilings; the ping-pong kernel gives a wave
@@ -491,7 +494,7 @@ __global__ __launch_bounds__(NTHREADS) void simmap_kernel(const T* __restrict__ 
                 union { u32x4 v; float f[4]; } u; u.v = fa;
                 ss += u.f[0] * u.f[0] + u.f[1] * u.f[1] + u.f[2] * u.f[2] + u.f[3] * u.f[3];
             } else {
-                union { u32x4 v; bf16x8 h; } u; u.v = fa;
+                union { u32x4 v; h16x8<T> h; } u; u.v = fa;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) { const float f = (float)u.h[e]; ss += f * f; }
             }
@@ -589,8 +592,8 @@ int launch(const GemmParams& p, int splitk, hipStream_t stream) {
 template <int BKE> __device__ __forceinline__ int kc_swz(int r) { return BKE == 64 ? ((r >> 1) & 7) : ((r >> 2) & 3); }
 
 // issue the global->LDS copies of one operand slab (ROWS tile rows/cols x BKE k) for this wave
-template <int BKE, bool TRANS, int ROWS, int NW>
-__device__ __forceinline__ void glds_slab(const bf16_t* __restrict__ base, long ld, int row0, int lim, int k0, char* lds_slab,
+template <typename H, int BKE, bool TRANS, int ROWS, int NW>
+__device__ __forceinline__ void glds_slab(const H* __restrict__ base, long ld, int row0, int lim, int k0, char* lds_slab,
                                           int wave, int lane) {
     constexpr int SLAB = ROWS * BKE * 2;
     constexpr int NI = SLAB / 1024 / NW;             // 1-KiB pieces per wave
@@ -598,7 +601,7 @@ __device__ __forceinline__ void glds_slab(const bf16_t* __restrict__ base, long 
 #pragma unroll
     for (int i = 0; i < NI; ++i) {
         const int piece = wave * NI + i;
-        const bf16_t* src;
+        const H* src;
         if (!TRANS) {
             constexpr int SPR = BKE / 8;                 // 16-B slots per row
             constexpr int RPP = 64 / SPR;                // rows per 1-KiB piece
@@ -644,7 +647,7 @@ __device__ __forceinline__ u32x4 read_frag_l(const char* slab, int row32, int kk
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // TM x TN block tile, 8 waves as WM_ x WN_, each wave (TM/WM_) x (TN/WN_) = FM x FN MFMA 32x32 blocks.
-template <typename TO, bool TA, bool TB, int BKE, int NSTAGE, int TM, int TN, int WM_, int WN_, int MINW>
+template <typename H, typename TO, bool TA, bool TB, int BKE, int NSTAGE, int TM, int TN, int WM_, int WN_, int MINW>
 __global__ __launch_bounds__(WM_ * WN_ * 64, MINW) void gemm_large_kernel(GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     constexpr int NW = WM_ * WN_;
@@ -666,8 +669,8 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, MINW) void gemm_large_kernel(GemmPa
     const int nk = p.K / BKE;
     const int kt0 = kz * p.ksplit;
     const int kt1 = min(nk, kt0 + p.ksplit);
-    const bf16_t* A = static_cast<const bf16_t*>(p.A);
-    const bf16_t* B = static_cast<const bf16_t*>(p.B);
+    const H* A = static_cast<const H*>(p.A);
+    const H* B = static_cast<const H*>(p.B);
 
     f32x16 acc[FM][FN];
     {
@@ -681,8 +684,8 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, MINW) void gemm_large_kernel(GemmPa
 #pragma unroll
     for (int s = 0; s < NSTAGE - 1; ++s) {
         if (kt0 + s < kt1) {
-            glds_slab<BKE, TA, TM, NW>(A, p.lda, m0, p.M, (kt0 + s) * BKE, lds + s * STAGE, wave, lane);
-            glds_slab<BKE, TB, TN, NW>(B, p.ldb, n0, p.N, (kt0 + s) * BKE, lds + s * STAGE + SLAB_A, wave, lane);
+            glds_slab<H, BKE, TA, TM, NW>(A, p.lda, m0, p.M, (kt0 + s) * BKE, lds + s * STAGE, wave, lane);
+            glds_slab<H, BKE, TB, TN, NW>(B, p.ldb, n0, p.N, (kt0 + s) * BKE, lds + s * STAGE + SLAB_A, wave, lane);
         }
     }
     int stage = 0;
@@ -700,8 +703,8 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, MINW) void gemm_large_kernel(GemmPa
         const int nxt = kt + NSTAGE - 1;
         if (nxt < kt1) {
             int ns = stage + NSTAGE - 1; ns = ns >= NSTAGE ? ns - NSTAGE : ns;
-            glds_slab<BKE, TA, TM, NW>(A, p.lda, m0, p.M, nxt * BKE, lds + ns * STAGE, wave, lane);
-            glds_slab<BKE, TB, TN, NW>(B, p.ldb, n0, p.N, nxt * BKE, lds + ns * STAGE + SLAB_A, wave, lane);
+            glds_slab<H, BKE, TA, TM, NW>(A, p.lda, m0, p.M, nxt * BKE, lds + ns * STAGE, wave, lane);
+            glds_slab<H, BKE, TB, TN, NW>(B, p.ldb, n0, p.N, nxt * BKE, lds + ns * STAGE + SLAB_A, wave, lane);
         }
         const char* sa = lds + stage * STAGE;
         const char* sb = sa + SLAB_A;
@@ -715,7 +718,7 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, MINW) void gemm_large_kernel(GemmPa
 #pragma unroll
             for (int i = 0; i < FM; ++i)
 #pragma unroll
-                for (int j = 0; j < FN; ++j) mma<bf16_t>(acc[i][j], fa[i], fb[j]);
+                for (int j = 0; j < FN; ++j) mma<H>(acc[i][j], fa[i], fb[j]);
         }
         stage = stage + 1 == NSTAGE ? 0 : stage + 1;
     }
@@ -745,11 +748,11 @@ __global__ __launch_bounds__(WM_ * WN_ * 64, MINW) void gemm_large_kernel(GemmPa
     }
 }
 
-template <typename TO, bool TA, bool TB, int BKE, int NSTAGE, int TM, int TN, int WM_, int WN_, int MINW>
+template <typename H, typename TO, bool TA, bool TB, int BKE, int NSTAGE, int TM, int TN, int WM_, int WN_, int MINW>
 int launch_large(const GemmParams& p, int splitk, hipStream_t stream) {
     constexpr int SMEM = NSTAGE * (TM + TN) * BKE * 2;
     static bool configured = false;
-    auto kern = gemm_large_kernel<TO, TA, TB, BKE, NSTAGE, TM, TN, WM_, WN_, MINW>;
+    auto kern = gemm_large_kernel<H, TO, TA, TB, BKE, NSTAGE, TM, TN, WM_, WN_, MINW>;
     if (!configured) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
         if (e != hipSuccess) return simseg_set_error("simseg_gemm: cannot reserve %d bytes of LDS: %s", SMEM, hipGetErrorString(e));
@@ -881,20 +884,20 @@ struct PPFrag {
 // 8-bit image of the saved GELU' (simseg_gemm act 7 / 8): q = round((g + 0.132) * 255 / 1.264), g in [-0.1290, 1.1290]
 constexpr float GELU8_SCALE = 255.0f / 1.264f, GELU8_OFF = 0.132f * (255.0f / 1.264f);
 
-template <int EK = 1>
+template <typename H, int EK = 1>
 __device__ __forceinline__ void pp_epilogue_bf16(const GemmParams& p, const f32x16 (&acc)[4][2], char* tl, int m0, int c0, int c1, int grp, int lane) {
     constexpr int TP = 72;                                   // bytes per staged column (32 rows x 2 B + 8 B pad: conflict-free)
     const int cl = lane & 31, h2 = lane >> 5, g4 = lane >> 4, a16 = lane & 15;
     const float bL = p.bias ? p.bias[c0 + cl] : 0.f, bR = p.bias ? p.bias[c1 + cl] : 0.f;
-    bf16_t* Cb = reinterpret_cast<bf16_t*>(p.C);
-    bf16_t* Xb = reinterpret_cast<bf16_t*>(p.aux_out);
+    H* Cb = reinterpret_cast<H*>(p.C);
+    H* Xb = reinterpret_cast<H*>(p.aux_out);
     typedef s16x4 __attribute__((address_space(3))) * lptr;
-    auto emit = [&](const f32x16& xl, const f32x16& xr, bf16_t* dst, int row0) {
+    auto emit = [&](const f32x16& xl, const f32x16& xr, H* dst, int row0) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-            union { bf16_t h[4]; uint2 u; } pl, pr;
+            union { H h[4]; uint2 u; } pl, pr;
 #pragma unroll
-            for (int e = 0; e < 4; ++e) { pl.h[e] = (bf16_t)xl[4 * q + e]; pr.h[e] = (bf16_t)xr[4 * q + e]; }
+            for (int e = 0; e < 4; ++e) { pl.h[e] = (H)xl[4 * q + e]; pr.h[e] = (H)xr[4 * q + e]; }
             *reinterpret_cast<uint2*>(tl + cl * TP + (8 * q + 4 * h2) * 2) = pl.u;
             *reinterpret_cast<uint2*>(tl + (32 + cl) * TP + (8 * q + 4 * h2) * 2) = pr.u;
         }
@@ -902,7 +905,7 @@ __device__ __forceinline__ void pp_epilogue_bf16(const GemmParams& p, const f32x
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         // this lane's four 8-column groups of its row: columns c0 + 8 (g4 >> 1) + {0, 16, 128, 144} (c1 = c0 + 128): one
         // address, immediate offsets
-        bf16_t* drow = dst + (long)(row0 + (g4 & 1) * 16 + a16) * p.ldc + c0 + (g4 >> 1) * 8;
+        H* drow = dst + (long)(row0 + (g4 & 1) * 16 + a16) * p.ldc + c0 + (g4 >> 1) * 8;
         const char* src0 = tl + ((g4 >> 1) * 8 + (a16 >> 2)) * TP + ((g4 & 1) * 16 + (a16 & 3) * 4) * 2;
 #pragma unroll
         for (int sidx = 0; sidx < 4; ++sidx) {
@@ -955,7 +958,7 @@ __device__ __forceinline__ void pp_epilogue_bf16(const GemmParams& p, const f32x
             if (lane < 32) { atomicAdd(p.colsum + c0 + cl, sL); atomicAdd(p.colsum + c1 + cl, sR); }
         }
     } else if (EK == 3 && p.act == 4 && p.aux_blocked == 1) {
-        const bf16_t* Ab = reinterpret_cast<const bf16_t*>(p.aux) + blk0;
+        const H* Ab = reinterpret_cast<const H*>(p.aux) + blk0;
         u32x4 ax[2][4];                                      // [buffer][j * 2 + half]: 16 rows of the left / right column
         // (one operand set requested right after the previous one is consumed, or scheduling barriers between the blocks, leave the
         //  register count where it is - 38 spilled in the persistent instantiation, 21 per-tile: it is the accumulators + the tile-walking
@@ -972,7 +975,7 @@ __device__ __forceinline__ void pp_epilogue_bf16(const GemmParams& p, const f32x
             f32x16 l, r;
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
-                union { u32x4 v; bf16_t h[8]; } gl, gr;
+                union { u32x4 v; H h[8]; } gl, gr;
                 gl.v = ax[i & 1][q]; gr.v = ax[i & 1][2 + q];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {        // (left, right) as one pair: packed fp32 arithmetic
@@ -1019,18 +1022,18 @@ __device__ __forceinline__ void pp_epilogue_bf16(const GemmParams& p, const f32x
             emit(l, r, Cb, m0 + (i >> 1) * 128 + grp * 64 + (i & 1) * 32);
         }
     } else if (EK == 2 && p.act == 3 && Xb && p.aux_blocked == 1) {
-        bf16_t* Bb = Xb + blk0;
+        H* Bb = Xb + blk0;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             f32x16 l, r;
-            union { u32x4 v[2]; bf16_t h[16]; } dl, dr;
+            union { u32x4 v[2]; H h[16]; } dl, dr;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {           // the left / right element as one pair: packed fp32 arithmetic (common.h)
                 f32x2 d;
                 f32x2 y = __builtin_elementwise_fma((f32x2){acc[i][0][e], acc[i][1][e]}, (f32x2){p.alpha, p.alpha}, (f32x2){bL, bR});
                 y = gelu_poly_grad2(y, d);
                 l[e] = y.x; r[e] = y.y;
-                dl.h[e] = (bf16_t)d.x; dr.h[e] = (bf16_t)d.y;
+                dl.h[e] = (H)d.x; dr.h[e] = (H)d.y;
             }
 #pragma unroll
             for (int q = 0; q < 2; ++q) {
@@ -1049,12 +1052,12 @@ __device__ __forceinline__ void pp_epilogue_bf16(const GemmParams& p, const f32x
         // multiplication, as torch's autocast does (a 16-bit matmul output feeding GELU's backward).  The loads of block i + 1 are requested
         // before the stores of block i.  Column sums: 32 per-lane partials (a lane's four column octets are the same in all four blocks),
         // reduced over the 32 lanes that share them through the wave's scratch.
-        const bf16_t* Ab = reinterpret_cast<const bf16_t*>(p.aux);
+        const H* Ab = reinterpret_cast<const H*>(p.aux);
         const int trow = (g4 & 1) * 16 + a16;
-        const bf16_t* arow = Ab + (long)(m0 + grp * 64 + trow) * p.ldc + c0 + (g4 >> 1) * 8;
+        const H* arow = Ab + (long)(m0 + grp * 64 + trow) * p.ldc + c0 + (g4 >> 1) * 8;
         u32x4 ax[2][4];              // (all sixteen pieces requested at once - the K loop's fragment registers are free - measured slower: 16.9 vs 14.5 us of epilogue per tile, spills)
         auto load_aux = [&](int i, u32x4 (&dst)[4]) {
-            const bf16_t* a_i = arow + (long)((i >> 1) * 128 + (i & 1) * 32) * p.ldc;
+            const H* a_i = arow + (long)((i >> 1) * 128 + (i & 1) * 32) * p.ldc;
 #pragma unroll
             for (int sidx = 0; sidx < 4; ++sidx) dst[sidx] = *reinterpret_cast<const u32x4*>(a_i + (sidx & 1) * 16 + (sidx >> 1) * 128);
         };
@@ -1068,32 +1071,32 @@ __device__ __forceinline__ void pp_epilogue_bf16(const GemmParams& p, const f32x
             const int row0 = m0 + (i >> 1) * 128 + grp * 64 + (i & 1) * 32;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                union { bf16_t h[4]; uint2 u; } pl, pr;
+                union { H h[4]; uint2 u; } pl, pr;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    pl.h[e] = (bf16_t)(acc[i][0][4 * q + e] * p.alpha + bL);
-                    pr.h[e] = (bf16_t)(acc[i][1][4 * q + e] * p.alpha + bR);
+                    pl.h[e] = (H)(acc[i][0][4 * q + e] * p.alpha + bL);
+                    pr.h[e] = (H)(acc[i][1][4 * q + e] * p.alpha + bR);
                 }
                 *reinterpret_cast<uint2*>(tl + cl * TP + (8 * q + 4 * h2) * 2) = pl.u;
                 *reinterpret_cast<uint2*>(tl + (32 + cl) * TP + (8 * q + 4 * h2) * 2) = pr.u;
             }
             __builtin_amdgcn_wave_barrier();
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            bf16_t* drow = Cb + (long)(row0 + (g4 & 1) * 16 + a16) * p.ldc + c0 + (g4 >> 1) * 8;
+            H* drow = Cb + (long)(row0 + (g4 & 1) * 16 + a16) * p.ldc + c0 + (g4 >> 1) * 8;
             const char* src0 = tl + ((g4 >> 1) * 8 + (a16 >> 2)) * TP + ((g4 & 1) * 16 + (a16 & 3) * 4) * 2;
 #pragma unroll
             for (int sidx = 0; sidx < 4; ++sidx) {
                 const char* src = src0 + sidx * 16 * TP;
-                union { struct { s16x4 lo, hi; } s; bf16_t h[8]; } u;
+                union { struct { s16x4 lo, hi; } s; H h[8]; } u;
                 u.s.lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(src));
                 u.s.hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(src + 4 * TP));
-                union { u32x4 v; bf16_t h[8]; } a, o;
+                union { u32x4 v; H h[8]; } a, o;
                 a.v = ax[i & 1][sidx];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     const float pv = (float)u.h[e] * (float)a.h[e];
                     cs[sidx * 8 + e] += pv;
-                    o.h[e] = (bf16_t)pv;
+                    o.h[e] = (H)pv;
                 }
                 *reinterpret_cast<u32x4*>(drow + (sidx & 1) * 16 + (sidx >> 1) * 128) = o.v;
             }
@@ -1262,7 +1265,7 @@ __device__ __forceinline__ void pp_trace_end(const GemmParams& p, int tid, unsig
 // GROUPED: the argument is a WgradGroupParams and only the front differs - the block finds its problem, then its (slice, tile) in it.
 // ATOMIC_DIRECT (grouped launches): the split-K adds of a full tile are issued from the accumulators in the MFMA layout
 // (pp_epilogue_atomic_direct) instead of through the staged epilogue.
-template <typename TO, bool TA, bool TB, int EK = 1, bool GROUPED = false, bool ATOMIC_DIRECT = false>
+template <typename H, typename TO, bool TA, bool TB, int EK = 1, bool GROUPED = false, bool ATOMIC_DIRECT = false>
 __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(typename std::conditional<GROUPED, WgradGroupParams, GemmParams>::type arg) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     GemmParams own;
@@ -1369,7 +1372,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(typename std::condition
 #define PP_CLUSTER(RH, CH, FB)                                                                       \
     __builtin_amdgcn_s_setprio(1);                                                                   \
     _Pragma("unroll") for (int kk_ = 0; kk_ < 4; ++kk_)                                              \
-        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) mma<bf16_t>(acc[2 * (RH) + i_][CH], fa[i_ * 4 + kk_], FB[kk_]); \
+        _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_) mma<H>(acc[2 * (RH) + i_][CH], fa[i_ * 4 + kk_], FB[kk_]); \
     __builtin_amdgcn_s_setprio(0);
 
     if (p.stagger > 0 && blockIdx.x < 256) {                         // never taken: stagger is always 0 (see GemmParams)
@@ -1434,7 +1437,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(typename std::condition
                              (((EK == 1 && !p.aux_blocked) || (EK == 3 && p.aux_blocked == 1) || (EK == 5 && p.aux_blocked == 2)) && p.act == 4 && p.aux)) && (p.act == 4 || !p.colsum) &&
                             m0 + 256 <= p.M && n0 + 256 <= p.N;
         if (fastep) {
-            pp_epilogue_bf16<EK>(p, acc, reinterpret_cast<char*>(wlds), m0, c0, c1, grp, lane);
+            pp_epilogue_bf16<H, EK>(p, acc, reinterpret_cast<char*>(wlds), m0, c0, c1, grp, lane);
             if (pf_ok) wait_vm<16>();                                // >= 16 stores were issued after the tail's copies: those have landed
             pp_trace_end(p, tid, tr0, tr1, tr2);
             return;
@@ -1476,11 +1479,11 @@ __global__ __launch_bounds__(512, 2) void gemm_pp_kernel(typename std::condition
     pp_trace_end(p, tid, tr0, tr1, tr2);
 }
 
-template <typename TO, bool TA, bool TB, int EK = 1>
+template <typename H, typename TO, bool TA, bool TB, int EK = 1>
 int launch_pp(const GemmParams& p, int splitk, hipStream_t stream) {
     constexpr int SMEM = 9 * PP_HALF;
     static bool configured = false;
-    auto kern = gemm_pp_kernel<TO, TA, TB, EK>;
+    auto kern = gemm_pp_kernel<H, TO, TA, TB, EK>;
     if (!configured) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
         if (e != hipSuccess) return simseg_set_error("simseg_gemm: cannot reserve %d bytes of LDS: %s", SMEM, hipGetErrorString(e));
@@ -1542,7 +1545,7 @@ __device__ __forceinline__ PP2Item pp2_item(const GemmParams& p, int t, int tile
 
 // A phase's two global->LDS copies are issued in its load segment, behind the fragment reads (placing them inside the MFMA cluster or
 // ahead of the reads computed the same and measured no better: profiles/HISTORY.md).
-template <typename TO, bool TA, bool TB, int EK = 1>
+template <typename H, typename TO, bool TA, bool TB, int EK = 1>
 __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmParams p) {
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1605,7 +1608,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmParams p) {
         _Pragma("unroll") for (int kk_ = 0; kk_ < 4; ++kk_) fa[i_ * 4 + kk_] = fra.read(lds, (HALF) * PP_HALF, i_, kk_);
 #define PP_READ_B(FB, HALF) \
     _Pragma("unroll") for (int kk_ = 0; kk_ < 4; ++kk_) FB[kk_] = frb.read(lds, (HALF) * PP_HALF, 0, kk_);
-#define PP_MMA(RH, CH, FB, KK, I) mma<bf16_t>(acc[2 * (RH) + (I)][CH], fa[(I) * 4 + (KK)], FB[KK]);
+#define PP_MMA(RH, CH, FB, KK, I) mma<H>(acc[2 * (RH) + (I)][CH], fa[(I) * 4 + (KK)], FB[KK]);
     // the wave group's 8 MFMAs of a phase
 #define PP_CLUSTER(RH, CH, FB)                                                                       \
     __builtin_amdgcn_s_setprio(1);                                                                   \
@@ -1681,7 +1684,7 @@ __global__ __launch_bounds__(512, 2) void gemm_pp2_kernel(GemmParams p) {
         if constexpr (sizeof(TO) == 2) {
             const unsigned lp = cpar ^ 1u;
             char* tl = lds + (wave < 7 ? lp * (2 * PP_HALF) + wave * 4608 : PP_BREG + (lp * 2 + 1) * PP_HALF);
-            pp_epilogue_bf16<EK>(p, acc, tl, cur.m0, c0, c1, grp, lane);
+            pp_epilogue_bf16<H, EK>(p, acc, tl, cur.m0, c0, c1, grp, lane);
         } else {
             pp_epilogue_f32_direct(p, acc, cur.m0, c0, c1, grp, lane);
         }
@@ -1723,12 +1726,12 @@ bool pp2_ok(const GemmParams& p, int splitk) {
     return !p.aux && p.act == 0 && !p.colsum && !p.accumulate;
 }
 
-template <typename TO, bool TA, bool TB, int EK = 1>
+template <typename H, typename TO, bool TA, bool TB, int EK = 1>
 int launch_pp2(const GemmParams& p, hipStream_t stream, int reserve = 0) {
     constexpr int SMEM = 9 * PP_HALF;
     static bool configured = false;
     static int blocks = 0;
-    auto kern = gemm_pp2_kernel<TO, TA, TB, EK>;
+    auto kern = gemm_pp2_kernel<H, TO, TA, TB, EK>;
     if (!configured) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
         if (e != hipSuccess) return simseg_set_error("simseg_gemm: cannot reserve %d bytes of LDS: %s", SMEM, hipGetErrorString(e));
@@ -1912,8 +1915,8 @@ int with_pp_kind(const GemmParams& p, F&& f) {
 // 256x256 ping-pong kernels (persistent or one tile per block), one round of 128x128 tiles on the direct-to-LDS ring, everything else on
 // the 128x128 register-staged kernel.  (The small-problem kernel is taken in simseg_gemm, ahead of this.)  A forced selector (sel != 0)
 // replaces a kernel's measured size rule, never its requirements; a call it does not apply to ends on the 128x128 kernel.
-template <typename TO, bool TA, bool TB>
-int dispatch_bf16(const GemmParams& p, int splitk, bool aligned, hipStream_t s) {
+template <typename H, typename TO, bool TA, bool TB>
+int dispatch_h16(const GemmParams& p, int splitk, bool aligned, hipStream_t s) {
     const int sel = g_gemm_variant;
     const bool big_ok = aligned && p.K % 64 == 0 && p.M >= 256 && p.N >= 128;
     const int nk64 = p.K / 64;
@@ -1928,7 +1931,7 @@ int dispatch_bf16(const GemmParams& p, int splitk, bool aligned, hipStream_t s) 
             if (nk64 / sk < 16 && nk64 >= 64) sk = nk64 / 16;        // short contraction (packed text rows): fewer, 16-deep slices
             if (nk64 / sk >= 16 && tiles256 * sk >= 96) {
                 g_gemm_last_variant = 3;
-                return launch_pp<TO, TA, TB>(p, sk, s);
+                return launch_pp<H, TO, TA, TB>(p, sk, s);
             }
         }
     }
@@ -1954,11 +1957,11 @@ int dispatch_bf16(const GemmParams& p, int splitk, bool aligned, hipStream_t s) 
             if ((sel == 10 || (sel == 0 && tiles256 >= 600)) && (p.act != 4 || p.aux_blocked) && pp2_ok<TO>(p, splitk)) {
                 g_gemm_last_variant = 10;
                 return with_pp_kind<TO, TB>(p, [&](auto ek) {      // (the persistent kernel's fp32-output instantiations are the EK = 0 ones)
-                    return launch_pp2<TO, TA, TB, decltype(ek)::value == 1 ? 0 : decltype(ek)::value>(p, s, sel == 0 ? reserve : 0);
+                    return launch_pp2<H, TO, TA, TB, decltype(ek)::value == 1 ? 0 : decltype(ek)::value>(p, s, sel == 0 ? reserve : 0);
                 });
             }
             g_gemm_last_variant = 3;
-            return with_pp_kind<TO, TB>(p, [&](auto ek) { return launch_pp<TO, TA, TB, decltype(ek)::value>(p, splitk, s); });
+            return with_pp_kind<TO, TB>(p, [&](auto ek) { return launch_pp<H, TO, TA, TB, decltype(ek)::value>(p, splitk, s); });
         }
     }
     if (p.aux_blocked)
@@ -1970,11 +1973,11 @@ int dispatch_bf16(const GemmParams& p, int splitk, bool aligned, hipStream_t s) 
         const bool ring_ok = aligned && p.K % 64 == 0 && p.M >= 128 && p.N >= 128 && splitk <= 1;
         if (ring_ok && (sel == 5 || (sel == 0 && t128 >= 160 && t128 <= 256))) {
             g_gemm_last_variant = 5;
-            return launch_large<TO, TA, TB, 64, 4, 128, 128, 2, 2, 1>(p, splitk, s);
+            return launch_large<H, TO, TA, TB, 64, 4, 128, 128, 2, 2, 1>(p, splitk, s);
         }
     }
     g_gemm_last_variant = 1;
-    return launch<bf16_t, TO, TA, TB>(p, splitk, s);
+    return launch<H, TO, TA, TB>(p, splitk, s);
 }
 
 }  // namespace
@@ -1982,8 +1985,7 @@ int dispatch_bf16(const GemmParams& p, int splitk, bool aligned, hipStream_t s) 
 // which kernel the calling thread's last simseg_gemm launched: 1 = 128x128 register-staged, 3 = 256x256 ping-pong (one tile per block),
 // 4 = small-problem kernel, 5 = 128x128 ring, 10 = persistent ping-pong (the measurement code labels its per-kernel timings with this
 // instead of re-deriving the dispatch rule)
-extern "C" int simseg_gemm_last_variant(void) {
-    SS_HALF_FWD(simseg_gemm_last_variant); return g_gemm_last_variant; }
+extern "C" int simseg_gemm_last_variant(void) { return g_gemm_last_variant; }
 
 // debugging: the per-tile ping-pong kernel writes 5 x u64 per block (start / K loop start / K loop end / end wall-clock stamps at 100 MHz, HW_ID)
 extern "C" int simseg_debug_gemm_trace(void* buf) { g_gemm_debug_trace = static_cast<unsigned long long*>(buf); return 0; }
@@ -1991,23 +1993,21 @@ extern "C" int simseg_debug_gemm_trace(void* buf) { g_gemm_debug_trace = static_
 extern "C" int simseg_set_gemm_variant(int v) {
     SS_CHECK(v == 0 || v == 1 || v == 3 || v == 4 || v == 5 || v == 10,
              "set_gemm_variant: %d is not a kernel selection (0 = auto, 1 = 128x128, 3 = ping-pong per tile, 4 = small-problem, 5 = 128x128 ring, 10 = persistent ping-pong)", v);
-#ifndef SS_HALF
-    simseg_set_gemm_variant_h16(v);      // the fp16 flavour keeps its own (thread-local) selector
-#endif
     g_gemm_variant = v;
     return 0;
 }
 
 extern "C" int simseg_patch_text_sim(const void* x, const void* text, float* out, int64_t M, int64_t C, int64_t K, int dtype,
                                      float eps, int normalize, void* stream) {
-    SS_HALF_FWD(simseg_patch_text_sim, x, text, out, M, C, K, dtype, eps, normalize, stream);
     SS_CHECK(x && text && out, "patch_text_sim: null pointer");
     SS_CHECK(M > 0 && C > 0 && C <= 256 && K > 0 && M < (1ll << 31), "patch_text_sim: need 1 <= C <= 256 (got C=%lld)", (long long)C);
     SS_CHECK(dtype == 0 || dtype == 1, "patch_text_sim: dtype must be 0 (fp32) or 1 (bf16)");
     const int epc = dtype == 0 ? 4 : 8;
     SS_CHECK(K % epc == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)text % 16) == 0, "patch_text_sim: K must be a multiple of %d and the operands 16-byte aligned", epc);
     if (dtype == 0) return dispatch_simmap<float>(x, text, out, (int)M, (int)C, (int)K, eps, normalize, (hipStream_t)stream);
-    return dispatch_simmap<bf16_t>(x, text, out, (int)M, (int)C, (int)K, eps, normalize, (hipStream_t)stream);
+    return with_h16(g_ss_half, [&](auto tag) {
+        return dispatch_simmap<typename decltype(tag)::type>(x, text, out, (int)M, (int)C, (int)K, eps, normalize, (hipStream_t)stream);
+    });
 }
 
 // 1 when a 16-bit M x N x K problem (k-contiguous A) runs on the 256x256 ping-pong kernels with full tiles only - the condition under which
@@ -2019,14 +2019,30 @@ extern "C" int simseg_gemm_aux_blocked_ok(int64_t M, int64_t N, int64_t K) {
 
 // How many problems the calling thread's last simseg_gemm_wgrad_group launched as one group (0: not eligible, nothing launched).
 static thread_local int g_wgrad_group_last = 0;
-extern "C" int simseg_wgrad_group_last(void) {
-    SS_HALF_FWD(simseg_wgrad_group_last); return g_wgrad_group_last; }
+extern "C" int simseg_wgrad_group_last(void) { return g_wgrad_group_last; }
+
+// the grouped launch for the 16-bit type H (the LDS reservation is per kernel, so per H)
+template <typename H>
+static int launch_wgrad_group(const WgradGroupParams& g, unsigned blocks, hipStream_t stream) {
+    // the adds from the accumulator layout (median block epilogue 9.1 against 23.9 us on the ViT-B block, 17.0 against 30.0 us on a 21 760-row
+    // text block: profiles/wgrad_group.txt)
+    constexpr int SMEM = 9 * PP_HALF;
+    auto kern = gemm_pp_kernel<H, float, true, true, 1, true, true>;
+    static bool configured = false;
+    if (!configured) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
+        if (e != hipSuccess) return simseg_set_error("simseg_gemm_wgrad_group: cannot reserve %d bytes of LDS: %s", SMEM, hipGetErrorString(e));
+        configured = true;
+    }
+    hipLaunchKernelGGL(kern, dim3(blocks, 1, 1), dim3(512), SMEM, stream, g);
+    SS_LAUNCH_CHECK("simseg_gemm_wgrad_group");
+    return 0;
+}
 
 // n problems dW_i[out_i, in_i] += dY_i^T . X_i over the same `rows` in ONE split-K launch (gemm_pp_kernel<..., GROUPED>).  problems: n records of
 // 8 x int64 {dY, X, dW, out, in, ld_dY, ld_X, ld_dW} in host memory.  Returns 0 and launches nothing when the group is not eligible
 // (simseg_wgrad_group_last() then reads 0 and the caller issues per-problem simseg_gemm calls), -1 on a bad argument.
 extern "C" int simseg_gemm_wgrad_group(const int64_t* problems, int n, int64_t rows, int slices, void* stream) {
-    SS_HALF_FWD(simseg_gemm_wgrad_group, problems, n, rows, slices, stream);
     g_wgrad_group_last = 0;
     SS_CHECK(problems && n >= 1 && n <= WG_MAX, "simseg_gemm_wgrad_group: 1..%d problems", WG_MAX);
     SS_CHECK(rows > 0 && rows < (1ll << 31) && slices >= 1, "simseg_gemm_wgrad_group: bad rows %lld / slices %d", (long long)rows, slices);
@@ -2057,18 +2073,8 @@ extern "C" int simseg_gemm_wgrad_group(const int64_t* problems, int n, int64_t r
     for (int i = n; i <= WG_MAX; ++i) g.first[i] = (int)blocks;
     g.n = n; g.rows = (int)rows;
     g.dbg_trace = g_gemm_debug_trace;
-    // the adds from the accumulator layout (median block epilogue 9.1 against 23.9 us on the ViT-B block, 17.0 against 30.0 us on a 21 760-row
-    // text block: profiles/wgrad_group.txt)
-    constexpr int SMEM = 9 * PP_HALF;
-    auto kern = gemm_pp_kernel<float, true, true, 1, true, true>;
-    static bool configured = false;
-    if (!configured) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
-        if (e != hipSuccess) return simseg_set_error("simseg_gemm_wgrad_group: cannot reserve %d bytes of LDS: %s", SMEM, hipGetErrorString(e));
-        configured = true;
-    }
-    hipLaunchKernelGGL(kern, dim3((unsigned)blocks, 1, 1), dim3(512), SMEM, (hipStream_t)stream, g);
-    SS_LAUNCH_CHECK("simseg_gemm_wgrad_group");
+    if (int rc = with_h16(g_ss_half, [&](auto tag) { return launch_wgrad_group<typename decltype(tag)::type>(g, (unsigned)blocks, (hipStream_t)stream); }))
+        return rc;
     g_gemm_last_variant = 3;
     g_wgrad_group_last = n;
     return 0;
@@ -2080,7 +2086,6 @@ extern "C" int simseg_gemm(const void* A, const void* B, void* C, int64_t M, int
                            const float* bias, const float* rowscale, const float* residual, int64_t ldr, int act,
                            const void* aux, void* aux_out, int row_group, int res_mod, int accumulate, int splitk,
                            uint64_t drop_seed, float drop_p, float* colsum, void* stream) {
-    SS_HALF_FWD(simseg_gemm, A, B, C, M, N, K, lda, ldb, ldc, in_dtype, out_dtype, transA, transB, alpha, bias, rowscale, residual, ldr, act, aux, aux_out, row_group, res_mod, accumulate, splitk, drop_seed, drop_p, colsum, stream);
     SS_CHECK(A && B && C, "simseg_gemm: null operand");
     SS_CHECK(M > 0 && N > 0 && K > 0 && M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31), "simseg_gemm: bad shape %lld x %lld x %lld",
              (long long)M, (long long)N, (long long)K);
@@ -2132,10 +2137,16 @@ extern "C" int simseg_gemm(const void* A, const void* B, void* C, int64_t M, int
     if ((g_gemm_variant == 0 && small_auto) || (g_gemm_variant == 4 && small_fit)) {
         g_gemm_last_variant = 4;
         if (in_dtype == 0) return dispatch_small<float, float>(p, s);
-        return out_dtype ? dispatch_small<bf16_t, bf16_t>(p, s) : dispatch_small<bf16_t, float>(p, s);
+        return with_h16(g_ss_half, [&](auto tag) {
+            typedef typename decltype(tag)::type H;
+            return out_dtype ? dispatch_small<H, H>(p, s) : dispatch_small<H, float>(p, s);
+        });
     }
     if (in_dtype == 0) return aligned ? launch<float, float, false, false, true>(p, splitk, s) : launch<float, float, false, false, false>(p, splitk, s);
-    if (!transA && !transB) return out_dtype ? dispatch_bf16<bf16_t, false, false>(p, splitk, aligned, s) : dispatch_bf16<float, false, false>(p, splitk, aligned, s);
-    if (!transA && transB) return out_dtype ? dispatch_bf16<bf16_t, false, true>(p, splitk, aligned, s) : dispatch_bf16<float, false, true>(p, splitk, aligned, s);
-    return out_dtype ? dispatch_bf16<bf16_t, true, true>(p, splitk, aligned, s) : dispatch_bf16<float, true, true>(p, splitk, aligned, s);
+    return with_h16(g_ss_half, [&](auto tag) {
+        typedef typename decltype(tag)::type H;
+        if (!transA && !transB) return out_dtype ? dispatch_h16<H, H, false, false>(p, splitk, aligned, s) : dispatch_h16<H, float, false, false>(p, splitk, aligned, s);
+        if (!transA && transB) return out_dtype ? dispatch_h16<H, H, false, true>(p, splitk, aligned, s) : dispatch_h16<H, float, false, true>(p, splitk, aligned, s);
+        return out_dtype ? dispatch_h16<H, H, true, true>(p, splitk, aligned, s) : dispatch_h16<H, float, true, true>(p, splitk, aligned, s);
+    });
 }

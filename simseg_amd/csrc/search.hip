@@ -91,12 +91,12 @@ struct SearchParams {
 
 template <typename T> struct Op;
 template <> struct Op<float> { static constexpr int EPC = 4; };
-template <> struct Op<bf16_t> { static constexpr int EPC = 8; };
+template <> struct Op<__bf16> { static constexpr int EPC = 8; };
 
 template <typename T>
 __device__ __forceinline__ void mma(f32x16& acc, const u32x4& a, const u32x4& b) {
     if constexpr (sizeof(T) == 2) {
-        union { u32x4 v; bf16x8 h; } ua, ub;
+        union { u32x4 v; h16x8<__bf16> h; } ua, ub;
         ua.v = a; ub.v = b;
         acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ua.h, ub.h, acc, 0, 0, 0);
     } else {
@@ -377,7 +377,7 @@ extern "C" int simseg_topk_search(const void* q, const void* g, int dtype, int64
     p.index_offset = index_offset; p.score = score; p.idx = idx; p.ws = S > 1 ? static_cast<u64*>(workspace) : nullptr;
     int rc;
     if (dtype == 0) rc = K <= 32 ? launch_search<float, 64>(p, S, STREAM) : launch_search<float, 256>(p, S, STREAM);
-    else rc = K <= 32 ? launch_search<bf16_t, 64>(p, S, STREAM) : launch_search<bf16_t, 256>(p, S, STREAM);
+    else rc = K <= 32 ? launch_search<__bf16, 64>(p, S, STREAM) : launch_search<__bf16, 256>(p, S, STREAM);
     if (rc != 0) return rc;
     if (S > 1) {
         hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)((M + 3) / 4)), dim3(NTHR), 0, STREAM, p.ws, S, nullptr, nullptr, nullptr, nullptr,

@@ -146,7 +146,7 @@ def _table():
                                             (511, 136, 256, "2 row tiles - 1, N just past the 128 minimum; 8-wide staged epilogue")], LIN_ALL)
     t += _mk(3, "h", ["NN"], ["f32", "h"], [(257, 248, 128, "NN partial tiles (N % 8 == 0)"), (256, 128, 192, "N = half a tile")], ["plain", "lin"])
     t += _mk(3, "h", ["NT", "NN"], ["f32"], [(512, 264, 512, "forced split-K of a k-contiguous-A problem: staged atomics, 8 K-tiles in slices of 3 + 3 + 2")], ["splitk"], splitk=3)
-    # The weight-gradient entry of dispatch_bf16: M % 256 == N % 256 == 0, tiles256 <= 128, sk = 256 / tiles256, and if nk64 / sk < 16 with
+    # The weight-gradient entry of dispatch_h16: M % 256 == N % 256 == 0, tiles256 <= 128, sk = 256 / tiles256, and if nk64 / sk < 16 with
     # nk64 >= 64 then sk = nk64 / 16; taken when nk64 / sk >= 16 and tiles256 * sk >= 96.  tiles256 * nk64 >= 16 * 96 = 1536 follows; at
     # K = 4096 (nk64 = 64, sk = 4) the smallest tile count is 24 = 4 x 6: 1024 x 1536 x 4096, 1.5 x 2^32 multiply-adds (16 tiles at K = 6144 tie).
     t += _mk(3, "h", ["TT"], ["f32"], [(1024, 1536, 4096, "the smallest split-K weight gradient the rule admits: 24 tiles x 4 slices of 16 K-tiles")], ["splitk"], splitk=8)
@@ -188,7 +188,7 @@ def _nl_table():
 
 NL_CASES = _nl_table()
 
-# ---- automatic dispatch (selector 0): the kernel simseg_gemm / dispatch_bf16 choose by their size rules ----------------------------------
+# ---- automatic dispatch (selector 0): the kernel simseg_gemm / dispatch_h16 choose by their size rules ----------------------------------
 Auto = collections.namedtuple("Auto", "op layout out M N K splitk want note")
 AUTO = [
     Auto("f32", "NT", "f32", 300, 200, 64, 1, 4, "fp32, K * 4 % 128 == 0, t128 = 6 < 200 (test_gemm_f32_epilogues' shape)"),

@@ -199,14 +199,17 @@ def test_c_abi_declares_and_exports_the_new_entries():
                                                                 "write_grad", "stream"]
     so = ctypes.CDLL(lib.LIB_PATH)          # (the built library: the suite runs after the build)
     from simseg_amd import build
-    assert "loss.hip" not in build.TWICE     # fp32 rows: one entry point each, no second flavour
+    import glob
+    objs = [os.path.basename(o) for o in glob.glob(os.path.join(REPO, "simseg_amd", "build", "loss*.o"))]
+    assert not getattr(build, "TWICE", ()) and objs in ([], ["loss.o"])     # fp32 rows, one entry point each: ONE object (none here when the library was built elsewhere)
     src = open(os.path.join(REPO, "simseg_amd/csrc/loss.hip")).read()
     for name in ("simseg_triplet_rows", "simseg_mix_nce_rows"):
         assert f'extern "C" int {name}(' in src, f"{name} is not defined in loss.hip"
         assert hasattr(so, name), f"{name} is not exported"
         assert not hasattr(so, name + "_h16"), f"{name}_h16 is exported"
     # the same for the row kernels these losses sit next to in a step: one object, the 16-bit type chosen per call
-    assert "rowops.hip" not in build.TWICE
+    objs = [os.path.basename(o) for o in glob.glob(os.path.join(REPO, "simseg_amd", "build", "rowops*.o"))]
+    assert not getattr(build, "TWICE", ()) and objs in ([], ["rowops.o"])     # the type is a template argument: ONE object (none here when the library was built elsewhere)
     src = open(os.path.join(REPO, "simseg_amd/csrc/rowops.hip")).read()
     for name in ("simseg_layernorm_fwd", "simseg_layernorm_bwd", "simseg_layernorm_bwd_workspace_bytes", "simseg_colsum_accum",
                  "simseg_vit_im2col", "simseg_topk_pool_workspace_bytes", "simseg_topk_pool_l2norm_fwd", "simseg_topk_pool_l2norm_bwd",

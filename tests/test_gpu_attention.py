@@ -136,12 +136,14 @@ def test_resident_longest(ops, p):
 # ------------------------------------------------------------------------------------------------------------------------------------------
 # 2. ring forward + streaming backward (delta, dkv, dq kernels)
 # ------------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("p", [0.0, 0.1])
-@pytest.mark.parametrize("T,B,lens", [(257, 3, None), (300, 4, (300, 257, 33, 1))])
-def test_ring_and_streaming_backward(ops, T, B, lens, p):
-    """The first length past the resident kernels, unmasked and masked, with and without dropout: attn_fwd_bf16_kernel<DROP, MASK>,
-    attn_delta_kernel, attn_bwd_dkv_kernel<DROP>, attn_bwd_dq_kernel<DROP> and the column-sum pass over dqkv."""
-    _dense(ops, "ring+streaming", B, T, 3, lens, p, colsum=True)
+@pytest.mark.parametrize("T,B,lens,p,dt", [(257, 3, None, 0.0, "bf16"), (257, 3, None, 0.1, "bf16"), (300, 4, (300, 257, 33, 1), 0.0, "bf16"),
+                                           (300, 4, (300, 257, 33, 1), 0.1, "bf16"), (300, 4, (300, 257, 33, 1), 0.1, "f16")],
+                         ids=["257-3-None-0.0", "257-3-None-0.1", "300-4-lens1-0.0", "300-4-lens1-0.1", "300-4-lens1-0.1-f16"])
+def test_ring_and_streaming_backward(ops, T, B, lens, p, dt):
+    """The first length past the resident kernels, unmasked and masked, with and without dropout: attn_fwd_bf16_kernel<H, DROP, MASK>,
+    attn_delta_kernel<H>, attn_bwd_dkv_kernel<H, DROP>, attn_bwd_dq_kernel<H, DROP> and the column-sum pass over dqkv.  The masked case
+    with dropout also in fp16: the one case that reaches <DROP, MASK> of all four kernels."""
+    _dense(ops, "ring+streaming", B, T, 3, lens, p, dt=dt, colsum=True)
 
 
 @pytest.mark.parametrize("T,B,H,lens", [(600, 3, 1, (600, 513, 1)), (1088, 2, 3, (1088, 5))])
@@ -158,7 +160,7 @@ def test_ring_kernels_forced_on_short_sequences(ops, T, B, lens):
 # 3. the 64-queries-per-wave forward
 # ------------------------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("variant", [0, 6, 7])
-@pytest.mark.parametrize("T,dt", [(512, "bf16"), (513, "bf16"), (513, "f16"), (577, "bf16"), (1025, "bf16")])
+@pytest.mark.parametrize("T,dt", [(512, "bf16"), (512, "f16"), (513, "bf16"), (513, "f16"), (577, "bf16"), (1025, "bf16")])
 def test_w64_forward(ops, T, dt, variant):
     _dense(ops, f"w64 fwd (variant {variant})", 1, T, 3, dt=dt, variant=variant, grads=False)
 
@@ -170,53 +172,53 @@ def test_w64_forward_feeds_the_streaming_backward(ops):
 
 @pytest.mark.parametrize("variant", [6, 7])
 @pytest.mark.parametrize("scale", [0.125, 0.2])
-@pytest.mark.parametrize("T", [513, 577])
-def test_w64_forward_qscaled(ops, T, scale, variant):
+@pytest.mark.parametrize("T,dt", [(513, "bf16"), (577, "bf16"), (513, "f16")], ids=["513", "577", "513-f16"])
+def test_w64_forward_qscaled(ops, T, dt, scale, variant):
     """q columns carry scale * log2(e) before their rounding; the reference divides the factor out of the ROUNDED q."""
     B, H = 1, 3
     c = ops.attention_qscale(scale)
     x = torch.randn(B, T, 3, H, 64, generator=torch.Generator().manual_seed(T + 7)) * 1.2
     x[:, :, 0] *= c
-    qkv = x.view(B, T, 3 * H * 64).bfloat16()
+    qkv = x.view(B, T, 3 * H * 64).to(DT[dt])
     ref = A.reference(qkv, None, H, scale, q_div=c)
-    yards = [A.emulate(qkv, None, H, scale, variant=v, device="cuda", qscaled=True) for v in "AB"]
+    yards = [A.emulate(qkv, None, H, scale, variant=v, rnd=DT[dt], device="cuda", qscaled=True) for v in "AB"]
     ops.set_attention_variant(variant)
     try:
         out, lse = ops.attention_fwd_qscaled(qkv.cuda(), H, save_lse=True)
     finally:
         ops.set_attention_variant(0)
-    _report(f"w64 qscaled (variant {variant}) bf16 B{B} H{H} T{T} scale={scale}", {"out": A.split(out, H)[0], "lse": lse}, ref, yards,
-            torch.ones(B, T, dtype=torch.bool), "bf16", FWD, (T,) * B, H)
+    _report(f"w64 qscaled (variant {variant}) {dt} B{B} H{H} T{T} scale={scale}", {"out": A.split(out, H)[0], "lse": lse}, ref, yards,
+            torch.ones(B, T, dtype=torch.bool), dt, FWD, (T,) * B, H)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------
 # 4. packed rows
 # ------------------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("p", [0.0, 0.1])
-def test_packed_rows(ops, p):
+@pytest.mark.parametrize("p,dt", [(0.0, "bf16"), (0.1, "bf16"), (0.1, "f16")], ids=["0.0", "0.1", "0.1-f16"])
+def test_packed_rows(ops, p, dt):
     """simseg_attention_fwd_rows / _bwd_rows per sequence against float64: the reference is the dense, prefix-masked attention of the
     same tokens (queries past a length carry no dout and are not compared).  The C entry points are called as ops.attention_*_rows call
     them, on buffers pre-filled with a sentinel: rows behind the last sequence and the lse of the EMPTY sequence are not written."""
     from simseg_amd.lib import call, ptr, raw, stream
     lens, T, H, scale, pad, sentinel = (77, 1, 9, 32, 33, 0), 77, 2, 0.125, 5, -1024.0
     B = len(lens)
-    qkv, dout = (t.clone() for t in _inputs(B, T, H, "bf16"))
+    qkv, dout = (t.clone() for t in _inputs(B, T, H, dt))
     valid = A.key_mask(lens, T)
     dout[~valid] = 0
     keep = _keep(B, H, T, p)
     ref_lens = tuple(n or T for n in lens)                      # (the empty sequence is not compared: any mask will do for it)
     ref = A.reference(qkv, dout, H, scale, ref_lens, keep)
-    yards = [{k: t.cpu() for k, t in A.emulate(qkv, dout, H, scale, ref_lens, keep, v, device="cuda").items()} for v in "AB"]
+    yards = [{k: t.cpu() for k, t in A.emulate(qkv, dout, H, scale, ref_lens, keep, v, rnd=DT[dt], device="cuda").items()} for v in "AB"]
     idx = valid.view(-1).nonzero().flatten()
     n = idx.numel()
-    qp = torch.cat([qkv.view(B * T, -1)[idx], torch.full((pad, 3 * H * 64), float("nan"), dtype=torch.bfloat16)]).cuda()
-    dp = torch.cat([dout.view(B * T, -1)[idx], torch.zeros(pad, H * 64, dtype=torch.bfloat16)]).cuda()
+    qp = torch.cat([qkv.view(B * T, -1)[idx], torch.full((pad, 3 * H * 64), float("nan"), dtype=DT[dt])]).cuda()
+    dp = torch.cat([dout.view(B * T, -1)[idx], torch.zeros(pad, H * 64, dtype=DT[dt])]).cuda()
     rs = torch.zeros(B + 1, dtype=torch.int32)
     rs[1:] = torch.tensor(lens).cumsum(0)
     rs = rs.cuda()
-    out = torch.full((n + pad, H * 64), sentinel, dtype=torch.bfloat16, device="cuda")
+    out = torch.full((n + pad, H * 64), sentinel, dtype=DT[dt], device="cuda")
     lse = torch.full((B, H, T), sentinel, device="cuda")
-    dqkv = torch.full((n + pad, 3 * H * 64), sentinel, dtype=torch.bfloat16, device="cuda")
+    dqkv = torch.full((n + pad, 3 * H * 64), sentinel, dtype=DT[dt], device="cuda")
     cs = torch.zeros(3 * H * 64, device="cuda")
     ws = torch.empty(raw("simseg_attention_bwd_workspace_bytes", B, T, H) // 4, device="cuda")
     ops.set_attention_variant(0)
@@ -231,7 +233,7 @@ def test_packed_rows(ops, p):
         return full.view(B, T, width)
     got = {"out": A.split(dense(out, H * 64), H)[0], "lse": lse.cpu()}
     got["dq"], got["dk"], got["dv"] = A.split(dense(dqkv, 3 * H * 64), H)
-    _report(f"packed rows bf16 B{B} H{H} T{T} {'x'.join(map(str, lens))} p={p} scale={scale}", got, ref, yards, valid, "bf16", GRADS, lens, H, cs)
+    _report(f"packed rows {dt} B{B} H{H} T{T} {'x'.join(map(str, lens))} p={p} scale={scale}", got, ref, yards, valid, dt, GRADS, lens, H, cs)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------

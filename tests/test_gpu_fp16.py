@@ -1,6 +1,6 @@
 """The fp16 flavour of the 16-bit kernels - the type of the reference's AMP mode (torch.cuda.amp.autocast() + GradScaler,
-simseg/tasks/clip/clip_runner.py:226-230, simseg/core/hooks/optimizer.py:73-82).  Same sources as the bf16 kernels (compiled with
--DSS_HALF: v_mfma_f32_32x32x16_f16), selected per call by the tensors' dtype.  Kernels against fp64 / fp32 references; the model's
+simseg/tasks/clip/clip_runner.py:226-230, simseg/core/hooks/optimizer.py:73-82).  The same kernels as bf16 with _Float16 as their type
+argument (v_mfma_f32_32x32x16_f16), selected per call by the tensors' dtype.  Kernels against fp64 / fp32 references; the model's
 fp16 gradients against its exact-fp32 gradients; the trainer's live loss scaling (scaled backward, unscale, overflow -> skipped step +
 back-off, growth, checkpointed state)."""
 import os
@@ -253,6 +253,79 @@ def test_rowops_pick_the_16bit_type_per_call(hd):
         ref = twin[k] if k in twin else plain[k]
         assert v.dtype == hd and ref.dtype == torch.float32 and torch.equal(_bits(v), _bits(ref.to(hd))), k
     assert not torch.equal(_bits(h16["cast"]), _bits(oh16["cast"]))          # (the two runs did differ in type)
+
+
+def _gemm_case(kernel, layout, out, M, N, K, epi="plain"):
+    import _gemm_ref as G
+    (c,) = [c for c in G.CASES if (c.kernel, c.op, c.layout, c.out, c.M, c.N, c.K, c.epi) == (kernel, "h", layout, out, M, N, K, epi)]
+    return c
+
+
+def _launch_gemm(site, hd):
+    """-> (output, exact result) of one launch of a GEMM launch site in the type hd: a case of the GEMM suite, judged as there (integers)."""
+    import _gemm_ref as G
+    import test_gpu_gemm as TG
+    from simseg_amd import ops
+    if site == "grouped":
+        grp = G.GROUPED[0]
+        bufs, wants = [], []
+        for i, (out, inn) in enumerate(grp.problems):
+            g = torch.Generator().manual_seed(G.seed_of(f"wg{grp.rows}-{i}"))
+            dy, x = G._randint(-4, 4, (grp.rows, out), g).cuda(), G._randint(-4, 4, (grp.rows, inn), g).cuda()
+            w0 = G._randint(-16, 16, (out, inn), g).cuda()
+            bufs.append((TG.Buf(grp.rows, out, hd, dy.to(hd), False), TG.Buf(grp.rows, inn, hd, x.to(hd), False), TG.Buf(out, inn, torch.float32, w0, False)))
+            wants.append((w0.double() + dy.double().T @ x.double()).float().flatten())
+        n, ran = TG._group_call(ops, bufs, grp.rows, grp.slices)          # (lib.call raises on a non-zero status)
+        assert n == len(grp.problems) and ran == 3
+        return torch.cat([dw.t.flatten() for _, _, dw in bufs]), torch.cat(wants)
+    case = {"small": _gemm_case(4, "NT", "h", 31, 63, 64), "ring": _gemm_case(5, "NT", "h", 128, 128, 64),
+            "pp": _gemm_case(3, "NT", "h", 256, 256, 128), "pp f32": _gemm_case(3, "NT", "f32", 256, 256, 128),
+            "pp split-K": _gemm_case(3, "TT", "f32", 1024, 1536, 4096, "splitk"), "pp2": _gemm_case(10, "NT", "h", 11008, 1536, 128)}[site]
+    got = TG.run_linear(ops, case, hd, padded=False)["C"]            # (asserts the kernel that ran; lib.call raises on a non-zero status)
+    want = G.linear_ref(case, TG._lin_inputs(case))["C"].float().to(got.dtype)
+    return got, want
+
+
+def _launch_attention(site, hd):
+    """-> outputs of one forward (+ backward) of an attention launch site in the type hd, on the attention suite's inputs for that shape."""
+    import test_gpu_attention as TA
+    from simseg_amd import ops
+    B, T, H, lens, grads = {"resident + one-kernel": (3, 33, 3, (33, 9, 1), True), "w64": (1, 512, 3, None, False)}[site]
+    qkv, dout = TA._inputs(B, T, H, {BF16: "bf16", F16: "f16"}[hd])
+    mask = None if lens is None else TA.A.key_mask(lens, T).long().cuda()      # (the same instantiations as TA._dense on these arguments)
+    out, lse = ops.attention_fwd(qkv.cuda(), H, mask, scale=0.125, save_lse=True)
+    res = [out, lse]
+    if grads:
+        res.append(ops.attention_bwd(qkv.cuda(), out, dout.cuda(), lse, H, mask, scale=0.125))
+    torch.cuda.synchronize()
+    return res
+
+
+@pytest.mark.parametrize("site", ["small", "ring", "pp", "pp f32", "pp split-K", "pp2", "grouped", "resident + one-kernel", "w64"])
+def test_launch_sites_reserve_their_lds_per_16bit_type(site):
+    """csrc/gemm.hip and csrc/attn.hip are compiled once; their launchers raise a kernel's dynamic-LDS limit on its first launch, behind a
+    function-local flag.  A flag shared by the __bf16 and the _Float16 instantiation of a kernel would leave the second type's kernel at the
+    default limit: its first launch fails (invalid value).  So every such launcher runs bf16, fp16, bf16 in this process, at the smallest
+    shape of the GEMM / attention suite that reaches it (one instantiation per launcher; the GEMM and attention suites run the others in
+    both types): every call returns 0 (lib.call raises otherwise); the GEMM outputs - integer
+    operands, the split-K and grouped fp32 atomics included - equal the exact result bit for bit, as in test_gpu_gemm.test_exact; the
+    attention kernels are deterministic, so the second bf16 run equals the first bit for bit, and the fp16 run is judged by the attention
+    suite's float64 rule (tests/_attn_ref.py)."""
+    if site in ("resident + one-kernel", "w64"):
+        import test_gpu_attention as TA
+        from simseg_amd import ops
+        first = _launch_attention(site, BF16)
+        if site == "w64":
+            TA._dense(ops, "w64 fwd (launch sites)", 1, 512, 3, dt="f16", grads=False)
+        else:
+            TA._dense(ops, "resident+one (launch sites)", 3, 33, 3, (33, 9, 1), dt="f16")
+        again = _launch_attention(site, BF16)
+        assert len(first) == len(again) and all(torch.equal(_bits(a), _bits(b)) for a, b in zip(first, again))
+        return
+    runs = [_launch_gemm(site, hd) for hd in (BF16, F16, BF16)]
+    for hd, (got, want) in zip((BF16, F16, BF16), runs):
+        assert int((got != want).sum()) == 0, (site, hd)
+    assert torch.equal(_bits(runs[0][0]), _bits(runs[2][0]))
 
 
 def test_model_fp16_gradients_vs_exact_fp32(golden, monkeypatch):

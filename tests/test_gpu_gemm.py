@@ -193,7 +193,7 @@ def test_guards_linear(ops, case, half):
 @pytest.mark.parametrize("auto,half", [pytest.param(a, h, id=f"{a.op}-{a.layout}-o{a.out}-{a.M}x{a.N}x{a.K}-{HALF_IDS[h]}")
                                        for a in G.AUTO for h in (G.HALVES if a.op == "h" else [None])])
 def test_auto_dispatch_names_its_kernel(ops, auto, half):
-    """Selector 0: simseg_gemm / dispatch_bf16 pick the kernel by their size rules; the rule's both sides are in the list, so a changed
+    """Selector 0: simseg_gemm / dispatch_h16 pick the kernel by their size rules; the rule's both sides are in the list, so a changed
     threshold fails here.  The result is checked exactly, as in test_exact."""
     case = G.Case(auto.want, auto.op, auto.layout, auto.out, auto.M, auto.N, auto.K, "splitk" if auto.splitk > 1 else "plain", auto.splitk, auto.note)
     d = {k: (v.cuda() if torch.is_tensor(v) else v) for k, v in G.int_inputs(case).items()}

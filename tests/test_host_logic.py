@@ -94,67 +94,47 @@ def test_qscaled_threshold_is_the_attention_kernels():
     assert int(mint) == ops.ATTN_QSCALED_MIN_T
 
 
-def test_fp16_flavour_is_built_selectable_and_its_rename_header_is_current():
-    """The 16-bit sources are compiled twice (bf16 as they stand, fp16 with -DSS_HALF); csrc/half_names.h - generated from the sources'
-    entry points and the public header's prototypes - is the committed, current generation; every renamed twin is exported; the
-    selector validates its argument and forwards (callable without a GPU: argument checks come before any device work)."""
+def test_one_library_serves_both_16bit_types_without_renamed_twins():
+    """Every source is compiled once and serves both 16-bit types: no exported symbol carries the old fp16 suffix, the build's list of
+    twice-compiled sources is empty and there is no generated rename header; the selector validates its argument, and with fp16 selected the same entry point
+    answers (callable without a GPU: argument checks come before any device work)."""
     import os
+    import subprocess
     from simseg_amd import build, lib
-    text = build.gen_half_names(write=False)
-    assert open(os.path.join(build.CSRC, "half_names.h")).read() == text, "csrc/half_names.h is stale: python -m simseg_amd.build"
-    so = ctypes.CDLL(lib.LIB_PATH)
-    twins = [ln.split()[2] for ln in text.splitlines() if ln.startswith("#define ")]
-    import re
-    defined = [m.group(1) + "_h16" for f in build.TWICE
-               for m in re.finditer(r'^extern "C"\s+(?:const char\*|int64_t|int)\s+(simseg_\w+)\s*\([^)]*\)\s*\{', open(os.path.join(build.CSRC, f)).read(), flags=re.M)]
-    assert defined and len(defined) == len(set(defined))
-    assert sorted(twins) == sorted(defined) and all(hasattr(so, t) for t in twins)      # exactly the entry points the TWICE sources define
+    exported = [ln.split()[-1] for ln in subprocess.run(["nm", "-D", "--defined-only", lib.LIB_PATH], capture_output=True, text=True, check=True).stdout.splitlines()]
+    assert any(n == "simseg_gemm" for n in exported)
+    assert not [n for n in exported if n.endswith("_h16")]
+    assert not getattr(build, "TWICE", ())
+    assert not hasattr(build, "gen_half_names") and not os.path.exists(os.path.join(build.CSRC, "half_names.h"))
     l = lib.load()
     assert l.simseg_set_half_type(3) != 0 and b"simseg_set_half_type" in l.simseg_last_error()
     assert l.simseg_set_half_type(2) == 0
-    try:        # the bf16 entry hands the call to its fp16 twin, whose own argument check answers
+    try:
         assert l.simseg_gemm(None, None, None, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 1.0, None, None, None, 0, 0, None, None, 0, 0, 0, 1, 0, 0.0, None, None) != 0
         assert b"null operand" in l.simseg_last_error()
     finally:
         assert l.simseg_set_half_type(1) == 0
 
 
-def test_no_unreachable_twin_in_the_twice_compiled_sources():
-    """Every C-ABI entry point DEFINED in a twice-compiled source hands over to its _h16 twin (an SS_HALF_FWD( call in its body) - or is
-    listed here with the reason why it does not.  An entry whose kernels do not depend on the 16-bit type belongs in a once-compiled source
-    (loss.hip, optim.hip, rowops.hip, ...): there its twin would be a second copy nothing can call.  Source text only."""
+def test_every_entry_point_is_defined_once_and_without_a_second_compilation():
+    """Every simseg_* entry point of csrc/*.hip is defined exactly once across all sources, and no source or header knows a second
+    compilation (SS_HALF): one definition serves fp32 and both 16-bit types, so no host state exists twice.  Source text only."""
+    import glob
     import os
     import re
     from simseg_amd import build
-    allowed = {
-        "simseg_set_gemm_variant": "forwards by hand: sets both flavours' thread-local selectors after one argument check",
-        "simseg_set_attention_variant": "forwards by hand: sets both flavours' thread-local selectors after one argument check",
-        "simseg_debug_gemm_trace": "debug: arms the bf16 build's trace pointer only",
-        "simseg_debug_attn_trace": "debug: arms the bf16 build's trace pointer only",
-        "simseg_debug_attention_timeline": "debug: times the bf16 forward only",
-        "simseg_gemm_aux_blocked_ok": "host arithmetic on the shape, the same in both flavours; states the condition of gemm.hip's own dispatch",
-        "simseg_attention_bwd_workspace_bytes": "host arithmetic on the shape, the same in both flavours",
-        "simseg_attention_fwd_x3": "exact mode: always the bf16 pieces of fp32 operands, next to the attention kernels' tile code it shares",
-    }
-    seen = set()
-    for f in build.TWICE:
-        src = open(os.path.join(build.CSRC, f)).read()
-        for m in re.finditer(r'extern "C"\s+(?:const char\*|int64_t|int)\s+(simseg_\w+)\s*\([^)]*\)\s*([{;])', src):
-            if m.group(2) == ";":            # a declaration of another file's entry point
-                continue
-            depth, i = 1, m.end()
-            while depth:
-                depth += {"{": 1, "}": -1}.get(src[i], 0)
-                i += 1
-            name, body = m.group(1), src[m.end():i]
-            assert name not in seen, f"{name} is defined twice"
-            seen.add(name)
-            if "SS_HALF_FWD(" in body:
-                assert name not in allowed, f"{name} forwards to its twin: take it off the allow-list"
-            else:
-                assert name in allowed, f"{f}: {name} never reaches its _h16 twin - move it to a once-compiled source (or say here why not)"
-    assert set(allowed) <= seen, sorted(set(allowed) - seen)
-    assert len(seen) == 20 and len(allowed) <= 8
+    seen = {}
+    for path in sorted(glob.glob(os.path.join(build.CSRC, "*.hip")) + glob.glob(os.path.join(build.CSRC, "*.h"))):
+        src = open(path).read()
+        assert "SS_HALF" not in src, os.path.basename(path)
+        for m in re.finditer(r'extern "C"\s+(?:const char\*|int64_t|int|void)\s+(simseg_\w+)\s*\([^)]*\)\s*\{', src):
+            assert not m.group(1).endswith("_h16"), m.group(1)
+            assert m.group(1) not in seen, f"{m.group(1)} is defined in {seen[m.group(1)]} and in {os.path.basename(path)}"
+            seen[m.group(1)] = os.path.basename(path)
+    per_file = {f: sum(1 for v in seen.values() if v == f) for f in set(seen.values())}
+    assert per_file["gemm.hip"] == 8 and per_file["attn.hip"] == 12, per_file      # the twenty that used to exist twice
+    hdr = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "simseg_hip.h")).read(), flags=re.S)
+    assert set(seen) == set(re.findall(r"\b(simseg_\w+)\s*\([^)]*\)\s*;", hdr))     # ... and it is the public header's list
 
 
 def test_interpolate_pos_embed_and_miou_match_reference(golden):
@@ -401,24 +381,25 @@ def test_ping_pong_gemm_kernels_spill_nothing_outside_the_saved_derivative_epilo
     spec.loader.exec_module(kr)
     if not os.path.exists(os.path.join(kr.LLVM, "llvm-readelf")):
         pytest.skip("no llvm-readelf in this image")
-    seen = {0: 0, 1: 0, 2: 0, 3: 0, 4: 0, 5: 0}        # (4 / 5: the 8-bit derivative image of round 4 - forward like 2, backward like 3)
-    for obj in ("gemm.o", "gemm_h16.o"):
-        path = os.path.join(REPO, "simseg_amd", "build", obj)
-        if not os.path.exists(path):
-            pytest.skip("simseg_amd/build/*.o not present (the library was built elsewhere)")
-        for name, vgpr, spill, scratch, lds in kr.kernel_resources(path):
-            m = re.search(r"gemm_pp2?_kernel(?:I|<)(.*)", name)
-            if not m:
-                continue
-            args = re.findall(r"Li(\d+)E|, (\d+)(?=[,>])", m.group(1))
-            ek = int([a or b for a, b in args][-1])                       # the last integer template argument: the epilogue kind
-            is16 = "float" not in name.split("kernel")[1][:12] and not re.search(r"kernelIf", name)
-            seen[ek] += 1
-            if not is16 or ek in (0, 2, 4):
-                assert spill == 0 and scratch == 0, (obj, name, vgpr, spill, scratch)
-            else:
-                assert spill <= 48 and scratch <= 200, (obj, name, vgpr, spill, scratch)
-    assert all(seen[k] > 0 for k in seen), seen
+    seen = set()        # (16-bit type, epilogue kind); kinds 4 / 5: the 8-bit derivative image of round 4 - forward like 2, backward like 3
+    path = os.path.join(REPO, "simseg_amd", "build", "gemm.o")          # one object: the 16-bit type is the kernels' first template argument
+    if not os.path.exists(path):
+        pytest.skip("simseg_amd/build/*.o not present (the library was built elsewhere)")
+    types = {"DF16b": "bf16", "DF16_": "fp16"}
+    for name, vgpr, spill, scratch, lds in kr.kernel_resources(path, demangle=False):
+        # <H, TO, TA, TB, EK, ...>: the operand type, the output type (H or float), two transposition flags, the epilogue kind
+        m = re.search(r"gemm_pp2?_kernelI(DF16b|DF16_)(DF16b|DF16_|f)Lb[01]ELb[01]ELi(\d)E", name)
+        if not m:
+            assert "gemm_pp" not in name, name
+            continue
+        h, is16, ek = types[m.group(1)], m.group(2) != "f", int(m.group(3))
+        assert not is16 or m.group(2) == m.group(1), name
+        seen.add((h, ek))
+        if not is16 or ek in (0, 2, 4):
+            assert spill == 0 and scratch == 0, (name, vgpr, spill, scratch)
+        else:
+            assert spill <= 48 and scratch <= 200, (name, vgpr, spill, scratch)
+    assert {(h, k) for h in ("bf16", "fp16") for k in range(6)} <= seen, seen
 
 
 def test_gradsync_zero_copy_target_is_handed_out_once_and_only_without_a_gradient():
@@ -524,7 +505,7 @@ def test_layernorm_backward_kernels_fit_four_waves_per_simd():
 
 
 def test_long_sequence_attention_forward_register_budget():
-    """Code-object metadata of the built attn.o / attn_h16.o: the 64-queries-per-wave forward (attn_fwd_w64_kernel) sits AT its register budget
+    """Code-object metadata of the built attn.o, both 16-bit types: the 64-queries-per-wave forward (attn_fwd_w64_kernel) sits AT its register budget
     (256 per wave = two waves per SIMD) and its register allocation is fragile - a second inlined tile loop, a branch inside the tile body or
     loop-invariant addresses kept live each put scratch reloads inside the tile loop, where they wait for the K / V copies in flight (DESIGN.md
     7.1).  The production instantiations (two query blocks per wave, no masked last tile) keep <= 4 spilled registers, all outside the loop; the
@@ -537,24 +518,25 @@ def test_long_sequence_attention_forward_register_budget():
     if not os.path.exists(os.path.join(kr.LLVM, "llvm-readelf")):
         pytest.skip("no llvm-readelf in this image")
     seen = set()
-    for obj in ("attn.o", "attn_h16.o"):
-        path = os.path.join(REPO, "simseg_amd", "build", obj)
-        if not os.path.exists(path):
-            pytest.skip("simseg_amd/build/*.o not present (the library was built elsewhere)")
-        for name, vgpr, spill, scratch, lds in kr.kernel_resources(path):
-            m = re.search(r"attn_fwd_w64_kernel<(\d), (true|false), (true|false), (true|false)>", name)
-            if not m:
-                continue
-            nqb, edge, dbg = int(m.group(1)), m.group(2) == "true", m.group(4) == "true"
-            if dbg:
-                continue                                   # (the instrumented timeline build: tools only)
-            seen.add((obj, nqb, edge))
-            assert lds == 3 * 16384, (obj, name, lds)      # three 16-KiB stages: two (three) blocks per CU
-            if nqb == 1:
-                assert vgpr <= 168 and spill == 0 and scratch == 0, (obj, name, vgpr, spill, scratch)
-            else:
-                assert vgpr <= 256 and spill <= (16 if edge else 4) and scratch <= (64 if edge else 16), (obj, name, vgpr, spill, scratch)
-    assert {(o, n, e) for o in ("attn.o", "attn_h16.o") for n in (1, 2) for e in (False, True)} <= seen, seen
+    path = os.path.join(REPO, "simseg_amd", "build", "attn.o")          # one object: the 16-bit type is the kernels' first template argument
+    if not os.path.exists(path):
+        pytest.skip("simseg_amd/build/*.o not present (the library was built elsewhere)")
+    types = {"DF16b": "bf16", "DF16_": "fp16"}
+    for name, vgpr, spill, scratch, lds in kr.kernel_resources(path, demangle=False):
+        m = re.search(r"attn_fwd_w64_kernelI(DF16b|DF16_)Li(\d)ELb([01])ELb[01]ELb([01])E", name)      # <H, NQB, HAS_EDGE, QS, DBG>
+        if not m:
+            assert "attn_fwd_w64_kernel" not in name, name
+            continue
+        h, nqb, edge, dbg = types[m.group(1)], int(m.group(2)), m.group(3) == "1", m.group(4) == "1"
+        if dbg:
+            continue                                   # (the instrumented timeline build: tools only)
+        seen.add((h, nqb, edge))
+        assert lds == 3 * 16384, (name, lds)           # three 16-KiB stages: two (three) blocks per CU
+        if nqb == 1:
+            assert vgpr <= 168 and spill == 0 and scratch == 0, (name, vgpr, spill, scratch)
+        else:
+            assert vgpr <= 256 and spill <= (16 if edge else 4) and scratch <= (64 if edge else 16), (name, vgpr, spill, scratch)
+    assert {(h, n, e) for h in ("bf16", "fp16") for n in (1, 2) for e in (False, True)} <= seen, seen
 
 
 def test_gradsync_zero_copy_targets():

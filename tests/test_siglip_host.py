@@ -68,7 +68,10 @@ def test_c_abi_declares_and_exports_siglip_rows():
                                                                "out4", "N1", "N2", "target0", "write_grad", "stream"]
     assert protos["simseg_siglip_rows"][0] is ctypes.c_int
     so = ctypes.CDLL(lib.LIB_PATH)          # (the built library: the suite runs after the build)
-    assert "loss.hip" not in build.TWICE     # fp32 rows: one entry point, no second flavour
+    import glob
+    objs = [os.path.basename(o) for o in glob.glob(os.path.join(REPO, "simseg_amd", "build", "loss*.o"))]
+    assert not getattr(build, "TWICE", ()) and objs in ([], ["loss.o"])     # fp32 rows, one entry point: ONE object (none here when the library was built elsewhere)
+    assert glob.glob(os.path.join(REPO, "simseg_amd", "csrc", "loss*.hip")) == [os.path.join(REPO, "simseg_amd", "csrc", "loss.hip")]
     src = open(os.path.join(REPO, "simseg_amd/csrc/loss.hip")).read()
     assert 'extern "C" int simseg_siglip_rows(' in src, "simseg_siglip_rows is not defined in loss.hip"
     assert "siglip_rows_kernel" in src and "siglip_finalize_kernel" in src

@@ -65,7 +65,7 @@ else:
     out = torch.zeros(M, N, device="cuda")
     sk = _splitk(M, N, K)
     kw = dict(trans_a=True, trans_b=True, out=out, accumulate=True, splitk=sk)
-    # the slice count the library derives for the 256x256 kernel (dispatch_bf16): one round of 256 blocks, slices at least 16 K-tiles deep
+    # the slice count the library derives for the 256x256 kernel (dispatch_h16): one round of 256 blocks, slices at least 16 K-tiles deep
     tiles = ((M + 255) // 256) * ((N + 255) // 256)
     nk = K // 64
     sk256 = 256 // tiles

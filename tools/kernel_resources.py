@@ -12,8 +12,10 @@ import tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 
 
-def kernel_resources(obj):
-    """-> [(demangled-ish name, vgpr_count, vgpr_spill_count, private_segment_fixed_size, group_segment_fixed_size)]"""
+def kernel_resources(obj, demangle=True):
+    """-> [(demangled-ish name, vgpr_count, vgpr_spill_count, private_segment_fixed_size, group_segment_fixed_size)]
+    demangle=False keeps the symbol names: a c++filt that does not know DF16b (__bf16) / DF16_ (_Float16) garbles a name that has one of them
+    in front of other template arguments."""
     tmp = tempfile.mkdtemp(prefix="ss_co_")
     try:
         local = os.path.join(tmp, os.path.basename(obj))
@@ -30,6 +32,8 @@ def kernel_resources(obj):
         name = re.search(r"\.name:\s+(\S+)", k).group(1)
         f = lambda key: int(re.search(r"\." + key + r":\s+(\d+)", k).group(1))      # noqa: E731
         out.append((name, f("vgpr_count"), f("vgpr_spill_count"), f("private_segment_fixed_size"), f("group_segment_fixed_size")))
+    if not demangle:
+        return out
     names = subprocess.run(["c++filt"], input="\n".join(n for n, *_ in out), capture_output=True, text=True).stdout.splitlines()
     return [(d,) + r[1:] for d, r in zip(names, out)]
 

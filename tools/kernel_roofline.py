@@ -53,7 +53,7 @@ def main():
                 out[f"attn_bwd_bf16_{name}"] = {"B": B, "T": T, "H": H, "ms": round(s * 1e3, 4), "tflops": round(fl / s / 1e12, 1),
                                                 "frac_mfma_peak": round(fl / s / PEAK[dt], 4)}
     # the evaluation towers' form of the long-sequence forward (round 6): q columns carry scale * log2(e) (towers._wt_qscaled),
-    # simseg_attention_fwd_qscaled; both 16-bit types, the seg-eval batch sizes; fp16 runs through the same source compiled with -DSS_HALF
+    # simseg_attention_fwd_qscaled; both 16-bit types, the seg-eval batch sizes; fp16 runs the same kernels instantiated for _Float16
     c = ops.attention_qscale(0.125)
     for dt, tdt in (("bf16", torch.bfloat16), ("fp16", torch.float16)):
         for name, B, T, H in (("vitb_512", 16, 1025, 12), ("vitb_512", 63, 1025, 12), ("vitb_512", 256, 1025, 12), ("vitb_384", 256, 577, 12),
