@@ -623,6 +623,19 @@ int64_t simseg_train_transforms_scratch_bytes(int64_t B, int64_t S);
 int simseg_train_transforms(const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
                             const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S, void* scratch,
                             int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes, void* stream);
+/* Training chain (simseg_amd/pipeline.py parse_chain(full = True), DESIGN.md "SimCLR colour distortion and Gaussian blur"):
+ * simseg_train_transforms with room for the whole transform registry, on the same two kernels, arguments, scratch rule and erase noise.
+ * A chain of up to 12 ops; the codes of simseg_train_transforms plus 12 grayscale (Pillow's convert("L") in all three channels), 13 hue
+ * (slot 0 = the byte 0..255 added to H modulo 256 between Pillow's convert("HSV") and convert("RGB"); 0 still makes the round trip),
+ * 14 Gaussian blur (slots R, ww, fw of ImageFilter.GaussianBlur's box passes: three along the rows, then three along the columns, each
+ * out[x] = (ww * sum_{|d| <= R} in[x + d] + fw * (in[x - R - 1] + in[x + R + 1]) + 2^23) >> 24 with indices clamped to the line).
+ * img_tab int64 [B, 144] = columns 0..35 as simseg_train_transforms', 36..47 op codes, 48..143 eight parameter slots per op.  Checked
+ * on the HOST copy before anything is launched, besides what simseg_train_transforms checks: at most 12 ops, codes 0..14, the hue byte,
+ * 0 <= R <= 7, ww > 0, fw >= 0 and (2R + 1) ww + 2 fw = 2^24 or 2^24 - 1 (fw is the floor of a half). */
+int64_t simseg_train_chain_scratch_bytes(int64_t B, int64_t S);
+int simseg_train_chain(const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
+                       const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S, void* scratch,
+                       int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes, void* stream);
 /* cv2.dilate / cv2.erode with a 7x7 ones kernel, ONE iteration (the third positional argument in :156-157 is `dst`, not
  * `iterations`), default border (never wins) on byte images [M,H,W]; erode = 0 dilate, 1 erode.  out must not alias in. */
 int simseg_morph7(const void* in, void* out, int64_t M, int64_t H, int64_t W, int erode, void* stream);

@@ -6,7 +6,8 @@ build_device_transforms is the eval-time route that leaves only the decode on th
 (simseg_amd/preproc.py).  build_train_pipeline is the general training route: every train_transforms list of the grammar
 list := geometry+ colour* (geometry: resize | resize_bicubic | random_resize_crop | center_crop | random_crop | random_flip; colour:
 autoaug | color_jitter), plus random erasing when transforms.random_erasing.reprob > 0, sampled on the host and applied on the device
-in two launches (simseg_amd/pipeline.py); the three other builders keep their behaviour."""
+in two launches (simseg_amd/pipeline.py); the three other builders keep their behaviour.  build_train_views is build_train_pipeline for
+the whole registry: color_distortion and gaussian_blur (the SimCLR pair) join the colour ops, any order, each at most once."""
 import numpy as np
 import torch
 from PIL import Image
@@ -14,7 +15,8 @@ from PIL import Image
 from simseg.utils import logger
 from simseg.utils.registry import Registry
 
-__all__ = ["TRANSFORMS", "build_transforms", "build_device_transforms", "build_train_augmentation", "build_train_pipeline"]
+__all__ = ["TRANSFORMS", "build_transforms", "build_device_transforms", "build_train_augmentation", "build_train_pipeline",
+           "build_train_views"]
 
 TRANSFORMS = Registry("TRANSFORMS")
 
@@ -160,6 +162,17 @@ def build_train_pipeline(cfg):
     from simseg_amd.pipeline import TrainPipeline, parse_chain
     pipe = TrainPipeline(parse_chain(list(cfg.transforms.train_transforms), cfg, lut=_normalize_lut(cfg)))
     logger.emph("train image transforms on the device:", pipe)
+    return _to_u8, pipe
+
+
+def build_train_views(cfg):
+    """build_train_pipeline for the whole registry: the grammar list := geometry+ pixel* with pixel := autoaug | color_jitter |
+    color_distortion | gaussian_blur (the SimCLR pair under transforms.color_distortion.strength and transforms.gaussian_blur.{p,
+    radius_min, radius_max}; strength 1.0 and p 0.5, radii 0.1 .. 2.0 where the config has no such keys).  -> (host_op, pipeline) as
+    build_train_pipeline; a list of the old grammar gives the same parameters and the same bytes as build_train_pipeline's."""
+    from simseg_amd.pipeline import TrainPipeline, parse_chain
+    pipe = TrainPipeline(parse_chain(list(cfg.transforms.train_transforms), cfg, lut=_normalize_lut(cfg), full=True))
+    logger.emph("train image views on the device:", pipe)
     return _to_u8, pipe
 
 

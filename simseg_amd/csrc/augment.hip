@@ -15,9 +15,14 @@
 // host-filled [3, 256] fp32 table.
 //
 // simseg_train_transforms (DESIGN.md "Device-side training transforms") is the general chain on the same two kernels, instantiated for
-// its wider table (WIDE): launch 1 resamples the source box with either filter to RH x RW, keeps the S x S output window and mirrors its
+// its wider table (WIDE = 1): launch 1 resamples the source box with either filter to RH x RW, keeps the S x S output window and mirrors its
 // columns for a flip; launch 2 runs a chain of up to five ops (brightness added) and replaces the look-up value inside the image's erase
-// boxes by the fill of the mode.  The WIDE = false instances are simseg_train_augment's, as they were.
+// boxes by the fill of the mode.  The WIDE = 0 instances are simseg_train_augment's, as they were.
+//
+// simseg_train_chain (DESIGN.md "SimCLR colour distortion and Gaussian blur") is the third layout (WIDE = 2): the same geometry and erase
+// columns, twelve ops, and three more op codes: grayscale, the hue shift (Pillow's RGB -> HSV -> RGB round trip per pixel) and the Gaussian
+// blur (Pillow's three box passes along the rows, then along the columns; one thread per (line, channel) runs a pass in place, the R + 1
+// bytes behind its position kept in a 64-bit register, so every byte of a pass is read before it is overwritten).
 //
 // Exactness: the blends, the 3x3 smoothing, autocontrast's scale and the bicubic shear must round as Pillow's C code does, so floating-
 // point contraction is off for this file (build.py compiles with -O3 and the default contraction, which would form FMAs).
@@ -34,6 +39,12 @@ enum { OP_NONE = 0, OP_POSTERIZE, OP_SOLARIZE, OP_INVERT, OP_AUTOCONTRAST, OP_EQ
 constexpr int TT_COLS = 81, TT_MAX_OPS = 5, TT_MAX_ERASE = 4;
 enum { TT_RH = 11, TT_RW, TT_WTOP, TT_WLEFT, TT_FLIP, TT_NOPS, TT_NERASE, TT_MODE, TT_SEED, TT_BOX = 20, TT_OP = 36, TT_P = 41 };
 enum { ER_CONST = 0, ER_RAND, ER_PIXEL, ER_MODES };
+// the table of simseg_train_chain: columns 0 .. 35 as TT's, then
+constexpr int TC_COLS = 144, TC_MAX_OPS = 12, TC_P = 48;
+enum { OP_GRAY = OP_COUNT_WIDE, OP_HUE, OP_BLUR, OP_COUNT_CHAIN };
+constexpr int AG_BLUR_MAX_R = 7;                                    // R + 1 bytes of a line fit one 64-bit register
+__host__ __device__ constexpr int ag_cols(int wide) { return wide == 2 ? TC_COLS : wide ? TT_COLS : AG_COLS; }
+__host__ __device__ constexpr int ag_slot0(int wide) { return wide == 2 ? TC_P : wide ? TT_P : AG_P1; }
 constexpr int AG_MIN_S = 32, AG_MAX_S = 384;
 constexpr int AG_THREADS = 1024;
 constexpr int AG_LDS_MAX_S = 230;                                   // 230 * 230 * 3 = 158,700 bytes + the static LDS below <= 160 KiB
@@ -43,13 +54,13 @@ __host__ __device__ inline int64_t ag_slot_bytes(int64_t S) { return (3 * S * S 
 static inline bool ag_in_lds(int64_t S) { return S <= AG_LDS_MAX_S; }
 
 // ---- launch 1: crop + resize -------------------------------------------------------------------------------------------------------------
-template <bool WIDE>
+template <int WIDE>
 __global__ __launch_bounds__(256) void augment_resize_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ img_tab,
                                                              const int* __restrict__ tab, uint8_t* __restrict__ scratch, int S,
                                                              int tiles_per_image) {
     __shared__ uint32_t hbuf[PP_CR * PP_TW];
     const int b = blockIdx.x / tiles_per_image, tile = blockIdx.x % tiles_per_image;
-    const int64_t* it = img_tab + (long)b * (WIDE ? TT_COLS : AG_COLS);
+    const int64_t* it = img_tab + (long)b * ag_cols(WIDE);
     const long pitch = it[AG_W];
     const int* __restrict__ hb = tab + it[AG_HOFF];               // bounds [RW, 2] inside the crop, then coefficients [RW, hks]
     const int* __restrict__ vb = tab + it[AG_VOFF];
@@ -101,6 +112,62 @@ __device__ __forceinline__ float ag_normal(uint64_t seed, uint64_t i) {
     return sqrtf(-2.0f * logf(u1)) * cospif(u2x2);
 }
 
+// torchvision's adjust_hue on one pixel: Pillow's convert("HSV") (float32 quotients; h in float32 when red is the maximum, else formed in
+// double; fmod(h / 6 + 1, 1) in double, h / 6 + 1 lying in [5/6, 11/6]), H + shift modulo 256, Pillow's convert("RGB") (all in double)
+__device__ __forceinline__ uint32_t ag_hue(uint32_t v, int shift) {
+    const int r = v & 255u, g = (v >> 8) & 255u, b = (v >> 16) & 255u;
+    const int mx = max(r, max(g, b)), mn = min(r, min(g, b));
+    int H = 0, Sv = 0;
+    if (mx != mn) {
+        const float cr = (float)(mx - mn);
+        const float s = cr / (float)mx;
+        const float rc = (float)(mx - r) / cr, gc = (float)(mx - g) / cr, bc = (float)(mx - b) / cr;
+        float h;
+        if (r == mx) h = bc - gc;
+        else if (g == mx) h = (float)(2.0 + (double)rc - (double)bc);
+        else h = (float)(4.0 + (double)gc - (double)rc);
+        const double t = (double)h / 6.0 + 1.0;
+        const float hh = (float)(t >= 1.0 ? t - 1.0 : t);
+        H = min(max((int)((double)hh * 255.0), 0), 255);
+        Sv = min(max((int)((double)s * 255.0), 0), 255);
+    }
+    H = (H + shift) & 255;
+    const uint32_t V = (uint32_t)mx;
+    if (Sv == 0) return V | (V << 8) | (V << 16);
+    const double fv = (double)mx, fs = (double)Sv / 255.0, h6 = (double)H * 6.0 / 255.0;
+    const double fi = floor(h6), f = h6 - fi;
+    const uint32_t p = (uint32_t)min((int)(fv * (1.0 - fs) + 0.5), 255);
+    const uint32_t q = (uint32_t)min((int)(fv * (1.0 - fs * f) + 0.5), 255);
+    const uint32_t t = (uint32_t)min((int)(fv * (1.0 - fs * (1.0 - f)) + 0.5), 255);
+    switch ((int)fi % 6) {
+        case 0: return V | (t << 8) | (p << 16);
+        case 1: return q | (V << 8) | (p << 16);
+        case 2: return p | (V << 8) | (t << 16);
+        case 3: return p | (q << 8) | (V << 16);
+        case 4: return t | (p << 8) | (V << 16);
+        default: return V | (p << 8) | (q << 16);
+    }
+}
+
+// One box pass of Pillow's Gaussian blur over a line of n bytes (q, stride st), in place, by one thread:
+// out[x] = (ww * sum_{|d| <= R} in[x + d] + fw * (in[x - R - 1] + in[x + R + 1]) + 2^23) >> 24, indices clamped to the line; the sum
+// slides.  Byte j of `hist` is in[x - 1 - j] as it was before the pass (in[0] left of the line), bytes at and right of x are still
+// unwritten, so every input is read before it is overwritten.  R <= AG_BLUR_MAX_R; (2R + 1) ww + 2 fw <= 2^24, so uint32 holds it.
+__device__ __forceinline__ void ag_box_line(uint8_t* q, int n, int st, int R, uint32_t ww, uint32_t fw) {
+    const uint32_t first = q[0];
+    uint64_t hist = (uint64_t)first * 0x0101010101010101ull;
+    uint32_t W = (uint32_t)(R + 1) * first;
+    for (int d = 1; d <= R; ++d) W += q[min(d, n - 1) * st];
+    for (int x = 0; x < n; ++x) {
+        const uint32_t cur = q[x * st];
+        const uint32_t er = q[min(x + R + 1, n - 1) * st];
+        const uint32_t el = (uint32_t)(hist >> (8 * R)) & 255u;
+        q[x * st] = (uint8_t)((ww * W + fw * (el + er) + (1u << 23)) >> 24);
+        hist = (hist << 8) | cur;
+        W += er - ((uint32_t)(hist >> (8 * R)) & 255u);
+    }
+}
+
 // Every pixel through f(p) -> packed RGB, all reads before any write: the results go to `alt` (global memory), the workgroup waits, and
 // then the LDS path copies them back into LDS (16-byte pieces) while the global path makes `alt` the image.  (Keeping them in registers
 // instead - 52 pixels per thread at S = 230 - spills the bicubic's working set at 1024 threads.)
@@ -118,7 +185,7 @@ __device__ __forceinline__ void ag_gather(uint8_t*& buf, uint8_t*& alt, int n, l
     }
 }
 
-template <bool LDS, bool WIDE>
+template <bool LDS, int WIDE>
 __global__ __launch_bounds__(AG_THREADS) void augment_ops_kernel(const int64_t* __restrict__ img_tab, uint8_t* __restrict__ scratch,
                                                                  uint8_t* __restrict__ scratch2, int S, const float* __restrict__ lut,
                                                                  float* __restrict__ out, uint8_t* __restrict__ out_u8) {
@@ -127,7 +194,7 @@ __global__ __launch_bounds__(AG_THREADS) void augment_ops_kernel(const int64_t* 
     __shared__ uint8_t tlut[3][256];
     __shared__ int lsum;
     const int b = blockIdx.x, tid = threadIdx.x;
-    const int64_t* it = img_tab + (long)b * (WIDE ? TT_COLS : AG_COLS);
+    const int64_t* it = img_tab + (long)b * ag_cols(WIDE);
     const int n = S * S;
     const long slot = ag_slot_bytes(S);
     const int nops = WIDE ? (int)it[TT_NOPS] : 2;
@@ -144,8 +211,8 @@ __global__ __launch_bounds__(AG_THREADS) void augment_ops_kernel(const int64_t* 
         alt = scratch2 + b * slot;
     }
     for (int k = 0; k < nops; ++k) {
-        const int op = (int)it[(WIDE ? TT_OP : AG_OP1) + k];
-        const int64_t* P = it + (WIDE ? TT_P : AG_P1) + k * AG_SLOTS;
+        const int op = (int)it[(WIDE ? TT_OP : AG_OP1) + k];                  // (TT_OP in both wide layouts)
+        const int64_t* P = it + ag_slot0(WIDE) + k * AG_SLOTS;
         __syncthreads();                                         // the image as the last step left it
         if (op == OP_NONE) continue;
         if (op <= OP_EQUALIZE) {
@@ -294,6 +361,26 @@ __global__ __launch_bounds__(AG_THREADS) void augment_ops_kernel(const int64_t* 
                 }
                 return r;
             });
+        } else if (WIDE == 2 && op == OP_GRAY) {                 // convert("L") in all three channels
+            for (int p = tid; p < n; p += AG_THREADS) {
+                const uint32_t L = (uint32_t)ag_luma(ag_px(buf, p));
+                ag_put(buf, p, L | (L << 8) | (L << 16));
+            }
+        } else if (WIDE == 2 && op == OP_HUE) {
+            const int shift = (int)P[0];
+            for (int p = tid; p < n; p += AG_THREADS) ag_put(buf, p, ag_hue(ag_px(buf, p), shift));
+        } else if (WIDE == 2 && op == OP_BLUR) {                 // three passes along the rows, a barrier, three along the columns
+            const int R = (int)P[0];
+            const uint32_t ww = (uint32_t)P[1], fw = (uint32_t)P[2];
+            for (int dir = 0; dir < 2; ++dir) {
+                // task 3 * line + channel: along the columns a wave's bytes are contiguous, along the rows 3 lanes share a pixel
+                for (int t = tid; t < 3 * S; t += AG_THREADS) {
+                    const int line = t / 3;
+                    uint8_t* q = buf + (dir == 0 ? 3 * line * S + (t - 3 * line) : t);
+                    for (int pass = 0; pass < 3; ++pass) ag_box_line(q, S, dir == 0 ? 3 : 3 * S, R, ww, fw);
+                }
+                __syncthreads();
+            }
         }
     }
     __syncthreads();
@@ -342,6 +429,7 @@ extern "C" int64_t simseg_train_augment_scratch_bytes(int64_t B, int64_t S) {
     return B * ag_slot_bytes(S) * (ag_in_lds(S) ? 1 : 2);
 }
 extern "C" int64_t simseg_train_transforms_scratch_bytes(int64_t B, int64_t S) { return simseg_train_augment_scratch_bytes(B, S); }
+extern "C" int64_t simseg_train_chain_scratch_bytes(int64_t B, int64_t S) { return simseg_train_augment_scratch_bytes(B, S); }
 
 static bool ag_finite(double v) { return v == v && v - v == 0.0; }
 
@@ -365,11 +453,22 @@ static int ag_check_op(const char* who, int64_t b, int k, int64_t op, const int6
             memcpy(&v, &P[i], 8);
             SS_CHECK(ag_finite(v) && fabs(v) < 1e6, "%s: image %ld: affine coefficient %d is not finite and small", who, (long)b, i);
         }
+    if (op == OP_HUE) SS_CHECK(P[0] >= 0 && P[0] <= 255, "%s: image %ld: hue shift %ld, a byte is needed", who, (long)b, (long)P[0]);
+    if (op == OP_BLUR) {                                         // fw = (2^24 - (2R + 1) ww) // 2: the weights sum to 2^24 or 2^24 - 1
+        const int64_t R = P[0], ww = P[1], fw = P[2];
+        SS_CHECK(R >= 0 && R <= AG_BLUR_MAX_R, "%s: image %ld: blur box radius %ld, 0 .. %d", who, (long)b, (long)R, AG_BLUR_MAX_R);
+        SS_CHECK(ww > 0 && ww <= (1 << 24) && fw >= 0 && fw <= (1 << 23), "%s: image %ld: blur weights ww %ld, fw %ld out of range", who,
+                 (long)b, (long)ww, (long)fw);
+        const int64_t rest = (1 << 24) - (2 * R + 1) * ww - 2 * fw;
+        SS_CHECK(rest == 0 || rest == 1, "%s: image %ld: blur weights ww %ld, fw %ld do not sum to 2^24 with R %ld", who, (long)b, (long)ww,
+                 (long)fw, (long)R);
+    }
     return 0;
 }
 
-// Both entry points: every field of the host copy is checked, then the two launches.  WIDE: the table of simseg_train_transforms.
-template <bool WIDE>
+// The entry points: every field of the host copy is checked, then the two launches.  WIDE: 1 the table of simseg_train_transforms,
+// 2 that of simseg_train_chain.
+template <int WIDE>
 static int ag_run(const char* who, const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
                   const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S, void* scratch,
                   int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes, void* stream) {
@@ -382,7 +481,7 @@ static int ag_run(const char* who, const void* src, int64_t src_bytes, const int
              (long)simseg_train_augment_scratch_bytes(B, S));
     PpAxisCache axes{tab_host, tab_numel};                       // (a batch shares few axes)
     for (int64_t b = 0; b < B; ++b) {
-        const int64_t* it = img_tab_host + b * (WIDE ? TT_COLS : AG_COLS);
+        const int64_t* it = img_tab_host + b * ag_cols(WIDE);
         const int64_t H = it[AG_H], W = it[AG_W], top = it[AG_TOP], left = it[AG_LEFT], ch = it[AG_CH], cw = it[AG_CW];
         const int64_t RH = WIDE ? it[TT_RH] : S, RW = WIDE ? it[TT_RW] : S;
         SS_CHECK(pp_extent_ok(H, W), "%s: image %ld: bad source extent %ld x %ld", who, (long)b, (long)H, (long)W);
@@ -400,10 +499,11 @@ static int ag_run(const char* who, const void* src, int64_t src_bytes, const int
         e = axes.check(it[AG_VOFF], it[AG_VKS], ch, RH);
         SS_CHECK(!e, "%s: image %ld, vertical: %s", who, (long)b, e);
         const int64_t nops = WIDE ? it[TT_NOPS] : 2;
-        SS_CHECK(nops >= 0 && nops <= TT_MAX_OPS, "%s: image %ld: a chain of %ld ops, at most %d", who, (long)b, (long)nops, TT_MAX_OPS);
+        constexpr int max_ops = WIDE == 2 ? TC_MAX_OPS : TT_MAX_OPS;
+        SS_CHECK(nops >= 0 && nops <= max_ops, "%s: image %ld: a chain of %ld ops, at most %d", who, (long)b, (long)nops, max_ops);
         for (int k = 0; k < (int)nops; ++k)
-            if (int rc = ag_check_op(who, b, k, it[(WIDE ? TT_OP : AG_OP1) + k], it + (WIDE ? TT_P : AG_P1) + k * AG_SLOTS,
-                                     WIDE ? OP_COUNT_WIDE : OP_COUNT))
+            if (int rc = ag_check_op(who, b, k, it[(WIDE ? TT_OP : AG_OP1) + k], it + ag_slot0(WIDE) + k * AG_SLOTS,
+                                     WIDE == 2 ? OP_COUNT_CHAIN : WIDE ? OP_COUNT_WIDE : OP_COUNT))
                 return rc;
         if (WIDE) {
             const int64_t ne = it[TT_NERASE];
@@ -419,7 +519,7 @@ static int ag_run(const char* who, const void* src, int64_t src_bytes, const int
     const int tiles = ((int)S + PP_TW - 1) / PP_TW * (((int)S + PP_TH - 1) / PP_TH);
     hipLaunchKernelGGL(augment_resize_kernel<WIDE>, dim3((unsigned)(B * tiles)), dim3(256), 0, (hipStream_t)stream,
                        static_cast<const uint8_t*>(src), img_tab, tab, static_cast<uint8_t*>(scratch), (int)S, tiles);
-    SS_LAUNCH_CHECK(WIDE ? "train_transforms (resize)" : "train_augment (resize)");
+    SS_LAUNCH_CHECK(WIDE == 2 ? "train_chain (resize)" : WIDE ? "train_transforms (resize)" : "train_augment (resize)");
     uint8_t* s1 = static_cast<uint8_t*>(scratch);
     if (ag_in_lds(S)) {
         static bool attr = false;                                // (one per instance of this template)
@@ -435,7 +535,7 @@ static int ag_run(const char* who, const void* src, int64_t src_bytes, const int
         hipLaunchKernelGGL((augment_ops_kernel<false, WIDE>), dim3((unsigned)B), dim3(AG_THREADS), 0, (hipStream_t)stream, img_tab, s1,
                            s1 + B * ag_slot_bytes(S), (int)S, lut, out, static_cast<uint8_t*>(out_u8));
     }
-    SS_LAUNCH_CHECK(WIDE ? "train_transforms (ops)" : "train_augment (ops)");
+    SS_LAUNCH_CHECK(WIDE == 2 ? "train_chain (ops)" : WIDE ? "train_transforms (ops)" : "train_augment (ops)");
     return 0;
 }
 
@@ -443,14 +543,21 @@ extern "C" int simseg_train_augment(const void* src, int64_t src_bytes, const in
                                     const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S,
                                     void* scratch, int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes,
                                     void* stream) {
-    return ag_run<false>("train_augment", src, src_bytes, img_tab, img_tab_host, B, tab, tab_host, tab_numel, lut, S, scratch, scratch_bytes,
-                         out, out_numel, out_u8, u8_bytes, stream);
+    return ag_run<0>("train_augment", src, src_bytes, img_tab, img_tab_host, B, tab, tab_host, tab_numel, lut, S, scratch, scratch_bytes, out,
+                     out_numel, out_u8, u8_bytes, stream);
 }
 
 extern "C" int simseg_train_transforms(const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
                                        const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S,
                                        void* scratch, int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes,
                                        void* stream) {
-    return ag_run<true>("train_transforms", src, src_bytes, img_tab, img_tab_host, B, tab, tab_host, tab_numel, lut, S, scratch,
-                        scratch_bytes, out, out_numel, out_u8, u8_bytes, stream);
+    return ag_run<1>("train_transforms", src, src_bytes, img_tab, img_tab_host, B, tab, tab_host, tab_numel, lut, S, scratch,
+                     scratch_bytes, out, out_numel, out_u8, u8_bytes, stream);
+}
+
+extern "C" int simseg_train_chain(const void* src, int64_t src_bytes, const int64_t* img_tab, const int64_t* img_tab_host, int64_t B,
+                                  const int32_t* tab, const int32_t* tab_host, int64_t tab_numel, const float* lut, int64_t S, void* scratch,
+                                  int64_t scratch_bytes, float* out, int64_t out_numel, void* out_u8, int64_t u8_bytes, void* stream) {
+    return ag_run<2>("train_chain", src, src_bytes, img_tab, img_tab_host, B, tab, tab_host, tab_numel, lut, S, scratch, scratch_bytes, out,
+                     out_numel, out_u8, u8_bytes, stream);
 }

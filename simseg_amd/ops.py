@@ -1157,6 +1157,22 @@ def train_transforms(src, plan, lut, want_u8=False):
     return out, u8
 
 
+def train_chain(src, plan, lut, want_u8=False):
+    """train_transforms for a chain of the full grammar (pipeline.parse_chain(full=True)): the 144-column table with up to twelve ops,
+    grayscale, hue shift and Gaussian blur among them.  Same arguments, same results, same two launches."""
+    it, th = _check_packed_batch("train_chain", src, plan, lut, 144, need_2d=True)
+    if it.shape[1] != 144:
+        raise ValueError(f"train_chain: the image table has 144 columns, got {it.shape[1]} (a plan of the old grammar goes to train_transforms)")
+    B, S = it.shape[0], plan["size"]
+    dev = src.device
+    scratch = torch.empty(max(raw("simseg_train_chain_scratch_bytes", B, S), 16), device=dev, dtype=torch.uint8)
+    out = torch.empty(B, 3, S, S, device=dev, dtype=torch.float32)
+    u8 = torch.empty(B, S, S, 3, device=dev, dtype=torch.uint8) if want_u8 else None
+    call("simseg_train_chain", ptr(_c(src)), src.numel(), ptr(plan["img_tab"]), it.ctypes.data, B, ptr(plan["tab"]), th.ctypes.data,
+         th.size, ptr(_c(lut)), S, ptr(scratch), scratch.numel(), ptr(out), out.numel(), ptr(u8), 0 if u8 is None else u8.numel(), stream())
+    return out, u8
+
+
 # ---- linear-probe task (csrc/probe.hip; LARS: csrc/optim.hip) --------------------------------------------------------------------
 CE_MAX_CLASSES = 65536         # simseg_ce_rows: 1 <= C <= 65536
 

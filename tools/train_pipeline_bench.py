@@ -8,7 +8,13 @@
            spread (max - min).
   clip     [resize_bicubic, random_crop, random_flip, color_jitter] with random erasing reprob 0.25, mode pixel, through the new route.
 
+  views    (profiles/train_views.txt) the SimCLR list [random_resize_crop, random_flip, color_distortion, gaussian_blur] through
+           simseg_train_chain beside the shipped list through simseg_train_transforms, interleaved in one process; the blur alone:
+           [random_resize_crop, gaussian_blur] with the blur applied to every image at radius 0.1 and at 2.0, beside [random_resize_crop];
+           and Pillow on the host (apply_pipeline_pil, one process, `--host-images` images of the same batch and parameters).
+
     python tools/train_pipeline_bench.py [--parts shipped,clip] [--reps 24] [--iters 5] [--warmup 3]
+    python tools/train_pipeline_bench.py --parts views [--host-images 64]
     rocprofv3 --kernel-trace --stats -f csv -d <dir> -- python tools/train_pipeline_bench.py --parts clip --reps 1 --iters 4 --warmup 0
       (launches per batch = kernel calls / 4)
 """
@@ -102,12 +108,66 @@ def part_clip(reps, iters, warmup):
             "clip_images_flipped": int(p["flip"].sum()), "clip_new_route": _stats(ms)}
 
 
+def part_views(reps, iters, warmup, host_images):
+    import time
+
+    import numpy as np
+    import torch
+    from PIL import Image
+    from simseg_amd import ops, pipeline as P, preproc
+    batch, sizes = _batch(), [(H, W)] * B
+    simclr = ["random_resize_crop", "random_flip", "color_distortion", "gaussian_blur"]
+    lists = {"shipped": (["random_resize_crop", "autoaug"], False, None), "simclr": (simclr, True, None),
+             "crop_only": (["random_resize_crop"], True, None), "blur_r0.1": (["random_resize_crop", "gaussian_blur"], True, 0.1),
+             "blur_r2.0": (["random_resize_crop", "gaussian_blur"], True, 2.0)}
+    runs, info, src = {}, {}, None
+    for key, (names, full, radius) in lists.items():
+        cfg = _cfg(names)
+        chain = P.parse_chain(cfg.transforms.train_transforms, cfg, full=full)
+        p = P.sample_pipeline_params(sizes, np.random.default_rng(0), chain)
+        if radius is not None:                                   # the blur on every image, at one radius
+            p["blur_apply"][:] = 1
+            p["blur_radius"][:] = radius
+        pl = P.plan_pipeline(sizes, p, chain, "cuda")
+        lut = preproc._lut_on(chain["lut"], "cuda")
+        if src is None:
+            src = preproc._pack(batch, pl, "cuda")
+        fn = ops.train_chain if full else ops.train_transforms
+        runs[key] = (lambda fn=fn, pl=pl, lut=lut: fn(src, pl, lut))
+        info[key] = (chain, p)
+    for _ in range(warmup):
+        for fn in runs.values():
+            _timed(fn, iters)
+    ms = {k: [] for k in runs}
+    for _ in range(reps):                                        # interleaved: every list once per repetition
+        for k, fn in runs.items():
+            ms[k].append(_timed(fn, iters))
+    res = {f"views_{k}": _stats(v) for k, v in ms.items()}
+    chain, p = info["simclr"]
+    nops = [len(P.op_chain(chain, p, i)) for i in range(B)]
+    res.update(views_simclr_list=simclr, views_simclr_mean_ops=sum(nops) / B, views_simclr_blurred=int(p["blur_apply"].sum()),
+               views_simclr_jittered=int(p["d_apply"].sum()), views_simclr_gray=int(p["d_gray"].sum()),
+               views_simclr_images_per_s=B / (res["views_simclr"]["median_ms"] * 1e-3),
+               views_shipped_images_per_s=B / (res["views_shipped"]["median_ms"] * 1e-3))
+    # the same list, the same parameters, Pillow on the host (one process, decoded images in memory), checked against the device
+    n = min(host_images, B)
+    got = runs["simclr"]()[0][:n].cpu()
+    pil = [Image.fromarray(batch[i].cpu().numpy()) for i in range(n)]
+    t0 = time.perf_counter()
+    want = [P.apply_pipeline_pil(pil[i], p, i, chain)[0] for i in range(n)]
+    dt = time.perf_counter() - t0
+    res.update(views_host_images=n, views_host_ms_per_image=dt / n * 1e3, views_host_images_per_s=n / dt,
+               views_simclr_equals_host=bool(all(torch.equal(got[i], want[i]) for i in range(n))))
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--parts", default="shipped,clip")
     ap.add_argument("--reps", type=int, default=24)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--host-images", type=int, default=64)
     a = ap.parse_args()
     res = {"batch": B, "raw": [H, W], "size": S, "iters_per_rep": a.iters}
     parts = a.parts.split(",")
@@ -115,6 +175,8 @@ def main():
         res.update(part_shipped(a.reps, a.iters, a.warmup))
     if "clip" in parts:
         res.update(part_clip(a.reps, a.iters, a.warmup))
+    if "views" in parts:
+        res.update(part_views(a.reps, a.iters, a.warmup, a.host_images))
     print(json.dumps(res, indent=1))
 
 
