@@ -319,6 +319,30 @@ int simseg_triplet_rows(float* sims, float* row_loss, float* row_correct, float*
  * target0 + N1 > N2 and N2 >= 2^31 (the kernel's column and row indices are 32-bit). */
 int simseg_siglip_rows(float* sims, const float* temperature, const float* bias, float* row_loss, float* row_correct, float* row_tdot,
                        float* row_bdot, float* out4, int64_t N1, int64_t N2, int64_t target0, int write_grad, void* stream);
+/* NT-Xent rows: the normalised temperature-scaled cross-entropy of SimCLR (Chen et al., ICML'20) in the global form of SLIP's SIMCLRLoss
+ * (Mu et al., ECCV'22) over sims[N1,N2] (fp32, from simseg_gemm), one block of 256 threads per row, fp32 only.  N1 = 2B is even: rows
+ * [0, B) are view a and rows [B, 2B) view b of the local batch, the columns are the gathered stacked embeddings, and this rank's own 2B
+ * rows are columns [target0, target0 + N1).  It is simseg_nce_rows over that block with two changes: the row's own column takes no part,
+ * and the positive sits half a block away.  For row i, with temp = clamp(T, 1e-3f, 0.5f) (temperature[0] = T; the fp32 constants of
+ * simseg_nce_rows) and inv_t = fl32(1 / temp):
+ *   self_i = target0 + i;   pos_i = target0 + (i + B) mod N1
+ *   z_ij = fl32(s_ij * inv_t)                      the same rounded product in every pass, never contracted into a subtraction
+ *   m_i  = max over j != self_i of z_ij;   lg_i = log(sum over j != self_i of exp(z_ij - m_i))
+ *          (the self column - its value is 1.0, always the row maximum - is in neither: it is never read as a value that matters)
+ *   rowloss_i = (m_i - z_i,pos) + lg_i             the difference from the maximum first, then the small logarithm (simseg_nce_rows)
+ *   loss = (1 / N1) * sum_i rowloss_i
+ *   dz_ij = (p_ij - [j == pos_i]) / N1 with p_ij = exp((z_ij - m_i) - lg_i) for j != self_i, and exactly 0 at j == self_i
+ *   write_grad: the row is overwritten IN PLACE by dLoss/ds_ij = dz_ij * inv_t; write_grad = 0 leaves sims bit for bit and gives the
+ *   same out4[0:3] and row losses
+ *   row_tdot_i = sum_j dz_ij * s_ij
+ *   top-1 hit: the FIRST index attaining m_i among j != self_i, against pos_i - simseg_nce_rows' rule.
+ * A second, one-block launch sums the rows in a fixed order (no atomics: the same input gives the same bits):
+ *   out4 = {loss, acc_a = hits of rows [0, B) / B, acc_b = hits of rows [B, 2B) / B, dLoss/dT},
+ *   dLoss/dT = -sum_i row_tdot_i / temp^2 when 1e-3f <= T <= 0.5f and exactly 0 outside the clamp.
+ * No label smoothing and no ignore mask.  row_loss / row_correct / row_tdot: N1 floats each.  Refused before any launch: N1 < 2, N1 odd,
+ * target0 < 0, target0 + N1 > N2 and N2 >= 2^31 (the kernel's column and row indices are 32-bit). */
+int simseg_ntxent_rows(float* sims, const float* temperature, float* row_loss, float* row_correct, float* row_tdot, float* out4, int64_t N1,
+                       int64_t N2, int64_t target0, int write_grad, void* stream);
 /* n <= 6 fp32 transposes in ONE launch (out[k][c, r] = in[k][r, c], in[k] [rows[k], cols[k]] contiguous); jobs with scale[k] != 0 are
  * multiplied by alpha * scalar[0] - in the transposed copy and IN PLACE; y0[0] = scalar[0] * x0[0] when y0 is given.  The loss head's
  * backward (mml_loss.py:73 differentiated) needs dS, dS^T and the transposed embeddings as row . row GEMM operands, all times the upstream

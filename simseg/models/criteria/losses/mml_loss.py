@@ -1,18 +1,19 @@
 """InfoNCE of the SimSeg contrastive objective (mirror of simseg/models/criteria/losses/mml_loss.py:12-103) on the
 fused HIP loss path: fp32 MFMA similarity block -> in-place cross-entropy rows -> gradient GEMMs, with the embedding
 exchange as an RCCL all-gather forward / reduce-scatter backward.  MixUpNCE (:105-197) and Triplet (:256-347) score the same
-similarity block with their own row kernels, and so does SigLip - the pairwise sigmoid loss of SigLIP, which the reference does not have."""
+similarity block with their own row kernels, and so do two losses the reference does not have: SigLip, the pairwise sigmoid loss of SigLIP, and NTXent, SimCLR's
+image-to-image loss over two views (the self-supervised half of SLIP)."""
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
 from simseg.utils import ENV, GatherLayer, logger
 from simseg.utils.dist import generate_local_groups
-from simseg_amd.heads import ClipLossFn, MixNCEFn, NCEFn, SigLipFn, TripletFn, TripletLocalFn, all_gather_rows
+from simseg_amd.heads import ClipLossFn, MixNCEFn, NCEFn, NTXentFn, SigLipFn, TripletFn, TripletLocalFn, all_gather_rows
 
 from .builder import LOSS
 
-__all__ = ["NCE", "MixUpNCE", "Triplet", "SigLip", "LabelSmoothingCrossEntropy", "SoftTargetCrossEntropy"]
+__all__ = ["NCE", "MixUpNCE", "Triplet", "SigLip", "NTXent", "LabelSmoothingCrossEntropy", "SoftTargetCrossEntropy"]
 
 
 @LOSS.register_obj
@@ -224,6 +225,56 @@ class SigLip(nn.Module):
         if feat2_global.shape[0] % feat1.shape[0] != 0:
             raise AssertionError(f"global size: {feat2_global.shape[0]}, batch size: {feat1.shape[0]}")
         return SigLipFn.apply(feat1, feat2_global, self.temperature, self.bias, self.rank)
+
+
+@LOSS.register_obj
+class NTXent(nn.Module):
+    """NT-Xent, the loss of SimCLR (Chen et al., ICML'20), in the global form of SLIP's SIMCLRLoss (Mu et al., ECCV'22) on the fused row
+    path (simseg_amd.heads.NTXentFn; formulas in include/simseg_hip.h, simseg_ntxent_rows): the two views' embeddings are stacked to
+    [2B, P], the stacked tensor is gathered ONCE (rank-major: this rank's rows are block `rank` of the gathered matrix, and every other
+    rank's a and b rows are negatives), and each of the 2B rows is a cross-entropy over all gathered rows but itself, its positive the
+    other view of the same image.  Not in the reference: an image-to-image loss, the consumer of simseg.transforms.build_train_views.
+
+    The temperature is read from loss.temperature.{name, value} - clamped to [1e-3, 0.5] like NCE's - unless the constructor's
+    `temperature` (a value) and `learnable` (True: an nn.Parameter, False: a non-persistent buffer) override it; the group and the
+    exchange are NCE's (_loss_group, NCE._gather, loss.nce_loss.gather_backward, loss.group_size).
+
+    forward(view_a, view_b, label=None, ignore_mask=None) -> (loss, top-1 acc of view_a's rows): the (loss, acc) shape of the other
+    global_reduce losses; forward(view_b, view_a) gives the same loss and view_b's accuracy.  loss.global_reduce=False, a non-zero
+    loss.smoothing and an ignore mask are refused.  It is not a CLIPModel main loss (image and text embeddings are not two views):
+    CLIPModel.enable_ssl builds one for the image self-supervision branch."""
+
+    def __init__(self, cfg, rank, temperature=None, learnable=None):
+        super().__init__()
+        self.cfg = cfg
+        self.global_reduce = cfg.loss.global_reduce
+        if not self.global_reduce:
+            raise NotImplementedError("NTXent: loss.global_reduce=False (a local form) is not built; the stacked views are scored against their gathered selves")
+        if float(cfg.loss.smoothing) != 0.0:
+            raise ValueError(f"NTXent: loss.smoothing={cfg.loss.smoothing} - the row kernel has no label smoothing, set it to 0")
+        if cfg.loss.temperature.name not in ("parameter", "constant"):
+            raise NotImplementedError(cfg.loss.temperature.name)
+        self.gather_backward = cfg.loss.nce_loss.gather_backward
+        self.group, self.rank = _loss_group(cfg, "NTXent")
+        t = torch.ones([]) * float(cfg.loss.temperature.value if temperature is None else temperature)
+        if cfg.loss.temperature.name == "parameter" if learnable is None else learnable:
+            self.temperature = nn.Parameter(t)
+        else:
+            self.register_buffer("temperature", t, persistent=False)
+
+    _gather = NCE._gather
+
+    def forward(self, view_a, view_b, label=None, ignore_mask=None):
+        if ignore_mask is not None:
+            raise NotImplementedError("NTXent: an ignore_mask is not supported (the row kernel builds no row weights)")
+        if view_a.shape != view_b.shape:
+            raise ValueError(f"NTXent: the two views differ in shape, {tuple(view_a.shape)} against {tuple(view_b.shape)}")
+        z = torch.cat([view_a, view_b])
+        zg = self._gather(z)
+        if zg.shape[0] % z.shape[0] != 0:
+            raise AssertionError(f"global size: {zg.shape[0]}, stacked batch size: {z.shape[0]}")
+        loss, acc_a, _ = NTXentFn.apply(z, zg, self.temperature, self.rank)
+        return loss, acc_a
 
 
 def _reduce(rows, reduction):

@@ -17,7 +17,7 @@ from simseg_amd.heads import discard_prefetched, prefetch_gather
 from simseg_amd.nn import compute_dtype
 from simseg_amd.towers import ProjectPoolFn, packed_text
 
-from ..components import AvgPooling, ComplexProjection, L2norm, SimpleProjection, TopKPooling
+from ..components import AvgPooling, ComplexProjection, L2norm, MlpProjection, SimpleProjection, TopKPooling
 from ..components.pooling import clip_k_to_shortest
 
 
@@ -43,6 +43,11 @@ class CLIPModel(nn.Module):
             self.text_pool, self.image_pool = AvgPooling(), AvgPooling()
         else:
             self.text_pool, self.image_pool = nn.Identity(), nn.Identity()
+        if cfg.loss.name == "NTXent":
+            raise NotImplementedError("loss.name=NTXent cannot be a CLIPModel's main loss: the image and the text embeddings are not two views of one "
+                                      "input (and the prefetched embedding gathers would never be taken).  Keep the image-text loss and call "
+                                      "CLIPModel.enable_ssl() - or Trainer(ssl={...}) - for the two-view image branch")
+        self.rank = rank
         self.loss = LOSS.get(cfg.loss.name)(cfg, rank)
         self.global_reduce = cfg.loss.global_reduce
         self.text_target_token_idx = cfg.model.text_encoder.target_token_idx
@@ -73,6 +78,70 @@ class CLIPModel(nn.Module):
             return ProjectPoolFn.apply(image_features, self.image_projection.linear.weight, self.image_pool.k, None, compute_dtype())
         emb = self.image_pool(self.image_projection(image_features))
         return L2norm(emb, dim=-1) if self.cfg.model.projection.name == "simple" else emb
+
+    # ---- image self-supervision (SLIP: the image-text loss plus SimCLR's NT-Xent on two augmented views through the same image tower) ----
+    def enable_ssl(self, scale=1.0, hidden_dim=4096, out_dim=256, temperature=0.1):
+        """Switch the two-view image branch on - before the optimizer is built, so that its parameters are trained.  Adds
+        `ssl_projection` (Linear(D, hidden_dim, bias) -> erf-GELU -> Linear(hidden_dim, out_dim, bias=False) on the [cls] token, one
+        autograd node; its output goes through L2norm) and `ssl_loss` = NTXent at a constant `temperature`.  From then on forward(batch)
+        with batch["image_ssl"] - a [2, B, 3, S, S] tensor or a pair of [B, 3, S, S] tensors: two outputs of
+        simseg.transforms.build_train_views on the same raw batch - runs the image tower ONCE on cat([image, view 1, view 2]) (one backward
+        per tower and step, which the gradient exchange and the lazy 16-bit residual gradients rely on), feeds rows [0, B) to the CLIP head
+        as before and the [cls] tokens of rows [B, 3B) to the branch, and adds "ssl_loss" = scale * NT-Xent to the loss dict (its top-1
+        accuracy of view 1's rows: self.ssl_acc).  Without the key, or for embeddings != False, forward is the one without the branch.
+        The switch is per instance: forward and _image_embeddings of a model that never calls this are the class's own, untouched."""
+        if getattr(self, "ssl_projection", None) is not None:
+            raise RuntimeError("enable_ssl: the branch is already on")
+        w = self.image_projection.linear.weight
+        self.ssl_projection = MlpProjection(self.cfg.model.image_encoder.embedding_dim, int(hidden_dim), int(out_dim)).to(w.device)
+        self.ssl_loss = LOSS.get("NTXent")(self.cfg, self.rank, temperature=temperature, learnable=False).to(w.device)
+        self.ssl_scale, self.ssl_acc, self._ssl_views, self._ssl_z = float(scale), None, None, None
+        self.forward = self._forward_ssl
+        self._image_embeddings = self._image_embeddings_ssl
+        return self
+
+    def forward_image_ssl(self, image, views):
+        """(CLIP image embeddings [B, P], view 1's and view 2's branch embeddings [B, out_dim] each) from ONE image-tower call on the 3B
+        images cat([image, views[0], views[1]]).  Patch dropout, when on, applies to all 3B images; [cls] is never dropped."""
+        B = image.shape[0]
+        feats = self.image_encoder(torch.cat([image, views[0], views[1]]))
+        if feats.dim() != 3:
+            raise NotImplementedError("the image self-supervision branch reads the [cls] token: the image tower must return tokens [B, N, D]")
+        head = feats[:B]
+        if self.cfg.model.pool.name == "identity":
+            img = self.forward_image_project(head[:, 0])
+        elif self._fused_heads and feats.is_cuda and os.environ.get("SIMSEG_AMD_FUSED_IMAGE_HEAD", "1") != "0":
+            sh16 = getattr(feats, "_simseg_fwd16", None)       # (the 16-bit copy the tower's last LayerNorm wrote: the head's rows of it)
+            if sh16 is not None and sh16[1] == feats._version:
+                head._simseg_fwd16 = (sh16[0][:B], head._version)
+            img = ProjectPoolFn.apply(head, self.image_projection.linear.weight, self.image_pool.k, None, compute_dtype(), 1)
+        else:
+            img = self.forward_image_project(head[:, 1:])
+        z = L2norm(self.ssl_projection(feats[B:, 0]), dim=-1)
+        return img, z[:B], z[B:]
+
+    def _image_embeddings_ssl(self, image):
+        if self._ssl_views is None:
+            return CLIPModel._image_embeddings(self, image)
+        img, za, zb = self.forward_image_ssl(image, self._ssl_views)
+        self._ssl_z = (za, zb)
+        return img
+
+    def _forward_ssl(self, batch, embeddings=False):
+        views = batch.get("image_ssl") if embeddings is False and isinstance(batch, dict) else None
+        if views is None:
+            return CLIPModel.forward(self, batch, embeddings)
+        if len(views) != 2 or tuple(views[0].shape) != tuple(batch["image"].shape) or tuple(views[1].shape) != tuple(batch["image"].shape):
+            raise ValueError(f"image_ssl: two views of the batch's images, [2, B, 3, S, S] or a pair of [B, 3, S, S], for images {tuple(batch['image'].shape)}")
+        self._ssl_views = views
+        try:
+            loss_dict, i2t_acc, t2i_acc = CLIPModel.forward(self, batch, embeddings)
+            za, zb = self._ssl_z
+        finally:
+            self._ssl_views = self._ssl_z = None
+        ssl, self.ssl_acc = self.ssl_loss(za, zb)
+        loss_dict["ssl_loss"] = self.ssl_scale * ssl
+        return loss_dict, i2t_acc, t2i_acc
 
     # ---- text side ----------------------------------------------------------------------------------------------
     def forward_text_feature(self, input_ids, attention_mask):

@@ -1,4 +1,4 @@
-// Row kernels behind the similarity matrices: InfoNCE / MixUpNCE cross-entropy rows (K13), Triplet hinge rows, SigLIP pairwise-sigmoid rows, the loss head's transposes
+// Row kernels behind the similarity matrices: InfoNCE / MixUpNCE cross-entropy rows (K13), Triplet hinge rows, SigLIP pairwise-sigmoid rows, NT-Xent rows, the loss head's transposes
 // and scales, retrieval first-match ranks (K16) and recall counts.  fp32 and integers only: compiled ONCE, no 16-bit flavour.
 #include "common.h"
 
@@ -330,6 +330,92 @@ __global__ __launch_bounds__(256) void siglip_finalize_kernel(const float* __res
     }
 }
 
+// NT-Xent rows (SimCLR, Chen et al., ICML'20; SLIP's SIMCLRLoss): NCE over the stacked [2B, 2B W] self-similarity block.  One block per row i
+// of sims[N1, N2], N1 = 2B: rows [0, B) are view a, rows [B, 2B) view b, this rank's own rows are columns [target0, target0 + N1).
+//   self = target0 + i  (the row's own column, s = 1.0, always the row maximum): left out of the maximum, the sum and the top-1, gradient 0
+//   pos  = target0 + (i + B) mod N1  (the other view of the same image)
+//   z_j = fl32(s_j * inv_t), temp and inv_t as nce_rows_kernel;  m = max_{j != self} z_j;  lg = log(sum_{j != self} exp(z_j - m))
+//   row loss = (m - z_pos) + lg  (the difference from the maximum first, for nce_rows_kernel's reason);  loss = (1 / N1) sum_i row loss
+//   dz_j = (exp((z_j - m) - lg) - [j == pos]) / N1, 0 at self;  write_grad: row_j <- dz_j * inv_t;  row_tdot = sum_j dz_j s_j
+// A kernel of its own, not a third flag on nce_rows_kernel: the skipped column sits in every loop, and the existing instantiations keep
+// their instructions.  The self column is never loaded; with write_grad it is only stored to.
+__global__ __launch_bounds__(256) void ntxent_rows_kernel(float* __restrict__ sims, const float* __restrict__ temperature,
+                                                          float* __restrict__ row_loss, float* __restrict__ row_correct,
+                                                          float* __restrict__ row_tdot, int N1, int N2, int target0, int write_grad) {
+    // (z = s * inv_t is the SAME rounded product in every pass, see nce_rows_kernel)
+#pragma clang fp contract(off)
+    __shared__ float sh[8];
+    __shared__ int shi[8];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    float* row = sims + (long)i * N2;
+    const float temp = fminf(fmaxf(temperature[0], 0.001f), 0.5f);
+    const float inv_t = 1.0f / temp;
+    const int half = N1 >> 1;
+    const int self = target0 + i;
+    const int pos = target0 + (i < half ? i + half : i - half);
+    float mx = -INFINITY;
+    int arg = 0x7fffffff;
+    for (int j = tid; j < N2; j += 256) {
+        if (j == self) continue;
+        const float z = row[j] * inv_t;
+        if (z > mx) { mx = z; arg = j; }
+    }
+    const float bmx = block_reduce_max(mx, sh);       // (N2 >= N1 >= 2: at least one column is not the row's own)
+    const int best = block_reduce_min_int(mx == bmx ? arg : 0x7fffffff, shi);          // first index attaining the maximum
+    float se = 0.f;
+    for (int j = tid; j < N2; j += 256) {
+        if (j == self) continue;
+        se += __expf(row[j] * inv_t - bmx);
+    }
+    se = block_reduce_sum(se, sh);
+    const float lg = __logf(se);
+    const float loss = (bmx - row[pos] * inv_t) + lg;
+    __syncthreads();       // (every thread holds z_pos before any thread rewrites the row)
+    float tdot = 0.f;
+    if (write_grad) {
+        const float n1 = (float)N1;
+        for (int j = tid; j < N2; j += 256) {
+            if (j == self) { row[j] = 0.f; continue; }
+            const float s = row[j];
+            const float pj = __expf((s * inv_t - bmx) - lg);
+            // (one rounded division per element, as siglip_rows_kernel)
+            const float dz = (j == pos ? pj - 1.0f : pj) / n1;
+            tdot += dz * s;
+            row[j] = dz * inv_t;
+        }
+        tdot = block_reduce_sum(tdot, sh);
+    }
+    if (tid == 0) {
+        row_loss[i] = loss;
+        row_correct[i] = (best == pos) ? 1.f : 0.f;
+        row_tdot[i] = tdot;
+    }
+}
+
+// out = {loss = sum_i row_loss / N1, top-1 acc of view a's rows [0, B), of view b's rows [B, 2B), dLoss/dT}; one block, a fixed order of
+// additions.  dLoss/dT as nce_finalize_kernel: -sum_i row_tdot_i / temp^2, 0 outside the clamp.
+__global__ __launch_bounds__(256) void ntxent_finalize_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_correct,
+                                                              const float* __restrict__ row_tdot, const float* __restrict__ temperature,
+                                                              float* __restrict__ out, int N1) {
+    __shared__ float sh[8];
+    const int half = N1 >> 1;
+    float l = 0.f, c0 = 0.f, c1 = 0.f, t = 0.f;
+    for (int i = threadIdx.x; i < N1; i += 256) {
+        l += row_loss[i];
+        t += row_tdot[i];
+        if (i < half) c0 += row_correct[i]; else c1 += row_correct[i];
+    }
+    l = block_reduce_sum(l, sh); c0 = block_reduce_sum(c0, sh); c1 = block_reduce_sum(c1, sh); t = block_reduce_sum(t, sh);
+    if (threadIdx.x == 0) {
+        const float T = temperature[0];
+        const float temp = fminf(fmaxf(T, 0.001f), 0.5f);
+        out[0] = l / N1;
+        out[1] = c0 / half;
+        out[2] = c1 / half;
+        out[3] = (T >= 0.001f && T <= 0.5f) ? -t / (temp * temp) : 0.f;
+    }
+}
+
 // The loss head's backward preparation in ONE launch: up to six fp32 matrices are transposed (32 x 32 LDS tiles), the ones flagged `scale`
 // are multiplied by alpha * scalar[0] on the way - in the transposed copy AND in place - and y0[0] = scalar[0] * x0[0].  (The fp32
 // GEMM kernel contracts row . row: its transposed operands are made here, together with the upstream-gradient scale the round-3 loss head
@@ -519,6 +605,21 @@ extern "C" int simseg_siglip_rows(float* sims, const float* temperature, const f
     hipLaunchKernelGGL(siglip_finalize_kernel, dim3(1), dim3(256), 0, STREAM, row_loss, row_correct, row_tdot, row_bdot, temperature, out4,
                        (int)N1);
     SS_LAUNCH_CHECK("siglip_rows");
+    return 0;
+}
+
+extern "C" int simseg_ntxent_rows(float* sims, const float* temperature, float* row_loss, float* row_correct, float* row_tdot, float* out4,
+                                  int64_t N1, int64_t N2, int64_t target0, int write_grad, void* stream) {
+    SS_CHECK(N1 >= 2, "ntxent_rows: N1 = %lld rows; two views of at least one image need N1 >= 2", (long long)N1);
+    SS_CHECK(N1 % 2 == 0, "ntxent_rows: N1 = %lld is odd; the rows are view a stacked on view b, N1 = 2B", (long long)N1);
+    SS_CHECK(target0 >= 0 && target0 + N1 <= N2, "ntxent_rows: own block [%lld, %lld) outside [0, %lld)", (long long)target0,
+             (long long)(target0 + N1), (long long)N2);
+    SS_CHECK(N2 <= 0x7fffffffLL, "ntxent_rows: N2 = %lld columns do not fit the kernel's 32-bit indices", (long long)N2);      // (N1, target0 <= N2)
+    SS_CHECK(sims && temperature && row_loss && row_correct && row_tdot && out4, "ntxent_rows: null pointer");
+    hipLaunchKernelGGL(ntxent_rows_kernel, dim3((unsigned)N1), dim3(256), 0, STREAM, sims, temperature, row_loss, row_correct, row_tdot,
+                       (int)N1, (int)N2, (int)target0, write_grad);
+    hipLaunchKernelGGL(ntxent_finalize_kernel, dim3(1), dim3(256), 0, STREAM, row_loss, row_correct, row_tdot, temperature, out4, (int)N1);
+    SS_LAUNCH_CHECK("ntxent_rows");
     return 0;
 }
 

@@ -234,6 +234,39 @@ class SigLipFn(Function):
         return df1, df2, dt, db, None
 
 
+class NTXentFn(Function):
+    """The NT-Xent loss of SimCLR in the global form of SLIP's SIMCLRLoss: z [2B, P] is the stacked local batch (view a on view b), zg
+    [W * 2B, P] the gathered stacked embeddings, the own block at columns rank * 2B (ops.ntxent_rows: the row's own column is left out,
+    the positive sits B rows away).  Built like SigLipFn: one fp32 GEMM, the rows in place, two gradient GEMMs times the upstream
+    gradient; the temperature is a 0-dim fp32 tensor.  With no process group the caller passes the same tensor in both roles and autograd
+    adds the two gradients.  Returns (loss, top-1 acc of view a's rows, of view b's rows)."""
+
+    @staticmethod
+    def forward(ctx, z, zg, temperature, rank):
+        f1 = z.contiguous().float()
+        f2 = zg.contiguous().float()
+        sims = ops.gemm(f1, f2)
+        need = any(ctx.needs_input_grad[:3])
+        out4, _ = ops.ntxent_rows(sims, temperature.detach().reshape(1).float(), rank * f1.shape[0], write_grad=need)
+        ctx.save_for_backward(sims if need else None, f1, f2, out4)
+        loss, acc_a, acc_b = out4[0].clone(), out4[1].clone(), out4[2].clone()
+        ctx.mark_non_differentiable(acc_a, acc_b)
+        return loss, acc_a, acc_b
+
+    @staticmethod
+    def backward(ctx, gloss, _ga, _gb):
+        ds, f1, f2, out4 = ctx.saved_tensors
+        g = gloss.contiguous().float().reshape(1)
+        df1 = df2 = dt = None
+        if ctx.needs_input_grad[0]:
+            df1 = ops.scale_by_scalar(ops.gemm(ds, ops.transpose_f32(f2)), g)
+        if ctx.needs_input_grad[1]:
+            df2 = ops.scale_by_scalar(ops.gemm(ops.transpose_f32(ds), ops.transpose_f32(f1)), g)
+        if ctx.needs_input_grad[2]:
+            dt = ops.scale_by_scalar(out4[3:4], g).reshape(())
+        return df1, df2, dt, None
+
+
 class TripletFn(Function):
     """The global direction of the Triplet loss (mml_loss.py:285-314): feat1 [N1,P] against feat2_global [N2,P], own columns
     [rank * N1, (rank + 1) * N1) - all of them masked, as in the reference.  Built like NCEFn: one GEMM, ops.triplet_rows in place,

@@ -650,6 +650,26 @@ def siglip_rows(sims, temperature, bias, target0, write_grad=True):
     return out4, scratch[0]
 
 
+def ntxent_rows(sims, temperature, target0, write_grad=True):
+    """The NT-Xent rows of SimCLR / SLIP (include/simseg_hip.h simseg_ntxent_rows) of sims [N1, N2], N1 = 2B: rows [0, B) are view a, rows
+    [B, 2B) view b, the own block is columns [target0, target0 + N1); row i leaves its own column target0 + i out of the softmax and has its
+    positive at target0 + (i + B) mod N1.  In place: sims <- dLoss/dsims (write_grad=False leaves it).  temperature: fp32 device tensor of
+    one element.  -> (out4 = [loss, acc of view a's rows, acc of view b's rows, dLoss/dT], row losses [N1])."""
+    N1, N2 = _sim_block_check("ntxent_rows", sims, target0)
+    require_gpu(temperature)
+    if temperature.dtype != torch.float32:
+        raise TypeError(f"ntxent_rows: temperature must be fp32, got {temperature.dtype}")
+    if temperature.numel() != 1:
+        raise ValueError(f"ntxent_rows: temperature holds one element, got {tuple(temperature.shape)}")
+    if N1 % 2:
+        raise ValueError(f"ntxent_rows: N1 = {N1} is odd; the rows are view a stacked on view b, N1 = 2B")
+    scratch = torch.empty(3, max(N1, 1), device=sims.device, dtype=torch.float32)
+    out4 = torch.empty(4, device=sims.device, dtype=torch.float32)
+    call("simseg_ntxent_rows", ptr(sims), ptr(temperature), ptr(scratch[0]), ptr(scratch[1]), ptr(scratch[2]), ptr(out4), N1, N2, int(target0),
+         int(bool(write_grad)), stream())
+    return out4, scratch[0]
+
+
 def transpose_multi(mats, scale_flags, scalar=None, alpha=1.0, x0=None):
     """Transposes of up to six contiguous fp32 matrices in ONE launch; matrices whose flag is set are multiplied by alpha * scalar[0] in
     the copy and in place.  Returns (list of transposed tensors, scalar[0] * x0[0] as a 1-element tensor or None)."""

@@ -412,6 +412,39 @@ class LinearFn(_GradAwareFn):
         return dx, dw, db, None
 
 
+class MlpHeadFn(_GradAwareFn):
+    """y = gelu(x W1^T + b1) W2^T on [rows, in] -> [rows, out] (erf GELU, no second bias): a two-layer projection head as ONE node on the
+    GEMM epilogues the transformer blocks use - act 3 saves GELU' in the forward, act 4 multiplies by it in the backward; the weight and
+    bias gradients are LinearFn's (_wgrad / _bgrad).  fp32 in / fp32 out at the module boundary."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, adt):
+        x2 = x.reshape(-1, x.shape[-1]).contiguous()
+        xa = x2 if adt == F32 else ops.cast(x2.float(), adt)
+        save = _saving(ctx)
+        pre = torch.empty(x2.shape[0], w1.shape[0], device=x.device, dtype=adt) if save else None
+        h = _fwd_gemm(xa, w1, adt, save, bias=b1.detach(), act=3 if save else 1, aux_out=pre)          # pre holds GELU'(x W1^T + b1)
+        y = _fwd_gemm(h, w2, adt, save, out_dtype=F32)
+        if save:
+            ctx.adt, ctx.shp = adt, x.shape
+            ctx.save_for_backward(xa, h, pre, _wt(w1, adt), _wt(w2, adt))
+        return y.view(*x.shape[:-1], w2.shape[0])
+
+    @staticmethod
+    def backward(ctx, dy):
+        xa, h, pre, w1_, w2_ = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        d16 = _act_grad(dy.reshape(-1, dy.shape[-1]).contiguous(), ctx.adt)
+        dw2 = _wgrad(d16, h) if need[3] else None
+        dx = dw1 = db1 = None
+        if need[0] or need[1] or need[2]:
+            dpre = _dgrad(d16, w2_, act=4, aux=pre)
+            dx = _dgrad(dpre, w1_, out_dtype=F32).view(ctx.shp) if need[0] else None
+            dw1 = _wgrad(dpre, xa) if need[1] else None
+            db1 = _bgrad(dpre) if need[2] else None
+        return dx, dw1, db1, dw2, None
+
+
 class LayerNormFn(Function):
     @staticmethod
     def forward(ctx, x, w, b, eps, adt=None, lazy_ok=False):

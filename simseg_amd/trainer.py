@@ -79,8 +79,11 @@ def set_patch_drop(model, cfg, rate):
 
 
 class Trainer:
-    def __init__(self, model, cfg, steps_per_epoch, net=None, amp_dtype=None, patch_drop_rate=None):
+    def __init__(self, model, cfg, steps_per_epoch, net=None, amp_dtype=None, patch_drop_rate=None, ssl=None):
         """model: the bare CLIPModel; net: what is called (model or its DDP wrapper).
+        ssl (None: nothing is touched): the keyword arguments of CLIPModel.enable_ssl - the two-view image self-supervision branch (SLIP) is
+        switched on before the parameter groups are made, so that its projection head is trained; batches then carry "image_ssl", and
+        train_step reports ssl_loss and ssl_acc.
         patch_drop_rate (None: nothing is touched): the image tower's ViT trains on [cls] + a random share 1 - rate of every image's patch
         tokens (simseg_amd/patchdrop.py; ViT.set_patch_drop).  Under LoDA pooling the kept tokens must still number cfg.model.pool.loda.image_k.
         amp_dtype ("bf16" default / "fp16", or SIMSEG_AMD_AMP_DTYPE): the 16-bit type of the AMP mode cfg.dist.fp16 switches on.  "fp16" is
@@ -88,6 +91,8 @@ class Trainer:
         scaled loss, unscale + overflow check + skipped steps, scale growth / back-off, the scaler's state in the checkpoint.  bf16 needs
         no loss scale (fp32's exponent range): the scaler then runs disabled, as an identity."""
         self.model, self.net, self.cfg = model, net or model, cfg
+        if ssl is not None:
+            model.enable_ssl(**dict(ssl))
         if patch_drop_rate is not None:
             set_patch_drop(model, cfg, patch_drop_rate)
         amp = str(amp_dtype or os.environ.get("SIMSEG_AMD_AMP_DTYPE", "bf16")).lower().replace("torch.", "")
@@ -130,6 +135,8 @@ class Trainer:
         loss = sum(loss_dict.values())
         self.scaler.scale(loss).backward()           # (disabled scaler: the loss itself)
         out = {"loss": loss.detach(), "i2t_acc": i2t_acc, "t2i_acc": t2i_acc, "lr": lrs[0]}
+        if "ssl_loss" in loss_dict:                  # (CLIPModel.enable_ssl: already times its scale, and part of `loss`)
+            out["ssl_loss"], out["ssl_acc"] = loss_dict["ssl_loss"].detach(), self.model.ssl_acc
         clip = dict(self.cfg.optim.grad_clip)
         if clip:                                     # the reference unscales, THEN clips, then scaler.step: core/hooks/optimizer.py:45-47, 82-86
             out["grad_norm"] = self.clip_gradients(clip)

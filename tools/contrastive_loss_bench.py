@@ -5,13 +5,15 @@ direction with the own-rank block masked), at P = 512 on similarity blocks of [5
 one; [512, 512] is the one-rank case, where the Triplet's block mask covers every column and loss and gradients are 0 on both routes).
 The local symmetric Triplet (heads.TripletLocalFn) is timed at [512, 512] as well.  SigLip (heads.SigLipFn, the pairwise sigmoid loss
 at T = 0.1, b = -10, gradients w.r.t. the temperature and the bias too) has no statement in the reference: its torch route is
--F.logsigmoid(y * (s / T + b)).sum() / N1.
+-F.logsigmoid(y * (s / T + b)).sum() / N1.  NTXent (heads.NTXentFn, SimCLR's loss over two stacked views at T = 0.1: the 512 rows are 256
+images' view a on their view b, the own block of the gathered matrix holds the same rows) is timed against SLIP's torch statement: four
+logit blocks, a -1e9 self mask, two cross-entropies and their mean.
 
 All in one process on one GPU, routes interleaved round by round; every window is `--iters` back-to-back iterations between two device
 events.  Median [min .. max] over `--rounds` windows, and the loss both routes computed.
 
     python tools/contrastive_loss_bench.py [--quick] [--legs NCE,SigLip] [--out profiles/contrastive_losses.txt]
-(profiles/siglip_loss.txt is `--legs NCE,SigLip`.)"""
+(profiles/siglip_loss.txt is `--legs NCE,SigLip`, profiles/ntxent_loss.txt `--legs NCE,NTXent`.)"""
 import argparse
 import os
 import statistics
@@ -77,6 +79,23 @@ def torch_siglip(f1, f2g, temperature, bias, rank):
     return -F.logsigmoid(y * (s / torch.clamp(temperature, 0.001, 0.5) + bias)).sum() / N1
 
 
+def torch_ntxent(z, zg, temperature, rank):
+    """SLIP's SIMCLRLoss on the stacked layout: z = cat([view a, view b]) of the local batch, zg the rank-major gathered stacks."""
+    N1 = z.shape[0]
+    B, W = N1 // 2, zg.shape[0] // N1
+    tau = torch.clamp(temperature, 0.001, 0.5)
+    qa, qb = z[:B], z[B:]
+    g = zg.view(W, 2, B, -1)
+    ka, kb = g[:, 0].reshape(W * B, -1), g[:, 1].reshape(W * B, -1)
+    labels = rank * B + torch.arange(B, device=z.device)
+    masks = F.one_hot(labels, W * B) * 1e9
+    logits_aa, logits_bb = qa @ ka.T / tau - masks, qb @ kb.T / tau - masks
+    logits_ab, logits_ba = qa @ kb.T / tau, qb @ ka.T / tau
+    loss_a = F.cross_entropy(torch.cat([logits_ab, logits_aa], dim=1), labels)
+    loss_b = F.cross_entropy(torch.cat([logits_ba, logits_bb], dim=1), labels)
+    return (loss_a + loss_b) / 2
+
+
 def torch_triplet(f1, f2g, rank, margin, reduce):
     N1 = f1.shape[0]
     scores = f1.mm(f2g.t())
@@ -114,10 +133,23 @@ def section(a, N1, N2, P):
     sig_t = torch.tensor(0.1, device="cuda", requires_grad=True)          # the SigLIP paper's init: t = 1 / T = 10, b = -10
     sig_b = torch.tensor(-10.0, device="cuda", requires_grad=True)
     margin, got = 0.2, {}
+    # NTXent: the N1 rows are view a stacked on view b (b = a plus noise of twice its norm); one rank: the same tensor in both roles
+    with torch.no_grad():
+        va = F.normalize(torch.randn(N1 // 2, P, device="cuda", generator=g), dim=-1)
+        vb = F.normalize(va + 2.0 * F.normalize(torch.randn(N1 // 2, P, device="cuda", generator=g), dim=-1), dim=-1)
+    zs = torch.cat([va, vb]).requires_grad_(True)
+    if N2 > N1:
+        with torch.no_grad():
+            zg = F.normalize(torch.randn(N2, P, device="cuda", generator=g), dim=-1)
+            zg[rank * N1:(rank + 1) * N1] = zs
+        zg.requires_grad_(True)
+    else:
+        zg = zs
+    ntx_t = torch.tensor(0.1, device="cuda", requires_grad=True)
 
     def run(name, loss_fn):
         def fn():
-            f1.grad = f2g.grad = temperature.grad = sig_t.grad = sig_b.grad = None
+            f1.grad = f2g.grad = temperature.grad = sig_t.grad = sig_b.grad = zs.grad = zg.grad = ntx_t.grad = None
             loss = loss_fn()
             loss.backward()
             got[name] = loss.detach()
@@ -130,6 +162,7 @@ def section(a, N1, N2, P):
         ("Triplet-max", lambda: heads.TripletFn.apply(f1, f2g, rank, margin, 1)[0], lambda: torch_triplet(f1, f2g, rank, margin, "max")),
         ("Triplet-mean", lambda: heads.TripletFn.apply(f1, f2g, rank, margin, 0)[0], lambda: torch_triplet(f1, f2g, rank, margin, "mean")),
         ("SigLip", lambda: heads.SigLipFn.apply(f1, f2g, sig_t, sig_b, rank)[0], lambda: torch_siglip(f1, f2g, sig_t, sig_b, rank)),
+        ("NTXent", lambda: heads.NTXentFn.apply(zs, zg, ntx_t, rank)[0], lambda: torch_ntxent(zs, zg, ntx_t, rank)),
     ]
     if N2 == N1:
         legs += [
@@ -155,7 +188,7 @@ def main():
     ap.add_argument("--quick", action="store_true", help="small blocks, one round (a rehearsal of the script, not a measurement)")
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--iters", type=int, default=50)
-    ap.add_argument("--legs", default=None, help="comma-separated subset of NCE,MixUpNCE,Triplet-max,Triplet-mean,SigLip (default: all)")
+    ap.add_argument("--legs", default=None, help="comma-separated subset of NCE,MixUpNCE,Triplet-max,Triplet-mean,SigLip,NTXent (default: all)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -166,10 +199,11 @@ def main():
     pr = torch.cuda.get_device_properties(0)
     say(f"# tools/contrastive_loss_bench.py{' --quick' if a.quick else ''}{' --legs ' + a.legs if a.legs else ''}   device: {pr.name}, torch {torch.__version__}")
     say(f"# loss head forward + backward from the embeddings (gradients w.r.t. both embedding matrices, the temperature for the NCE "
-        f"legs, temperature and bias for SigLip), fp32; ms per iteration: median [min .. max] over {a.rounds} windows of {a.iters} back-to-back iterations between two "
+        f"legs and NTXent, temperature and bias for SigLip), fp32; ms per iteration: median [min .. max] over {a.rounds} windows of {a.iters} back-to-back iterations between two "
         "device events, routes interleaved round by round")
-    say("# HIP = simseg_amd.heads (NCEFn / MixNCEFn / TripletFn / TripletLocalFn / SigLipFn); torch = the reference's statements "
-        "(mml_loss.py) in torch ops with autograd; SigLip, which the reference lacks: -F.logsigmoid(y * (s / T + b)).sum() / N1")
+    say("# HIP = simseg_amd.heads (NCEFn / MixNCEFn / TripletFn / TripletLocalFn / SigLipFn / NTXentFn); torch = the reference's statements "
+        "(mml_loss.py) in torch ops with autograd; SigLip, which the reference lacks: -F.logsigmoid(y * (s / T + b)).sum() / N1; NTXent, "
+        "which it lacks too: SLIP's four logit blocks, -1e9 self mask, two cross-entropies, their mean")
     say()
     for N1, N2 in shapes:
         section(a, N1, N2, P)
