@@ -689,6 +689,22 @@ int simseg_dense_crf(const uint8_t* rgb, const float* prob, uint8_t* mask, float
                      float compat_g, float sxy_b, float srgb, float compat_b, int iters, void* workspace, int64_t workspace_bytes,
                      int reuse_spatial, void* stream);
 
+/* PAMR, pixel-adaptive mask refinement (Araslanov & Roth, CVPR 2020) - the device alternative to the DenseCRF above; the reference has
+ * none.  rgb [B,H,W,3] bytes, prob [B,K,H/scale,W/scale] fp32 in [0,1] (scale > 1: the first iteration reads it through (y / scale,
+ * x / scale) - the tool's nearest upsampling, never materialised; H and W are then multiples of scale), cand_idx (optional) [B,K] ints:
+ * slots with a negative entry are not computed and come back zero; NULL = every slot is visited.  dilations: n_dil (1..8) HOST ints in
+ * 1..64; taps = (dilation, offset) dilation-major over the offsets (-1,-1) (-1,0) (-1,1) (0,-1) (0,1) (1,-1) (1,0) (1,1), neighbours
+ * with replicate padding.  Per pixel and channel sigma = the unbiased standard deviation over the 9 n_dil samples of the dilated 3x3
+ * neighbourhoods (integer sums), logit_t = -(1/3) sum_c |rgb_c(p) - rgb_c(q_t)| / (1e-8 + 0.1 sigma_c(p)), w = softmax over the taps;
+ * m <- sum_t w_t m(q_t), iters (0..64) times in fp32 with a fixed tap order (a result does not depend on the batch position) ->
+ * mask [B,K,H,W] bytes (255 where m > 0.5) and, optionally, m_out [B,K,H,W] fp32.  iters = 0: the unary decision prob > 0.5.
+ * ws: caller-allocated, 16-byte aligned, simseg_pamr_workspace_bytes(...) = the weights [B][8 n_dil][H][W] fp32 plus two map buffers
+ * (-1 for arguments out of range).  A refused call launches nothing and leaves the outputs untouched.  No atomics, no host read and
+ * no inter-block dependence: the call may be captured in a graph. */
+int64_t simseg_pamr_workspace_bytes(int64_t B, int64_t K, int64_t H, int64_t W, int n_dil);
+int simseg_pamr(const uint8_t* rgb, const float* prob, const int* cand_idx, uint8_t* mask, float* m_out, int64_t B, int64_t K, int64_t H,
+                int64_t W, const int* dilations, int n_dil, int iters, int64_t scale, void* ws, int64_t ws_bytes, void* stream);
+
 /* debug: bf16 attention forward that also writes a 5-entry cycle-counter timeline of block (0,0) to dbg (tools/dbg_attn_timeline.py). */
 int simseg_debug_attention_timeline(const void* qkv, void* out, float* lse, void* dbg, int64_t B, int64_t T, int64_t H, void* stream);
 

@@ -985,6 +985,62 @@ def dense_crf(rgb, prob, sxy_g=3.0, compat_g=3.0, sxy_b=40.0, srgb=13.0, compat_
     return mask, q
 
 
+_PAMR_WS = {}          # (device, stream) -> workspace
+PAMR_DILATIONS = (1, 2, 4, 8, 12, 24)
+
+
+def pamr_check(dilations, iters, K=1, scale=1):
+    """The ranges simseg_pamr accepts, checked before a device is needed -> the dilations as a tuple of ints."""
+    try:
+        given = list(dilations)
+        dil = tuple(int(d) for d in given)
+    except (TypeError, ValueError):
+        raise ValueError(f"pamr: dilations are a sequence of 1..8 integers in 1..64, got {dilations!r}")
+    if not 1 <= len(dil) <= 8 or any(d < 1 or d > 64 or d != f for d, f in zip(dil, given)):
+        raise ValueError(f"pamr: dilations are a sequence of 1..8 integers in 1..64, got {dilations!r}")
+    if int(iters) != iters or not 0 <= iters <= 64:
+        raise ValueError(f"pamr: 0..64 iterations (got {iters!r})")
+    if not 1 <= K <= 8:
+        raise ValueError(f"pamr: 1..8 candidate maps per image (got {K})")
+    if int(scale) != scale or scale < 1:
+        raise ValueError(f"pamr: the map scale is a positive integer (got {scale!r})")
+    return dil
+
+
+def pamr(rgb, prob, cand_idx=None, dilations=PAMR_DILATIONS, iters=10, scale=1, want_m=False):
+    """Pixel-adaptive mask refinement (include/simseg_hip.h simseg_pamr) of the K candidate maps of each image of a batch.  rgb
+    [B,H,W,3] (or [H,W,3]) uint8, prob [B,K,H/scale,W/scale] (or [K,...]) fp32 in [0,1], cand_idx (optional) [B,K] (or [K]) int32: slots
+    with a negative entry are skipped and come back zero -> (mask uint8 0/255 [B,K,H,W], refined map fp32 or None)."""
+    if rgb.dtype != torch.uint8 or prob.dtype != torch.float32 or rgb.dim() not in (3, 4) or prob.dim() != rgb.dim():
+        raise TypeError("pamr: rgb uint8 [B,H,W,3], prob fp32 [B,K,H/scale,W/scale]")
+    single = prob.dim() == 3
+    if single:
+        rgb, prob = rgb[None], prob[None]
+        cand_idx = cand_idx[None] if cand_idx is not None else None
+    B, K, h, w = prob.shape
+    dil = pamr_check(dilations, iters, K, scale)
+    H, W = h * int(scale), w * int(scale)
+    if tuple(rgb.shape) != (B, H, W, 3):
+        raise ValueError(f"pamr: images {tuple(rgb.shape)} do not match the maps {tuple(prob.shape)} at scale {scale}")
+    if cand_idx is not None and (cand_idx.dtype != torch.int32 or tuple(cand_idx.shape) != (B, K)):
+        raise ValueError(f"pamr: cand_idx int32 [{B},{K}] expected, got {cand_idx.dtype} {tuple(cand_idx.shape)}")
+    require_gpu(rgb, prob, cand_idx)
+    nbytes = raw("simseg_pamr_workspace_bytes", B, K, H, W, len(dil)) if iters else 0
+    key = (rgb.device, torch.cuda.current_stream().cuda_stream)
+    ws = _PAMR_WS.get(key)
+    if nbytes and (ws is None or ws.numel() < nbytes):
+        _PAMR_WS.pop(key, None)
+        ws = None                  # (the old workspace is released before the new one is requested)
+        ws = _PAMR_WS[key] = torch.empty(nbytes, device=rgb.device, dtype=torch.uint8)
+    mask = torch.empty(B, K, H, W, device=rgb.device, dtype=torch.uint8)
+    m = torch.empty(B, K, H, W, device=rgb.device, dtype=torch.float32) if want_m else None
+    call("simseg_pamr", ptr(_c(rgb)), ptr(_c(prob)), ptr(_c(cand_idx)), ptr(mask), ptr(m), B, K, H, W, (ctypes.c_int * len(dil))(*dil), len(dil),
+         int(iters), int(scale), ptr(ws) if nbytes else None, nbytes, stream())
+    if single:
+        return mask[0], (m[0] if want_m else None)
+    return mask, m
+
+
 # ---- sliding windows over images of any size (segpost.slide_windows; include/simseg_hip.h simseg_slide_*) ---------------------------------
 def slide_plan(sizes, win, stride, device, ncand=5):
     """Host geometry + device tables of a sliding-window pass over images of sizes [(H, W), ...]: windows at segpost.slide_windows offsets,

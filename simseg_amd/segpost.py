@@ -8,7 +8,8 @@
 Between the normalised map and the morphology the reference runs a fully connected CRF on the CPU for every visited candidate
 (pydensecrf, :31-54 / :153).  Here it is `ops.dense_crf` - mean-field inference on two permutohedral lattices built on the device -
 when the caller hands over the de-normalised network inputs (`images_u8`, what the tool builds at :104); without them the binary
-map is the CRF's unary decision (prob > 0.5), and a caller-supplied `refine` hook can replace either.  Everything after it (7x7
+map is the CRF's unary decision (prob > 0.5), and a caller-supplied `refine` hook can replace either.  `refiner="pamr"` runs PAMR
+(`ops.pamr`, pixel-adaptive mask refinement: no lattice, no host read) in the CRF's place; the reference has none.  Everything after it (7x7
 dilate + erode, nearest resize, score-weighted argmax, IoU histograms) is the reference's arithmetic again.
 """
 import os
@@ -78,6 +79,65 @@ def crf_masks(prob, cand_idx, images_u8, chunk=None, scale=1, static=None, **par
     return masks
 
 
+PAMR_PARAMS = dict(dilations=(1, 2, 4, 8, 12, 24), iters=10)
+
+
+def pamr_masks(prob, cand_idx, images_u8, scale=1, chunk=None, **params):
+    """crf_masks() with PAMR (ops.pamr) in the DenseCRF's place: prob [B,K,h,w] fp32 normalised candidate maps at 1/scale of the image
+    resolution (read through (y / scale, x / scale) by the first iteration: the upsampled maps never exist), cand_idx [B,K] (-1 = slot not
+    visited), images_u8 [B,H,W,3] -> uint8 masks [B,K,H,W] (0/255; unvisited slots zero).  No host read and no per-image loop: unvisited
+    slots are skipped inside the kernels, `chunk` images per call.  chunk = None: from the shapes and the device's free memory only -
+    the workspace is 4 * 8 D + 8 K bytes per pixel (232 at the defaults), and memory the caching allocator holds but has not handed out
+    counts as free.  A pixel's result does not depend on the chunking."""
+    B, K, h, w = prob.shape
+    H, W = h * scale, w * scale
+    kw = dict(PAMR_PARAMS, **params)
+    dil = ops.pamr_check(kw["dilations"], kw["iters"], K, scale)
+    if chunk is None:
+        chunk = B
+        if prob.device.type == "cuda":
+            per_pixel = 4 * 8 * len(dil) + 8 * K + K                                  # workspace + the masks
+            held = ops._PAMR_WS.get((prob.device, torch.cuda.current_stream().cuda_stream))
+            free, _ = torch.cuda.mem_get_info(prob.device)
+            free += torch.cuda.memory_reserved(prob.device) - torch.cuda.memory_allocated(prob.device) + (held.numel() if held is not None else 0)
+            chunk = int(0.5 * free / per_pixel) // (H * W)
+    chunk = max(1, min(B, int(chunk)))
+    cand_idx, images_u8, prob = cand_idx.contiguous(), images_u8.contiguous(), prob.contiguous()
+    if chunk >= B:
+        return ops.pamr(images_u8, prob, cand_idx, scale=scale, **kw)[0]
+    masks = torch.empty(B, K, H, W, device=prob.device, dtype=torch.uint8)
+    for s in range(0, B, chunk):
+        masks[s:s + chunk] = ops.pamr(images_u8[s:s + chunk], prob[s:s + chunk], cand_idx[s:s + chunk], scale=scale, **kw)[0]
+    return masks
+
+
+def parse_refiner(refiner, crf=True):
+    """The `refiner` keyword of the encode_* / eval functions: None or "crf" -> None (the DenseCRF under crf=True: the default);
+    "pamr" or ("pamr", {parameters of pamr_masks}) -> ("pamr", {checked parameters}).  PAMR needs the images, so crf=False with it is an
+    error."""
+    if refiner is None or refiner == "crf":
+        return None
+    pair = (refiner, {}) if isinstance(refiner, str) else tuple(refiner) if isinstance(refiner, (tuple, list)) else ()
+    if len(pair) != 2 or pair[0] != "pamr" or not isinstance(pair[1], dict):
+        raise ValueError(f'refiner: None, "crf", "pamr" or ("pamr", {{parameters}}) expected, got {refiner!r}')
+    params = dict(pair[1])
+    unknown = set(params) - {"dilations", "iters", "chunk"}
+    if unknown:
+        raise ValueError(f"refiner: unknown PAMR parameters {sorted(unknown)}")
+    kw = dict(PAMR_PARAMS, **params)
+    ops.pamr_check(kw["dilations"], kw["iters"])
+    if not crf:
+        raise ValueError('refiner="pamr" refines the maps with the images: it cannot be combined with crf=False')
+    return ("pamr", params)
+
+
+def refine_masks(prob, cand_idx, images_u8, scale, refiner=None):
+    """The refinement stage of a state: the DenseCRF, or what parse_refiner() stored."""
+    if refiner is None:
+        return crf_masks(prob, cand_idx, images_u8, scale=scale)
+    return pamr_masks(prob, cand_idx, images_u8, scale=scale, **refiner[1])
+
+
 def segment_begin(sim, scores, num_patch, top_cls_num, ncand=5, need_prob=False):
     """First half of segment(): candidate selection and the per-candidate min-max maps - device work only, nothing is read back."""
     cand_idx, cand_score, thr = ops.seg_select(scores, top_cls_num, ncand)
@@ -87,7 +147,8 @@ def segment_begin(sim, scores, num_patch, top_cls_num, ncand=5, need_prob=False)
 
 
 def segment_finish(st, labels, num_classes=None, ignore_index=255, refine=None, hist=None, want_pred=True, closing=True, images_u8=None):
-    """Second half of segment(): DenseCRF (ONE host read of the candidate table), closing, resize + argmax + IoU histograms."""
+    """Second half of segment(): DenseCRF (ONE host read of the candidate table) - or PAMR where the state says so (st["refiner"],
+    parse_refiner) - closing, resize + argmax + IoU histograms."""
     cand_idx, cand_score, masks, prob, num_patch = st["cand_idx"], st["cand_score"], st["masks"], st["prob"], st["num_patch"]
     num_classes = num_classes or st["num_classes"]
     if refine is not None or images_u8 is not None:
@@ -98,7 +159,7 @@ def segment_finish(st, labels, num_classes=None, ignore_index=255, refine=None, 
             up = lo.repeat_interleave(16, 2).repeat_interleave(16, 3)
             masks = refine(up, cand_idx, cand_score).to(torch.uint8).contiguous()
         else:
-            masks = crf_masks(lo, cand_idx, images_u8, scale=16)
+            masks = refine_masks(lo, cand_idx, images_u8, 16, st.get("refiner"))
     if closing:
         masks = ops.close7(masks, cand_idx.reshape(-1))                       # cv2.dilate then cv2.erode (:156-157), visited slots only
     pred, hist = ops.seg_predict(masks, cand_idx, cand_score, labels, num_classes, ignore_index, hist=hist, want_pred=want_pred)
@@ -113,11 +174,14 @@ def segment(sim, scores, labels, num_patch, top_cls_num, num_classes=None, ncand
     return segment_finish(st, labels, num_classes or sim.shape[2], ignore_index, refine, hist, want_pred, closing, images_u8)
 
 
-def encode_batch(model, image, text, top_cls_num, crf=True, mean=None, std=None, sim_dtype=None, refine=None):
+def encode_batch(model, image, text, top_cls_num, crf=True, mean=None, std=None, sim_dtype=None, refine=None, refiner=None):
     """Everything of eval_batch() up to the candidate maps: towers -> pooled embedding + projected patch tokens -> similarity map for all
     classes -> candidate selection + min-max maps.  Device work only (no host read): the caller may enqueue the NEXT batch's encoder
     before it finishes this one (EvalPipeline)."""
     from .heads import patch_text_similarity
+    refiner = parse_refiner(refiner, crf)
+    if refiner is not None and refine is not None:
+        raise ValueError("encode_batch: a refine hook and refiner= are two answers to one question")
     feats = model.forward_image_feature(image)                    # [B, n*n, D]
     pooled = model.forward_image_project(feats)                   # [B, 512]
     n = int(round(feats.shape[1] ** 0.5))
@@ -127,6 +191,7 @@ def encode_batch(model, image, text, top_cls_num, crf=True, mean=None, std=None,
         raw = (((image * std) + mean) * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
     st = segment_begin(sim, ops.gemm(pooled.float(), text), n, top_cls_num, need_prob=refine is not None or raw is not None)
     st["images_u8"] = raw
+    st["refiner"] = refiner
     return st
 
 
@@ -156,11 +221,13 @@ def extract_windows(image, win=512, stride=256):
     return v.permute(0, 2, 3, 1, 4, 5).reshape(B * wy * wx, C, win, win)
 
 
-def encode_batch_sliding(model, image, text, top_cls_num, win=512, stride=256, crf=True, mean=None, std=None, sim_dtype=None, window_batch=None):
+def encode_batch_sliding(model, image, text, top_cls_num, win=512, stride=256, crf=True, mean=None, std=None, sim_dtype=None, window_batch=None,
+                         refiner=None):
     """encode_batch() for source images larger than the network input: image [B,3,H,W] -> B*wy*wx windows through the towers (at most
     `window_batch` windows per call), similarity maps stitched on the [H/16, W/16] patch grid (ops.stitch_windows), image-level scores =
     the mean of the windows' pooled scores -> candidate selection and min-max maps on the stitched grid.  Device work only."""
     from .heads import patch_text_similarity
+    refiner = parse_refiner(refiner, crf)
     B, _, H, W = image.shape
     wy, wx = window_grid(H, W, win, stride)
     wins = extract_windows(image, win, stride)
@@ -181,6 +248,7 @@ def encode_batch_sliding(model, image, text, top_cls_num, win=512, stride=256, c
         raw = (((image * std) + mean) * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()
     st = segment_begin(sim, sc, (H // 16, W // 16), top_cls_num, need_prob=raw is not None)
     st["images_u8"] = raw
+    st["refiner"] = refiner
     st["windows"] = (wy, wx)
     return st
 
@@ -206,7 +274,7 @@ def slide_windows(H, W, win=512, stride=256):
 
 
 def encode_images_sliding(model, images, text, top_cls_num, win=512, stride=256, crf=True, mean=None, std=None, sim_dtype=None, window_batch=None,
-                          sizes=None):
+                          sizes=None, refiner=None):
     """encode_batch_sliding() for images of any sizes: images = a list of [3, H_i, W_i] normalised fp32 tensors (or one [B,3,H,W] tensor),
     or - with sizes = [(H_i, W_i), ...] - the flat fp32 buffer that already holds them back to back (what preproc.preprocess writes: taken
     as it is, nothing is concatenated).
@@ -214,6 +282,7 @@ def encode_images_sliding(model, images, text, top_cls_num, win=512, stride=256,
     image scores = the mean of an image's window scores (ops.slide_scores) -> candidate selection -> per visited slot the pixel-resolution
     stitched map, min-max normalised, and its binary map (ops.slide_stitch).  Device work only (no host read).  finish_sliding() ends it."""
     from .heads import patch_text_similarity
+    refiner = parse_refiner(refiner, crf)
     if sizes is not None:
         sizes = [(int(h), int(w)) for h, w in sizes]
         flat = images.contiguous().reshape(-1)
@@ -259,7 +328,7 @@ def encode_images_sliding(model, images, text, top_cls_num, win=512, stride=256,
         # the de-normalised source images (tools/seg_evaluation.py:104), one [g, H, W, 3] tensor per image size
         raw = {hw: (bs, (((x * std) + mean) * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous()) for hw, (bs, x) in groups.items()}
     return {"cand_idx": cand_idx, "cand_score": cand_score, "threshold": thr, "scores": sc, "prob": prob, "masks": masks, "minmax": minmax,
-            "plan": plan, "images_u8": raw, "num_classes": sim_w.shape[2]}
+            "plan": plan, "images_u8": raw, "num_classes": sim_w.shape[2], "refiner": refiner}
 
 
 # ---- multi-scale and flip test-time augmentation (DESIGN.md "Multi-scale and flip test-time augmentation") ------------------------------
@@ -285,7 +354,7 @@ def tta_nearest_index(i, L, Lp):
 
 
 def encode_images_multiscale(model, passes, text, top_cls_num, win=512, stride=256, crf=True, mean=None, std=None, sim_dtype=None,
-                             window_batch=None, base=0):
+                             window_batch=None, base=0, refiner=None):
     """encode_images_sliding() with test-time augmentation.  passes = [(flat, sizes, flip), ...]: per pass the flat fp32 buffer that holds
     the batch's normalised [3, H_p, W_p] images back to back (what preproc.preprocess writes for that scale; NOT mirrored), their sizes,
     and whether the pass runs on the mirrored images (the mirror is taken while the windows are cut: ops.slide_extract_flip).
@@ -296,6 +365,7 @@ def encode_images_multiscale(model, passes, text, top_cls_num, win=512, stride=2
     (plan = the base plan, scores = the fused scores): finish_sliding() ends it.  One pass (the base alone) gives encode_images_sliding's
     result bit for bit."""
     from .heads import patch_text_similarity
+    refiner = parse_refiner(refiner, crf)
     P = len(passes)
     if P == 0 or not 0 <= base < P:
         raise ValueError(f"encode_images_multiscale: {P} passes, base index {base}")
@@ -346,7 +416,7 @@ def encode_images_multiscale(model, passes, text, top_cls_num, win=512, stride=2
         raw = {hw: (bs, (((x * std) + mean) * 255).to(torch.uint8).permute(0, 2, 3, 1).contiguous())
                for hw, (bs, x) in ((hw, (bs, v[0][None] if len(v) == 1 else torch.stack(v))) for hw, (bs, v) in groups.items())}
     return {"cand_idx": cand_idx, "cand_score": cand_score, "threshold": thr, "scores": sc, "prob": prob, "masks": masks, "minmax": minmax,
-            "plan": plan, "images_u8": raw, "num_classes": sims[0].shape[2]}
+            "plan": plan, "images_u8": raw, "num_classes": sims[0].shape[2], "refiner": refiner}
 
 
 def _crf_cached_size(device):
@@ -358,8 +428,8 @@ def _crf_cached_size(device):
 def finish_sliding(st, labels, hist=None, num_classes=None, ignore_index=255, want_pred=False, closing=True):
     """Second half of the any-size sliding-window evaluation: labels = a list of [Hl_i, Wl_i] uint8 tensors (or one [B,Hl,Wl] tensor).
     Images are grouped by (H, W, label shape); per group: DenseCRF on the full-resolution prob maps (crf_masks(..., scale=1)) when
-    encode_images_sliding was given crf=True, else the binary maps; 7x7 closing; nearest resize to the labels + score-weighted argmax +
-    IoU histograms (ops.seg_predict, accumulated into `hist`).  Groups that share an image size run back to back, starting with the size
+    encode_images_sliding was given crf=True (PAMR, pamr_masks(..., scale=1), under refiner="pamr"), else the binary maps; 7x7 closing;
+    nearest resize to the labels + score-weighted argmax + IoU histograms (ops.seg_predict, accumulated into `hist`).  Groups that share an image size run back to back, starting with the size
     whose spatial lattice the CRF holds, so that lattice is rebuilt once per size.
     -> dict(hist, cand_idx, cand_score, masks [per image: ncand x H x W uint8, after closing], pred [per image, or None])."""
     plan = st["plan"]
@@ -376,7 +446,8 @@ def finish_sliding(st, labels, hist=None, num_classes=None, ignore_index=255, wa
         keys.setdefault(hw + tuple(lab.shape[-2:]), []).append(b)
     order = sorted(keys)
     raw = st.get("images_u8")
-    if raw is not None:
+    refiner = st.get("refiner")
+    if raw is not None and refiner is None:
         first = _crf_cached_size(dev)
         order.sort(key=lambda k: (k[:2] != first, k))
     out_masks, out_pred = [None] * len(sizes), [None] * len(sizes)
@@ -395,7 +466,7 @@ def finish_sliding(st, labels, hist=None, num_classes=None, ignore_index=255, wa
         if raw is not None:
             gb, u8 = raw[key[:2]]
             img = take(u8, [gb.index(b) for b in bs])
-            maps = crf_masks(maps, cand, img, scale=1)
+            maps = refine_masks(maps, cand, img, 1, refiner)
         if closing:
             maps = ops.close7(maps, cand.reshape(-1))
         lab = labels[bs[0]][None] if len(bs) == 1 else torch.stack([labels[b] for b in bs])
@@ -416,7 +487,7 @@ def shard_batches(batches, rank, world):
 
 
 def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=None, slide=None, crf=True, mean=None, std=None, sim_dtype=None,
-                     device=None, pipelined=None, window_batch=None, presharded=False, preprocess=None):
+                     device=None, pipelined=None, window_batch=None, presharded=False, preprocess=None, refiner=None):
     """The zero-shot segmentation evaluation over `batches` = an iterable of (image [b,3,H,W], label [b,Hl,Wl] uint8) - the SAME iterable on
     every rank - data-parallel over the ranks of `group` (default: the world, or a single process when torch.distributed is not
     initialised): batches are dealt round-robin (shard_batches; the reference's loader gives every rank every image,
@@ -434,6 +505,7 @@ def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=
     (encode_images_multiscale).
     -> dict(iou [C] float64, miou, hist [3,C] int64 (global), images (global count), images_local)."""
     import torch.distributed as dist
+    refiner = parse_refiner(refiner, crf)
     on = dist.is_available() and dist.is_initialized()
     rank = dist.get_rank(group) if on else 0
     world = dist.get_world_size(group) if on else 1
@@ -448,28 +520,28 @@ def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=
             if isinstance(res, dict) and slide is not None and "passes" in res:
                 # test-time augmentation: preprocess returned dict(passes=[(packed, sizes, flip), ...], base=index) (encode_images_multiscale)
                 st = encode_images_multiscale(model, res["passes"], text, top_cls_num, win=slide[0], stride=slide[1], crf=crf, mean=mean, std=std,
-                                              sim_dtype=sim_dtype, window_batch=window_batch, base=res["base"])
+                                              sim_dtype=sim_dtype, window_batch=window_batch, base=res["base"], refiner=refiner)
                 st["preprocessed"] = res
                 return st
             if isinstance(res, dict) and slide is not None:
                 st = encode_images_sliding(model, res["packed"], text, top_cls_num, win=slide[0], stride=slide[1], crf=crf, mean=mean, std=std,
-                                           sim_dtype=sim_dtype, window_batch=window_batch, sizes=res["sizes"])
+                                           sim_dtype=sim_dtype, window_batch=window_batch, sizes=res["sizes"], refiner=refiner)
                 st["preprocessed"] = res
                 return st
             image = res["images"] if isinstance(res, dict) else res
             if not torch.is_tensor(image):
                 raise ValueError("evaluate_sharded: without slide=(win, stride) the preprocessed images of a batch must share one size")
             if slide is None:
-                st = encode_batch(model, image, text, top_cls_num, crf=crf, mean=mean, std=std, sim_dtype=sim_dtype)
+                st = encode_batch(model, image, text, top_cls_num, crf=crf, mean=mean, std=std, sim_dtype=sim_dtype, refiner=refiner)
                 st["preprocessed"] = res
                 return st
         if isinstance(image, (list, tuple)):        # images of any sizes: the any-size sliding-window path
             return encode_images_sliding(model, image, text, top_cls_num, win=slide[0], stride=slide[1], crf=crf, mean=mean, std=std,
-                                         sim_dtype=sim_dtype, window_batch=window_batch)
+                                         sim_dtype=sim_dtype, window_batch=window_batch, refiner=refiner)
         if slide is not None:
             return encode_batch_sliding(model, image, text, top_cls_num, win=slide[0], stride=slide[1], crf=crf, mean=mean, std=std,
-                                        sim_dtype=sim_dtype, window_batch=window_batch)
-        return encode_batch(model, image, text, top_cls_num, crf=crf, mean=mean, std=std, sim_dtype=sim_dtype)
+                                        sim_dtype=sim_dtype, window_batch=window_batch, refiner=refiner)
+        return encode_batch(model, image, text, top_cls_num, crf=crf, mean=mean, std=std, sim_dtype=sim_dtype, refiner=refiner)
 
     def finish(st, image, label):
         if "plan" in st:                            # the any-size path's state (encode_images_sliding)
@@ -479,7 +551,8 @@ def evaluate_sharded(model, batches, text, top_cls_num, num_classes=None, group=
         return finish_batch(st, label, hist=hist)
 
     count = 0
-    pipe = EvalPipeline(dev, encode, finish, pipelined=crf if pipelined is None else pipelined)
+    # (PAMR has no host read for the pipeline to hide: whole batches back to back, as under crf=False - DESIGN.md "PAMR refinement")
+    pipe = EvalPipeline(dev, encode, finish, pipelined=(crf and refiner is None) if pipelined is None else pipelined)
     with torch.no_grad():
         for image, label in (batches if presharded else shard_batches(batches, rank, world)):      # presharded: `batches` is already this rank's share
             if preprocess is not None:
@@ -534,12 +607,13 @@ def finish_batch(st, label, hist=None, refine=None, want_pred=False):
 
 
 def eval_batch(model, image, label, text, top_cls_num, hist=None, crf=True, mean=None, std=None, sim_dtype=None, refine=None,
-               want_pred=False):
+               want_pred=False, refiner=None):
     """One batch of the zero-shot segmentation evaluation, everything on the device (tools/seg_evaluation.py:99-170 for every image of
     the batch at once): towers -> pooled embedding + projected patch tokens -> similarity map for all classes -> segment().
     image [B,3,S,S] normalised network input, label [B,H,W] uint8, text [C,512] unit-norm class embeddings.  crf: run the DenseCRF on
-    the de-normalised input (image * std + mean, :104) as the reference does; hist [3,C] int64 accumulates."""
-    st = encode_batch(model, image, text, top_cls_num, crf=crf, mean=mean, std=std, sim_dtype=sim_dtype, refine=refine)
+    the de-normalised input (image * std + mean, :104) as the reference does; refiner="pamr" (or ("pamr", {parameters})): PAMR in its
+    place (pamr_masks); hist [3,C] int64 accumulates."""
+    st = encode_batch(model, image, text, top_cls_num, crf=crf, mean=mean, std=std, sim_dtype=sim_dtype, refine=refine, refiner=refiner)
     return finish_batch(st, label, hist=hist, refine=refine, want_pred=want_pred)
 
 

@@ -8,7 +8,8 @@ how the work is laid out, not in what is computed:
     image, up to five GEMVs with host syncs, :99-143);
   * candidate selection, min-max normalisation, binarisation, 7x7 dilate/erode, nearest resize, score-weighted argmax and
     the IoU histograms run on the device (simseg_amd.segpost, :112-170), and so does the DenseCRF between normalisation and
-    morphology (:31-54 / :153: mean-field inference on two permutohedral lattices, simseg_dense_crf).  `--no-crf` stops at the
+    morphology (:31-54 / :153: mean-field inference on two permutohedral lattices, simseg_dense_crf).  `--refine pamr` runs PAMR
+    (pixel-adaptive mask refinement, simseg_pamr; `--pamr-iters`, `--pamr-dilations`) in its place.  `--no-crf` stops at the
     CRF's unary decision; with pydensecrf installed `--host-crf` routes the maps through the library on the host instead
     (cross-check of the device CRF against the package the reference uses).
 
@@ -76,7 +77,39 @@ def parse_args():
                                                         "them and sent through the config's valid transforms on the host or, with --device-preproc, on the device")
     ap.add_argument("--scales", default="", help="S1,S2,...: multi-scale test-time augmentation (needs --slide and --device-preproc; 1.0 must be among them)")
     ap.add_argument("--flip", action="store_true", help="add a horizontally mirrored pass per scale (needs --slide and --device-preproc)")
-    return ap.parse_known_args()
+    ap.add_argument("--refine", choices=("crf", "pamr"), default="crf", help="the refinement between the normalised maps and the morphology: the reference's "
+                                                                             "DenseCRF, or PAMR (pixel-adaptive mask refinement, segpost.pamr_masks)")
+    ap.add_argument("--pamr-iters", type=int, default=None, help="PAMR propagation steps (default 10)")
+    ap.add_argument("--pamr-dilations", default="", help="d1,d2,...: PAMR dilations (default 1,2,4,8,12,24)")
+    args, rest = ap.parse_known_args()
+    try:
+        args.refiner = refiner_option(args)
+    except ValueError as e:
+        ap.error(str(e))
+    return args, rest
+
+
+def refiner_option(args):
+    """--refine / --pamr-iters / --pamr-dilations -> the `refiner` keyword of segpost (None = the DenseCRF); ValueError with the reason when
+    they do not fit the other options."""
+    given = args.pamr_iters is not None or bool(args.pamr_dilations)
+    if args.refine != "pamr":
+        if given:
+            raise ValueError("--pamr-iters / --pamr-dilations need --refine pamr")
+        return None
+    if args.no_crf or args.host_crf:
+        raise ValueError("--refine pamr replaces the DenseCRF: it cannot be combined with --no-crf or --host-crf")
+    params = {}
+    if args.pamr_iters is not None:
+        params["iters"] = args.pamr_iters
+    if args.pamr_dilations:
+        try:
+            params["dilations"] = tuple(int(v) for v in args.pamr_dilations.split(","))
+        except ValueError:
+            raise ValueError(f"--pamr-dilations takes comma-separated integers, got {args.pamr_dilations!r}")
+    from simseg_amd import ops
+    ops.pamr_check(params.get("dilations", ops.PAMR_DILATIONS), params.get("iters", 10))
+    return ("pamr", params)
 
 
 def tta_options(args):
@@ -398,7 +431,7 @@ def main():
             on = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
             shard = (dist.get_rank(), dist.get_world_size()) if on else None
             res = segpost.evaluate_sharded(model, batches(name, shard), text, top_cls_num, slide=slide, crf=not args.no_crf, mean=mean, std=std,
-                                           device=ENV.device, presharded=on, preprocess=preprocess)
+                                           device=ENV.device, presharded=on, preprocess=preprocess, refiner=args.refiner)
             torch.cuda.synchronize()
             iou, miou, count, hist = res["iou"], res["miou"], res["images"], res["hist"]
         dt = time.perf_counter() - t0
