@@ -16,30 +16,32 @@ from .builder import LOSS
 __all__ = ["NCE", "MixUpNCE", "Triplet", "SigLip", "NTXent", "LabelSmoothingCrossEntropy", "SoftTargetCrossEntropy"]
 
 
-@LOSS.register_obj
-class NCE(nn.Module):
-    def __init__(self, cfg, rank):
-        super().__init__()
-        self.cfg = cfg
-        self.global_reduce = cfg.loss.global_reduce
-        self.rank, self.group = 0, None
-        self.gather_backward = False
-        if self.global_reduce:
-            self.gather_backward = cfg.loss.nce_loss.gather_backward
-            if dist.is_available() and dist.is_initialized():
-                group_size = cfg.loss.group_size if cfg.loss.group_size >= 0 else ENV.size
-                self.group, self.rank = generate_local_groups(group_size)
-                logger.info("NCE Loss Group size, Group Rank, Env Rank:", group_size, self.rank, ENV.rank, root_only=False)
-            else:   # single process: the gather is the identity (the reference insists on a process group)
-                logger.info("NCE: no process group, global_reduce degenerates to the local batch")
-        t = torch.ones([]) * cfg.loss.temperature.value
-        if cfg.loss.temperature.name == "parameter":
+class _GlobalLoss(nn.Module):
+    """What the global_reduce losses share: the loss group, the temperature, and the exchange of the other side's embeddings."""
+
+    group, rank, gather_backward = None, 0, False
+
+    def _loss_group(self, cfg, who):
+        """self.group, self.rank: generate_local_groups(loss.group_size) under a process group, (None, 0) without one."""
+        if dist.is_available() and dist.is_initialized():
+            group_size = cfg.loss.group_size if cfg.loss.group_size >= 0 else ENV.size
+            self.group, self.rank = generate_local_groups(group_size)
+            logger.info(f"{who} Loss Group size, Group Rank, Env Rank:", group_size, self.rank, ENV.rank, root_only=False)
+        else:   # single process: the gather is the identity (the reference insists on a process group)
+            self.group, self.rank = None, 0
+            logger.info(f"{who}: no process group, global_reduce degenerates to the local batch")
+
+    def _init_temperature(self, cfg, value=None, learnable=None):
+        """self.temperature = loss.temperature.value (or `value`): an nn.Parameter under loss.temperature.name=parameter, a non-persistent
+        buffer under `constant`; `learnable` (True / False) overrides the name's choice."""
+        name = cfg.loss.temperature.name
+        if name not in ("parameter", "constant"):
+            raise NotImplementedError(name)
+        t = torch.ones([]) * float(cfg.loss.temperature.value if value is None else value)
+        if name == "parameter" if learnable is None else learnable:
             self.temperature = nn.Parameter(t)
-        elif cfg.loss.temperature.name == "constant":
-            self.register_buffer("temperature", t, persistent=False)
         else:
-            raise NotImplementedError(cfg.loss.temperature.name)
-        self.smoothing = float(cfg.loss.smoothing)
+            self.register_buffer("temperature", t, persistent=False)
 
     def _gather(self, t):
         if self.group is None:
@@ -47,6 +49,29 @@ class NCE(nn.Module):
         if self.gather_backward and t.requires_grad:
             return GatherLayer.apply(t, self.group, self.rank)
         return all_gather_rows(t, self.group)
+
+    def _gather_global(self, feat1, feat2, what="batch size"):
+        """feat2's rows of every rank of the group: a whole number of blocks of feat1's size."""
+        feat2_global = self._gather(feat2)
+        if feat2_global.shape[0] % feat1.shape[0] != 0:
+            raise AssertionError(f"global size: {feat2_global.shape[0]}, {what}: {feat1.shape[0]}")
+        return feat2_global
+
+    def _gather_ignore(self, ignore_mask):
+        return None if ignore_mask is None else all_gather_rows(ignore_mask.float(), self.group) if self.group else ignore_mask.float()
+
+
+@LOSS.register_obj
+class NCE(_GlobalLoss):
+    def __init__(self, cfg, rank):
+        super().__init__()
+        self.cfg = cfg
+        self.global_reduce = cfg.loss.global_reduce
+        if self.global_reduce:
+            self.gather_backward = cfg.loss.nce_loss.gather_backward
+            self._loss_group(cfg, "NCE")
+        self._init_temperature(cfg)
+        self.smoothing = float(cfg.loss.smoothing)
 
     def both(self, image_embeddings, text_embeddings):
         """0.5 * (self(image, text)[0] + self(text, image)[0]) and the two top-1 accuracies - what CLIPModel.forward_loss computes with
@@ -58,11 +83,8 @@ class NCE(nn.Module):
 
     def forward(self, feat1, feat2, label=None, ignore_mask=None):
         if self.global_reduce:
-            feat2_global = self._gather(feat2)
-            ignore_global = None if ignore_mask is None else all_gather_rows(ignore_mask.float(), self.group) if self.group else ignore_mask.float()
-            if feat2_global.shape[0] % feat1.shape[0] != 0:
-                raise AssertionError(f"global size: {feat2_global.shape[0]}, batch size: {feat1.shape[0]}")
-            return NCEFn.apply(feat1, feat2_global, self.temperature, ignore_mask, ignore_global, self.rank, self.smoothing)
+            feat2_global = self._gather_global(feat1, feat2)
+            return NCEFn.apply(feat1, feat2_global, self.temperature, ignore_mask, self._gather_ignore(ignore_mask), self.rank, self.smoothing)
         if ignore_mask is not None:
             raise NotImplementedError("ignore_mask with loss.global_reduce=False is outside the accelerated path")
         # local branch (:79-86): symmetric loss over the local batch, three return values
@@ -71,19 +93,8 @@ class NCE(nn.Module):
         return 0.5 * (l1 + l2), a1, a2
 
 
-def _loss_group(cfg, who):
-    """(group, group rank) of a global_reduce loss: generate_local_groups(loss.group_size) under a process group, (None, 0) without one."""
-    if dist.is_available() and dist.is_initialized():
-        group_size = cfg.loss.group_size if cfg.loss.group_size >= 0 else ENV.size
-        group, rank = generate_local_groups(group_size)
-        logger.info(f"{who} Loss Group size, Group Rank, Env Rank:", group_size, rank, ENV.rank, root_only=False)
-        return group, rank
-    logger.info(f"{who}: no process group, global_reduce degenerates to the local batch")
-    return None, 0
-
-
 @LOSS.register_obj
-class MixUpNCE(nn.Module):
+class MixUpNCE(_GlobalLoss):
     """InfoNCE against mixed targets (mml_loss.py:105-197 of the reference): one modality of the batch was mixed with its flipped self
     (x_i <- alpha_i x_i + (1 - alpha_i) x_{B-1-i}), and row i is scored against its own column with weight alpha_i and against column
     B - 1 - i (`targets.flip(0)`) with 1 - alpha_i, on the fused row path (simseg_amd.heads.MixNCEFn).  Constructed like NCE;
@@ -102,17 +113,9 @@ class MixUpNCE(nn.Module):
         if not self.global_reduce:
             raise NotImplementedError("MixUpNCE: loss.global_reduce=False")
         self.gather_backward = cfg.loss.nce_loss.gather_backward
-        self.group, self.rank = _loss_group(cfg, "MixUpNCE")
-        t = torch.ones([]) * cfg.loss.temperature.value
-        if cfg.loss.temperature.name == "parameter":
-            self.temperature = nn.Parameter(t)
-        elif cfg.loss.temperature.name == "constant":
-            self.register_buffer("temperature", t, persistent=False)
-        else:
-            raise NotImplementedError(cfg.loss.temperature.name)
+        self._loss_group(cfg, "MixUpNCE")
+        self._init_temperature(cfg)
         self.smoothing = float(cfg.loss.smoothing)
-
-    _gather = NCE._gather
 
     def forward(self, feat1, feat2, label=None, ignore_mask=None, **kwargs):
         if ("image_alpha" in kwargs) == ("text_alpha" in kwargs):
@@ -122,15 +125,12 @@ class MixUpNCE(nn.Module):
         alpha = torch.as_tensor(alpha, dtype=torch.float32).to(feat1.device).detach().reshape(-1).contiguous()
         if alpha.numel() not in (1, N1):
             raise ValueError(f"MixUpNCE: alpha holds {alpha.numel()} values for a batch of {N1}")
-        feat2_global = self._gather(feat2)
-        ignore_global = None if ignore_mask is None else all_gather_rows(ignore_mask.float(), self.group) if self.group else ignore_mask.float()
-        if feat2_global.shape[0] % N1 != 0:
-            raise AssertionError(f"global size: {feat2_global.shape[0]}, batch size: {N1}")
-        return MixNCEFn.apply(feat1, feat2_global, self.temperature, alpha, ignore_mask, ignore_global, self.rank, self.smoothing)
+        feat2_global = self._gather_global(feat1, feat2)
+        return MixNCEFn.apply(feat1, feat2_global, self.temperature, alpha, ignore_mask, self._gather_ignore(ignore_mask), self.rank, self.smoothing)
 
 
 @LOSS.register_obj
-class Triplet(nn.Module):
+class Triplet(_GlobalLoss):
     """The max-violation hinge of VSE++ (mml_loss.py:256-347 of the reference) on the fused row path: cost_ij = max(margin + s_ij - s_ii, 0)
     over the negatives of row i, reduced per row by loss.triplet_loss.reduce_mode = "max" (the hardest negative) or "mean"
     (sum / (N1 - 1)), and SUMMED over rows.  Gradient passes the clamp where margin + s_ij - s_ii > 0 (include/simseg_hip.h).
@@ -140,7 +140,7 @@ class Triplet(nn.Module):
     exactly 0.  loss.global_reduce=False: the symmetric local form over one matrix (rows: 1 -> 2, columns: 2 -> 1), only the diagonal
     masked; returns (loss, i2t acc, t2i acc).
 
-    Gathering follows NCE._gather without gather_backward: with no process group the local tensor is used and gradient flows through
+    Gathering follows _GlobalLoss._gather without gather_backward: with no process group the local tensor is used and gradient flows through
     both roles; with a group the gather is detached, as the reference's all_gather / all_gather_group are.  The diagonal block is taken at
     the GROUP rank: the reference overwrites it with the global rank (mml_loss.py:272), which is only correct where the two coincide.
     ignore_mask is accepted and not applied, as in the reference.  There is no `both` method."""
@@ -153,20 +153,18 @@ class Triplet(nn.Module):
         if self.reduce not in ("mean", "max"):
             raise NotImplementedError("Reduce method {} is not implemented yet".format(self.reduce))
         self.global_reduce = cfg.loss.global_reduce
-        self.group, self.rank = _loss_group(cfg, "Triplet") if self.global_reduce else (None, 0)
+        if self.global_reduce:
+            self._loss_group(cfg, "Triplet")
 
     def forward(self, feat1, feat2, label=None, ignore_mask=None):
         reduce = 0 if self.reduce == "mean" else 1
         if not self.global_reduce:
             return TripletLocalFn.apply(feat1, feat2, self.margin, reduce)
-        feat2_global = feat2 if self.group is None else all_gather_rows(feat2, self.group)
-        if feat2_global.shape[0] % feat1.shape[0] != 0:
-            raise AssertionError(f"global size: {feat2_global.shape[0]}, batch size: {feat1.shape[0]}")
-        return TripletFn.apply(feat1, feat2_global, self.rank, self.margin, reduce)
+        return TripletFn.apply(feat1, self._gather_global(feat1, feat2), self.rank, self.margin, reduce)       # (no gather_backward: detached)
 
 
 @LOSS.register_obj
-class SigLip(nn.Module):
+class SigLip(_GlobalLoss):
     """The pairwise sigmoid loss of SigLIP (Zhai et al., "Sigmoid Loss for Language Image Pre-Training", ICCV'23; open_clip's SigLipLoss)
     on the fused row path (simseg_amd.heads.SigLipFn; formulas in include/simseg_hip.h, simseg_siglip_rows): every (row, column) pair of
     the [N1, N2] similarity block is a binary problem, loss = (1 / N1) sum_ij -log sigmoid(y_ij (s_ij / T + b)) with y = +1 on the row's
@@ -183,7 +181,7 @@ class SigLip(nn.Module):
     bias from -10 towards 0 and shrinks T.  open_clip exempts its logit scale and bias; to do the same add an optim.param_group_rules
     entry such as {regex: "^loss\\.(bias|temperature)$", param: {weight_decay: 0.0}}.
 
-    The group and the exchange are NCE's (_loss_group, NCE._gather).  With a process group and gather_backward=False the gathered
+    The group and the exchange are _GlobalLoss's (_loss_group, _gather).  With a process group and gather_backward=False the gathered
     embeddings are detached: each rank's loss then differentiates only through its own rows' role as feat1, and the gradient a rank's
     embeddings receive as OTHER ranks' negatives - for this loss every off-diagonal pair is a term of its own, so that is most of the
     negatives' signal - is dropped; gather_backward=True (or no process group) keeps it.  The loss is normalised by the local batch N1
@@ -204,31 +202,22 @@ class SigLip(nn.Module):
         if float(cfg.loss.smoothing) != 0.0:
             raise ValueError(f"SigLip: loss.smoothing={cfg.loss.smoothing} - the pairwise sigmoid loss has no label smoothing, set it to 0")
         self.gather_backward = cfg.loss.nce_loss.gather_backward
-        self.group, self.rank = _loss_group(cfg, "SigLip")
-        t = torch.ones([]) * cfg.loss.temperature.value
+        self._loss_group(cfg, "SigLip")
+        self._init_temperature(cfg)
         b = torch.ones([]) * float(self.INIT_BIAS if init_bias is None else init_bias)
-        if cfg.loss.temperature.name == "parameter":
-            self.temperature = nn.Parameter(t)
+        if isinstance(self.temperature, nn.Parameter):
             self.bias = nn.Parameter(b)
-        elif cfg.loss.temperature.name == "constant":
-            self.register_buffer("temperature", t, persistent=False)
-            self.register_buffer("bias", b, persistent=True)
         else:
-            raise NotImplementedError(cfg.loss.temperature.name)
-
-    _gather = NCE._gather
+            self.register_buffer("bias", b, persistent=True)
 
     def forward(self, feat1, feat2, label=None, ignore_mask=None):
         if ignore_mask is not None:
             raise NotImplementedError("SigLip: an ignore_mask is not supported (every pair is a term of the loss; no row weights are built)")
-        feat2_global = self._gather(feat2)
-        if feat2_global.shape[0] % feat1.shape[0] != 0:
-            raise AssertionError(f"global size: {feat2_global.shape[0]}, batch size: {feat1.shape[0]}")
-        return SigLipFn.apply(feat1, feat2_global, self.temperature, self.bias, self.rank)
+        return SigLipFn.apply(feat1, self._gather_global(feat1, feat2), self.temperature, self.bias, self.rank)
 
 
 @LOSS.register_obj
-class NTXent(nn.Module):
+class NTXent(_GlobalLoss):
     """NT-Xent, the loss of SimCLR (Chen et al., ICML'20), in the global form of SLIP's SIMCLRLoss (Mu et al., ECCV'22) on the fused row
     path (simseg_amd.heads.NTXentFn; formulas in include/simseg_hip.h, simseg_ntxent_rows): the two views' embeddings are stacked to
     [2B, P], the stacked tensor is gathered ONCE (rank-major: this rank's rows are block `rank` of the gathered matrix, and every other
@@ -237,7 +226,7 @@ class NTXent(nn.Module):
 
     The temperature is read from loss.temperature.{name, value} - clamped to [1e-3, 0.5] like NCE's - unless the constructor's
     `temperature` (a value) and `learnable` (True: an nn.Parameter, False: a non-persistent buffer) override it; the group and the
-    exchange are NCE's (_loss_group, NCE._gather, loss.nce_loss.gather_backward, loss.group_size).
+    exchange are _GlobalLoss's (_loss_group, _gather, loss.nce_loss.gather_backward, loss.group_size).
 
     forward(view_a, view_b, label=None, ignore_mask=None) -> (loss, top-1 acc of view_a's rows): the (loss, acc) shape of the other
     global_reduce losses; forward(view_b, view_a) gives the same loss and view_b's accuracy.  loss.global_reduce=False, a non-zero
@@ -252,17 +241,9 @@ class NTXent(nn.Module):
             raise NotImplementedError("NTXent: loss.global_reduce=False (a local form) is not built; the stacked views are scored against their gathered selves")
         if float(cfg.loss.smoothing) != 0.0:
             raise ValueError(f"NTXent: loss.smoothing={cfg.loss.smoothing} - the row kernel has no label smoothing, set it to 0")
-        if cfg.loss.temperature.name not in ("parameter", "constant"):
-            raise NotImplementedError(cfg.loss.temperature.name)
         self.gather_backward = cfg.loss.nce_loss.gather_backward
-        self.group, self.rank = _loss_group(cfg, "NTXent")
-        t = torch.ones([]) * float(cfg.loss.temperature.value if temperature is None else temperature)
-        if cfg.loss.temperature.name == "parameter" if learnable is None else learnable:
-            self.temperature = nn.Parameter(t)
-        else:
-            self.register_buffer("temperature", t, persistent=False)
-
-    _gather = NCE._gather
+        self._loss_group(cfg, "NTXent")
+        self._init_temperature(cfg, temperature, learnable)
 
     def forward(self, view_a, view_b, label=None, ignore_mask=None):
         if ignore_mask is not None:
@@ -270,10 +251,7 @@ class NTXent(nn.Module):
         if view_a.shape != view_b.shape:
             raise ValueError(f"NTXent: the two views differ in shape, {tuple(view_a.shape)} against {tuple(view_b.shape)}")
         z = torch.cat([view_a, view_b])
-        zg = self._gather(z)
-        if zg.shape[0] % z.shape[0] != 0:
-            raise AssertionError(f"global size: {zg.shape[0]}, stacked batch size: {z.shape[0]}")
-        loss, acc_a, _ = NTXentFn.apply(z, zg, self.temperature, self.rank)
+        loss, acc_a, _ = NTXentFn.apply(z, self._gather_global(z, z, "stacked batch size"), self.temperature, self.rank)
         return loss, acc_a
 
 

@@ -4,13 +4,17 @@
 
 namespace {
 
+// Every kernel of this file is launched with 256 threads, so a block is 4 waves: the reducers add the per-wave partials in the fixed order
+// 0, wave 0, 1, 2, 3 and have no blockDim loop.
+constexpr int kWaves = 4;
+
 __device__ __forceinline__ float block_reduce_sum(float v, float* sh) {
     v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     float s = 0.f;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s += sh[i];
+    for (int i = 0; i < kWaves; ++i) s += sh[i];
     return s;
 }
 __device__ __forceinline__ float block_reduce_max(float v, float* sh) {
@@ -19,7 +23,7 @@ __device__ __forceinline__ float block_reduce_max(float v, float* sh) {
     if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
     __syncthreads();
     float s = -INFINITY;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) s = fmaxf(s, sh[i]);
+    for (int i = 0; i < kWaves; ++i) s = fmaxf(s, sh[i]);
     return s;
 }
 __device__ __forceinline__ int block_reduce_min_int(int v, int* shi) {
@@ -29,8 +33,23 @@ __device__ __forceinline__ int block_reduce_min_int(int v, int* shi) {
     if ((threadIdx.x & 63) == 0) shi[threadIdx.x >> 6] = v;
     __syncthreads();
     int b = 0x7fffffff;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) b = min(b, shi[w]);
+    for (int w = 0; w < kWaves; ++w) b = min(b, shi[w]);
     return b;
+}
+// The block's maximum of the per-thread maxima mx, and in `best` the FIRST index attaining it (arg: the thread's first index attaining mx).
+__device__ __forceinline__ float block_first_argmax(float mx, int arg, float* sh, int* shi, int& best) {
+    const float bmx = block_reduce_max(mx, sh);
+    best = block_reduce_min_int(mx == bmx ? arg : 0x7fffffff, shi);
+    return bmx;
+}
+
+// temp = clamp(T, 1e-3, 0.5), the temperature every row kernel divides by; and d/dT of a loss in z = s / temp from num = -sum dz s:
+// num / temp^2 where T lies inside the clamp, 0 outside.  (Comparisons and one division each: nothing here can contract.)
+__device__ __forceinline__ float clamp_temp(float T) { return fminf(fmaxf(T, 0.001f), 0.5f); }
+__device__ __forceinline__ float inv_temp(float T) { return 1.0f / clamp_temp(T); }
+__device__ __forceinline__ float temp_grad(float T, float num) {
+    const float temp = clamp_temp(T);
+    return (T >= 0.001f && T <= 0.5f) ? num / (temp * temp) : 0.f;
 }
 
 // One block per local row i of sims[N1,N2] = feat1 . feat2_global^T  (mml_loss.py:73-77, 89-95, 350-376).
@@ -54,27 +73,16 @@ __global__ __launch_bounds__(256) void nce_rows_kernel(float* __restrict__ sims,
     __shared__ int shi[8];
     const int i = blockIdx.x, tid = threadIdx.x;
     float* row = sims + (long)i * N2;
-    const float temp = fminf(fmaxf(temperature[0], 0.001f), 0.5f);
-    const float inv_t = 1.0f / temp;
+    const float inv_t = inv_temp(temperature[0]);
     const int il = i % N1;
     const int tgt = target0 + il;
     float mx = -INFINITY;
-    int arg = 0x7fffffff;
+    int arg = 0x7fffffff, best;
     for (int j = tid; j < N2; j += 256) {
         const float z = row[j] * inv_t;
         if (z > mx) { mx = z; arg = j; }
     }
-    const float bmx = block_reduce_max(mx, sh);
-    // first index attaining the maximum
-    // (block_reduce_min_int with the wave count fixed at 4: the helper's blockDim loop makes this kernel 101 instructions longer)
-    int cand = (mx == bmx) ? arg : 0x7fffffff;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cand = min(cand, __shfl_xor(cand, o, 64));
-    __syncthreads();
-    if ((tid & 63) == 0) shi[tid >> 6] = cand;
-    __syncthreads();
-    int best = 0x7fffffff;
-    for (int w = 0; w < 4; ++w) best = min(best, shi[w]);
+    const float bmx = block_first_argmax(mx, arg, sh, shi, best);
     float se = 0.f, sz = 0.f;
     for (int j = tid; j < N2; j += 256) {
         const float z = row[j] * inv_t;
@@ -124,49 +132,42 @@ __global__ __launch_bounds__(256) void nce_rows_kernel(float* __restrict__ sims,
     }
 }
 
-// out[0] = loss = mean_i row_loss ; out[1] = top-1 acc over kept rows ; out[2] = dLoss/dTemperature
-__global__ __launch_bounds__(256) void nce_finalize_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_correct,
-                                                           const float* __restrict__ row_tdot, const float* __restrict__ ignore,
-                                                           const float* __restrict__ temperature, float* __restrict__ out, int N1) {
+// The one-block finalize of every row kernel above and below - what nce_finalize_kernel, nce_finalize_pair_kernel, triplet_finalize_kernel,
+// siglip_finalize_kernel and ntxent_finalize_kernel were, the names in the profiles taken before - a fixed order of additions over the per-row arrays, then
+//   out = {loss, top-1 acc of rows [0, split) [, of rows [split, rows) when split < rows] [, dLoss/dT when there is a row_tdot]
+//          [, dLoss/db when there is a row_bdot]}
+//   loss = (factor * sum_i row_loss_i) / divisor;  acc = hits / kept rows of its segment (kept: ignore_i < 1; without a mask the segment's
+//   size);  dLoss/dT = temp_grad(T, -factor * sum_i row_tdot_i): z = s / temp -> -(1 / temp) sum_ij dz_ij s_ij / temp;  dLoss/db = sum_i row_bdot_i.
+// Products with 1 and divisions by 1 are exact, so the entries whose loss has no factor or divisor pass 1.
+struct Finalize {
+    const float *row_loss, *row_correct, *row_tdot, *row_bdot, *ignore, *temperature;      // row_tdot (with temperature), row_bdot, ignore: null where absent
+    float* out;
+    int rows, split;
+    float factor, divisor;
+};
+__global__ __launch_bounds__(256) void rows_finalize_kernel(Finalize F) {
     __shared__ float sh[8];
-    float l = 0.f, c = 0.f, k = 0.f, t = 0.f;
-    for (int i = threadIdx.x; i < N1; i += 256) {
-        const bool keep = !ignore || ignore[i] < 1.0f;
-        l += row_loss[i];
-        t += row_tdot[i];
-        if (keep) { c += row_correct[i]; k += 1.f; }
+    const bool two = F.split < F.rows;
+    float l = 0.f, t = 0.f, d = 0.f, c0 = 0.f, k0 = 0.f, c1 = 0.f, k1 = 0.f;
+    for (int i = threadIdx.x; i < F.rows; i += 256) {
+        l += F.row_loss[i];
+        if (F.row_tdot) t += F.row_tdot[i];
+        if (F.row_bdot) d += F.row_bdot[i];
+        if (!F.ignore || F.ignore[i] < 1.0f) {
+            if (i < F.split) { c0 += F.row_correct[i]; k0 += 1.f; } else { c1 += F.row_correct[i]; k1 += 1.f; }
+        }
     }
-    l = block_reduce_sum(l, sh); c = block_reduce_sum(c, sh); k = block_reduce_sum(k, sh); t = block_reduce_sum(t, sh);
+    l = block_reduce_sum(l, sh); c0 = block_reduce_sum(c0, sh); k0 = block_reduce_sum(k0, sh);
+    if (two) { c1 = block_reduce_sum(c1, sh); k1 = block_reduce_sum(k1, sh); }
+    if (F.row_tdot) t = block_reduce_sum(t, sh);
+    if (F.row_bdot) d = block_reduce_sum(d, sh);
     if (threadIdx.x == 0) {
-        const float T = temperature[0];
-        const float temp = fminf(fmaxf(T, 0.001f), 0.5f);
-        out[0] = l / N1;
-        out[1] = c / k;
-        // z = s / temp  ->  dL/dtemp = -(1/temp) * sum_ij dz_ij * s_ij / temp ... with tdot = sum dz*s:  -tdot / temp^2
-        out[2] = (T >= 0.001f && T <= 0.5f) ? -t / (temp * temp) : 0.f;
-    }
-}
-
-// Both directions of the CLIP loss at once (pipelines/clip.py:129-140: 0.5 (i2t + t2i)): rows [0, N1) are the image -> text matrix, rows
-// [N1, 2 N1) the text -> image one.  out = {loss, i2t acc, t2i acc, dLoss/dTemperature}.
-__global__ __launch_bounds__(256) void nce_finalize_pair_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_correct,
-                                                                const float* __restrict__ row_tdot, const float* __restrict__ temperature,
-                                                                float* __restrict__ out, int N1) {
-    __shared__ float sh[8];
-    float l = 0.f, c0 = 0.f, c1 = 0.f, t = 0.f;
-    for (int i = threadIdx.x; i < 2 * N1; i += 256) {
-        l += row_loss[i];
-        t += row_tdot[i];
-        if (i < N1) c0 += row_correct[i]; else c1 += row_correct[i];
-    }
-    l = block_reduce_sum(l, sh); c0 = block_reduce_sum(c0, sh); c1 = block_reduce_sum(c1, sh); t = block_reduce_sum(t, sh);
-    if (threadIdx.x == 0) {
-        const float T = temperature[0];
-        const float temp = fminf(fmaxf(T, 0.001f), 0.5f);
-        out[0] = 0.5f * l / N1;
-        out[1] = c0 / N1;
-        out[2] = c1 / N1;
-        out[3] = (T >= 0.001f && T <= 0.5f) ? -0.5f * t / (temp * temp) : 0.f;
+        float* o = F.out;
+        *o++ = (F.factor * l) / F.divisor;
+        *o++ = c0 / k0;
+        if (two) *o++ = c1 / k1;
+        if (F.row_tdot) *o++ = temp_grad(F.temperature[0], -F.factor * t);
+        if (F.row_bdot) *o++ = d;
     }
 }
 
@@ -191,7 +192,7 @@ __global__ __launch_bounds__(256) void triplet_rows_kernel(float* __restrict__ s
     const int m0 = mask_block ? target0 : tgt, m1 = mask_block ? target0 + N1 : tgt + 1;      // masked columns [m0, m1)
     const float d = row[tgt];
     float mx = -INFINITY, cmx = 0.f, sum = 0.f, cnt = 0.f;
-    int arg = 0x7fffffff, carg = 0x7fffffff;
+    int arg = 0x7fffffff, carg = 0x7fffffff, best;
     for (int j = tid; j < N2; j += 256) {
         const float s = row[j];
         if (s > mx) { mx = s; arg = j; }
@@ -202,8 +203,7 @@ __global__ __launch_bounds__(256) void triplet_rows_kernel(float* __restrict__ s
             if (pre > cmx) { cmx = pre; carg = j; }
         }
     }
-    const float bmx = block_reduce_max(mx, sh);
-    const int best = block_reduce_min_int(mx == bmx ? arg : 0x7fffffff, shi);
+    block_first_argmax(mx, arg, sh, shi, best);
     float loss;
     int carg_b = 0x7fffffff;
     if (reduce == 0) {
@@ -211,8 +211,8 @@ __global__ __launch_bounds__(256) void triplet_rows_kernel(float* __restrict__ s
         cnt = block_reduce_sum(cnt, sh);          // (an integer below 2^24: exact)
         loss = sum / (float)(N1 - 1);
     } else {
-        loss = block_reduce_max(cmx, sh);         // >= 0: the masked columns cost 0
-        carg_b = block_reduce_min_int((loss > 0.f && cmx == loss) ? carg : 0x7fffffff, shi);
+        // (>= 0: the masked columns cost 0.  At 0 no thread has set its carg, and carg_b stays "no column")
+        loss = block_first_argmax(cmx, carg, sh, shi, carg_b);
     }
     __syncthreads();       // (every thread holds d = row[tgt] and its pass-1 values before any thread rewrites the row)
     if (write_grad) {
@@ -230,24 +230,6 @@ __global__ __launch_bounds__(256) void triplet_rows_kernel(float* __restrict__ s
     if (tid == 0) {
         row_loss[i] = loss;
         row_correct[i] = (best == tgt) ? 1.f : 0.f;
-    }
-}
-
-// out = {sum of the row losses, top-1 acc} (blocks = 1) or {sum over both matrices' rows, acc of matrix 0, acc of matrix 1} (blocks = 2).
-// The loss is a SUM over rows, as in the reference (loss.sum()).
-__global__ __launch_bounds__(256) void triplet_finalize_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_correct,
-                                                               float* __restrict__ out, int N1, int blocks) {
-    __shared__ float sh[8];
-    float l = 0.f, c0 = 0.f, c1 = 0.f;
-    for (int i = threadIdx.x; i < blocks * N1; i += 256) {
-        l += row_loss[i];
-        if (i < N1) c0 += row_correct[i]; else c1 += row_correct[i];
-    }
-    l = block_reduce_sum(l, sh); c0 = block_reduce_sum(c0, sh); c1 = block_reduce_sum(c1, sh);
-    if (threadIdx.x == 0) {
-        out[0] = l;
-        out[1] = c0 / N1;
-        if (blocks == 2) out[2] = c1 / N1;
     }
 }
 
@@ -272,13 +254,12 @@ __global__ __launch_bounds__(256) void siglip_rows_kernel(float* __restrict__ si
     __shared__ int shi[8];
     const int i = blockIdx.x, tid = threadIdx.x;
     float* row = sims + (long)i * N2;
-    const float temp = fminf(fmaxf(temperature[0], 0.001f), 0.5f);
-    const float inv_t = 1.0f / temp;
+    const float inv_t = inv_temp(temperature[0]);
     const float b = bias[0];
     const float n1 = (float)N1;
     const int tgt = target0 + i;
     float mx = -INFINITY, loss = 0.f, tdot = 0.f, bdot = 0.f;
-    int arg = 0x7fffffff;
+    int arg = 0x7fffffff, best;
     for (int j = tid; j < N2; j += 256) {
         const float s = row[j];
         if (s > mx) { mx = s; arg = j; }
@@ -293,8 +274,7 @@ __global__ __launch_bounds__(256) void siglip_rows_kernel(float* __restrict__ si
         bdot += dz;
         if (write_grad) row[j] = dz * inv_t;
     }
-    const float bmx = block_reduce_max(mx, sh);
-    const int best = block_reduce_min_int(mx == bmx ? arg : 0x7fffffff, shi);
+    block_first_argmax(mx, arg, sh, shi, best);
     loss = block_reduce_sum(loss, sh);
     tdot = block_reduce_sum(tdot, sh);
     bdot = block_reduce_sum(bdot, sh);
@@ -303,30 +283,6 @@ __global__ __launch_bounds__(256) void siglip_rows_kernel(float* __restrict__ si
         row_correct[i] = (best == tgt) ? 1.f : 0.f;
         row_tdot[i] = tdot;
         row_bdot[i] = bdot;
-    }
-}
-
-// out = {loss = sum_i row_loss / N1, top-1 acc = hits / N1, dLoss/dT, dLoss/db}; one block, a fixed order of additions.
-// z = s / temp + b  ->  dLoss/dtemp = -sum_ij dz_ij s_ij / temp^2 (0 outside the clamp, as nce_finalize_kernel);  dLoss/db = sum_ij dz_ij.
-__global__ __launch_bounds__(256) void siglip_finalize_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_correct,
-                                                              const float* __restrict__ row_tdot, const float* __restrict__ row_bdot,
-                                                              const float* __restrict__ temperature, float* __restrict__ out, int N1) {
-    __shared__ float sh[8];
-    float l = 0.f, c = 0.f, t = 0.f, d = 0.f;
-    for (int i = threadIdx.x; i < N1; i += 256) {
-        l += row_loss[i];
-        c += row_correct[i];
-        t += row_tdot[i];
-        d += row_bdot[i];
-    }
-    l = block_reduce_sum(l, sh); c = block_reduce_sum(c, sh); t = block_reduce_sum(t, sh); d = block_reduce_sum(d, sh);
-    if (threadIdx.x == 0) {
-        const float T = temperature[0];
-        const float temp = fminf(fmaxf(T, 0.001f), 0.5f);
-        out[0] = l / N1;
-        out[1] = c / N1;
-        out[2] = (T >= 0.001f && T <= 0.5f) ? -t / (temp * temp) : 0.f;
-        out[3] = d;
     }
 }
 
@@ -348,20 +304,18 @@ __global__ __launch_bounds__(256) void ntxent_rows_kernel(float* __restrict__ si
     __shared__ int shi[8];
     const int i = blockIdx.x, tid = threadIdx.x;
     float* row = sims + (long)i * N2;
-    const float temp = fminf(fmaxf(temperature[0], 0.001f), 0.5f);
-    const float inv_t = 1.0f / temp;
+    const float inv_t = inv_temp(temperature[0]);
     const int half = N1 >> 1;
     const int self = target0 + i;
     const int pos = target0 + (i < half ? i + half : i - half);
     float mx = -INFINITY;
-    int arg = 0x7fffffff;
+    int arg = 0x7fffffff, best;
     for (int j = tid; j < N2; j += 256) {
         if (j == self) continue;
         const float z = row[j] * inv_t;
         if (z > mx) { mx = z; arg = j; }
     }
-    const float bmx = block_reduce_max(mx, sh);       // (N2 >= N1 >= 2: at least one column is not the row's own)
-    const int best = block_reduce_min_int(mx == bmx ? arg : 0x7fffffff, shi);          // first index attaining the maximum
+    const float bmx = block_first_argmax(mx, arg, sh, shi, best);       // (N2 >= N1 >= 2: at least one column is not the row's own)
     float se = 0.f;
     for (int j = tid; j < N2; j += 256) {
         if (j == self) continue;
@@ -389,30 +343,6 @@ __global__ __launch_bounds__(256) void ntxent_rows_kernel(float* __restrict__ si
         row_loss[i] = loss;
         row_correct[i] = (best == pos) ? 1.f : 0.f;
         row_tdot[i] = tdot;
-    }
-}
-
-// out = {loss = sum_i row_loss / N1, top-1 acc of view a's rows [0, B), of view b's rows [B, 2B), dLoss/dT}; one block, a fixed order of
-// additions.  dLoss/dT as nce_finalize_kernel: -sum_i row_tdot_i / temp^2, 0 outside the clamp.
-__global__ __launch_bounds__(256) void ntxent_finalize_kernel(const float* __restrict__ row_loss, const float* __restrict__ row_correct,
-                                                              const float* __restrict__ row_tdot, const float* __restrict__ temperature,
-                                                              float* __restrict__ out, int N1) {
-    __shared__ float sh[8];
-    const int half = N1 >> 1;
-    float l = 0.f, c0 = 0.f, c1 = 0.f, t = 0.f;
-    for (int i = threadIdx.x; i < N1; i += 256) {
-        l += row_loss[i];
-        t += row_tdot[i];
-        if (i < half) c0 += row_correct[i]; else c1 += row_correct[i];
-    }
-    l = block_reduce_sum(l, sh); c0 = block_reduce_sum(c0, sh); c1 = block_reduce_sum(c1, sh); t = block_reduce_sum(t, sh);
-    if (threadIdx.x == 0) {
-        const float T = temperature[0];
-        const float temp = fminf(fmaxf(T, 0.001f), 0.5f);
-        out[0] = l / N1;
-        out[1] = c0 / half;
-        out[2] = c1 / half;
-        out[3] = (T >= 0.001f && T <= 0.5f) ? -t / (temp * temp) : 0.f;
     }
 }
 
@@ -536,29 +466,38 @@ __global__ __launch_bounds__(256) void recall_count_kernel(const int* __restrict
 
 #define STREAM ((hipStream_t)stream)
 
+// The argument check the six row entries share: the own columns [target0, target0 + N1) lie inside the N2 columns of a non-empty block.
+// `what` is the entry's word for those columns in its message.
+#define SS_CHECK_OWN_COLUMNS(who, what)                                                                                   \
+    SS_CHECK(N1 >= 1 && N2 >= 1 && target0 >= 0 && target0 + N1 <= N2, who ": " what " [%lld, %lld) outside [0, %lld)", \
+             (long long)target0, (long long)(target0 + N1), (long long)N2)
+
+static void launch_finalize(const Finalize& F, void* stream) {
+    hipLaunchKernelGGL(rows_finalize_kernel, dim3(1), dim3(256), 0, STREAM, F);
+}
+
 extern "C" int simseg_nce_rows(float* sims, const float* temperature, const float* ignore_mask, float* row_loss, float* row_correct,
                                float* row_tdot, float* out3, int64_t N1, int64_t N2, int64_t target0, float smoothing,
                                int write_grad, void* stream) {
     SS_CHECK(sims && temperature && row_loss && row_correct && row_tdot && out3, "nce_rows: null pointer");
-    SS_CHECK(N1 > 0 && N2 > 0 && target0 >= 0 && target0 + N1 <= N2, "nce_rows: targets [%lld, %lld) outside [0, %lld)",
-             (long long)target0, (long long)(target0 + N1), (long long)N2);
+    SS_CHECK_OWN_COLUMNS("nce_rows", "targets");
     hipLaunchKernelGGL(nce_rows_kernel<false>, dim3((unsigned)N1), dim3(256), 0, STREAM, sims, temperature, ignore_mask, row_loss, row_correct,
                        row_tdot, (int)N1, (int)N2, (int)target0, smoothing, write_grad, (const float*)nullptr, 0);
-    hipLaunchKernelGGL(nce_finalize_kernel, dim3(1), dim3(256), 0, STREAM, row_loss, row_correct, row_tdot, ignore_mask, temperature,
-                       out3, (int)N1);
+    launch_finalize({row_loss, row_correct, row_tdot, nullptr, ignore_mask, temperature, out3, (int)N1, (int)N1, 1.f, (float)N1}, stream);
     SS_LAUNCH_CHECK("nce_rows");
     return 0;
 }
 
+// Both directions of the CLIP loss at once (pipelines/clip.py:129-140: 0.5 (i2t + t2i)): rows [0, N1) are the image -> text matrix, rows
+// [N1, 2 N1) the text -> image one.
 extern "C" int simseg_nce_pair(float* sims2, const float* temperature, float* row_scratch, float* out4, int64_t N1, int64_t N2, int64_t target0,
                                float smoothing, int write_grad, void* stream) {
     SS_CHECK(sims2 && temperature && row_scratch && out4, "nce_pair: null pointer");
-    SS_CHECK(N1 > 0 && N2 > 0 && target0 >= 0 && target0 + N1 <= N2, "nce_pair: targets [%lld, %lld) outside [0, %lld)",
-             (long long)target0, (long long)(target0 + N1), (long long)N2);
+    SS_CHECK_OWN_COLUMNS("nce_pair", "targets");
     float* rl = row_scratch; float* rc = rl + 2 * N1; float* rt = rc + 2 * N1;
     hipLaunchKernelGGL(nce_rows_kernel<false>, dim3((unsigned)(2 * N1)), dim3(256), 0, STREAM, sims2, temperature, (const float*)nullptr, rl, rc, rt, (int)N1,
                        (int)N2, (int)target0, smoothing, write_grad, (const float*)nullptr, 0);
-    hipLaunchKernelGGL(nce_finalize_pair_kernel, dim3(1), dim3(256), 0, STREAM, rl, rc, rt, temperature, out4, (int)N1);
+    launch_finalize({rl, rc, rt, nullptr, nullptr, temperature, out4, 2 * (int)N1, (int)N1, 0.5f, (float)N1}, stream);
     SS_LAUNCH_CHECK("nce_pair");
     return 0;
 }
@@ -568,27 +507,25 @@ extern "C" int simseg_mix_nce_rows(float* sims, const float* temperature, const 
                                    int64_t target0, float smoothing, int write_grad, void* stream) {
     SS_CHECK(sims && temperature && alpha && row_loss && row_correct && row_tdot && out3, "mix_nce_rows: null pointer");
     SS_CHECK(alpha_stride == 0 || alpha_stride == 1, "mix_nce_rows: alpha_stride %d is neither 0 (scalar) nor 1 (per row)", alpha_stride);
-    SS_CHECK(N1 > 0 && N2 > 0 && target0 >= 0 && target0 + N1 <= N2, "mix_nce_rows: targets [%lld, %lld) outside [0, %lld)",
-             (long long)target0, (long long)(target0 + N1), (long long)N2);
+    SS_CHECK_OWN_COLUMNS("mix_nce_rows", "targets");
     hipLaunchKernelGGL(nce_rows_kernel<true>, dim3((unsigned)N1), dim3(256), 0, STREAM, sims, temperature, ignore_mask, row_loss, row_correct,
                        row_tdot, (int)N1, (int)N2, (int)target0, smoothing, write_grad, alpha, alpha_stride);
-    hipLaunchKernelGGL(nce_finalize_kernel, dim3(1), dim3(256), 0, STREAM, row_loss, row_correct, row_tdot, ignore_mask, temperature,
-                       out3, (int)N1);
+    launch_finalize({row_loss, row_correct, row_tdot, nullptr, ignore_mask, temperature, out3, (int)N1, (int)N1, 1.f, (float)N1}, stream);
     SS_LAUNCH_CHECK("mix_nce_rows");
     return 0;
 }
 
+// The loss is a SUM over rows, as in the reference (loss.sum()): no divisor.  blocks = 2: the second accuracy is the second matrix's.
 extern "C" int simseg_triplet_rows(float* sims, float* row_loss, float* row_correct, float* out, int64_t N1, int64_t N2, int64_t target0,
                                    float margin, int reduce, int mask_block, int blocks, int write_grad, void* stream) {
     SS_CHECK(sims && row_loss && row_correct && out, "triplet_rows: null pointer");
     SS_CHECK(blocks == 1 || blocks == 2, "triplet_rows: blocks %d is neither 1 nor 2", blocks);
     SS_CHECK(reduce == 0 || reduce == 1, "triplet_rows: reduce %d is neither 0 (mean) nor 1 (max)", reduce);
-    SS_CHECK(N1 >= 1 && N2 >= 1 && target0 >= 0 && target0 + N1 <= N2, "triplet_rows: targets [%lld, %lld) outside [0, %lld)",
-             (long long)target0, (long long)(target0 + N1), (long long)N2);
+    SS_CHECK_OWN_COLUMNS("triplet_rows", "targets");
     SS_CHECK(!(reduce == 0 && N1 < 2), "triplet_rows: the mean over N1 - 1 negatives needs N1 >= 2");
     hipLaunchKernelGGL(triplet_rows_kernel, dim3((unsigned)(blocks * N1)), dim3(256), 0, STREAM, sims, row_loss, row_correct, (int)N1, (int)N2,
                        (int)target0, margin, reduce, mask_block ? 1 : 0, write_grad);
-    hipLaunchKernelGGL(triplet_finalize_kernel, dim3(1), dim3(256), 0, STREAM, row_loss, row_correct, out, (int)N1, blocks);
+    launch_finalize({row_loss, row_correct, nullptr, nullptr, nullptr, nullptr, out, blocks * (int)N1, (int)N1, 1.f, 1.f}, stream);
     SS_LAUNCH_CHECK("triplet_rows");
     return 0;
 }
@@ -597,28 +534,26 @@ extern "C" int simseg_siglip_rows(float* sims, const float* temperature, const f
                                   float* row_tdot, float* row_bdot, float* out4, int64_t N1, int64_t N2, int64_t target0, int write_grad,
                                   void* stream) {
     SS_CHECK(sims && temperature && bias && row_loss && row_correct && row_tdot && row_bdot && out4, "siglip_rows: null pointer");
-    SS_CHECK(N1 >= 1 && N2 >= 1 && target0 >= 0 && target0 + N1 <= N2, "siglip_rows: targets [%lld, %lld) outside [0, %lld)",
-             (long long)target0, (long long)(target0 + N1), (long long)N2);
+    SS_CHECK_OWN_COLUMNS("siglip_rows", "targets");
     SS_CHECK(N2 <= 0x7fffffffLL, "siglip_rows: N2 = %lld columns do not fit the kernel's 32-bit indices", (long long)N2);      // (N1, target0 <= N2)
     hipLaunchKernelGGL(siglip_rows_kernel, dim3((unsigned)N1), dim3(256), 0, STREAM, sims, temperature, bias, row_loss, row_correct, row_tdot,
                        row_bdot, (int)N1, (int)N2, (int)target0, write_grad);
-    hipLaunchKernelGGL(siglip_finalize_kernel, dim3(1), dim3(256), 0, STREAM, row_loss, row_correct, row_tdot, row_bdot, temperature, out4,
-                       (int)N1);
+    launch_finalize({row_loss, row_correct, row_tdot, row_bdot, nullptr, temperature, out4, (int)N1, (int)N1, 1.f, (float)N1}, stream);
     SS_LAUNCH_CHECK("siglip_rows");
     return 0;
 }
 
+// The two accuracies are view a's rows [0, B) and view b's rows [B, 2B).
 extern "C" int simseg_ntxent_rows(float* sims, const float* temperature, float* row_loss, float* row_correct, float* row_tdot, float* out4,
                                   int64_t N1, int64_t N2, int64_t target0, int write_grad, void* stream) {
     SS_CHECK(N1 >= 2, "ntxent_rows: N1 = %lld rows; two views of at least one image need N1 >= 2", (long long)N1);
     SS_CHECK(N1 % 2 == 0, "ntxent_rows: N1 = %lld is odd; the rows are view a stacked on view b, N1 = 2B", (long long)N1);
-    SS_CHECK(target0 >= 0 && target0 + N1 <= N2, "ntxent_rows: own block [%lld, %lld) outside [0, %lld)", (long long)target0,
-             (long long)(target0 + N1), (long long)N2);
+    SS_CHECK_OWN_COLUMNS("ntxent_rows", "own block");
     SS_CHECK(N2 <= 0x7fffffffLL, "ntxent_rows: N2 = %lld columns do not fit the kernel's 32-bit indices", (long long)N2);      // (N1, target0 <= N2)
     SS_CHECK(sims && temperature && row_loss && row_correct && row_tdot && out4, "ntxent_rows: null pointer");
     hipLaunchKernelGGL(ntxent_rows_kernel, dim3((unsigned)N1), dim3(256), 0, STREAM, sims, temperature, row_loss, row_correct, row_tdot,
                        (int)N1, (int)N2, (int)target0, write_grad);
-    hipLaunchKernelGGL(ntxent_finalize_kernel, dim3(1), dim3(256), 0, STREAM, row_loss, row_correct, row_tdot, temperature, out4, (int)N1);
+    launch_finalize({row_loss, row_correct, row_tdot, nullptr, nullptr, temperature, out4, (int)N1, (int)N1 / 2, 1.f, (float)N1}, stream);
     SS_LAUNCH_CHECK("ntxent_rows");
     return 0;
 }

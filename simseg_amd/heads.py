@@ -137,69 +137,87 @@ def all_gather_rows(tensor, group):
     return out
 
 
-class NCEFn(Function):
+def _operands(*tensors):
+    """The embeddings as contiguous fp32 (the similarity GEMM's operands)."""
+    return tuple(t.contiguous().float() for t in tensors)
+
+
+def _scalar(t):
+    """A 0-dim temperature / bias as the detached fp32 one-element tensor the row kernels read."""
+    return t.detach().reshape(1).float()
+
+
+def _outputs(ctx, out, n_acc):
+    """(loss, accuracies) = clones of out[0 .. n_acc], the accuracies marked non-differentiable."""
+    res = tuple(out[i].clone() for i in range(1 + n_acc))
+    ctx.mark_non_differentiable(*res[1:])
+    return res
+
+
+class _RowLossFn(Function):
+    """What the row losses share.  _forward: one fp32 MFMA GEMM gives the [N1, N2] similarity block, `rows(sims, need)` - the loss's
+    ops.*_rows call - overwrites it in place with its own gradient (when an input needs one) and returns out = [loss, accuracies, scalar
+    parameter gradients].  backward: the two gradient GEMMs times the upstream gradient, and out[slot] times it for each scalar parameter
+    - `scalar_slots` lists their out slots in the order of the forward arguments that follow (feat1, feat2g).  ignore_g (the two NCE forms):
+    the gathered ignore mask zeroes feat2g's ignored rows, and the same rows of its gradient."""
+
+    @staticmethod
+    def _forward(ctx, feat1, feat2g, rows, n_acc=1, scalar_slots=(), ignore_g=None):
+        f1, f2 = _operands(feat1, feat2g)
+        if ignore_g is not None:
+            f2 = ops.scale_rows(f2, ignore_g.contiguous().float(), one_minus=True)       # mml_loss.py:70-71, 172-173
+        sims = ops.gemm(f1, f2)
+        need = any(ctx.needs_input_grad[:2 + len(scalar_slots)])
+        out = rows(sims, need)
+        ctx.scalar_slots = scalar_slots
+        ctx.save_for_backward(sims if need else None, f1, f2, out, ignore_g)
+        return _outputs(ctx, out, n_acc)
+
+    @staticmethod
+    def backward(ctx, gloss, *_gacc):
+        ds, f1, f2, out, ignore_g = ctx.saved_tensors
+        g = gloss.contiguous().float().reshape(1)
+        grads = [None] * len(ctx.needs_input_grad)
+        if ctx.needs_input_grad[0]:
+            grads[0] = ops.scale_by_scalar(ops.gemm(ds, ops.transpose_f32(f2)), g)
+        if ctx.needs_input_grad[1]:
+            df2 = ops.gemm(ops.transpose_f32(ds), ops.transpose_f32(f1))
+            if ignore_g is not None:
+                df2 = ops.scale_rows(df2, ignore_g.contiguous().float(), one_minus=True)
+            grads[1] = ops.scale_by_scalar(df2, g)
+        for k, slot in enumerate(ctx.scalar_slots, 2):
+            if ctx.needs_input_grad[k]:
+                grads[k] = ops.scale_by_scalar(out[slot:slot + 1], g).reshape(())
+        return tuple(grads)
+
+
+class NCEFn(_RowLossFn):
     """One direction of the global InfoNCE (mml_loss.py:51-103): feat1 [Bl,P] against feat2_global [Bg,P].
     Returns (loss, top-1 acc) as 0-dim tensors.  The [Bl,Bg] similarity block is produced by the fp32 MFMA GEMM and
     overwritten in place by its own gradient, so forward+backward touch it twice."""
 
     @staticmethod
     def forward(ctx, feat1, feat2g, temperature, ignore, ignore_g, rank, smoothing):
-        f1 = feat1.contiguous().float()
-        f2 = feat2g.contiguous().float()
-        if ignore_g is not None:
-            f2 = ops.scale_rows(f2, ignore_g.contiguous().float(), one_minus=True)       # :70-71
-        sims = ops.gemm(f1, f2)
-        need = any(ctx.needs_input_grad[:3])
-        out3 = ops.nce_rows(sims, temperature.detach().reshape(1).float(), rank * f1.shape[0],
-                            None if ignore is None else ignore.contiguous().float(), smoothing, write_grad=need)
-        ctx.save_for_backward(sims if need else None, f1, f2, out3, ignore_g)
-        loss, acc = out3[0].clone(), out3[1].clone()
-        ctx.mark_non_differentiable(acc)
-        return loss, acc
-
-    @staticmethod
-    def backward(ctx, gloss, _gacc):
-        ds, f1, f2, out3, ignore_g = ctx.saved_tensors
-        g = gloss.contiguous().float().reshape(1)
-        df1 = df2 = dt = None
-        if ctx.needs_input_grad[0]:
-            df1 = ops.scale_by_scalar(ops.gemm(ds, ops.transpose_f32(f2)), g)
-        if ctx.needs_input_grad[1]:
-            df2 = ops.gemm(ops.transpose_f32(ds), ops.transpose_f32(f1))
-            if ignore_g is not None:
-                df2 = ops.scale_rows(df2, ignore_g.contiguous().float(), one_minus=True)
-            df2 = ops.scale_by_scalar(df2, g)
-        if ctx.needs_input_grad[2]:
-            dt = ops.scale_by_scalar(out3[2:3], g).reshape(())
-        return df1, df2, dt, None, None, None, None
+        def rows(sims, need):
+            return ops.nce_rows(sims, _scalar(temperature), rank * sims.shape[0], None if ignore is None else ignore.contiguous().float(),
+                                smoothing, write_grad=need)
+        return _RowLossFn._forward(ctx, feat1, feat2g, rows, scalar_slots=(2,), ignore_g=ignore_g)
 
 
-class MixNCEFn(Function):
+class MixNCEFn(_RowLossFn):
     """NCEFn against the two targets of MixUpNCE (mml_loss.py:146-197): row i is scored against column rank * Bl + i with weight alpha_i
     and against column rank * Bl + (Bl - 1 - i) with 1 - alpha_i (ops.mix_nce_rows).  alpha: fp32 device tensor of one element or [Bl],
     not differentiable.  Returns (loss, top-1 acc against the row's own column)."""
 
     @staticmethod
     def forward(ctx, feat1, feat2g, temperature, alpha, ignore, ignore_g, rank, smoothing):
-        f1 = feat1.contiguous().float()
-        f2 = feat2g.contiguous().float()
-        if ignore_g is not None:
-            f2 = ops.scale_rows(f2, ignore_g.contiguous().float(), one_minus=True)       # :172-173
-        sims = ops.gemm(f1, f2)
-        need = any(ctx.needs_input_grad[:3])
-        out3, _ = ops.mix_nce_rows(sims, temperature.detach().reshape(1).float(), rank * f1.shape[0], alpha,
-                                   None if ignore is None else ignore.contiguous().float(), smoothing, write_grad=need)
-        ctx.save_for_backward(sims if need else None, f1, f2, out3, ignore_g)
-        loss, acc = out3[0].clone(), out3[1].clone()
-        ctx.mark_non_differentiable(acc)
-        return loss, acc
-
-    @staticmethod
-    def backward(ctx, gloss, _gacc):
-        return NCEFn.backward(ctx, gloss, _gacc)[:3] + (None,) * 5
+        def rows(sims, need):
+            return ops.mix_nce_rows(sims, _scalar(temperature), rank * sims.shape[0], alpha,
+                                    None if ignore is None else ignore.contiguous().float(), smoothing, write_grad=need)[0]
+        return _RowLossFn._forward(ctx, feat1, feat2g, rows, scalar_slots=(2,), ignore_g=ignore_g)
 
 
-class SigLipFn(Function):
+class SigLipFn(_RowLossFn):
     """One direction of the pairwise sigmoid loss of SigLIP (Zhai et al., ICCV'23): feat1 [N1,P] against feat2_global [N2,P], the positive
     of row i at column rank * N1 + i, every other column a negative; z = s / clamp(T, 1e-3, 0.5) + b (ops.siglip_rows).  Built like NCEFn:
     one GEMM, the rows in place, gradient GEMMs times the upstream gradient; temperature and bias are 0-dim fp32 tensors, both
@@ -207,34 +225,12 @@ class SigLipFn(Function):
 
     @staticmethod
     def forward(ctx, feat1, feat2g, temperature, bias, rank):
-        f1 = feat1.contiguous().float()
-        f2 = feat2g.contiguous().float()
-        sims = ops.gemm(f1, f2)
-        need = any(ctx.needs_input_grad[:4])
-        out4, _ = ops.siglip_rows(sims, temperature.detach().reshape(1).float(), bias.detach().reshape(1).float(), rank * f1.shape[0],
-                                  write_grad=need)
-        ctx.save_for_backward(sims if need else None, f1, f2, out4)
-        loss, acc = out4[0].clone(), out4[1].clone()
-        ctx.mark_non_differentiable(acc)
-        return loss, acc
-
-    @staticmethod
-    def backward(ctx, gloss, _gacc):
-        ds, f1, f2, out4 = ctx.saved_tensors
-        g = gloss.contiguous().float().reshape(1)
-        df1 = df2 = dt = db = None
-        if ctx.needs_input_grad[0]:
-            df1 = ops.scale_by_scalar(ops.gemm(ds, ops.transpose_f32(f2)), g)
-        if ctx.needs_input_grad[1]:
-            df2 = ops.scale_by_scalar(ops.gemm(ops.transpose_f32(ds), ops.transpose_f32(f1)), g)
-        if ctx.needs_input_grad[2]:
-            dt = ops.scale_by_scalar(out4[2:3], g).reshape(())
-        if ctx.needs_input_grad[3]:
-            db = ops.scale_by_scalar(out4[3:4], g).reshape(())
-        return df1, df2, dt, db, None
+        def rows(sims, need):
+            return ops.siglip_rows(sims, _scalar(temperature), _scalar(bias), rank * sims.shape[0], write_grad=need)[0]
+        return _RowLossFn._forward(ctx, feat1, feat2g, rows, scalar_slots=(2, 3))
 
 
-class NTXentFn(Function):
+class NTXentFn(_RowLossFn):
     """The NT-Xent loss of SimCLR in the global form of SLIP's SIMCLRLoss: z [2B, P] is the stacked local batch (view a on view b), zg
     [W * 2B, P] the gathered stacked embeddings, the own block at columns rank * 2B (ops.ntxent_rows: the row's own column is left out,
     the positive sits B rows away).  Built like SigLipFn: one fp32 GEMM, the rows in place, two gradient GEMMs times the upstream
@@ -243,57 +239,21 @@ class NTXentFn(Function):
 
     @staticmethod
     def forward(ctx, z, zg, temperature, rank):
-        f1 = z.contiguous().float()
-        f2 = zg.contiguous().float()
-        sims = ops.gemm(f1, f2)
-        need = any(ctx.needs_input_grad[:3])
-        out4, _ = ops.ntxent_rows(sims, temperature.detach().reshape(1).float(), rank * f1.shape[0], write_grad=need)
-        ctx.save_for_backward(sims if need else None, f1, f2, out4)
-        loss, acc_a, acc_b = out4[0].clone(), out4[1].clone(), out4[2].clone()
-        ctx.mark_non_differentiable(acc_a, acc_b)
-        return loss, acc_a, acc_b
-
-    @staticmethod
-    def backward(ctx, gloss, _ga, _gb):
-        ds, f1, f2, out4 = ctx.saved_tensors
-        g = gloss.contiguous().float().reshape(1)
-        df1 = df2 = dt = None
-        if ctx.needs_input_grad[0]:
-            df1 = ops.scale_by_scalar(ops.gemm(ds, ops.transpose_f32(f2)), g)
-        if ctx.needs_input_grad[1]:
-            df2 = ops.scale_by_scalar(ops.gemm(ops.transpose_f32(ds), ops.transpose_f32(f1)), g)
-        if ctx.needs_input_grad[2]:
-            dt = ops.scale_by_scalar(out4[3:4], g).reshape(())
-        return df1, df2, dt, None
+        def rows(sims, need):
+            return ops.ntxent_rows(sims, _scalar(temperature), rank * sims.shape[0], write_grad=need)[0]
+        return _RowLossFn._forward(ctx, z, zg, rows, n_acc=2, scalar_slots=(3,))
 
 
-class TripletFn(Function):
+class TripletFn(_RowLossFn):
     """The global direction of the Triplet loss (mml_loss.py:285-314): feat1 [N1,P] against feat2_global [N2,P], own columns
     [rank * N1, (rank + 1) * N1) - all of them masked, as in the reference.  Built like NCEFn: one GEMM, ops.triplet_rows in place,
     gradient GEMMs times the upstream gradient.  reduce: 0 mean, 1 max.  Returns (loss = SUM of the row losses, top-1 acc)."""
 
     @staticmethod
     def forward(ctx, feat1, feat2g, rank, margin, reduce):
-        f1 = feat1.contiguous().float()
-        f2 = feat2g.contiguous().float()
-        sims = ops.gemm(f1, f2)
-        need = any(ctx.needs_input_grad[:2])
-        out, _ = ops.triplet_rows(sims, rank * f1.shape[0], margin, reduce, True, write_grad=need)
-        ctx.save_for_backward(sims if need else None, f1, f2)
-        loss, acc = out[0].clone(), out[1].clone()
-        ctx.mark_non_differentiable(acc)
-        return loss, acc
-
-    @staticmethod
-    def backward(ctx, gloss, _gacc):
-        ds, f1, f2 = ctx.saved_tensors
-        g = gloss.contiguous().float().reshape(1)
-        df1 = df2 = None
-        if ctx.needs_input_grad[0]:
-            df1 = ops.scale_by_scalar(ops.gemm(ds, ops.transpose_f32(f2)), g)
-        if ctx.needs_input_grad[1]:
-            df2 = ops.scale_by_scalar(ops.gemm(ops.transpose_f32(ds), ops.transpose_f32(f1)), g)
-        return df1, df2, None, None, None
+        def rows(sims, need):
+            return ops.triplet_rows(sims, rank * sims.shape[0], margin, reduce, True, write_grad=need)[0]
+        return _RowLossFn._forward(ctx, feat1, feat2g, rows)
 
 
 class TripletLocalFn(Function):
@@ -305,8 +265,7 @@ class TripletLocalFn(Function):
 
     @staticmethod
     def forward(ctx, feat1, feat2, margin, reduce):
-        f1 = feat1.contiguous().float()
-        f2 = feat2.contiguous().float()
+        f1, f2 = _operands(feat1, feat2)
         N = f1.shape[0]
         if f2.shape[0] != N:
             raise ValueError(f"TripletLocalFn: {N} rows against {f2.shape[0]}: the local form pairs row i with row i")
@@ -316,9 +275,7 @@ class TripletLocalFn(Function):
         need = any(ctx.needs_input_grad[:2])
         out, _ = ops.triplet_rows(sims, 0, margin, reduce, False, write_grad=need)
         ctx.save_for_backward(sims if need else None, f1, f2)
-        loss, a1, a2 = out[0].clone(), out[1].clone(), out[2].clone()
-        ctx.mark_non_differentiable(a1, a2)
-        return loss, a1, a2
+        return _outputs(ctx, out, 2)
 
     @staticmethod
     def backward(ctx, gloss, _g1, _g2):
@@ -346,7 +303,7 @@ class ClipLossFn(Function):
 
     @staticmethod
     def forward(ctx, img, txt, temperature, group, rank, smoothing, gather_backward):
-        img32, txt32 = img.contiguous().float(), txt.contiguous().float()
+        img32, txt32 = _operands(img, txt)
         world = dist.get_world_size(group) if group is not None else 1
         multi = group is not None and not _one(world)          # the exchange runs: several ranks, or a one-rank group with SIMSEG_FORCE_COLLECTIVES=1
         if multi:
@@ -366,12 +323,10 @@ class ClipLossFn(Function):
         ops.gemm(img32, txt_g, out=sims[0])
         ops.gemm(txt32, img_g, out=sims[1])
         need = any(ctx.needs_input_grad[:3])
-        out4 = ops.nce_pair(sims, temperature.detach().reshape(1).float(), rank * Bl, smoothing, write_grad=need)
+        out4 = ops.nce_pair(sims, _scalar(temperature), rank * Bl, smoothing, write_grad=need)
         ctx.group, ctx.world, ctx.rank, ctx.gb, ctx.multi = group, world, rank, gather_backward, multi
         ctx.save_for_backward(sims if need else None, img32, txt32, img_g if multi else None, txt_g if multi else None, out4)
-        loss, a1, a2 = out4[0].clone(), out4[1].clone(), out4[2].clone()
-        ctx.mark_non_differentiable(a1, a2)
-        return loss, a1, a2
+        return _outputs(ctx, out4, 2)
 
     @staticmethod
     def backward(ctx, gloss, _g1, _g2):
@@ -388,7 +343,7 @@ class ClipLossFn(Function):
             (dsi_t, dst_t, txtg_t, imgg_t, txt_t, img_t), dt = ops.transpose_multi([ds[0], ds[1], txt_g, img_g, txt32, img32], [1, 1, 0, 0, 0, 0],
                                                                                     scalar=g, alpha=0.5, x0=x0)
         dimg = dtxt = None
-        # gradients flow through the gathered role with gather_backward, and with NO process group (NCE._gather then returns the local
+        # gradients flow through the gathered role with gather_backward, and with NO process group (the loss module's _gather then returns the local
         # tensor itself).  A real group of one rank with gather_backward=False detaches like all_gather_rows / the reference's
         # all_gather_group (utils/dist.py:65-74) - same gradients as the unfused NCE.forward path.
         through_gather = ctx.gb or ctx.group is None

@@ -564,28 +564,6 @@ def dropout_apply_(g, seed, p):
     return g
 
 
-def nce_rows(sims, temperature, target0, ignore_mask=None, smoothing=0.0, write_grad=True):
-    """In place: sims <- dLoss/dsims.  Returns out3 = [loss, acc, dLoss/dT] (device tensor)."""
-    require_gpu(sims)
-    N1, N2 = sims.shape
-    scratch = torch.empty(3, N1, device=sims.device, dtype=torch.float32)
-    out3 = torch.empty(3, device=sims.device, dtype=torch.float32)
-    call("simseg_nce_rows", ptr(_c(sims)), ptr(temperature), ptr(_c(ignore_mask)), ptr(scratch[0]), ptr(scratch[1]), ptr(scratch[2]),
-         ptr(out3), N1, N2, int(target0), float(smoothing), int(write_grad), stream())
-    return out3
-
-
-def nce_pair(sims2, temperature, target0, smoothing=0.0, write_grad=True):
-    """Both directions at once (include/simseg_hip.h simseg_nce_pair): sims2 [2, N1, N2] fp32, in place -> gradients w.r.t. the
-    similarities.  Returns out4 = [loss, i2t acc, t2i acc, dLoss/dT] (device tensor)."""
-    require_gpu(sims2)
-    _, N1, N2 = sims2.shape
-    scratch = torch.empty(6 * N1, device=sims2.device, dtype=torch.float32)
-    out4 = torch.empty(4, device=sims2.device, dtype=torch.float32)
-    call("simseg_nce_pair", ptr(_c(sims2)), ptr(temperature), ptr(scratch), ptr(out4), N1, N2, int(target0), float(smoothing), int(write_grad), stream())
-    return out4
-
-
 def _sim_block_check(who, sims, target0, blocks=False):
     require_gpu(sims)
     if sims.dim() != (3 if blocks else 2) or (blocks and sims.shape[0] not in (1, 2)):
@@ -594,6 +572,44 @@ def _sim_block_check(who, sims, target0, blocks=False):
         raise TypeError(f"{who}: sims must be fp32, got {sims.dtype}")
     _c(sims)
     return sims.shape[-2], sims.shape[-1]
+
+
+def _one_f32_check(who, **tensors):
+    """Each named tensor is an fp32 device tensor of one element."""
+    require_gpu(*tensors.values())
+    for name, t in tensors.items():
+        if t.dtype != torch.float32:
+            raise TypeError(f"{who}: {name} must be fp32, got {t.dtype}")
+        if t.numel() != 1:
+            raise ValueError(f"{who}: {name} holds one element, got {tuple(t.shape)}")
+
+
+def _rows_call(entry, sims, dims, *, head=(), tail, k, rows, n_out):
+    """What the row wrappers share: k row arrays of `rows` floats each and the small `out`, then the C entry, whose arguments are all
+    (sims, *head, row arrays, out, N1, N2, target0, *tail, stream).  -> (out, the row arrays [k, rows]: the first holds the row losses)"""
+    scratch = torch.empty(k, rows, device=sims.device, dtype=torch.float32)
+    out = torch.empty(n_out, device=sims.device, dtype=torch.float32)
+    base = scratch.data_ptr()          # (the row arrays' addresses by arithmetic: no tensor is made per array; 0 stays 0 for an empty scratch)
+    call(entry, ptr(sims), *head, *(base + 4 * rows * i for i in range(k)), ptr(out), *dims, *tail, stream())
+    return out, scratch
+
+
+def nce_rows(sims, temperature, target0, ignore_mask=None, smoothing=0.0, write_grad=True):
+    """In place: sims <- dLoss/dsims.  Returns out3 = [loss, acc, dLoss/dT] (device tensor)."""
+    N1, N2 = _sim_block_check("nce_rows", sims, target0)
+    return _rows_call("simseg_nce_rows", sims, (N1, N2, int(target0)), head=(ptr(temperature), ptr(_c(ignore_mask))),
+                      tail=(float(smoothing), int(write_grad)), k=3, rows=N1, n_out=3)[0]
+
+
+def nce_pair(sims2, temperature, target0, smoothing=0.0, write_grad=True):
+    """Both directions at once (include/simseg_hip.h simseg_nce_pair): sims2 [2, N1, N2] fp32, in place -> gradients w.r.t. the
+    similarities.  Returns out4 = [loss, i2t acc, t2i acc, dLoss/dT] (device tensor)."""
+    N1, N2 = _sim_block_check("nce_pair", sims2, target0, blocks=True)
+    if sims2.shape[0] != 2:
+        raise ValueError(f"nce_pair: sims2 [2, N1, N2], got {tuple(sims2.shape)}")
+    # (one scratch pointer: the entry cuts its three row arrays of 2 N1 out of it)
+    return _rows_call("simseg_nce_pair", sims2, (N1, N2, int(target0)), head=(ptr(temperature),), tail=(float(smoothing), int(write_grad)),
+                      k=1, rows=6 * N1, n_out=4)[0]
 
 
 def mix_nce_rows(sims, temperature, target0, alpha, ignore_mask=None, smoothing=0.0, write_grad=True):
@@ -608,11 +624,10 @@ def mix_nce_rows(sims, temperature, target0, alpha, ignore_mask=None, smoothing=
         raise ValueError(f"mix_nce_rows: alpha holds one element or [{N1}], got {tuple(alpha.shape)}")
     if ignore_mask is not None and (ignore_mask.dtype != torch.float32 or tuple(ignore_mask.shape) != (N1,)):
         raise ValueError(f"mix_nce_rows: ignore_mask must be fp32 [{N1}], got {ignore_mask.dtype} {tuple(ignore_mask.shape)}")
-    scratch = torch.empty(3, N1, device=sims.device, dtype=torch.float32)
-    out3 = torch.empty(3, device=sims.device, dtype=torch.float32)
-    call("simseg_mix_nce_rows", ptr(sims), ptr(temperature), ptr(_c(ignore_mask)), ptr(_c(alpha)), 0 if alpha.numel() == 1 else 1,
-         ptr(scratch[0]), ptr(scratch[1]), ptr(scratch[2]), ptr(out3), N1, N2, int(target0), float(smoothing), int(bool(write_grad)), stream())
-    return out3, scratch[0]
+    out3, rows = _rows_call("simseg_mix_nce_rows", sims, (N1, N2, int(target0)),
+                            head=(ptr(temperature), ptr(_c(ignore_mask)), ptr(_c(alpha)), 0 if alpha.numel() == 1 else 1),
+                            tail=(float(smoothing), int(bool(write_grad))), k=3, rows=N1, n_out=3)
+    return out3, rows[0]
 
 
 def triplet_rows(sims, target0, margin, reduce, mask_block, write_grad=True):
@@ -625,11 +640,10 @@ def triplet_rows(sims, target0, margin, reduce, mask_block, write_grad=True):
     reduce = {"mean": 0, "max": 1}.get(reduce, reduce)
     if reduce == 0 and N1 < 2:
         raise ValueError("triplet_rows: the mean over N1 - 1 negatives needs N1 >= 2 (the reference divides by zero here)")
-    scratch = torch.empty(2, blocks * max(N1, 1), device=sims.device, dtype=torch.float32)
-    out = torch.empty(1 + blocks, device=sims.device, dtype=torch.float32)
-    call("simseg_triplet_rows", ptr(sims), ptr(scratch[0]), ptr(scratch[1]), ptr(out), N1, N2, int(target0), float(margin), int(reduce),
-         int(bool(mask_block)), blocks, int(bool(write_grad)), stream())
-    return out, (scratch[0].view(blocks, N1) if stacked else scratch[0])
+    out, rows = _rows_call("simseg_triplet_rows", sims, (N1, N2, int(target0)),
+                           tail=(float(margin), int(reduce), int(bool(mask_block)), blocks, int(bool(write_grad))),
+                           k=2, rows=blocks * max(N1, 1), n_out=1 + blocks)
+    return out, (rows[0].view(blocks, N1) if stacked else rows[0])
 
 
 def siglip_rows(sims, temperature, bias, target0, write_grad=True):
@@ -637,17 +651,10 @@ def siglip_rows(sims, temperature, bias, target0, write_grad=True):
     row i's positive is column target0 + i, every other column a negative.  In place: sims <- dLoss/dsims (write_grad=False leaves it).
     temperature, bias: fp32 device tensors of one element.  -> (out4 = [loss, acc, dLoss/dT, dLoss/db], row losses [N1])."""
     N1, N2 = _sim_block_check("siglip_rows", sims, target0)
-    require_gpu(temperature, bias)
-    for name, t in (("temperature", temperature), ("bias", bias)):
-        if t.dtype != torch.float32:
-            raise TypeError(f"siglip_rows: {name} must be fp32, got {t.dtype}")
-        if t.numel() != 1:
-            raise ValueError(f"siglip_rows: {name} holds one element, got {tuple(t.shape)}")
-    scratch = torch.empty(4, max(N1, 1), device=sims.device, dtype=torch.float32)
-    out4 = torch.empty(4, device=sims.device, dtype=torch.float32)
-    call("simseg_siglip_rows", ptr(sims), ptr(temperature), ptr(bias), ptr(scratch[0]), ptr(scratch[1]), ptr(scratch[2]), ptr(scratch[3]),
-         ptr(out4), N1, N2, int(target0), int(bool(write_grad)), stream())
-    return out4, scratch[0]
+    _one_f32_check("siglip_rows", temperature=temperature, bias=bias)
+    out4, rows = _rows_call("simseg_siglip_rows", sims, (N1, N2, int(target0)), head=(ptr(temperature), ptr(bias)),
+                            tail=(int(bool(write_grad)),), k=4, rows=max(N1, 1), n_out=4)
+    return out4, rows[0]
 
 
 def ntxent_rows(sims, temperature, target0, write_grad=True):
@@ -656,18 +663,12 @@ def ntxent_rows(sims, temperature, target0, write_grad=True):
     positive at target0 + (i + B) mod N1.  In place: sims <- dLoss/dsims (write_grad=False leaves it).  temperature: fp32 device tensor of
     one element.  -> (out4 = [loss, acc of view a's rows, acc of view b's rows, dLoss/dT], row losses [N1])."""
     N1, N2 = _sim_block_check("ntxent_rows", sims, target0)
-    require_gpu(temperature)
-    if temperature.dtype != torch.float32:
-        raise TypeError(f"ntxent_rows: temperature must be fp32, got {temperature.dtype}")
-    if temperature.numel() != 1:
-        raise ValueError(f"ntxent_rows: temperature holds one element, got {tuple(temperature.shape)}")
+    _one_f32_check("ntxent_rows", temperature=temperature)
     if N1 % 2:
         raise ValueError(f"ntxent_rows: N1 = {N1} is odd; the rows are view a stacked on view b, N1 = 2B")
-    scratch = torch.empty(3, max(N1, 1), device=sims.device, dtype=torch.float32)
-    out4 = torch.empty(4, device=sims.device, dtype=torch.float32)
-    call("simseg_ntxent_rows", ptr(sims), ptr(temperature), ptr(scratch[0]), ptr(scratch[1]), ptr(scratch[2]), ptr(out4), N1, N2, int(target0),
-         int(bool(write_grad)), stream())
-    return out4, scratch[0]
+    out4, rows = _rows_call("simseg_ntxent_rows", sims, (N1, N2, int(target0)), head=(ptr(temperature),), tail=(int(bool(write_grad)),),
+                            k=3, rows=max(N1, 1), n_out=4)
+    return out4, rows[0]
 
 
 def transpose_multi(mats, scale_flags, scalar=None, alpha=1.0, x0=None):
